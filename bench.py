@@ -8,12 +8,21 @@ Bx3x256x224x224 clips (B = 8 clips per GPU by default), one process per GPU, gra
         bench.py --gpus N --steps K --warmup W
 
 Rank 0 prints ONE JSON line.  ``value`` = clips all ranks processed / max-over-ranks wall time of the K
-timed steps (inputs already resident in HBM).  ``roofline`` is measured live: HIP events bracket every
+timed steps (inputs already resident in HBM); ``ms_per_step`` = that wall time / K.  A plain run does only
+that: set up, warm up, time the K steps, print the line.
+
+``--full`` adds the secondary figures (their own runs and instrumentation, minutes in all):
+``roofline`` is measured live: HIP events bracket every
 launch of the depthwise-conv forward kernels (the headline kernel family) on the stream they
 run on; achieved = algorithmic bytes (N_in + N_out elements x 4 B + weights, per launch) / device time.
+``roofline_coarse`` runs a few x3d_coarse steps behind the timed ones (fine stream, fp32, eager, N=1).
 ``cpu_baseline`` times the CPU oracle (plain torch fp32; 16 threads by default -- torch's CPU conv kernels stop scaling far
 below the GPU box's 256 logical CPUs; CFN_CPU_THREADS overrides, `cores` in the JSON is what was used) on a bounded sample
 of the same workload (rank 0, N=1 only).
+
+``--dump-outputs DIR`` writes what the last timed step returned on rank 0 (cls / loc loss, per-frame probabilities) and the
+parameters and floating-point buffers it left behind, as DIR/<name>.npy (float32 / float64; an array above 4M elements is
+replaced by a fixed, seeded sample of 4M): the inputs are seeded, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -195,6 +204,39 @@ def staged_leg(step, resident, dev, steps, warmup, world):
     return dt, stager.bytes_staged // max(stager.batches, 1)
 
 
+DUMP_MAX_ELEMS = 4 << 20          # per array: at most 5 arrays of <= 16 MB each stay under 64 MB
+
+
+def _flat_state(nets):
+    """every parameter, then every floating-point buffer, of `nets` in state_dict order, flattened"""
+    ps, bs = [], []
+    for n in nets:
+        names = {id(p) for p in n.parameters()}
+        for v in n.state_dict(keep_vars=True).values():
+            if v.is_floating_point():
+                (ps if id(v) in names else bs).append(v.detach().reshape(-1))
+    return ps, bs
+
+
+def dump_outputs(d, res, nets):
+    """DIR/<name>.npy of what the last timed step computed (see the module docstring).  Called right behind the timed region."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    ps, bs = _flat_state(nets)
+    arrays = {'cls_loss': res[0], 'loc_loss': res[1]}
+    if len(res) > 2:                  # a replayed graph hands back the two losses only
+        arrays['probs'] = res[2]
+    arrays['params'] = torch.cat([p.to(torch.float64 if p.dtype == torch.float64 else torch.float32) for p in ps])
+    if bs:
+        arrays['buffers'] = torch.cat([b.to(torch.float64 if b.dtype == torch.float64 else torch.float32) for b in bs])
+    for name, t in arrays.items():
+        a = t.detach().cpu()
+        a = (a.double() if a.dtype == torch.float64 else a.float()).numpy()
+        if a.size > DUMP_MAX_ELEMS:    # a fixed, seeded sample of the same positions in every run with these arguments
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, DUMP_MAX_ELEMS, replace=False))]
+        np.save(os.path.join(d, name + '.npy'), a)
+
+
 def _self_launch(n):
     """`python bench.py --gpus N` outside torchrun: one rank per GPU under torch.distributed.run (as train_fine._spawn)"""
     import socket
@@ -230,8 +272,11 @@ def main():
     ap.add_argument('--eager', action='store_true', help='--stream coarse / joint: launch every kernel from Python instead of replaying a hipGraph')
     ap.add_argument('--staged', action='store_true', help='after the resident measurement, time the same steps with the inputs arriving from (pinned) HOST memory every step through '
                                                           'cfn_hip.staging (copy stream, double buffered) and report pcie_inclusive_clips_per_s beside `value`')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-coarse-roofline', action='store_true', help='skip the coarse-stream roofline leg (figure B) of the default line')
+    ap.add_argument('--full', action='store_true', help='also measure the secondary figures: `roofline` (HIP events around the headline kernel family), '
+                                                        '`roofline_coarse` and `cpu_baseline` (off by default: a plain run times the steps only)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='write what the last timed step computed (rank 0) as DIR/<name>.npy')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU oracle leg')
+    ap.add_argument('--no-coarse-roofline', action='store_true', help='with --full: skip the coarse-stream roofline leg (figure B) of the default line')
     ap.add_argument('--cpu-sample-frames', type=int, default=None, help='frames of the CPU baseline clip (default: the metric\'s T -- no scaling; a shorter sample is scaled linearly and says so)')
     args = ap.parse_args()
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
@@ -320,13 +365,15 @@ def main():
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
-    fams = ROOFLINE_FAMILIES[args.stream]
+    fams = ROOFLINE_FAMILIES[args.stream] if args.full else ()     # --full: HIP events around the roofline kernels of the timed steps
     for f in fams:
         cfn_hip.prof_enable(f, True)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        losses.append(step()[:2])
+        last = None                   # (the previous step's outputs go back to the allocator first, as in the warm-up)
+        last = step()
+        losses.append(last[:2])
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -335,6 +382,9 @@ def main():
     if world > 1:
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
     dt = float(tt.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last, (fine_net, net) if joint else (net,))
+    last = None
     staged = None
     if args.staged:
         sdt, sbytes = staged_leg(step, resident, dev, args.steps, max(args.warmup, 2), world)
@@ -343,7 +393,7 @@ def main():
             dist.all_reduce(st, op=dist.ReduceOp.MAX)
         staged = (float(st.item()), sbytes)
     roofline_from = 'the timed steps'
-    if args.graph and world == 1:
+    if args.full and args.graph and world == 1:
         # the HIP events that time the roofline kernels are recorded by the C ABI at launch time: a replayed graph holds none.  The roofline leg of
         # a graphed line therefore comes from two EAGER steps of the same model behind the timed region (same kernels, same shapes)
         for f in fams:                    # (nothing was collected under the replays; one untimed eager step first: it allocates the
@@ -419,13 +469,14 @@ def main():
                                   'overlapped with it as in the eager path)' if args.graph and world > 1 else ''),
                        'dist': cdist.describe()},
             'loss': {'first_step_cls_loc': [round(v, 6) for v in loss_first], 'last_step_cls_loc': [round(v, 6) for v in loss_last]},
-            'roofline': {'bound': 'hbm', 'achieved': round(achieved, 1), 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
-                         'frac': round(achieved / HBM_PEAK_GBS, 4), 'traffic': traffic,
-                         'traffic_note': traffic_note,
-                         'kernel': kernel,
-                         'launches': launches, 'avg_launch_ms': round(ms / max(launches, 1), 4),
-                         'algorithmic_bytes_per_launch': round(by / max(launches, 1)), 'measured_over': roofline_from},
         }
+        if args.full:
+            out['roofline'] = {'bound': 'hbm', 'achieved': round(achieved, 1), 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
+                               'frac': round(achieved / HBM_PEAK_GBS, 4), 'traffic': traffic,
+                               'traffic_note': traffic_note,
+                               'kernel': kernel,
+                               'launches': launches, 'avg_launch_ms': round(ms / max(launches, 1), 4),
+                               'algorithmic_bytes_per_launch': round(by / max(launches, 1)), 'measured_over': roofline_from}
         if staged is not None:
             sdt, sbytes = staged
             out['pcie_inclusive_clips_per_s'] = round(world * B * args.steps / sdt, 4)
@@ -435,12 +486,12 @@ def main():
                              'note': 'inputs (clip, labels, masks%s) leave PINNED host memory every step through cfn_hip.staging: one device slab per batch, '
                                      'copy stream, double buffered, event ordered (no host synchronisation); `value` above is the resident measurement'
                                      % (', 5 fine feature maps, feature masks, meta' if coarse else '')}
-        if world == 1 and args.stream == 'fine' and args.dtype == 'f32' and not args.graph and not args.no_coarse_roofline and not args.staged:
+        if args.full and world == 1 and args.stream == 'fine' and args.dtype == 'f32' and not args.graph and not args.no_coarse_roofline and not args.staged:
             del losses
             net = optimizer = reducer = x = labels = masks = None          # the fine step's tensors go back to the allocator first
             torch.cuda.empty_cache()
             out['roofline_coarse'] = coarse_roofline(dev, B, T)
-        if world == 1 and not args.no_cpu_baseline and not joint:       # joint: the CPU legs of the two streams are reported by their own runs
+        if args.full and world == 1 and not args.no_cpu_baseline and not joint:       # joint: the CPU legs of the two streams are reported by their own runs
             out['cpu_baseline'] = cpu_baseline(T, args.cpu_sample_frames, stream=args.stream)   # joint: none (see below)
         print(json.dumps(out), flush=True)
     if world > 1:

@@ -24,6 +24,13 @@ def _free_port():
     return p
 
 
+def _cpu_rank(rank, port):
+    """rendezvous env of one gloo rank, run on the CPU: on a host with a GPU, cdist.init_from_env would otherwise bind rank r to
+    cuda:r (and fail for r >= the device count); this worker process never opens the GPU"""
+    os.environ.update(MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(WORLD), LOCAL_RANK=str(rank))
+    torch.cuda.is_available = lambda: False
+
+
 def _model():
     torch.manual_seed(0)
     return nn.Sequential(nn.Conv1d(6, 16, 1), nn.ReLU(), nn.Conv1d(16, 5, 1))
@@ -41,7 +48,7 @@ def _batch():
 
 def _worker(rank, port, out):
     sys.path.insert(0, PKG)
-    os.environ.update(MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(WORLD), LOCAL_RANK=str(rank))
+    _cpu_rank(rank, port)
     from cfn_hip import dist as cdist
     import train_fine
     r, w, dev = cdist.init_from_env(backend='gloo')
@@ -101,7 +108,7 @@ def test_param_groups_follow_the_reference_rule():
 # ---------------------------------------------------------------------------------------------------------------------
 def _worker_sync(rank, port, out):
     sys.path.insert(0, PKG)
-    os.environ.update(MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(WORLD), LOCAL_RANK=str(rank))
+    _cpu_rank(rank, port)
     from cfn_hip import dist as cdist
     import train_fine
     cdist.init_from_env(backend='gloo')
@@ -166,7 +173,7 @@ def test_bucket_plan_on_the_real_parameter_sets():
 
 def _worker_partial(rank, port, out):
     sys.path.insert(0, PKG)
-    os.environ.update(MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(WORLD), LOCAL_RANK=str(rank))
+    _cpu_rank(rank, port)
     from cfn_hip import dist as cdist
     cdist.init_from_env(backend='gloo')
     torch.manual_seed(0)
@@ -199,7 +206,7 @@ def test_finish_reduces_buckets_with_gradientless_parameters():
 
 def _worker_asymmetric(rank, port, out):
     sys.path.insert(0, PKG)
-    os.environ.update(MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(WORLD), LOCAL_RANK=str(rank))
+    _cpu_rank(rank, port)
     from cfn_hip import dist as cdist
     cdist.init_from_env(backend='gloo')
     torch.manual_seed(0)
@@ -241,7 +248,7 @@ def test_ranks_that_saw_different_gradients_issue_the_same_collectives():
 
 def _worker_accum(rank, port, out):
     sys.path.insert(0, PKG)
-    os.environ.update(MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(WORLD), LOCAL_RANK=str(rank))
+    _cpu_rank(rank, port)
     from cfn_hip import dist as cdist
     import train_fine
     cdist.init_from_env(backend='gloo')
@@ -293,7 +300,7 @@ def test_gradient_accumulation_two_backwards_per_finish():
 
 def _worker_begin_pass(rank, port, out):
     sys.path.insert(0, PKG)
-    os.environ.update(MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(WORLD), LOCAL_RANK=str(rank))
+    _cpu_rank(rank, port)
     from cfn_hip import dist as cdist
     import train_fine
     cdist.init_from_env(backend='gloo')

@@ -6,24 +6,24 @@ rm -rf $O; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 FILT="^RCCL\|^HIP\|^ROCm\|^Host\|^Lib\|amdgpu.ids"
 # kernel stats of the FINE step alone (the default line's coarse leg would mix x3d_coarse kernels into the table); then the default line itself
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/bench -- python $R/bench.py --no-coarse-roofline --no-cpu-baseline > $O/bench_rocprof.json 2> $O/bench.err
-python $R/bench.py > $O/bench.json 2>> $O/bench.err
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/bench_bf16 -- python $R/bench.py --dtype bf16 > $O/bench_bf16.json 2>> $O/bench.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/bench -- python $R/bench.py --full --no-coarse-roofline --no-cpu-baseline > $O/bench_rocprof.json 2> $O/bench.err
+python $R/bench.py --full > $O/bench.json 2>> $O/bench.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/bench_bf16 -- python $R/bench.py --full --dtype bf16 > $O/bench_bf16.json 2>> $O/bench.err
 # coarse stream: the kernel tables come from the EAGER step (launch counts per step); the bench lines proper are the default hipGraph replays (round 6)
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/bench_coarse -- python $R/bench.py --stream coarse --eager --no-cpu-baseline > $O/bench_coarse_eager_rocprof.json 2>> $O/bench.err
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/bench_coarse_t256 -- python $R/bench.py --stream coarse --eager --frames 256 --no-cpu-baseline > $O/bench_coarse_t256_eager_rocprof.json 2>> $O/bench.err
-python $R/bench.py --stream coarse --steps 20 --staged > $O/bench_coarse.json 2>> $O/bench.err
-python $R/bench.py --stream coarse --steps 20 --eager --no-cpu-baseline > $O/bench_coarse_eager.json 2>> $O/bench.err
-python $R/bench.py --stream coarse --frames 256 --no-cpu-baseline > $O/bench_coarse_t256.json 2>> $O/bench.err
-python $R/bench.py --stream coarse --frames 256 --eager --no-cpu-baseline > $O/bench_coarse_t256_eager.json 2>> $O/bench.err
-python $R/bench.py --stream coarse --steps 20 --dtype bf16 --no-cpu-baseline > $O/bench_coarse_bf16.json 2>> $O/bench.err
-python $R/bench.py --stream coarse --steps 20 --dtype fp16 --no-cpu-baseline > $O/bench_coarse_fp16.json 2>> $O/bench.err
-python $R/bench.py --stream coarse --steps 20 --eager --staged --no-cpu-baseline > $O/bench_coarse_eager_staged.json 2>> $O/bench.err
-python $R/bench.py --stream joint --staged > $O/bench_joint.json 2>> $O/bench.err
-python $R/bench.py --stream joint --dtype bf16 > $O/bench_joint_bf16tower.json 2>> $O/bench.err
-python $R/bench.py --stream joint --dtype fp16 > $O/bench_joint_fp16tower.json 2>> $O/bench.err
-python $R/bench.py --dtype fp16 --no-cpu-baseline > $O/bench_fp16.json 2>> $O/bench.err
-python $R/bench.py --staged --no-cpu-baseline --no-coarse-roofline > $O/bench_staged.json 2>> $O/bench.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/bench_coarse -- python $R/bench.py --full --stream coarse --eager --no-cpu-baseline > $O/bench_coarse_eager_rocprof.json 2>> $O/bench.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/bench_coarse_t256 -- python $R/bench.py --full --stream coarse --eager --frames 256 --no-cpu-baseline > $O/bench_coarse_t256_eager_rocprof.json 2>> $O/bench.err
+python $R/bench.py --full --stream coarse --steps 20 --staged > $O/bench_coarse.json 2>> $O/bench.err
+python $R/bench.py --full --stream coarse --steps 20 --eager --no-cpu-baseline > $O/bench_coarse_eager.json 2>> $O/bench.err
+python $R/bench.py --full --stream coarse --frames 256 --no-cpu-baseline > $O/bench_coarse_t256.json 2>> $O/bench.err
+python $R/bench.py --full --stream coarse --frames 256 --eager --no-cpu-baseline > $O/bench_coarse_t256_eager.json 2>> $O/bench.err
+python $R/bench.py --full --stream coarse --steps 20 --dtype bf16 --no-cpu-baseline > $O/bench_coarse_bf16.json 2>> $O/bench.err
+python $R/bench.py --full --stream coarse --steps 20 --dtype fp16 --no-cpu-baseline > $O/bench_coarse_fp16.json 2>> $O/bench.err
+python $R/bench.py --full --stream coarse --steps 20 --eager --staged --no-cpu-baseline > $O/bench_coarse_eager_staged.json 2>> $O/bench.err
+python $R/bench.py --full --stream joint --staged > $O/bench_joint.json 2>> $O/bench.err
+python $R/bench.py --full --stream joint --dtype bf16 > $O/bench_joint_bf16tower.json 2>> $O/bench.err
+python $R/bench.py --full --stream joint --dtype fp16 > $O/bench_joint_fp16tower.json 2>> $O/bench.err
+python $R/bench.py --full --dtype fp16 --no-cpu-baseline > $O/bench_fp16.json 2>> $O/bench.err
+python $R/bench.py --full --staged --no-cpu-baseline --no-coarse-roofline > $O/bench_staged.json 2>> $O/bench.err
 # HBM traffic of the depthwise forward family: separate --pmc passes, kernel trace only
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch -- python $R/tools/dwfwd_only.py > /dev/null 2>&1
 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $O/pmc_write -- python $R/tools/dwfwd_only.py > /dev/null 2>&1
@@ -42,7 +42,7 @@ python $R/tools/salb_bench.py 2>&1 | grep -v "$FILT" > $O/salb_bench.txt
 { CFN_PWF_SPLIT=2 python $R/tools/pwfs_bench.py; L3=1 python $R/tools/pwfs_bench.py; L1=1 python $R/tools/pwfs_bench.py; echo '## layer-3 variant, knock-outs (CFN_PWFS_DBG: 1 weight gradient, 2 data gradient, 8 stores)'; for d in 1 2 3 11; do echo -n "dbg=$d  "; L3=1 CFN_PWFS_DBG=$d python $R/tools/pwfs_bench.py | grep fused; done; } 2>&1 | grep -v "$FILT" > $O/pwfs_bench.txt
 CFN_PWF_SPLIT=2 bash $R/tools/pwfs_knockouts.sh 2>&1 | grep -v "$FILT" > $O/pwfs_knockouts.txt
 RUNS=200 python $R/tools/pwfs_stress.py 2>&1 | grep -v "$FILT" > $O/pwfs_stress.txt
-{ for i in 1 2; do for v in "0 1" "1 0" "1 1" "2 1"; do set -- $v; echo -n "CFN_PWF_SPLIT=$1 CFN_PWF_L3=$2  "; CFN_PWF_SPLIT=$1 CFN_PWF_L3=$2 python $R/bench.py --no-cpu-baseline --no-coarse-roofline 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['ms_per_step'], 'ms/step', d['value'], 'clips/s  figure A', d['roofline']['frac'])"; done; done; } > $O/pwfs_step_ab.txt
+{ for i in 1 2; do for v in "0 1" "1 0" "1 1" "2 1"; do set -- $v; echo -n "CFN_PWF_SPLIT=$1 CFN_PWF_L3=$2  "; CFN_PWF_SPLIT=$1 CFN_PWF_L3=$2 python $R/bench.py --full --no-cpu-baseline --no-coarse-roofline 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['ms_per_step'], 'ms/step', d['value'], 'clips/s  figure A', d['roofline']['frac'])"; done; done; } > $O/pwfs_step_ab.txt
 { echo "# one profiled step at the benchmarked shape (8 clips x 256 frames):"; FRAMES=256 python $R/tools/glue_profile_coarse.py 8 2>&1 | grep "in the step"
   echo "# 2 clips x 64 frames, with the call sites:"; python $R/tools/glue_profile_coarse.py 2 2>&1 | grep -v "$FILT\|Warn\|_warn_once\|ROCTracer"; } > $O/glue_coarse.txt
 python $R/tools/sync_debug.py 2>&1 | grep -v "$FILT" > $O/sync_debug.txt

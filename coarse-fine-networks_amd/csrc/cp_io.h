@@ -1,7 +1,7 @@
-// Element access of the column-pair wave kernels (dwcp.hip, dwcpb.hip, dwcpb2.hip).  The sources are compiled twice: as they
-// are (fp32 tensors) and through dwcp*_bf16.hip with DW_BF16 defined (bf16 storage, identical fp32 arithmetic, host functions
-// and the C entry point suffixed _bf16, argument structs renamed so that the kernel symbols differ) -- the scheme of
-// dwconv3d.hip / dwconv3d_bf16.hip.  LDS images, accumulators, statistics and every reduction stay fp32 / fp64.
+// Element access of the wave kernels of the depthwise conv (dwcp.hip, dwcpbx.hip, dwcpb2x.hip, dwflatb.hip, dwsmall.hip).  The sources
+// are compiled as they are (fp32 tensors; dwcp.hip: nothing) and through <name>_bf16.hip / <name>_f16.hip with DW_BF16 defined (2-byte
+// storage, identical fp32 arithmetic, host functions and the C entry points suffixed _bf16 / _f16, argument structs renamed so that
+// the kernel symbols differ) -- the scheme of dwconv3d.hip / dwconv3d_bf16.hip.  LDS images, accumulators, statistics and every reduction stay fp32 / fp64.
 #pragma once
 #include "cfn_common.h"
 #include "h16.h"

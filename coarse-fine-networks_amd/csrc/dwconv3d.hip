@@ -73,23 +73,20 @@ __device__ __forceinline__ float dw_rt(float v) { return v; }
 
 enum { DW_FWD = 0, DW_DGRAD = 1, DW_WGRAD = 2 };
 int DWN(dw_small_fwd_try)(const dwe_t* x, const double* A, const double* B, int act, const float* w, dwe_t* y, double* sum, double* sumsq,
-                          int N, int C, int T, int Hi, int Wi, int stride, hipStream_t st, bool probe);   // dwsmall.hip (both element types)
+                          int N, int C, int T, int Hi, int Wi, int stride, hipStream_t st, bool probe);   // dwsmall.hip (every element type)
 int DWN(dw_flatb_try)(const dwe_t* gy, const dwe_t* y, const double* gs, const double* gq, const float* w, const dwe_t* x,
                       const double* A, const double* B, int act, dwe_t* gx, double* gA, double* gB, double* gw,
-                      int N, int C, int T, int H, int W, hipStream_t st, bool probe);                  // dwflatb.hip (both element types)
+                      int N, int C, int T, int H, int W, hipStream_t st, bool probe);                  // dwflatb.hip (every element type)
 int DWN(dw_cpbx_try)(const dwe_t* gy, const dwe_t* y, const double* gs, const double* gq, const float* w, const dwe_t* x,
                      const double* A, const double* B, int act, dwe_t* gx, double* gA, double* gB, double* gw,
-                     int N, int C, int T, int H, int W, hipStream_t st, bool probe);                   // dwcpbx.hip (both element types)
+                     int N, int C, int T, int H, int W, hipStream_t st, bool probe);                   // dwcpbx.hip (every element type)
 #ifndef DW_BF16
 int dw_flat_fwd_try(const float* x, const double* A, const double* B, int act, const float* w, float* y, double* sum, double* sumsq,
-                    int N, int C, int T, int Hi, int Wi, int stride, hipStream_t st, bool probe);    // dwflat.hip
-#endif
-// column-pair wave kernels (dwcp.hip, dwcpb.hip; compiled for both element types like this file: cp_io.h)
+                    int N, int C, int T, int Hi, int Wi, int stride, hipStream_t st, bool probe);    // dwflat.hip (fp32)
+#else
 int DWN(dw_cp_fwd_try)(const dwe_t* x, const double* A, const double* B, int act, const float* w, dwe_t* y, double* sum, double* sumsq,
-                       int N, int C, int T, int Hi, int Wi, int stride, hipStream_t st, bool probe);
-int DWN(dw_cpb_try)(const dwe_t* gy, const dwe_t* y, const double* gs, const double* gq, const float* w, const dwe_t* x,
-                    const double* A, const double* B, int act, dwe_t* gx, double* gA, double* gB, double* gw,
-                    int N, int C, int T, int H, int W, hipStream_t st, bool probe);
+                       int N, int C, int T, int Hi, int Wi, int stride, hipStream_t st, bool probe);  // dwcp.hip (bf16 / fp16)
+#endif
 
 struct DwArgs {
     const dwe_t* src;    // FWD/WGRAD: x raw (N,C,T,Hi,Wi)      DGRAD: gy (N,C,T,H,W)
@@ -1089,9 +1086,9 @@ __global__ __launch_bounds__(256) void dw3d_dgrad_s2_fast_kernel(const DwS2Args 
 // ---------------------------------------------------------------------------------------------
 struct DwPlan { int HS, VEC, MAXLD, threads; bool UNIW; size_t lds; unsigned blocks; };
 
-static thread_local int g_force_hs = 0;   // fused backward: explicit strip height
-static int pick_hs(int Ho, int mode, int S) {
-    if (g_force_hs > 0 && Ho % g_force_hs == 0) return g_force_hs;
+// force_hs > 0: strip height asked for by the caller (fused backward), taken when it divides the plane
+static int pick_hs(int Ho, int mode, int S, int force_hs) {
+    if (force_hs > 0 && Ho % force_hs == 0) return force_hs;
     // stride 2 (forward / weight gradient): one output row per thread.  A 7-row strip needs a 15-row input window per
     // thread and leaves too few threads per plane (measured at 4 clips: 112->56 fwd 1.15 -> 0.67 ms, wgrad 1.17 -> 0.77)
     if (S == 2) return 1;
@@ -1104,10 +1101,10 @@ static int pick_hs(int Ho, int mode, int S) {
     return 1;
 }
 
-static int dw_plan_impl(DwArgs& a, int S, int mode, DwPlan& pl, bool allow_flat) {
+static int dw_plan_impl(DwArgs& a, int S, int mode, DwPlan& pl, bool allow_flat, int force_hs) {
     a.Ho = (a.Hi + 2 - 3) / S + 1;
     a.Wo = (a.Wi + 2 - 3) / S + 1;
-    const int HS = pick_hs(a.Ho, mode, S);
+    const int HS = pick_hs(a.Ho, mode, S, force_hs);
     const int G = a.Ho / HS;
     if (a.Wo > 512) return cfn_fail(CFN_ERR_UNSUPPORTED, "dwconv3d: output width %d > 512 not supported", a.Wo);
     // loader: whole-float4 rows (4); else, when the width is even and the plane a whole number of float4s, float4s over
@@ -1190,45 +1187,40 @@ static int dw_plan_impl(DwArgs& a, int S, int mode, DwPlan& pl, bool allow_flat)
     pl.HS = HS; pl.VEC = VEC; pl.MAXLD = MAXLD; pl.threads = threads;
     pl.lds = ((size_t)2 * CG * a.RIN * a.WP + 2 * CG + (mode == DW_WGRAD ? 27 : 2) * CG * (threads / 64)) * sizeof(float);
     pl.blocks = (unsigned)(planes * a.nchunks);
-    {   // CFN_DW_PLAN_DEBUG=1: print the launch plan (geometry audits)
-        static const int dbg = getenv("CFN_DW_PLAN_DEBUG") ? atoi(getenv("CFN_DW_PLAN_DEBUG")) : 0;
-        if (dbg) fprintf(stderr, "dw_plan mode %d S %d C %d %dx%d: HS %d VEC %d MAXLD %d UNIW %d thr %d CG %d TT %d chunks %d blocks %u per_cu %d lds %zu\n",
-                         mode, S, a.C, a.Hi, a.Wi, HS, VEC, MAXLD, (int)pl.UNIW, threads, CG, TT, a.nchunks, pl.blocks, per_cu, pl.lds);
-    }
     return CFN_OK;
 }
 
-static int dw_plan(DwArgs& a, int S, int mode, DwPlan& pl) {
-    int rc = dw_plan_impl(a, S, mode, pl, true);
+static int dw_plan(DwArgs& a, int S, int mode, DwPlan& pl, int force_hs = 0) {
+    int rc = dw_plan_impl(a, S, mode, pl, true, force_hs);
     // the flat loader exists for per-lane channels and <= 4 loads per thread only
-    if (rc == CFN_OK && pl.VEC == 2 && (pl.UNIW || pl.MAXLD == 8)) rc = dw_plan_impl(a, S, mode, pl, false);
+    if (rc == CFN_OK && pl.VEC == 2 && (pl.UNIW || pl.MAXLD == 8)) rc = dw_plan_impl(a, S, mode, pl, false, force_hs);
     return rc;
 }
 
 template <int MODE, int S, int HS>
 static int dw_launch_hs(const DwArgs& a, const DwPlan& pl, hipStream_t st) {
-#define CFN_DW_GO(VEC, MAXLD, UW)                                                                                      \
+#define DW_GO(VEC, MAXLD, UW)                                                                                          \
     do {                                                                                                               \
         auto k = dw3d_kernel<MODE, S, HS, VEC, MAXLD, UW>;                                                             \
         if (pl.lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds); \
         hipLaunchKernelGGL(k, dim3(pl.blocks), dim3(pl.threads), pl.lds, st, a);                                       \
     } while (0)
     if (pl.UNIW) {
-        if (pl.VEC == 4 && pl.MAXLD == 2) CFN_DW_GO(4, 2, true);
-        else if (pl.VEC == 4 && pl.MAXLD == 4) CFN_DW_GO(4, 4, true);
-        else if (pl.VEC == 4) CFN_DW_GO(4, 8, true);
-        else if (pl.MAXLD == 4) CFN_DW_GO(1, 4, true);
-        else CFN_DW_GO(1, 8, true);
+        if (pl.VEC == 4 && pl.MAXLD == 2) DW_GO(4, 2, true);
+        else if (pl.VEC == 4 && pl.MAXLD == 4) DW_GO(4, 4, true);
+        else if (pl.VEC == 4) DW_GO(4, 8, true);
+        else if (pl.MAXLD == 4) DW_GO(1, 4, true);
+        else DW_GO(1, 8, true);
     } else {
-        if (pl.VEC == 2 && pl.MAXLD == 2) CFN_DW_GO(2, 2, false);
-        else if (pl.VEC == 2) CFN_DW_GO(2, 4, false);
-        else if (pl.VEC == 4 && pl.MAXLD == 2) CFN_DW_GO(4, 2, false);
-        else if (pl.VEC == 4 && pl.MAXLD == 4) CFN_DW_GO(4, 4, false);
-        else if (pl.VEC == 4) CFN_DW_GO(4, 8, false);
-        else if (pl.MAXLD == 4) CFN_DW_GO(1, 4, false);
-        else CFN_DW_GO(1, 8, false);
+        if (pl.VEC == 2 && pl.MAXLD == 2) DW_GO(2, 2, false);
+        else if (pl.VEC == 2) DW_GO(2, 4, false);
+        else if (pl.VEC == 4 && pl.MAXLD == 2) DW_GO(4, 2, false);
+        else if (pl.VEC == 4 && pl.MAXLD == 4) DW_GO(4, 4, false);
+        else if (pl.VEC == 4) DW_GO(4, 8, false);
+        else if (pl.MAXLD == 4) DW_GO(1, 4, false);
+        else DW_GO(1, 8, false);
     }
-#undef CFN_DW_GO
+#undef DW_GO
     return cfn_check_launch("dwconv3d");
 }
 
@@ -1260,20 +1252,21 @@ extern "C" int DWN(cfn_dwconv3d_fwd)(const dwe_t* x, const double* A, const doub
     hipStream_t st = (hipStream_t)stream;
 #ifndef DW_BF16
     if (dw_flat_fwd_try(x, A, B, act, w, y, sum, sumsq, N, C, T, Hi, Wi, stride, st, true) == 0) {
-        // output planes 56x56 / 28x28 / 14x14, stride 1 and 2, fp32: flat kernels, every load of a work item up front (dwflat.hip)
+        // output planes 56x56 / 28x28 / 14x14 (stride 1 and 2) and 14 -> 7: flat kernels, every load of a work item up front (dwflat.hip)
         const double po_ = stride == 1 ? (double)Hi * Wi : ((Hi - 1) / 2 + 1.0) * ((Wi - 1) / 2 + 1.0);
         CfnProfScope prof(CFN_K_DWCONV_FWD, st, (double)DW_ES * N * C * T * ((double)Hi * Wi + po_) + 4.0 * C * 27);
         return dw_flat_fwd_try(x, A, B, act, w, y, sum, sumsq, N, C, T, Hi, Wi, stride, st, false);
     }
-#endif
+#else
     if (DWN(dw_cp_fwd_try)(x, A, B, act, w, y, sum, sumsq, N, C, T, Hi, Wi, stride, st, true) == 0) {
         // output planes 56x56 / 28x28 / 14x14, stride 1 and 2: column-pair wave kernel (dwcp.hip)
         const double po_ = stride == 1 ? (double)Hi * Wi : ((Hi - 1) / 2 + 1.0) * ((Wi - 1) / 2 + 1.0);
         CfnProfScope prof(CFN_K_DWCONV_FWD, st, (double)DW_ES * N * C * T * ((double)Hi * Wi + po_) + 4.0 * C * 27);
         return DWN(dw_cp_fwd_try)(x, A, B, act, w, y, sum, sumsq, N, C, T, Hi, Wi, stride, st, false);
     }
+#endif
     if (DWN(dw_small_fwd_try)(x, A, B, act, w, y, sum, sumsq, N, C, T, Hi, Wi, stride, st, true) == 0) {
-        // 14x14 / 7x7 stride 1: wave-per-channel kernel (dwsmall.hip)
+        // 7x7 stride 1: wave-per-channel kernel (dwsmall.hip)
         CfnProfScope prof(CFN_K_DWCONV_FWD, st, (double)DW_ES * N * C * T * 2.0 * Hi * Wi + 4.0 * C * 27);
         return DWN(dw_small_fwd_try)(x, A, B, act, w, y, sum, sumsq, N, C, T, Hi, Wi, stride, st, false);
     }
@@ -1382,11 +1375,6 @@ extern "C" int DWN(cfn_dwconv3d_bwd_fused)(const dwe_t* gy, const dwe_t* y, cons
         CfnProfScope prof(CFN_K_DWCONV_BWD, (hipStream_t)stream, (double)DW_ES * N * C * T * (double)H * W * (y ? 4 : 3));
         return DWN(dw_cpbx_try)(gy, y, gsum, gsumsq, w, x, A, B, act, gx, gA, gB, gw, N, C, T, H, W, (hipStream_t)stream, false);
     }
-    if (DWN(dw_cpb_try)(gy, y, gsum, gsumsq, w, x, A, B, act, gx, gA, gB, gw, N, C, T, H, W, (hipStream_t)stream, true) == 0) {
-        // 56x56 / 28x28 / 14x14: column-pair wave kernel (dwcpb.hip)
-        CfnProfScope prof(CFN_K_DWCONV_BWD, (hipStream_t)stream, (double)DW_ES * N * C * T * (double)H * W * (y ? 4 : 3));
-        return DWN(dw_cpb_try)(gy, y, gsum, gsumsq, w, x, A, B, act, gx, gA, gB, gw, N, C, T, H, W, (hipStream_t)stream, false);
-    }
     DwArgs a = {};
     a.N = N; a.C = C; a.T = T; a.Hi = H; a.Wi = W;
     DwPlan pl;
@@ -1395,9 +1383,7 @@ extern "C" int DWN(cfn_dwconv3d_bwd_fused)(const dwe_t* gy, const dwe_t* y, cons
     int rc = CFN_ERR_UNSUPPORTED;
     bool ok = false;
     for (int hs : {4, 0}) {
-        g_force_hs = hs;
-        rc = dw_plan(a, 1, DW_WGRAD, pl);
-        g_force_hs = 0;
+        rc = dw_plan(a, 1, DW_WGRAD, pl, hs);
         if (rc == CFN_OK && pl.UNIW && pl.VEC == 4 && pl.MAXLD != 8 && (pl.HS == 4 || pl.HS == 7)) { ok = true; break; }
     }
     if (!ok) return -1;                            // small planes keep the two separate kernels

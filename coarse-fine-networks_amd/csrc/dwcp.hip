@@ -1,5 +1,5 @@
 // Depthwise 3x3x3 forward, stride 1 and 2, onto the even square output planes of X3D at 224x224 input (56x56, 28x28, 14x14:
-// conv2 of layers 1-3 and the first block of layers 1-3; x3d_fine.py:89-97,171-201), fp32 or bf16 tensors (cp_io.h) --
+// conv2 of layers 1-3 and the first block of layers 1-3; x3d_fine.py:89-97,171-201), bf16 / fp16 tensors (cp_io.h) --
 // COLUMN-PAIR kernel: one WAVE per (sample, channel, t-chunk, row band), no
 // workgroup barrier.
 //
@@ -20,13 +20,13 @@
 // (unconditional buffer loads: exact vmcnt waits), staged through a wave-private LDS image with a zero halo.  The four waves
 // of a workgroup are the bands of one (n, c, t-chunk) (56x56) or neighbouring t-chunks of one channel: halo rows / frames
 // come out of L2.  Shapes / activations outside this list use the band kernel (dw_cp_fwd_try returns -1).
+// Built through dwcp_bf16.hip / dwcp_f16.hip only: fp32 tensors take the flat kernels of dwflat.hip on every plane served here.
+#ifdef DW_BF16
 #include "cp_io.h"
 #include <stdint.h>
 #include <stdlib.h>
 
-#ifdef DW_BF16
 #define DwCpArgs H16N(DwCpArgs)
-#endif
 struct DwCpArgs {
     const cpe_t* x; const double* A; const double* B; const float* w; cpe_t* y; double* s1; double* s2;
     int N, C, T, act, TT, nchunks;
@@ -218,14 +218,9 @@ __global__ __launch_bounds__(256, OCC) void dw3d_cp_fwd_kernel(const DwCpArgs a)
 // otherwise the launch status
 int CPN(dw_cp_fwd_try)(const cpe_t* x, const double* A, const double* B, int act, const float* w, cpe_t* y, double* sum, double* sumsq,
                   int N, int C, int T, int Hi, int Wi, int stride, hipStream_t st, bool probe) {
-    // bit mask of the shapes served: stride 1: 1 = 56x56, 2 = 28x28, 4 = 14x14; stride 2: 8 = 112->56, 16 = 56->28, 32 = 28->14
-    static const int enabled = getenv("CFN_DW_CP") ? atoi(getenv("CFN_DW_CP")) : 63;
-    static const int tt_env = getenv("CFN_DW_CP_TT") ? atoi(getenv("CFN_DW_CP_TT")) : 0;
     if (Hi != Wi || (stride != 1 && stride != 2)) return -1;
     const int Ho = stride == 1 ? Hi : Hi / 2;
     if ((stride == 2 && (Hi & 1)) || (Ho != 56 && Ho != 28 && Ho != 14)) return -1;
-    const int bit = (Ho == 56 ? 1 : Ho == 28 ? 2 : 4) << (stride == 2 ? 3 : 0);
-    if (!(enabled & bit)) return -1;
     if (act != CFN_ACT_NONE && act != CFN_ACT_RELU && A != nullptr) return -1;      // branch-free prologue: none / ReLU (every X3D conv2)
     if ((long)T * Hi * Wi * CP_ES >= 0x7fff0000L) return -1;
     if ((((uintptr_t)x | (uintptr_t)y) & (4 * CP_ES - 1)) != 0) return -1;
@@ -236,11 +231,7 @@ int CPN(dw_cp_fwd_try)(const cpe_t* x, const double* A, const double* B, int act
     // VGPRs, 5 waves: 5.1 TB/s; capped at 80 / 64 VGPRs the spills cost 1.6x / 3x)
     //   stride 1: 56x56: 28 x 2 lanes x 2 rows (14 bands of 4 rows); 28x28: 14 x 4 x 1 (7 bands); 14x14: 7 x 7 x 2 (the plane)
     //   stride 2: ->56: 28 x 2 x 2 (14 bands); ->28: 14 x 4 x 1 (7 bands); ->14: 7 x 7 x 1 (2 bands)
-    // CFN_DW_CP_TALL=1: stride-1 56x56 / 28x28 with 8-row bands (10 input rows per 8 output rows instead of 6 per 4: the halo rows
-    // are re-read by the neighbouring band, and re-reads cost the vector-memory path as much as first reads)
-    static const int tall = getenv("CFN_DW_CP_TALL") ? atoi(getenv("CFN_DW_CP_TALL")) : 0;
-    const bool tall56 = (tall & 1) && stride == 1 && Ho == 56, tall28 = (tall & 2) && stride == 1 && Ho == 28;
-    const int NB = tall56 ? 7 : tall28 ? 4 : Ho == 56 ? 14 : Ho == 28 ? 7 : (stride == 2 ? 2 : 1);
+    const int NB = Ho == 56 ? 14 : Ho == 28 ? 7 : (stride == 2 ? 2 : 1);
     // t-chunks: >= ~6 rounds of the chip's resident waves (16 per CU) so that the tail of the last round stays small; the
     // chunk length + 2 halo frames is a multiple of the unrolled trip (6 or 12 steps) where T allows it
     const long units = (long)N * C * NB;
@@ -254,7 +245,6 @@ int CPN(dw_cp_fwd_try)(const cpe_t* x, const double* A, const double* B, int act
     // at 8 clips x T = 256 (16 / 22 / 28 / 34 / 52 frames): 112->56 1.409 / 1.449 / 1.457 / 1.452 / 1.434 ms, 56->28 0.689 / 0.705 /
     // 0.730 / 0.731 / 0.723, 28->14 0.357 / 0.365 / 0.380 / 0.374 / 0.377; the stride-1 planes are within +-2 % from 16 up
     if (stride == 2 && TT > 16) TT = 16;
-    if (tt_env > 0) TT = tt_env;
     if (TT > T) TT = T;
     a.TT = TT;
     a.nchunks = (T + TT - 1) / TT;
@@ -262,11 +252,11 @@ int CPN(dw_cp_fwd_try)(const cpe_t* x, const double* A, const double* B, int act
     const unsigned blocks = (unsigned)((a.total_waves + 3) / 4);
 #define CFN_CP_GO(...) hipLaunchKernelGGL((dw3d_cp_fwd_kernel<__VA_ARGS__>), dim3(blocks), dim3(256), 0, st, a)
     if (stride == 1) {
-        if (tall56) CFN_CP_GO(56, 1, 4, 2, 2, 3); else if (tall28) CFN_CP_GO(28, 1, 2, 4, 2, 4);
-        else if (Ho == 56) CFN_CP_GO(56, 1, 2, 2, 2, 4); else if (Ho == 28) CFN_CP_GO(28, 1, 1, 4, 2, 4); else CFN_CP_GO(14, 1, 2, 7, 4, 4);
+        if (Ho == 56) CFN_CP_GO(56, 1, 2, 2, 2, 4); else if (Ho == 28) CFN_CP_GO(28, 1, 1, 4, 2, 4); else CFN_CP_GO(14, 1, 2, 7, 4, 4);
     } else {
         if (Ho == 56) CFN_CP_GO(56, 2, 2, 2, 2, 4); else if (Ho == 28) CFN_CP_GO(28, 2, 1, 4, 2, 4); else CFN_CP_GO(14, 2, 1, 7, 2, 4);
     }
 #undef CFN_CP_GO
     return cfn_check_launch("dwconv3d column-pair forward");
 }
+#endif

@@ -1,17 +1,25 @@
-// Fused backward of the STRIDE-2 depthwise 3x3x3 conv (112 -> 56, 56 -> 28, 28 -> 14), fp32 tensors: the column-pair wave kernel of dwcpb2.hip
-// with ONE LDS image instead of three (round 4; the stride-1 counterpart is dwcpbx.hip).
+// Fused backward of the STRIDE-2 depthwise 3x3x3 conv (first block of every X3D stage: 112 -> 56, 56 -> 28, 28 -> 14 at 224x224 input;
+// x3d_fine.py:89-97,171-201): data gradient AND weight gradient in one pass -- column-pair wave kernel with ONE LDS image (round 4; the
+// stride-1 counterpart is dwcpbx.hip).
 //
-// dwcpb2.hip stages g' at output resolution and a = act(A x + B) AND x at input resolution (4 x the size, both double buffered) because it
-// forms the weight gradient from an a WINDOW and the g' centre.  Re-indexed by the position of a, every weight-gradient term is the product of
-// one of the lane's OWN eight input positions with the very g' element the data gradient uses for the same tap: 9 products per output
-// position and temporal tap feed both.  a and x are needed only at the lane's 2 x 4 input block, so they are loaded straight into registers
-// (two 16-byte loads per frame) and only the small g' image goes through LDS.
+// Why: the two separate kernels (dw3d_dgrad_s2_fast_kernel, dw3d_kernel<WGRAD, 2>) read the input-resolution tensor x TWICE and write gx once:
+// 3 passes at input resolution (plus gy / y at output resolution, a quarter of the size, twice).  Fused: x once, gx once.
+// A lane owns two horizontally adjacent output positions (o, j), (o, j+1) = the 2 x 4 input block rows 2o..2o+1, columns 4cp..4cp+3
+// (cp = j / 2).  Tap parity: an even input row / column sees only the centre tap, an odd one the two outer taps, so the data gradient of
+// the 2 x 2 input block under output position (o, j) is (G = g' = gy + gs + 2 y gq, summed over kt with w = w[kt], frame f of g' feeding
+// gx(f - 1 + kt) through three rolling accumulator sets):
 //   (2o, 2j): w[1][1] G[o][j]                          (2o, 2j+1): w[1][0] G[o][j+1] + w[1][2] G[o][j]
 //   (2o+1, 2j): w[0][1] G[o+1][j] + w[2][1] G[o][j]    (2o+1, 2j+1): w[0][0] G[o+1][j+1] + w[0][2] G[o+1][j] + w[2][0] G[o][j+1] + w[2][2] G[o][j]
+// The forward is y(t) = sum_kt w[kt] a(t + kt - 1) with a = act(A x + B), so gw[kt][kh][kw] = sum g'(t)[o][j] a(t + kt - 1)[2o + kh - 1][2j + kw - 1].
+// Re-indexed by the position of a, every weight-gradient term is the product of one of the lane's OWN eight input positions with the very
+// g' element the data gradient uses for the same tap: 9 products per output position and temporal tap feed both.  a and x are needed only
+// at the lane's 2 x 4 input block, so they are loaded straight into registers (two 16-byte loads per frame) and only the small g' image
+// (output resolution, right / bottom halo) goes through LDS; no workgroup barrier.
 // Step f: G(f) is in the image; output frame f + 1 - s (set s) takes the taps kt = 2 - s; frame f - 1 is complete afterwards.  A wave owns the
-// weight-gradient terms of the a positions of ITS chunk (a is zero outside it).
+// weight-gradient terms of the a positions of ITS chunk (a is zero outside it).  Even input sizes only (no bottom / right input halo).
 // hipcc-flags: -fno-slp-vectorize
-// fp32 or bf16 tensors (cp_io.h: compiled a second time through dwcpb2x_bf16.hip; the LDS image, accumulators and every reduction stay fp32 / fp64).
+// fp32, bf16 or fp16 tensors (cp_io.h: compiled again through dwcpb2x_bf16.hip / dwcpb2x_f16.hip; the LDS image, accumulators and every
+// reduction stay fp32 / fp64).
 #include "cp_io.h"
 #include <stdint.h>
 #include <stdlib.h>
@@ -235,7 +243,9 @@ __global__ __launch_bounds__(256, OCC) void dw3d_cpx_bwd_s2_kernel(const DwCpb2x
             asm volatile("" : "+v"(st1), "+v"(st2));
         }
     }
-    // ---- reductions: gw (27 per channel) by transpose-reduce (see dwcpb.hip), then gA / gB ----
+    // ---- reductions: gw (27 per channel), then gA / gB ----
+    // transpose-reduce: 32 values x 64 lanes -> one total per lane pair in 16 + 8 + 4 + 2 + 1 + 1 = 32 shuffles (a wave sum per value would be
+    // 27 x 6); at the end lane l holds the total of value (l >> 1) (bits 5..1 of the lane, MSB first), and 27 lanes issue ONE atomic instruction
     {
         float v[32];
 #pragma unroll
@@ -261,15 +271,11 @@ __global__ __launch_bounds__(256, OCC) void dw3d_cpx_bwd_s2_kernel(const DwCpb2x
     }
 }
 
-// returns -1 when the shape is not handled (caller goes on to dwcpb2.hip); probe: 0 = handled, nothing launched.  H, W: input size.
+// returns -1 when the shape is not handled; probe: 0 = handled, nothing launched.  H, W: input size.
 int CPN(dw_cpb2x_try)(const cpe_t* gy, const cpe_t* y, const double* gs, const double* gq, const float* w, const cpe_t* x,
                  const double* A, const double* B, int act, cpe_t* gx, double* gA, double* gB, double* gw,
                  int N, int C, int T, int H, int W, hipStream_t st, bool probe) {
-    // bit mask of the shapes served: 1 = 112->56, 2 = 56->28, 4 = 28->14
-    static const int enabled = getenv("CFN_DW_CPB2X") ? atoi(getenv("CFN_DW_CPB2X")) : 7;
-    static const int tt_env = getenv("CFN_DW_CPB2_TT") ? atoi(getenv("CFN_DW_CPB2_TT")) : 0;
     if (H != W || (H != 112 && H != 56 && H != 28)) return -1;
-    if (!(enabled & (H == 112 ? 1 : H == 56 ? 2 : 4))) return -1;
     if (A != nullptr && act != CFN_ACT_NONE && act != CFN_ACT_RELU) return -1;      // act' from the sign of a: none / ReLU (every X3D conv2)
     if ((long)T * H * W * CP_ES >= 0x7fff0000L) return -1;
     if ((((uintptr_t)gy | (uintptr_t)x | (uintptr_t)gx | (uintptr_t)(y ? y : gy)) & (4 * CP_ES - 1)) != 0) return -1;
@@ -277,13 +283,16 @@ int CPN(dw_cpb2x_try)(const cpe_t* gy, const cpe_t* y, const double* gs, const d
     const bool hasy = y != nullptr && gq != nullptr;
     DwCpb2xArgs a = {gy, hasy ? y : nullptr, gs, hasy ? gq : nullptr, w, x, A, B, gx, A ? gA : nullptr, A ? gB : nullptr, gw, N, C, T, act, 0, 0, 0};
     const int NB = H == 112 ? 28 : H == 56 ? 7 : 2;
+    // t-chunks of ~52 frames (a wave's fixed cost -- LDS clear, pipeline fill, the 27-value reduction -- is worth a few frame steps); more
+    // chunks only while the grid has fewer than ~2 rounds of the resident waves (12 per CU)
     const long units = (long)N * C * NB;
     long nch = (T + 26) / 52;
     if (nch < 1) nch = 1;
     while (units * nch < 2L * 256 * 12 && (T + nch) / (nch + 1) >= 16) ++nch;
     int TT = (int)((T + nch - 1) / nch);
-    if (TT > 24) TT = 24;                                                           // (the sweep of dwcpb2.hip)
-    if (tt_env > 0) TT = tt_env;
+    // same-box sweep of the three-image predecessor of this kernel at 8 clips x T = 256 (16 / 24 / 32 / 48 / 52 / 64 frames): 112->56
+    // 2.76 / 2.68 / 2.76 / 2.82 / 2.88 / 2.76 ms, 56->28 1.36 / 1.38 / 1.40 / 1.44 / 1.40 / 1.41, 28->14 0.71 / 0.71 / 0.72 / 0.74 / 0.73 / 0.74
+    if (TT > 24) TT = 24;
     if (TT > T) TT = T;
     a.TT = TT;
     a.nchunks = (T + TT - 1) / TT;
@@ -296,4 +305,30 @@ int CPN(dw_cpb2x_try)(const cpe_t* gy, const cpe_t* y, const double* gs, const d
     else CFN_CPB2X_GO(14, 7, 3);
 #undef CFN_CPB2X_GO
     return cfn_check_launch("dwconv3d stride-2 column-pair fused backward (one image)");
+}
+
+int CPN(dw_flatb_s2_try)(const cpe_t* gy, const cpe_t* y, const double* gs, const double* gq, const float* w, const cpe_t* x,
+                         const double* A, const double* B, int act, cpe_t* gx, double* gA, double* gB, double* gw,
+                         int N, int C, int T, int H, int W, hipStream_t st, bool probe);              // dwflatb.hip (every element type)
+// C ABI (include/cfn_hip.h): data AND weight gradient of the stride-2 conv in one pass; -1 = not handled, call the two kernels
+extern "C" int CPN(cfn_dwconv3d_bwd_fused_s2)(const cpe_t* gy, const cpe_t* y, const double* gsum, const double* gsumsq, const float* w,
+                                         const cpe_t* x, const double* A, const double* B, int act, cpe_t* gx, double* gA, double* gB,
+                                         double* gw, int N, int C, int T, int H, int W, void* stream) {
+    CFN_REQUIRE(gy && w && x && gx && gw, "cfn_dwconv3d_bwd_fused_s2: null tensor");
+    CFN_REQUIRE(N > 0 && C > 0 && T > 0 && H > 0 && W > 0, "cfn_dwconv3d_bwd_fused_s2: bad shape");
+    CFN_REQUIRE((A == nullptr) == (B == nullptr), "cfn_dwconv3d_bwd_fused_s2: A/B mismatch");
+    CFN_REQUIRE(A == nullptr || (gA != nullptr && gB != nullptr), "cfn_dwconv3d_bwd_fused_s2: prologue needs gA, gB");
+    CFN_REQUIRE(gsumsq == nullptr || y != nullptr, "cfn_dwconv3d_bwd_fused_s2: gsumsq needs y");
+    hipStream_t st = (hipStream_t)stream;
+    if (CPN(dw_flatb_s2_try)(gy, y, gsum, gsumsq, w, x, A, B, act, gx, gA, gB, gw, N, C, T, H, W, st, true) == 0) {
+        // 14 -> 7: flat wave kernel (dwflatb.hip)
+        CfnProfScope prof(CFN_K_DWCONV_BWD, st, (double)CP_ES * N * C * T * (2.0 * H * W + 49.0 * (y ? 2 : 1)));
+        return CPN(dw_flatb_s2_try)(gy, y, gsum, gsumsq, w, x, A, B, act, gx, gA, gB, gw, N, C, T, H, W, st, false);
+    }
+    if (CPN(dw_cpb2x_try)(gy, y, gsum, gsumsq, w, x, A, B, act, gx, gA, gB, gw, N, C, T, H, W, st, true) == 0) {
+        // 112 -> 56, 56 -> 28, 28 -> 14: the column-pair wave kernel above
+        CfnProfScope prof(CFN_K_DWCONV_BWD, st, (double)CP_ES * N * C * T * (2.0 * H * W + (double)(H / 2) * (W / 2) * (y ? 2 : 1)));
+        return CPN(dw_cpb2x_try)(gy, y, gsum, gsumsq, w, x, A, B, act, gx, gA, gB, gw, N, C, T, H, W, st, false);
+    }
+    return -1;
 }

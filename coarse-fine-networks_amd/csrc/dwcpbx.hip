@@ -1,19 +1,26 @@
-// Fused backward of the stride-1 depthwise 3x3x3 conv on the 56x56 / 28x28 / 14x14 planes, fp32 tensors: the column-pair wave kernel of
-// dwcpb.hip with ONE LDS image instead of three (round 4).
+// Fused backward of the stride-1 depthwise 3x3x3 conv (data gradient AND weight gradient in one pass over gy, y, x) on the square planes
+// 56x56 / 28x28 / 14x14 (conv2 of X3D layers 1-3, x3d_fine.py:89-97,171-201) -- column-pair wave kernel with ONE LDS image (round 4), the
+// backward counterpart of dwcp.hip.
 //
-// dwcpb.hip stages three images per frame -- g' (window -> data gradient), a = act(A x + B) (window -> weight gradient) and x (centre ->
-// gA, gB) -- because it forms the weight gradient as  gw[k] += g'(t)[centre] * a(t + kt - 1)[window].  Re-indexed by the position of a,
+// Why: run separately the two gradients move 7 tensor passes (dgrad: gy, y, x -> gx; wgrad: gy, y, x), fused 5.  The band kernel
+// dw3d_bwd_fused_kernel (dwconv3d.hip) fuses them too, but with 7 / 4 output rows per lane it needs 211 / 163 VGPRs (2-3 waves per SIMD, one
+// workgroup barrier per frame).  Same skeleton as dwcp.hip: one WAVE per (sample, channel, t-chunk, row band), a lane owns two adjacent
+// columns x HS (1-2) rows, no workgroup barrier.  The forward is y(t) = sum_kt w[kt] a(t + kt - 1) with a = act(A x + B), so
+// gw[kt] = sum_t g'(t) a(t + kt - 1) with g' = gy + gs + 2 y gq.  Re-indexed by the position of a,
 //     gw[k] += a(t)[centre] * g'(t - kt + 1, r - kh + 1, c - kw + 1)
 // is the product of the lane's OWN a value with the very g' element the data gradient reads for the same tap (da(t) = sum_k w[k] g'(...)):
 // one window read feeds both, a and x are only ever needed at the lane's own positions, so they are loaded straight into registers (8-byte
-// loads per row of the lane's column pair, no LDS).  Per frame step: one image written instead of three, (HS + 2) x 4 LDS dwords read
-// instead of 2 (HS + 2) x 4 + 2 HS.  These kernels run at the board's power limit: what is not moved is not paid for.
+// loads per row of the lane's column pair, no LDS).  Per frame step: one image written instead of three (g', a and x images, the form with
+// an a window), (HS + 2) x 4 LDS dwords read instead of 2 (HS + 2) x 4 + 2 HS.  These kernels run at the board's power limit:
+// what is not moved is not paid for.
 // Step f: G(f) is in the LDS image; for kt = 0, 1, 2 the output frame tau = f + 1 - kt takes  acc[kt] += wflip[kt] G-window  and
 // gw[flip(kt, ., .)] += a(tau) G-window; frame f - 1 is complete afterwards (act' epilogue, gA / gB sums, store).  a / x of frames
 // f - 1, f, f + 1 and the three accumulator sets rotate in registers.  A wave owns the weight-gradient terms of the a positions of ITS chunk
 // (a is zero outside it).
 // hipcc-flags: -fno-slp-vectorize
-// fp32 or bf16 tensors (cp_io.h: compiled a second time through dwcpbx_bf16.hip; the LDS image, accumulators and every reduction stay fp32 / fp64).
+// (the SLP vectoriser re-pairs the scalar weight-gradient FMAs into v_pk_fma_f32 with pair-building moves and pushes the kernel into spills)
+// fp32, bf16 or fp16 tensors (cp_io.h: compiled again through dwcpbx_bf16.hip / dwcpbx_f16.hip; the LDS image, accumulators and every
+// reduction stay fp32 / fp64).
 #include "cp_io.h"
 #include <stdint.h>
 #include <stdlib.h>
@@ -235,7 +242,8 @@ __global__ __launch_bounds__(256, OCC) void dw3d_cpx_bwd_kernel(const DwCpbxArgs
         }
     }
     // ---- reductions: gw (27 per channel), then gA / gB ----
-    // transpose-reduce: 32 values x 64 lanes -> one total per lane pair in 32 shuffles; lane l ends with the total of value (l >> 1)
+    // transpose-reduce: 32 values x 64 lanes -> one total per lane pair in 16 + 8 + 4 + 2 + 1 + 1 = 32 shuffles (a wave sum per value would be
+    // 27 x 6); at the end lane l holds the total of value (l >> 1) (bits 5..1 of the lane, MSB first), and 27 lanes issue ONE atomic instruction
     {
         float v[32];
 #pragma unroll
@@ -261,15 +269,11 @@ __global__ __launch_bounds__(256, OCC) void dw3d_cpx_bwd_kernel(const DwCpbxArgs
     }
 }
 
-// returns -1 when the shape is not handled (caller goes on to dwcpb.hip / the band kernels); probe: 0 = handled, nothing launched
+// returns -1 when the shape is not handled (caller goes on to the band kernels); probe: 0 = handled, nothing launched
 int CPN(dw_cpbx_try)(const cpe_t* gy, const cpe_t* y, const double* gs, const double* gq, const float* w, const cpe_t* x,
                 const double* A, const double* B, int act, cpe_t* gx, double* gA, double* gB, double* gw,
                 int N, int C, int T, int H, int W, hipStream_t st, bool probe) {
-    // bit mask of the planes served: 1 = 56x56, 2 = 28x28, 4 = 14x14
-    static const int enabled = getenv("CFN_DW_CPBX") ? atoi(getenv("CFN_DW_CPBX")) : 7;
-    static const int tt_env = getenv("CFN_DW_CPB_TT") ? atoi(getenv("CFN_DW_CPB_TT")) : 0;
     if (H != W || (H != 56 && H != 28 && H != 14)) return -1;
-    if (!(enabled & (H == 56 ? 1 : H == 28 ? 2 : 4))) return -1;
     if (A != nullptr && act != CFN_ACT_NONE && act != CFN_ACT_RELU) return -1;      // act' from the sign of a: none / ReLU (every X3D conv2)
     if ((long)T * H * W * CP_ES >= 0x7fff0000L) return -1;
     if ((((uintptr_t)gy | (uintptr_t)x | (uintptr_t)gx | (uintptr_t)(y ? y : gy)) & (4 * CP_ES - 1)) != 0) return -1;
@@ -277,13 +281,15 @@ int CPN(dw_cpbx_try)(const cpe_t* gy, const cpe_t* y, const double* gs, const do
     const bool hasy = y != nullptr && gq != nullptr;
     DwCpbxArgs a = {gy, hasy ? y : nullptr, gs, hasy ? gq : nullptr, w, x, A, B, gx, A ? gA : nullptr, A ? gB : nullptr, gw, N, C, T, act, 0, 0, 0};
     const int NB = H == 56 ? 14 : H == 28 ? 7 : 1;                                    // 14x14: the plane is one band
-    // t-chunks as in dwcpb.hip: ~64 frames (a wave's fixed cost -- LDS clear, pipeline fill, the 27-value reduction -- is worth ~4 frame steps)
+    // t-chunks of ~64 frames: a wave's fixed cost (LDS clear, pipeline fill, the 27-value reduction) is worth ~4 frame steps (measured on the
+    // three-image predecessor of this kernel, 8 clips x T = 256, 56x56: chunks of 9 / 21 / 33 / 63 frames: 4.5 / 2.3 / 1.7 / 1.3 ms; same-box
+    // sweep 16 / 24 / 32 / 48 / 52 / 64: 56x56 1.39 / 1.29 / 1.23 / 1.26 / 1.22 / 1.20 ms, 28x28 0.76 / 0.70 / 0.64 / 0.65 / 0.64 / 0.61,
+    // 14x14 0.34 / 0.32 / 0.32 / 0.33 / 0.32 / 0.31); more chunks only while the grid has fewer than ~2 rounds of the resident waves (12 per CU)
     const long units = (long)N * C * NB;
     long nch = (T + 32) / 64;
     if (nch < 1) nch = 1;
     while (units * nch < 2L * 256 * 12 && (T + nch) / (nch + 1) >= 16) ++nch;
     int TT = (int)((T + nch - 1) / nch);
-    if (tt_env > 0) TT = tt_env;
     if (TT > T) TT = T;
     a.TT = TT;
     a.nchunks = (T + TT - 1) / TT;

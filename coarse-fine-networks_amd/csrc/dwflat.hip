@@ -466,15 +466,11 @@ __global__ __launch_bounds__(256, 4) void dw3d_flat14to7_fwd_kernel(const DwFlat
 // returns -1 when the shape is not handled; probe: 0 = handled, nothing launched; otherwise the launch status
 int dw_flat_fwd_try(const float* x, const double* A, const double* B, int act, const float* w, float* y, double* sum, double* sumsq,
                     int N, int C, int T, int Hi, int Wi, int stride, hipStream_t st, bool probe) {
-    // bit mask of the planes served: stride 1: 1 = 56x56, 2 = 28x28, 4 = 14x14; stride 2: 8 = 112 -> 56, 16 = 56 -> 28, 32 = 28 -> 14, 64 = 14 -> 7
-    static const int enabled = getenv("CFN_DW_FLAT") ? atoi(getenv("CFN_DW_FLAT")) : 127;
-    static const int to_env = getenv("CFN_DW_FLAT_TO") ? atoi(getenv("CFN_DW_FLAT_TO")) : 0;
     if (Hi != Wi) return -1;
     if (stride == 2 && Hi == 14) {
-        if (!(enabled & 64)) return -1;
         if (act != CFN_ACT_NONE && act != CFN_ACT_RELU && A != nullptr) return -1;
         if ((long)T * Hi * Wi * 4 >= 0x7fff0000L || (((uintptr_t)x | (uintptr_t)y) & 15) != 0) return -1;
-        const int TO = to_env == 4 || to_env == 8 ? to_env : (T >= 12 ? 8 : 4);
+        const int TO = T >= 12 ? 8 : 4;
         const long nch = (T + TO - 1) / TO, items = (long)N * C * nch, blocks = (items + 3) / 4;
         if (blocks >= 0x7fffffffL) return -1;
         if (probe) return 0;
@@ -485,12 +481,11 @@ int dw_flat_fwd_try(const float* x, const double* A, const double* B, int act, c
     }
     if (stride == 2) {
         if (Hi != 112 && Hi != 56 && Hi != 28) return -1;
-        if (!(enabled & (Hi == 112 ? 8 : Hi == 56 ? 16 : 32))) return -1;
         if (act != CFN_ACT_NONE && act != CFN_ACT_RELU && A != nullptr) return -1;
         if ((long)T * Hi * Wi * 4 >= 0x7fff0000L || (((uintptr_t)x | (uintptr_t)y) & 15) != 0) return -1;
         // same-box steady state, 8 clips x T = 256, dwcp.hip / this kernel at TO = 8 / 6 / 4: 112 -> 56 1373 / 1211 / 1260 / 1214 us, 56 -> 28
         // 686 / 622 / 618 / 623, 28 -> 14 358 / 309 / 302 / 311; 2-row bands on 112 -> 56 (7 workgroups per CU, 1.25 x row re-reads): 1250
-        const int TO = to_env == 4 || to_env == 8 ? to_env : (T >= 12 ? 8 : 4);
+        const int TO = T >= 12 ? 8 : 4;
         const int NB = Hi == 112 ? 14 : Hi == 56 ? 4 : 1;
         const long nch = (T + TO - 1) / TO, blocks = (long)N * C * nch * NB;
         if (blocks >= 0x7fffffffL) return -1;
@@ -504,12 +499,11 @@ int dw_flat_fwd_try(const float* x, const double* A, const double* B, int act, c
         return cfn_check_launch("dwconv3d flat stride-2 forward");
     }
     if (stride != 1 || (Hi != 56 && Hi != 28 && Hi != 14)) return -1;
-    if (!(enabled & (Hi == 56 ? 1 : Hi == 28 ? 2 : 4))) return -1;
     if (act != CFN_ACT_NONE && act != CFN_ACT_RELU && A != nullptr) return -1;      // branch-free prologue: none / ReLU (every X3D conv2)
     if ((long)T * Hi * Wi * 4 >= 0x7fff0000L) return -1;
     if ((((uintptr_t)x | (uintptr_t)y) & 15) != 0) return -1;
     // 8 output frames per item (10 input frames: 1.25 x temporal re-reads out of L2; 4 frames: 1.5 x, measured 5 % slower); short clips: 4
-    const int TO = to_env == 4 || to_env == 8 ? to_env : (T >= 12 ? 8 : 4);
+    const int TO = T >= 12 ? 8 : 4;
     const int NB = Hi == 56 ? 4 : 1;
     const long nch = (T + TO - 1) / TO, items = (long)N * C * nch * NB;
     const long blocks = Hi == 14 ? (items + 3) / 4 : items;

@@ -9,12 +9,13 @@
 // g' goes into an LDS image [TO + 2][rows][W], then the lane walks the g' frames once: per window value and temporal tap one FMA into the data-gradient accumulator of
 // an output frame and one into the weight-gradient partial of the flipped tap.  27 weight-gradient partials per lane, transpose-reduced over
 // the wave at the end of the item, fp64 atomics.
-// dw3d_flat7_bwd_kernel: 7x7 planes (layer 4), a WAVE per item, a lane per position (49 of 64 lanes; the column-pair kernel of dwcpb.hip keeps
-// 28 lanes busy on this plane and runs at 2.4 TB/s), no workgroup barrier.  The frames of an item are one contiguous run of floats that does
+// dw3d_flat7_bwd_kernel: 7x7 planes (layer 4), a WAVE per item, a lane per position (49 of 64 lanes; a column-pair kernel keeps
+// 4 pairs x 7 rows = 28 lanes busy on this plane and ran at 2.4 TB/s), no workgroup barrier.  The frames of an item are one contiguous run of floats that does
 // not start on a 16-byte boundary: 4-byte loads, lane l takes floats l, l + 64, ...; g' AND x go through LDS (a lane's loads are not its
 // position).
 // hipcc-flags: -fno-slp-vectorize
-// fp32 or bf16 tensors (cp_io.h: compiled a second time through dwflatb_bf16.hip; LDS images, accumulators and every reduction stay fp32 / fp64).
+// fp32, bf16 or fp16 tensors (cp_io.h: compiled again through dwflatb_bf16.hip / dwflatb_f16.hip; LDS images, accumulators and every
+// reduction stay fp32 / fp64).
 #include "cp_io.h"
 #include <stdint.h>
 #include <stdlib.h>
@@ -197,7 +198,7 @@ __global__ __launch_bounds__(256, 3) void dw3d_flat7_bwd_kernel(const DwFlatBArg
 // 2o, 2o + 1, columns 2j, 2j + 1 (x and a stay in registers: two 8-byte loads / stores per frame); g' (7x7, 4-byte loads of the contiguous
 // run) goes into an LDS image [TO + 2][8][8] with a zero row / column at the bottom / right.  Tap parity: of the 27 taps an even input row /
 // column sees only the centre one, an odd one the two outer ones -- 9 (input position, g' element) products per temporal tap, each feeding
-// the data gradient AND the weight gradient (dwcpb2.hip has the formulas):
+// the data gradient AND the weight gradient (the formulas are derived in dwcpb2x.hip):
 //   (2o, 2j): w[1][1] G[o][j]                          (2o, 2j+1): w[1][0] G[o][j+1] + w[1][2] G[o][j]
 //   (2o+1, 2j): w[0][1] G[o+1][j] + w[2][1] G[o][j]    (2o+1, 2j+1): w[0][0] G[o+1][j+1] + w[0][2] G[o+1][j] + w[2][0] G[o][j+1] + w[2][2] G[o][j]
 // Before: dw3d_dgrad_s2_fast_kernel + dw3d_kernel<WGRAD> (x read twice), 431 + 303 us per step.
@@ -346,19 +347,17 @@ __global__ __launch_bounds__(256, 3) void dw3d_flat14to7_bwd_kernel(const DwFlat
     }
 }
 
-// stride 2: returns -1 when the shape is not handled (caller goes on to the wave / band kernels); H, W: INPUT plane
+// stride 2: returns -1 when the shape is not handled (caller goes on to the column-pair kernel); H, W: INPUT plane
 int CPN(dw_flatb_s2_try)(const cpe_t* gy, const cpe_t* y, const double* gs, const double* gq, const float* w, const cpe_t* x,
                     const double* A, const double* B, int act, cpe_t* gx, double* gA, double* gB, double* gw,
                     int N, int C, int T, int H, int W, hipStream_t st, bool probe) {
-    static const int enabled = getenv("CFN_DW_FLATB") ? atoi(getenv("CFN_DW_FLATB")) : 24;      // 16 = 14 -> 7
-    static const int subs_env = getenv("CFN_DW_FLATB_SUBS") ? atoi(getenv("CFN_DW_FLATB_SUBS")) : 0;
-    if (H != 14 || W != 14 || !(enabled & 16)) return -1;
+    if (H != 14 || W != 14) return -1;
     if (A != nullptr && act != CFN_ACT_NONE && act != CFN_ACT_RELU) return -1;
     if ((long)T * H * W * CP_ES >= 0x7fff0000L) return -1;
     if ((((uintptr_t)x | (uintptr_t)gx) & (2 * CP_ES - 1)) != 0) return -1;
     const int TO = T >= 12 ? 8 : 4;
     const long nchunks = (T + TO - 1) / TO;
-    const int subs = subs_env > 0 ? subs_env : 8;
+    const int subs = 8;                                                             // chunks per wave, as in dw_flatb_try
     const long nch = (nchunks + subs - 1) / subs, items = (long)N * C * nch, blocks = (items + 3) / 4;
     if (blocks >= 0x7fffffffL) return -1;
     if (probe) return 0;
@@ -370,22 +369,18 @@ int CPN(dw_flatb_s2_try)(const cpe_t* gy, const cpe_t* y, const double* gs, cons
     return cfn_check_launch("dwconv3d flat stride-2 backward");
 }
 
-// returns -1 when the shape is not handled (caller goes on to the wave / band kernels); probe: 0 = handled, nothing launched
+// returns -1 when the shape is not handled (caller goes on to the column-pair / band kernels); probe: 0 = handled, nothing launched
 int CPN(dw_flatb_try)(const cpe_t* gy, const cpe_t* y, const double* gs, const double* gq, const float* w, const cpe_t* x,
                  const double* A, const double* B, int act, cpe_t* gx, double* gA, double* gB, double* gw,
                  int N, int C, int T, int H, int W, hipStream_t st, bool probe) {
-    // bit mask of the planes served: 8 = 7x7 (16 = 14 -> 7: dw_flatb_s2_try)
-    static const int enabled = getenv("CFN_DW_FLATB") ? atoi(getenv("CFN_DW_FLATB")) : 24;
-    static const int to_env = getenv("CFN_DW_FLATB_TO") ? atoi(getenv("CFN_DW_FLATB_TO")) : 0;
-    if (H != W || H != 7 || !(enabled & 8)) return -1;
+    if (H != W || H != 7) return -1;
     if (A != nullptr && act != CFN_ACT_NONE && act != CFN_ACT_RELU) return -1;
     if ((long)T * H * W * CP_ES >= 0x7fff0000L) return -1;
-    const int TO = to_env == 4 || to_env == 8 ? to_env : (T >= 12 ? 8 : 4);        // (16-frame items: 128 VGPRs + 670 spilled)
+    const int TO = T >= 12 ? 8 : 4;                                                // (16-frame items: 128 VGPRs + 670 spilled)
     // a wave takes `subs` consecutive chunks and reduces its 27 weight-gradient partials once (one chunk per wave: 55 k waves x 27 fp64 atomics per
     // launch made the kernel 2.6 x slower than the one it replaces)
-    static const int subs_env = getenv("CFN_DW_FLATB_SUBS") ? atoi(getenv("CFN_DW_FLATB_SUBS")) : 0;
     const long nchunks = (T + TO - 1) / TO;
-    const int subs = subs_env > 0 ? subs_env : 8;
+    const int subs = 8;
     const long nch = (nchunks + subs - 1) / subs, items = (long)N * C * nch, blocks = (items + 3) / 4;
     if (blocks >= 0x7fffffffL) return -1;
     if (probe) return 0;

@@ -16,7 +16,10 @@
 // instructions against 27 FMAs per lane) was the limit, hence the frame groups; 14x14 is ~70 % VALU bound (lane waste of
 // the 14-wide rows, 4.5 LDS reads per output).  LDS accesses of one wave execute in order, so the staged frame is visible to the wave's later reads
 // without a barrier (a wave-level fence keeps the compiler from reordering them).
-// fp32 or bf16 tensors (cp_io.h: compiled a second time through dwsmall_bf16.hip; LDS image, accumulators and statistics stay fp32).
+// Only the 7x7 instance is launched: 14x14 planes take the flat kernels of dwflat.hip (fp32) or the column-pair kernel of dwcp.hip
+// (bf16 / fp16), both faster; the template keeps its 14x14 geometry.
+// fp32, bf16 or fp16 tensors (cp_io.h: compiled again through dwsmall_bf16.hip / dwsmall_f16.hip; LDS image, accumulators and statistics
+// stay fp32).
 #include "cp_io.h"
 #include <stdlib.h>
 
@@ -216,11 +219,9 @@ __global__ __launch_bounds__(256, 4) void dw3d_small_fwd_kernel(const DwSmallArg
 // launch status
 int CPN(dw_small_fwd_try)(const cpe_t* x, const double* A, const double* B, int act, const float* w, cpe_t* y, double* sum, double* sumsq,
                      int N, int C, int T, int Hi, int Wi, int stride, hipStream_t st, bool probe) {
-    static const int enabled = getenv("CFN_DW_SMALL") ? atoi(getenv("CFN_DW_SMALL")) : 1;
-    if (!enabled || stride != 1 || Hi != Wi || (Hi != 14 && Hi != 7)) return -1;
+    if (stride != 1 || Hi != 7 || Wi != 7) return -1;
     if (act != CFN_ACT_NONE && act != CFN_ACT_RELU && A != nullptr) return -1;      // branch-free prologue: none / ReLU (every X3D conv2)
     if ((long)T * Hi * Wi * CP_ES >= 0x7ffffff0L) return -1;
-    if (Hi == 14 && (((uintptr_t)x & (4 * CP_ES - 1)) != 0)) return -1;
     if (probe) return 0;
     DwSmallArgs a = {x, A, B, w, y, sum, sumsq, N, C, T, act, 0, 0, 0};
     // t-chunks: ~2 rounds of the chip at 24 resident waves per CU (6 per SIMD), at least 8 frames per chunk (halo re-reads)
@@ -234,7 +235,6 @@ int CPN(dw_small_fwd_try)(const cpe_t* x, const double* A, const double* B, int 
     a.nchunks = (T + TT - 1) / TT;
     a.total_waves = planes * a.nchunks;
     const unsigned blocks = (unsigned)((a.total_waves + 3) / 4);
-    if (Hi == 14) hipLaunchKernelGGL((dw3d_small_fwd_kernel<14, 4>), dim3(blocks), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((dw3d_small_fwd_kernel<7, 1>), dim3(blocks), dim3(256), 0, st, a);
+    hipLaunchKernelGGL((dw3d_small_fwd_kernel<7, 1>), dim3(blocks), dim3(256), 0, st, a);
     return cfn_check_launch("dwconv3d small-plane forward");
 }

@@ -173,82 +173,14 @@ __global__ __launch_bounds__(256) void dwt5_kernel(const T5Args a) {
     }
 }
 
-// Forward, float4 rows (plane % 4 == 0): the same march, but every global access of the frame loop is an UNCONDITIONAL
-// buffer load / store (an unwanted access gets an out-of-range offset).  With the loads under `if (t < T)` the compiler can
-// only wait with vmcnt(0), i.e. for the load it issued a moment ago as well: one HBM round trip per frame and 4.9 TB/s; with
-// exact vmcnt(N) waits the PF look-ahead loads really stay in flight (a one-float4-per-thread copy of the same tensor runs at
-// 6.35 TB/s on this box, tools/probe/stream_probe.hip).  env CFN_T5_STREAM=0 falls back to dwt5_kernel<T5_FWD>.
-template <int BF>
-__global__ __launch_bounds__(256) void dwt5_fwd_stream_kernel(const T5Args a) {
-    typedef typename h16_types<BF ? BF : H16_BF16>::v4 bf4;
-    typedef unsigned __attribute__((ext_vector_type(2))) u2v;
-    constexpr int PF = 3, OOB = 0x7ffffff0, OES = BF ? 2 : 4;
-    __shared__ float sh[8];
-    const long nc = blockIdx.y + (long)blockIdx.z * gridDim.y;
-    const int c = (int)(nc % a.C);
-    const int chunk = blockIdx.x % a.nchunks, pc = blockIdx.x / a.nchunks;
-    const int p = (pc * 256 + (int)threadIdx.x) * 4;
-    const bool ok = p < a.plane;
-    const int T = a.T, t0 = chunk * a.TT, t1 = min(t0 + a.TT, T);
-    const int plane = (int)a.plane;
-    __amdgpu_buffer_rsrc_t rx = cfn_rsrc(static_cast<const float*>(a.src) + nc * T * a.plane, (unsigned)((long)T * plane * 4));
-    __amdgpu_buffer_rsrc_t ry = cfn_rsrc(static_cast<char*>(a.dst) + nc * T * a.plane * OES, (unsigned)((long)T * plane * OES));
-    const int vx = ok ? p * 4 : OOB, vy = ok ? p * OES : OOB;
-    float wk[5];
-#pragma unroll
-    for (int k = 0; k < 5; ++k) wk[k] = cfn_uni(a.w[c * 5 + k]);
-    auto ld = [&](int t) -> f4v {
-        const bool tv = t >= 0 && t < T && t <= t1 + 1;                   // wave uniform
-        return __builtin_bit_cast(f4v, __builtin_amdgcn_raw_buffer_load_b128(rx, tv ? vx : OOB, tv ? t * plane * 4 : 0, 0));
-    };
-    // ring of RING = 5 + PF frame registers with STATIC slots (the loop is unrolled RING steps): slot (k % RING) holds frame
-    // t0 - 2 + k.  No register moves between steps, so the wait before step j is for the load issued PF steps earlier and the
-    // PF - 1 younger loads (and the stores) stay in flight.
-    constexpr int RING = 5 + PF;
-    f4v R[RING];
-#pragma unroll
-    for (int k = 0; k < RING - 1; ++k) R[k] = ld(t0 - 2 + k);             // frames t0-2 .. t0+1+PF (slots 0 .. RING-2)
-    float st1 = 0.f, st2 = 0.f;
-    for (int tb = t0; tb < t1; tb += RING) {
-#pragma unroll
-        for (int j = 0; j < RING; ++j) {
-            const int t = tb + j;
-            const bool em = t < t1;                                        // wave uniform: steps beyond the chunk store nothing
-            R[(j + RING - 1) % RING] = ld(t + 2 + PF);                     // frame t-3's slot is free
-            f4v y = R[j % RING] * wk[0] + R[(j + 1) % RING] * wk[1] + R[(j + 2) % RING] * wk[2] + R[(j + 3) % RING] * wk[3] + R[(j + 4) % RING] * wk[4];
-            const int so = em ? t * plane * OES : 0;
-            if (BF) {                                                      // statistics over the rounded values the consumer reads
-                const bf4 yb = __builtin_convertvector(y, bf4);
-                __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u2v, yb), ry, em ? vy : OOB, so, 0);
-                y = __builtin_convertvector(yb, f4v);
-            } else {
-                cfn_bst128(__builtin_bit_cast(u4v_t5, y), ry, em ? vy : OOB, so);
-            }
-            const float m = (em && ok) ? 1.0f : 0.0f;
-            const f4v ym = y * m;
-            st1 += ym.x + ym.y + ym.z + ym.w;
-            st2 += ym.x * y.x + ym.y * y.y + ym.z * y.z + ym.w * y.w;
-        }
-    }
-    if (a.s1) {
-        const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-        st1 = cfn_wave_sum(st1); st2 = cfn_wave_sum(st2);
-        if (lane == 0) { sh[wave] = st1; sh[4 + wave] = st2; }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            cfn_add64(&a.s1[nc], (double)(sh[0] + sh[1] + sh[2] + sh[3]));
-            cfn_add64(&a.s2[nc], (double)(sh[4] + sh[5] + sh[6] + sh[7]));
-        }
-    }
-}
-
 // FLAT forward (round 3, tools/probe/t5_probe.hip): one thread = TO consecutive output frames of ONE float4 position, all
 // TO + 4 input frames requested up front, blocks in memory order, and each XCD walks one contiguous eighth of the items
 // (cfn_xcd_remap) so that the temporal halo re-reads of the neighbouring frame group hit ITS L2.  Measured on conv1_t
 // (8 x 24 x 256 x 112 x 112): marching kernel 5.0-5.2 TB/s (deeper look-ahead: +2 %), flat TO = 4 / 8: 5.66 / 5.77 TB/s; the same
 // flat kernel without the XCD remap 3.6 TB/s, with the block order scrambled inside each XCD 3.4-4.1 TB/s, TO = 1 (5 x L2 reads)
 // 4.0 TB/s: what this kernel responds to is the ORDER in which the chip walks memory and the L2 re-read factor, not the
-// look-ahead depth.  Ragged T / planes: surplus frames and threads get out-of-range offsets.
+// look-ahead depth.  Ragged T / planes: surplus frames and threads get out-of-range offsets (every global access is an UNCONDITIONAL
+// buffer load / store: with loads under `if (t < T)` the compiler can only wait with vmcnt(0), one HBM round trip per frame).
 template <int BF, int TO>
 __global__ __launch_bounds__(256) void dwt5_fwd_flat_kernel(const T5Args a) {
     typedef typename h16_types<BF ? BF : H16_BF16>::v4 bf4;
@@ -304,13 +236,12 @@ __global__ __launch_bounds__(256) void dwt5_fwd_flat_kernel(const T5Args a) {
     }
 }
 
-// -1 = not handled
+// -1 = not handled (planes that are not whole float4s, misaligned tensors, > 2 GiB per (n, c)): the caller runs dwt5_kernel
 template <int BF>
 static int t5_fwd_flat(T5Args& a, int N, hipStream_t st) {
-    static const int on = getenv("CFN_T5_FLAT") ? atoi(getenv("CFN_T5_FLAT")) : 1;       // 0: marching kernel, 4 / 8: force TO
-    if (!on || a.plane % 4 != 0 || (long)a.T * a.plane * 4 >= 0x7ffffff0L) return -1;
+    if (a.plane % 4 != 0 || (long)a.T * a.plane * 4 >= 0x7ffffff0L) return -1;
     if ((((uintptr_t)a.src | (uintptr_t)a.dst) & 15) != 0) return -1;
-    const int TO = on == 4 || on == 8 ? on : (a.T >= 32 ? 8 : 4);
+    const int TO = a.T >= 32 ? 8 : 4;
     const long per_nc = (long)cfn_cdiv(a.T, TO) * (a.plane / 4);
     const long bpn = cfn_cdiv(per_nc, 256L), blocks = bpn * N * a.C;
     if (blocks >= 0x7fffffffL || (long)N * a.C >= 0x7fffffffL) return -1;
@@ -318,96 +249,6 @@ static int t5_fwd_flat(T5Args& a, int N, hipStream_t st) {
     if (TO == 8) hipLaunchKernelGGL((dwt5_fwd_flat_kernel<BF, 8>), dim3((unsigned)blocks), dim3(256), 0, st, a);
     else hipLaunchKernelGGL((dwt5_fwd_flat_kernel<BF, 4>), dim3((unsigned)blocks), dim3(256), 0, st, a);
     return cfn_check_launch("dwconv_t5 flat forward");
-}
-
-// Backward, float4 rows: data gradient AND weight gradient in one march (gy, y, x read once, gx written once: 4 tensor
-// passes instead of the 6 of dwt5_kernel<T5_DGRAD> + <T5_WGRAD>), same streaming scheme as dwt5_fwd_stream_kernel: static
-// register rings, unconditional buffer accesses.  Ring slot (k % RING) holds frame t0 - 2 + k of g' = gy + gs + 2 y gq and of
-// x; a frame's raw gy / y land PF steps before it enters the 5-frame window and are combined in place at that step.
-//   gx(t)  = sum_k g'(t - 2 + k) w[4 - k]          gw[k] += sum_t g'(t) x(t - 2 + k)
-template <int BF, bool HASY>
-__global__ __launch_bounds__(256) void dwt5_bwd_fused_kernel(const T5Args a) {
-    typedef unsigned __attribute__((ext_vector_type(2))) u2v;
-    constexpr int PF = 3, RING = 5 + PF, OOB = 0x7ffffff0, GES = BF ? 2 : 4;
-    __shared__ float sh[20];
-    const long nc = blockIdx.y + (long)blockIdx.z * gridDim.y;
-    const int c = (int)(nc % a.C);
-    const int chunk = blockIdx.x % a.nchunks, pc = blockIdx.x / a.nchunks;
-    const int p = (pc * 256 + (int)threadIdx.x) * 4;
-    const bool ok = p < a.plane;
-    const int T = a.T, t0 = chunk * a.TT, t1 = min(t0 + a.TT, T);
-    const int plane = (int)a.plane;
-    // a.src = gy, a.src2 = y (output side: fp32 | bf16), a.yout = x (fp32), a.dst = gx (fp32), a.s1 = gw
-    __amdgpu_buffer_rsrc_t rg = cfn_rsrc(static_cast<const char*>(a.src) + nc * T * a.plane * GES, (unsigned)((long)T * plane * GES));
-    __amdgpu_buffer_rsrc_t ry = cfn_rsrc(static_cast<const char*>(HASY ? a.src2 : a.src) + nc * T * a.plane * GES, (unsigned)((long)T * plane * GES));
-    __amdgpu_buffer_rsrc_t rx = cfn_rsrc(static_cast<const float*>(a.yout) + nc * T * a.plane, (unsigned)((long)T * plane * 4));
-    __amdgpu_buffer_rsrc_t rd = cfn_rsrc(static_cast<float*>(a.dst) + nc * T * a.plane, (unsigned)((long)T * plane * 4));
-    const int vg = ok ? p * GES : OOB, vx = ok ? p * 4 : OOB;
-    float wk[5];
-#pragma unroll
-    for (int k = 0; k < 5; ++k) wk[k] = cfn_uni(a.w[c * 5 + 4 - k]);        // flipped taps
-    const float gsv = cfn_uni(a.gs ? (float)a.gs[nc] : 0.0f);
-    const float gqv = cfn_uni((HASY && a.gq) ? 2.0f * (float)a.gq[nc] : 0.0f);
-    auto wanted = [&](int t) { return t >= 0 && t < T && t <= t1 + 1; };     // wave uniform
-    auto ldg = [&](__amdgpu_buffer_rsrc_t r, int t) -> f4v {
-        const bool tv = wanted(t);
-        const int vo = tv ? vg : OOB, so = tv ? t * plane * GES : 0;
-        if (BF) {
-            const u2v u = __builtin_bit_cast(u2v, __builtin_amdgcn_raw_buffer_load_b64(r, vo, so, 0));
-            return (f4v){h16k_lo<BF ? BF : H16_BF16>(u.x), h16k_hi<BF ? BF : H16_BF16>(u.x), h16k_lo<BF ? BF : H16_BF16>(u.y), h16k_hi<BF ? BF : H16_BF16>(u.y)};
-        }
-        return __builtin_bit_cast(f4v, __builtin_amdgcn_raw_buffer_load_b128(r, vo, so, 0));
-    };
-    auto ldx = [&](int t) -> f4v {
-        const bool tv = wanted(t);
-        return __builtin_bit_cast(f4v, __builtin_amdgcn_raw_buffer_load_b128(rx, tv ? vx : OOB, tv ? t * plane * 4 : 0, 0));
-    };
-    auto fin = [&](f4v g, f4v y, int t) -> f4v {                            // g' of frame t (zero outside the clip)
-        const float m = (t >= 0 && t < T && ok) ? 1.0f : 0.0f;
-        f4v v = g + gsv;
-        if (HASY) v += y * gqv;
-        return v * m;
-    };
-    f4v RG[RING], RY[RING], RX[RING];
-#pragma unroll
-    for (int k = 0; k < RING - 1; ++k) {                                   // frames t0-2 .. t0+1+PF (slots 0 .. RING-2)
-        RG[k] = ldg(rg, t0 - 2 + k);
-        if (HASY) RY[k] = ldg(ry, t0 - 2 + k);
-        RX[k] = ldx(t0 - 2 + k);
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) RG[k] = fin(RG[k], HASY ? RY[k] : RG[k], t0 - 2 + k);   // frames t0-2 .. t0+1 enter the window now
-    f4v acc[5];
-#pragma unroll
-    for (int k = 0; k < 5; ++k) acc[k] = (f4v){0.f, 0.f, 0.f, 0.f};
-    for (int tb = t0; tb < t1; tb += RING) {
-#pragma unroll
-        for (int j = 0; j < RING; ++j) {
-            const int t = tb + j;
-            const bool em = t < t1;                                        // wave uniform: steps beyond the chunk contribute nothing
-            const int sn = (j + RING - 1) % RING;                          // frame t-3's slot is free: frame t + 2 + PF
-            RG[sn] = ldg(rg, t + 2 + PF);
-            if (HASY) RY[sn] = ldg(ry, t + 2 + PF);
-            RX[sn] = ldx(t + 2 + PF);
-            const int s4 = (j + 4) % RING;                                 // frame t+2 enters the window
-            RG[s4] = fin(RG[s4], HASY ? RY[s4] : RG[s4], t + 2);
-            const f4v gx = RG[j % RING] * wk[0] + RG[(j + 1) % RING] * wk[1] + RG[(j + 2) % RING] * wk[2] + RG[(j + 3) % RING] * wk[3] +
-                           RG[(j + 4) % RING] * wk[4];
-            cfn_bst128(__builtin_bit_cast(u4v_t5, gx), rd, em ? vx : OOB, em ? t * plane * 4 : 0);
-            const f4v gc = RG[(j + 2) % RING] * (em ? 1.0f : 0.0f);        // g'(t)
-#pragma unroll
-            for (int k = 0; k < 5; ++k) acc[k] += gc * RX[(j + k) % RING];
-        }
-    }
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-#pragma unroll
-    for (int k = 0; k < 5; ++k) {
-        const float v = cfn_wave_sum(acc[k].x + acc[k].y + acc[k].z + acc[k].w);
-        if (lane == 0) sh[k * 4 + wave] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < 5)
-        cfn_add64(&a.s1[c * 5 + threadIdx.x], (double)(sh[threadIdx.x * 4] + sh[threadIdx.x * 4 + 1] + sh[threadIdx.x * 4 + 2] + sh[threadIdx.x * 4 + 3]));
 }
 
 // FLAT fused backward (same mapping as dwt5_fwd_flat_kernel): one thread = TO consecutive frames of one float4 position.
@@ -489,43 +330,25 @@ __global__ __launch_bounds__(256) void dwt5_bwd_flat_kernel(const T5Args a) {
         cfn_add64(&a.s1[c * 5 + threadIdx.x], (double)(sh[threadIdx.x * 4] + sh[threadIdx.x * 4 + 1] + sh[threadIdx.x * 4 + 2] + sh[threadIdx.x * 4 + 3]));
 }
 
-// -1 = not handled (the plane is not a whole number of float4s): the caller runs the two separate kernels
+// -1 = not handled (planes that are not whole float4s, misaligned tensors, > 2 GiB per (n, c), a grid of 2^31 blocks): the caller runs
+// the two separate kernels
 template <int BF>
 static int t5_bwd_fused(const void* gy, const void* y, const double* gs, const double* gq, const float* w, const float* x, float* gx,
                         double* gw, int N, int C, int T, long plane, hipStream_t st) {
-    static const int on = getenv("CFN_T5_FUSED") ? atoi(getenv("CFN_T5_FUSED")) : 1;
-    if (!on || plane % 4 != 0 || (long)T * plane * 4 >= 0x7ffffff0L) return -1;
+    if (plane % 4 != 0 || (long)T * plane * 4 >= 0x7ffffff0L) return -1;
     if ((((uintptr_t)gy | (uintptr_t)x | (uintptr_t)gx | (uintptr_t)(y ? y : gy)) & 15) != 0) return -1;
     const bool hasy = y != nullptr && gq != nullptr;
     T5Args a = {};
     a.src = gy; a.src2 = hasy ? y : nullptr; a.gs = gs; a.gq = hasy ? gq : nullptr; a.w = w; a.yout = x; a.dst = gx; a.s1 = gw;
     a.C = C; a.T = T; a.plane = plane;
     const long NC = (long)N * C;
-    static const int flat = getenv("CFN_T5_FLAT_BWD") ? atoi(getenv("CFN_T5_FLAT_BWD")) : 8;    // 0: marching kernel, 4 / 8: frames per thread
-    if (flat == 4 || flat == 8) {
-        const long per_nc = (long)cfn_cdiv(T, flat) * (plane / 4);
-        const long bpn = cfn_cdiv(per_nc, 256L), blocks = bpn * NC;
-        if (blocks < 0x7fffffffL && NC < 0x7fffffffL) {
-            a.pchunks = (int)bpn;
-#define T5_FB(TOV) do { if (hasy) hipLaunchKernelGGL((dwt5_bwd_flat_kernel<BF, true, TOV>), dim3((unsigned)blocks), dim3(256), 0, st, a); \
-                        else hipLaunchKernelGGL((dwt5_bwd_flat_kernel<BF, false, TOV>), dim3((unsigned)blocks), dim3(256), 0, st, a); } while (0)
-            if (flat == 8) T5_FB(8); else T5_FB(4);
-#undef T5_FB
-            return cfn_check_launch("dwconv_t5 flat backward");
-        }
-    }
-    unsigned gy_, gz_;
-    CFN_REQUIRE(cfn_split_nc(NC, gy_, gz_), "dwconv_t5: N*C = %ld exceeds grid.y", NC);
-    a.pchunks = cfn_cdiv(plane, 1024L);
-    int TT = 64;
-    while (TT > 16 && NC * a.pchunks * cfn_cdiv(T, TT) < 2048) TT >>= 1;
-    if (TT > T) TT = T;
-    a.TT = TT;
-    a.nchunks = cfn_cdiv(T, TT);
-    dim3 grid((unsigned)(a.pchunks * a.nchunks), gy_, gz_);
-    if (hasy) hipLaunchKernelGGL((dwt5_bwd_fused_kernel<BF, true>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((dwt5_bwd_fused_kernel<BF, false>), grid, dim3(256), 0, st, a);
-    return cfn_check_launch("dwconv_t5 fused backward");
+    const long per_nc = (long)cfn_cdiv(T, 8) * (plane / 4);                       // 8 frames per thread
+    const long bpn = cfn_cdiv(per_nc, 256L), blocks = bpn * NC;
+    if (blocks >= 0x7fffffffL || NC >= 0x7fffffffL) return -1;
+    a.pchunks = (int)bpn;
+    if (hasy) hipLaunchKernelGGL((dwt5_bwd_flat_kernel<BF, true, 8>), dim3((unsigned)blocks), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((dwt5_bwd_flat_kernel<BF, false, 8>), dim3((unsigned)blocks), dim3(256), 0, st, a);
+    return cfn_check_launch("dwconv_t5 flat backward");
 }
 
 template <int MODE, int BF = 0>
@@ -546,11 +369,6 @@ static int t5_launch(T5Args& a, int N, hipStream_t st) {
     a.TT = TT;
     a.nchunks = cfn_cdiv(a.T, TT);
     dim3 grid((unsigned)(a.pchunks * a.nchunks), gy_, gz_);
-    static const int stream_on = getenv("CFN_T5_STREAM") ? atoi(getenv("CFN_T5_STREAM")) : 1;
-    if (MODE == T5_FWD && v4 && stream_on && (long)a.T * a.plane * 4 < 0x7ffffff0L) {
-        hipLaunchKernelGGL((dwt5_fwd_stream_kernel<BF>), grid, dim3(256), 0, st, a);
-        return cfn_check_launch("dwconv_t5");
-    }
     if (v4) hipLaunchKernelGGL((dwt5_kernel<MODE, 4, BF>), grid, dim3(256), 0, st, a);
     else hipLaunchKernelGGL((dwt5_kernel<MODE, 1, BF>), grid, dim3(256), 0, st, a);
     return cfn_check_launch("dwconv_t5");

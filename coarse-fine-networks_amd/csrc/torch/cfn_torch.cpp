@@ -113,7 +113,7 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> dwconv3d_backward(const Tensor& gy_, 
     double* b64 = pro ? a64 + N * C : nullptr;
     void* st = stream_of(x);
     const int n = (int)N, c = (int)C, t = (int)T, h = (int)H, wd = (int)W, a = (int)act, sd = (int)stride;
-#define CFN_DW_BWD(SFX, ET)                                                                                                                      \
+#define DW_BWD_CALL(SFX, ET)                                                                                                                      \
     do {                                                                                                                                         \
         const ET* gyp = (const ET*)gy.data_ptr(); const ET* yp = (const ET*)y.data_ptr(); const ET* xp = (const ET*)x.data_ptr(); ET* gxp = (ET*)gx.data_ptr(); \
         int rc = stride == 1 ? cfn_dwconv3d_bwd_fused##SFX(gyp, yp, dptr(gs64), dptr(gq64), w2.data_ptr<float>(), xp, dptr(A64), dptr(B64), a, gxp, a64, b64, \
@@ -127,10 +127,10 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> dwconv3d_backward(const Tensor& gy_, 
                "cfn_dwconv3d_bwd_weight");                                                                                                       \
         } else ok(rc, "cfn_dwconv3d_bwd_fused");                                                                                                 \
     } while (0)
-    if (x.scalar_type() == at::kFloat) CFN_DW_BWD(, float);
-    else if (x.scalar_type() == at::kBFloat16) CFN_DW_BWD(_bf16, unsigned short);
-    else CFN_DW_BWD(_f16, unsigned short);
-#undef CFN_DW_BWD
+    if (x.scalar_type() == at::kFloat) DW_BWD_CALL(, float);
+    else if (x.scalar_type() == at::kBFloat16) DW_BWD_CALL(_bf16, unsigned short);
+    else DW_BWD_CALL(_f16, unsigned short);
+#undef DW_BWD_CALL
     Tensor gwf = gw.to(at::kFloat).view(w.sizes());
     if (!pro) return {gx, gwf, at::zeros({1}, x.options().dtype(at::kFloat)), at::zeros({1}, x.options().dtype(at::kFloat))};
     return {gx, gwf, ab[0].to(at::kFloat), ab[1].to(at::kFloat)};

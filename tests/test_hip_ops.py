@@ -96,7 +96,7 @@ def test_dwconv3d(N, C, T, H, W, stride, act, pro):
 
 
 WAVE_CASES = [
-    # N, C, T, H, stride, act, prologue  -- the planes of the column-pair wave kernels (dwcp / dwcpb / dwcpb2)
+    # N, C, T, H, stride, act, prologue  -- the planes of the column-pair wave kernels (dwcp / dwcpbx / dwcpb2x)
     (2, 3, 1, 56, 1, 1, True), (1, 2, 2, 56, 1, 0, False), (1, 3, 61, 28, 1, 1, True), (2, 2, 7, 14, 1, 0, True),
     (1, 5, 4, 7, 1, 1, True), (1, 3, 3, 7, 1, 0, False),
     (1, 2, 1, 112, 2, 1, True), (2, 3, 5, 56, 2, 0, False), (1, 4, 58, 28, 2, 1, True),

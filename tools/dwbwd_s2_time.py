@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Backward time of the 14 -> 7 depthwise conv (432 channels, 8 clips x T = 256) through the autograd wrapper (events around backward()):
-    python tools/dwbwd_s2_time.py;  CFN_DW_FLATB=8 python tools/dwbwd_s2_time.py   # flat kernel off: dgrad + wgrad band kernels"""
+    python tools/dwbwd_s2_time.py                 # another build of the library: CFN_HIP_LIB=path/to/libcfn_hip_NAME.so"""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, 'coarse-fine-networks_amd'))

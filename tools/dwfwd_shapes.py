@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
 """Per-shape timing of the depthwise 3x3x3 forward entry point (the conv2 shapes of X3D-M at 224x224 input): HIP events around `--reps`
-launches per shape, algorithmic TB/s (input + output tensor once).  Same-box A/B of kernel generations through the environment:
+launches per shape, algorithmic TB/s (input + output tensor once).  Same-box A/B of kernel generations: build the other generation
+with tools/variant_lib.sh and select it with CFN_HIP_LIB (or compare two builds shape by shape with tools/ab_dwfwd.py):
 
-    CFN_DW_FLAT=0 python tools/dwfwd_shapes.py        # column-pair wave kernels (dwcp.hip) everywhere
-    python tools/dwfwd_shapes.py                      # flat kernels (dwflat.hip) where they are dispatched
+    python tools/dwfwd_shapes.py
+    CFN_HIP_LIB=coarse-fine-networks_amd/cfn_hip/variants/libcfn_hip_NAME.so python tools/dwfwd_shapes.py
     python tools/dwfwd_shapes.py --only 56 --frames 256 --batch 8"""
 import argparse
 import os

@@ -23,7 +23,7 @@ def per_kernel(path, counter):
     for r in rows:
         name = re.sub(r'\(.*', '', r['Kernel_Name']).replace('void ', '')
         if not (name.startswith('dw3d_kernel<0') or name.startswith('dwt5_kernel<0') or name.startswith('dw3d_small_fwd_kernel')
-                or name.startswith('dw3d_cp_fwd_kernel') or name.startswith('dwt5_fwd_stream_kernel') or name.startswith('dw3d_flat')
+                or name.startswith('dw3d_cp_fwd_kernel') or name.startswith('dw3d_flat')
                 or name.startswith('dwt5_fwd_flat_kernel')):
             continue
         v = float(r['Counter_Value']) * 1024.0

@@ -111,10 +111,16 @@ int cfn_pw_split_terms(int terms);
  * Returns the previous setting, < 0 on error.  Per process, bound to the device that is current at the call.  Host-side, no stream. */
 int cfn_deterministic(int on);
 
-/* Data AND weight gradient of a stride-1 pointwise conv with few channels in ONE pass (Cin, Cout <= 64 and not both > 32:
- * X3D layer 1, where the backward is HBM bound): gy, y, x leave HBM once for both products.  Same arguments and results
- * as cfn_pwconv_bwd_data_acc (stride 1) + cfn_pwconv_bwd_weight; x is always required.  Returns -1 WITHOUT launching
- * when the shape / alignment is not handled (callers then use the two separate entry points). */
+/* Data AND weight gradient of a stride-1 pointwise conv in ONE pass: gy, y, x leave HBM once for both products.  Windows taken
+ * (T*H*W a multiple of 4; gy, y, x 16-byte aligned; a prologue act of none / ReLU / swish):
+ *   fp32 kernel (pwfused.hip): Cin, Cout <= 64 and not both > 32 -- X3D layer 1 (24 -> 54, 54 -> 24), with or without a prologue;
+ *   split-bf16 kernel (pwfuseds.hip), no prologue: 33..64 -> 65..128 (layer 2 conv1, 48 -> 108), 16..32 -> 65..128 (its first
+ *   block, 24 -> 108), 65..128 -> 33..64; with CFN_PWF_SPLIT=2 the same windows with a prologue (layer 2 conv3, 108 -> 48);
+ *   layer-3 variant, no prologue: 33..96 -> 193..224 (layer 3 conv1, 96 -> 216, and its first block, 48 -> 216); with
+ *   CFN_PWF_L3E=1 also 193..224 -> 65..96 behind a prologue, without `acc` (layer 3 conv3, 216 -> 96).
+ * Same arguments and results as cfn_pwconv_bwd_data_acc (stride 1) + cfn_pwconv_bwd_weight (gw, gA, gB are added into); x is
+ * always required.  Returns -1 WITHOUT launching when the shape / alignment is not handled (callers then use the two separate
+ * entry points). */
 int cfn_pwconv_bwd_fused(const float* gy, const float* y, const double* gsum, const double* gsumsq, const float* w,
                          const float* x, const double* A, const double* B, int act, float* gx, double* gA, double* gB,
                          double* gw, int N, int Cin, int Cout, int T, int Hi, int Wi, const float* acc, int acc_stride,

@@ -1,6 +1,8 @@
 """GPU parity of every HIP kernel (through the C ABI / cfn_hip.ops) against plain fp32 torch on the
 CPU computing the same op, forward and backward.  Tolerances are written per test: fp32 kernels,
 different summation order => 1e-5 .. 1e-4 relative; index outputs bit-exact."""
+import os
+
 import numpy as np
 import pytest
 import torch
@@ -263,92 +265,153 @@ def test_pwconv_data_gradient_with_compact_shortcut_gradient(N, Cin, Cout, T, H,
     assert relerr(outs[0].double(), ref) <= 2e-6
 
 
+# ---- the one-pass pointwise backward (cfn_pwconv_bwd_fused): shared inputs, the two paths, and the fp64 reference of tests/pw_ref64.py ----
+PW_TERMS = {'all': ('gs', 'gq', 'gsc'), 'none': (), 'gs': ('gs',), 'gsc': ('gsc',)}      # which of gsum, gsumsq, gscale a call passes
+PW_CEIL = {'gx': 2e-6, 'gw': 3e-6, 'gA': 5e-6, 'gB': 5e-6}                                # relerr against fp64, unit-size cases
+PW_OUTS = ('gx', 'gA', 'gB', 'gw')
+
+
+def pw_bwd_inputs(N, Cin, Cout, T, H, W, act=None, acc_s=0, terms='all', edge=None):
+    """inputs of one cfn_pwconv_bwd_fused call: act None = no prologue (A = B = None); acc_s: stride of the compact shortcut gradient `acc`
+    (0 = none); terms: which of gs, gq, gscale are passed (PW_TERMS); edge 'relu0': x = 0 and B = 0 in every third channel, so A x + B == 0
+    exactly there; 'swish90': x scaled so that |A x + B| reaches ~90"""
+    f64 = lambda seed, *shape, scale=1.0: (rnd(seed, *shape) * scale).double().to(DEV)
+    on = PW_TERMS[terms]
+    c = dict(N=N, Cin=Cin, Cout=Cout, T=T, H=H, W=W, act=act, acc_s=acc_s)
+    c['gy'], c['y'], c['x'] = rnd(1, N, Cout, T, H, W).to(DEV), rnd(2, N, Cout, T, H, W).to(DEV), rnd(3, N, Cin, T, H, W).to(DEV)
+    c['w'] = (0.3 * rnd(4, Cout, Cin)).to(DEV)
+    c['gs'] = f64(5, N, Cout, scale=0.05) if 'gs' in on else None
+    c['gq'] = f64(6, N, Cout, scale=0.01) if 'gq' in on else None
+    c['gsc'] = 1.0 + f64(7, N, Cout, scale=0.3) if 'gsc' in on else None
+    c['A'] = c['B'] = None
+    if act is not None:
+        c['A'], c['B'] = 1.0 + f64(8, N, Cin, scale=0.2), f64(9, N, Cin, scale=0.2)
+    c['acc'] = rnd(10, N, Cin, T, (H - 1) // acc_s + 1, (W - 1) // acc_s + 1).to(DEV) if acc_s else None
+    if edge == 'relu0':
+        c['x'][:, ::3] = 0.0
+        c['B'][:, ::3] = 0.0
+    elif edge == 'swish90':
+        c['x'] = c['x'] * (90.0 / float((c['x'].double() * c['A'].view(N, Cin, 1, 1, 1)).abs().max()))
+    return c
+
+
+def pw_prefill(*shape):
+    """the known non-zero pattern gw / gA / gB start from where a test checks that the kernels add into them"""
+    n = int(np.prod(shape))
+    return ((torch.arange(n, dtype=torch.float64, device=DEV) % 7 - 3) * 0.25 + 0.125).view(shape)
+
+
+def pw_bwd_run(c, fused, prefill=False):
+    """(gx, gA, gB, gw) of cfn_pwconv_bwd_fused (fused; asserts that it did not decline) or of cfn_pwconv_bwd_data_acc +
+    cfn_pwconv_bwd_weight.  gx starts as NaN (every element must be written); gw, gA, gB start as zeros, or (prefill) as pw_prefill's
+    pattern, which is subtracted again from what the kernels added"""
+    import cfn_hip
+    N, Cin, Cout = c['N'], c['Cin'], c['Cout']
+    gx = torch.full_like(c['x'], float('nan'))
+    z = pw_prefill if prefill else (lambda *s: torch.zeros(*s, dtype=torch.float64, device=DEV))
+    gA = gB = None
+    if c['A'] is not None:
+        gA, gB = z(N, Cin), z(N, Cin)
+    gw = z(Cout, Cin)
+    a_, s_ = c['act'] or 0, c['acc_s'] or 1
+    args = (c['gy'], c['y'], c['gs'], c['gq'], c['w'], c['x'], c['A'], c['B'], a_, gx, gA, gB)
+    dims = (N, Cin, Cout, c['T'], c['H'], c['W'])
+    if fused:
+        assert cfn_hip.call_try('cfn_pwconv_bwd_fused', *args, gw, *dims, c['acc'], s_, c['gsc']) is True, 'declined'
+    else:
+        cfn_hip.call('cfn_pwconv_bwd_data_acc', *args, *dims, 1, c['acc'], s_, c['gsc'])
+        cfn_hip.call('cfn_pwconv_bwd_weight', c['gy'], c['y'], c['gs'], c['gq'], c['x'], c['A'], c['B'], a_, gw, *dims, 1, c['gsc'])
+    if prefill:
+        gw = gw - pw_prefill(Cout, Cin)
+        if gA is not None:
+            gA, gB = gA - pw_prefill(N, Cin), gB - pw_prefill(N, Cin)
+    return gx, gA, gB, gw
+
+
+def pw_ref(c, **drop):
+    """pw_ref64 on a case's inputs, as a dict of outputs; drop: arguments replaced (gs=None, acc=None, A=None + B=None, act=0, ...)"""
+    from pw_ref64 import pw_ref64
+    v = dict(c, **drop)
+    gx, gA, gB, gw = pw_ref64(v['gy'], v['y'], v['gs'], v['gq'], v['gsc'], v['w'], v['x'], v['A'], v['B'], v['act'] or 0, v['acc'],
+                              v['acc_s'] or 1)
+    return {k: r for k, r in zip(PW_OUTS, (gx, gA, gB, gw)) if r is not None}
+
+
+def pw_terms_visible(c, ref, ceil=PW_CEIL):
+    """term visibility: each term the case passes, removed from the fp64 reference, moves every output it feeds by >= 20 x that output's
+    ceiling -- a kernel that dropped or mis-scaled the term fails the case (and no input scale can shrink until a term hides in the bound)"""
+    every = PW_OUTS
+    drops = [('gs', dict(gs=None), every), ('gq*y', dict(gq=None), every), ('gscale', dict(gsc=None), every),
+             ('acc', dict(acc=None), ('gx', 'gA', 'gB')), ('prologue', dict(A=None, B=None), ('gx', 'gw')), ("act'", dict(act=0), every)]
+    present = {'gs': c['gs'] is not None, 'gq*y': c['gq'] is not None, 'gscale': c['gsc'] is not None, 'acc': c['acc'] is not None,
+               'prologue': c['A'] is not None, "act'": c['A'] is not None and c['act'] in (1, 2)}
+    for term, d, feeds in drops:
+        if not present[term]:
+            continue
+        moved = pw_ref(c, **d)
+        for k in feeds:
+            if k in ref:
+                assert relerr(moved[k], ref[k]) >= 20 * ceil[k], ('term not visible', term, k, relerr(moved[k], ref[k]))
+
+
+def pw_check_fp64(c, got, sep, record=None, ceil=PW_CEIL):
+    """every output of the one-pass kernel against pw_ref64: within its ceiling, and within 2 x the separate path's own error + 2e-7;
+    plus the term-visibility check of the case.  The errors {output: (one-pass, separate)} go to the junit report (record_property)"""
+    ref = pw_ref(c)
+    errs = {k: (relerr(g, ref[k]), relerr(s, ref[k])) for k, g, s in zip(PW_OUTS, got, sep) if k in ref}
+    if record is not None:
+        record('pw_fp64', repr(dict(Cin=c['Cin'], Cout=c['Cout'], act=c['act'], split=os.environ.get('CFN_PWF_SPLIT', '1'),
+                                    l3e=os.environ.get('CFN_PWF_L3E', '0'), errs=errs)))
+    for k, g in zip(PW_OUTS, got):
+        assert (g is None) == (k not in ref), k
+    for k, (e, es) in errs.items():
+        assert e <= ceil[k], ('fp64', k, e, es)
+        assert e <= 2.0 * es + 2e-7, ('fp64 vs separate', k, e, es)
+    pw_terms_visible(c, ref, ceil)
+
+
+def pw_env(monkeypatch, env):
+    """the routing switches of cfn_pwconv_bwd_fused at their product defaults, then `env` on top"""
+    for k in ('CFN_PWF_SPLIT', 'CFN_PWF_L3E', 'CFN_PWF_OFF'):
+        monkeypatch.delenv(k, raising=False)
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+
+
 @pytest.mark.parametrize('act', [None, 0, 1, 2])
 @pytest.mark.parametrize('cfg', [(2, 24, 54, 3, 8, 8, 0), (2, 54, 24, 2, 12, 12, 0), (1, 24, 24, 5, 6, 6, 2), (2, 64, 32, 1, 10, 10, 0),
                                  (1, 20, 12, 3, 6, 6, 2), (2, 24, 54, 4, 8, 8, 2), (1, 3, 7, 2, 4, 6, 0)])
-def test_pwconv_bwd_fused_matches_separate(cfg, act):
+def test_pwconv_bwd_fused_matches_separate(cfg, act, record_property):
     """cfn_pwconv_bwd_fused (one pass: data + weight gradient) against cfn_pwconv_bwd_data_acc + cfn_pwconv_bwd_weight on the
     same inputs: with / without prologue (act None = no A,B), statistics gradients, the tail scale `gscale` and the compact
-    shortcut gradient `acc` on its stride lattice; ragged position counts (not a multiple of the 64-position stage)."""
-    import cfn_hip
+    shortcut gradient `acc` on its stride lattice; ragged position counts (not a multiple of the 64-position stage).
+    Both against the fp64 reference (pw_check_fp64)."""
     N, Cin, Cout, T, H, W, acc_s = cfg
-    f64 = lambda seed, *shape, scale=1.0: (rnd(seed, *shape) * scale).double().to(DEV)
-    gy, y, x = rnd(1, N, Cout, T, H, W).to(DEV), rnd(2, N, Cout, T, H, W).to(DEV), rnd(3, N, Cin, T, H, W).to(DEV)
-    w = (0.3 * rnd(4, Cout, Cin)).to(DEV)
-    gs, gq, gsc = f64(5, N, Cout, scale=0.05), f64(6, N, Cout, scale=0.01), 1.0 + f64(7, N, Cout, scale=0.3)
-    A = B = None
-    if act is not None:
-        A, B = 1.0 + f64(8, N, Cin, scale=0.2), f64(9, N, Cin, scale=0.2)
-    acc = None
-    if acc_s:
-        acc = rnd(10, N, Cin, T, (H - 1) // acc_s + 1, (W - 1) // acc_s + 1).to(DEV)
-
-    def run(fused):
-        gx = torch.empty_like(x)
-        gA = gB = None
-        if A is not None:
-            gA, gB = (torch.zeros(N, Cin, dtype=torch.float64, device=DEV) for _ in range(2))
-        gw = torch.zeros(Cout, Cin, dtype=torch.float64, device=DEV)
-        a_ = 0 if act is None else act
-        if fused:
-            ok = cfn_hip.call_try('cfn_pwconv_bwd_fused', gy, y, gs, gq, w, x, A, B, a_, gx, gA, gB, gw, N, Cin, Cout, T, H, W,
-                                  acc, acc_s or 1, gsc)
-            assert ok, 'shape should be handled by the fused kernel'
-        else:
-            cfn_hip.call('cfn_pwconv_bwd_data_acc', gy, y, gs, gq, w, x, A, B, a_, gx, gA, gB, N, Cin, Cout, T, H, W, 1, acc,
-                         acc_s or 1, gsc)
-            cfn_hip.call('cfn_pwconv_bwd_weight', gy, y, gs, gq, x, A, B, a_, gw, N, Cin, Cout, T, H, W, 1, gsc)
-        return gx, gA, gB, gw
-
-    ref, got = run(False), run(True)
-    for name, r, g in zip(('gx', 'gA', 'gB', 'gw'), ref, got):
+    c = pw_bwd_inputs(N, Cin, Cout, T, H, W, act, acc_s)
+    ref, got = pw_bwd_run(c, False), pw_bwd_run(c, True)
+    for name, r, g in zip(PW_OUTS, ref, got):
         if r is not None:
             assert relerr(g, r) <= 2e-5, name
+    pw_check_fp64(c, got, ref, record_property)
 
 
 @pytest.mark.parametrize('act', [None, 0, 1, 2])
 @pytest.mark.parametrize('cfg', [(2, 48, 108, 3, 8, 8, 0), (2, 108, 48, 2, 12, 12, 0), (1, 48, 108, 5, 6, 6, 2), (1, 108, 48, 3, 10, 10, 2),
                                  (2, 40, 100, 1, 7, 8, 0), (1, 100, 40, 2, 6, 6, 0), (1, 64, 128, 9, 14, 14, 0), (1, 128, 64, 4, 28, 28, 0),
                                  (2, 24, 108, 3, 12, 12, 0), (1, 32, 128, 2, 10, 10, 2), (1, 16, 70, 5, 6, 6, 0)])
-def test_pwconv_bwd_fused_split_matches_separate(cfg, act, monkeypatch):
+def test_pwconv_bwd_fused_split_matches_separate(cfg, act, monkeypatch, record_property):
     """the layer-2 widths of cfn_pwconv_bwd_fused (csrc/pwfuseds.hip: one pass, split-bf16 matrix products) against the separate data /
-    weight gradient kernels: prologue / no prologue, statistics gradients, tail scale, compact shortcut gradient, ragged strips"""
-    import cfn_hip
-    monkeypatch.setenv('CFN_PWF_SPLIT', '2')
+    weight gradient kernels: prologue / no prologue, statistics gradients, tail scale, compact shortcut gradient, ragged strips; and
+    against the fp64 reference"""
+    pw_env(monkeypatch, {'CFN_PWF_SPLIT': '2'})
     N, Cin, Cout, T, H, W, acc_s = cfg
-    f64 = lambda seed, *shape, scale=1.0: (rnd(seed, *shape) * scale).double().to(DEV)
-    gy, y, x = rnd(1, N, Cout, T, H, W).to(DEV), rnd(2, N, Cout, T, H, W).to(DEV), rnd(3, N, Cin, T, H, W).to(DEV)
-    w = (0.3 * rnd(4, Cout, Cin)).to(DEV)
-    gs, gq, gsc = f64(5, N, Cout, scale=0.05), f64(6, N, Cout, scale=0.01), 1.0 + f64(7, N, Cout, scale=0.3)
-    A = B = None
-    if act is not None:
-        A, B = 1.0 + f64(8, N, Cin, scale=0.2), f64(9, N, Cin, scale=0.2)
-    acc = None
-    if acc_s:
-        acc = rnd(10, N, Cin, T, (H - 1) // acc_s + 1, (W - 1) // acc_s + 1).to(DEV)
-
-    def run(fused):
-        gx = torch.empty_like(x)
-        gA = gB = None
-        if A is not None:
-            gA, gB = (torch.zeros(N, Cin, dtype=torch.float64, device=DEV) for _ in range(2))
-        gw = torch.zeros(Cout, Cin, dtype=torch.float64, device=DEV)
-        a_ = 0 if act is None else act
-        if fused:
-            ok = cfn_hip.call_try('cfn_pwconv_bwd_fused', gy, y, gs, gq, w, x, A, B, a_, gx, gA, gB, gw, N, Cin, Cout, T, H, W,
-                                  acc, acc_s or 1, gsc)
-            assert ok, 'shape should be handled by the split fused kernel'
-        else:
-            cfn_hip.call('cfn_pwconv_bwd_data_acc', gy, y, gs, gq, w, x, A, B, a_, gx, gA, gB, N, Cin, Cout, T, H, W, 1, acc,
-                         acc_s or 1, gsc)
-            cfn_hip.call('cfn_pwconv_bwd_weight', gy, y, gs, gq, x, A, B, a_, gw, N, Cin, Cout, T, H, W, 1, gsc)
-        return gx, gA, gB, gw
-
-    ref, got = run(False), run(True)
-    for name, r, g in zip(('gx', 'gA', 'gB', 'gw'), ref, got):
+    c = pw_bwd_inputs(N, Cin, Cout, T, H, W, act, acc_s)
+    ref, got = pw_bwd_run(c, False), pw_bwd_run(c, True)
+    for name, r, g in zip(PW_OUTS, ref, got):
         if r is not None:
             assert relerr(g, r) <= 2e-5, (name, relerr(g, r))
-    again = run(True)                      # run-to-run bits (fp64 atomics of fp32 partials: exact)
+    pw_check_fp64(c, got, ref, record_property)
+    again = pw_bwd_run(c, True)            # run-to-run bits (fp64 atomics of fp32 partials: exact)
     for r, g in zip(got, again):
         if r is not None:
             assert torch.equal(r, g)
@@ -357,65 +420,208 @@ def test_pwconv_bwd_fused_split_matches_separate(cfg, act, monkeypatch):
 @pytest.mark.parametrize('two', [True, False])
 @pytest.mark.parametrize('cfg', [(1, 96, 216, 3, 14, 14, 0), (2, 96, 216, 2, 14, 14, 0), (1, 90, 200, 1, 10, 10, 0), (2, 72, 196, 5, 6, 6, 0), (1, 96, 216, 16, 14, 14, 0),
                                  (1, 48, 216, 3, 14, 14, 0), (2, 48, 216, 2, 28, 28, 2), (1, 40, 200, 2, 12, 12, 2), (1, 96, 216, 2, 14, 14, 2)])
-def test_pwconv_bwd_fused_split_layer3_matches_separate(cfg, two, monkeypatch):
+def test_pwconv_bwd_fused_split_layer3_matches_separate(cfg, two, monkeypatch, record_property):
     """the layer-3 variant of the one-pass backward (csrc/pwfuseds.hip, pw_bwd_fused_split3_kernel: W^T pre-split into a workspace and read out of L2, 6 weight-gradient
-    + 2 data-gradient waves, 32-position stages) against the separate kernels; no prologue (conv1 of a block), with / without the batch-norm terms"""
-    import cfn_hip
-    monkeypatch.setenv('CFN_PWF_SPLIT', '1')
+    + 2 data-gradient waves, 32-position stages) against the separate kernels and the fp64 reference; no prologue (conv1 of a block), with / without the batch-norm terms"""
+    pw_env(monkeypatch, {'CFN_PWF_SPLIT': '1'})
     N, Cin, Cout, T, H, W, acc_s = cfg
-    f64 = lambda seed, *shape, scale=1.0: (rnd(seed, *shape) * scale).double().to(DEV)
-    gy, y, x = rnd(1, N, Cout, T, H, W).to(DEV), rnd(2, N, Cout, T, H, W).to(DEV), rnd(3, N, Cin, T, H, W).to(DEV)
-    w = (0.3 * rnd(4, Cout, Cin)).to(DEV)
-    gs, gq, gsc = (f64(5, N, Cout, scale=0.05), f64(6, N, Cout, scale=0.01), 1.0 + f64(7, N, Cout, scale=0.3)) if two else (None, None, None)
-    acc = rnd(10, N, Cin, T, (H - 1) // acc_s + 1, (W - 1) // acc_s + 1).to(DEV) if acc_s else None      # compact shortcut gradient of a stage-first block
-
-    def run(fused):
-        gx = torch.full_like(x, float('nan'))
-        gw = torch.zeros(Cout, Cin, dtype=torch.float64, device=DEV)
-        if fused:
-            ok = cfn_hip.call_try('cfn_pwconv_bwd_fused', gy, y, gs, gq, w, x, None, None, 0, gx, None, None, gw, N, Cin, Cout, T, H, W, acc, acc_s or 1, gsc)
-            assert ok, 'shape should be handled by the layer-3 split fused kernel'
-        else:
-            cfn_hip.call('cfn_pwconv_bwd_data_acc', gy, y, gs, gq, w, x, None, None, 0, gx, None, None, N, Cin, Cout, T, H, W, 1, acc, acc_s or 1, gsc)
-            cfn_hip.call('cfn_pwconv_bwd_weight', gy, y, gs, gq, x, None, None, 0, gw, N, Cin, Cout, T, H, W, 1, gsc)
-        return gx, gw
-
-    ref, got, again = run(False), run(True), run(True)
-    for name, r, g, g2 in zip(('gx', 'gw'), ref, got, again):
+    c = pw_bwd_inputs(N, Cin, Cout, T, H, W, None, acc_s, 'all' if two else 'none')
+    ref, got, again = pw_bwd_run(c, False), pw_bwd_run(c, True), pw_bwd_run(c, True)
+    for name, r, g, g2 in zip(PW_OUTS, ref, got, again):
+        if r is None:
+            continue
         assert relerr(g, r) <= 2e-5, (name, relerr(g, r))
         assert torch.equal(g, g2), name                # run-to-run bits
+    pw_check_fp64(c, got, ref, record_property)
 
 
 @pytest.mark.parametrize('act', [0, 1, 2])
 @pytest.mark.parametrize('cfg', [(1, 216, 96, 3, 14, 14), (2, 216, 96, 2, 14, 14), (1, 200, 90, 1, 10, 10), (2, 196, 72, 5, 6, 6), (1, 216, 96, 16, 14, 14)])
-def test_pwconv_bwd_fused_split_layer3_conv3_matches_separate(cfg, act, monkeypatch):
+def test_pwconv_bwd_fused_split_layer3_conv3_matches_separate(cfg, act, monkeypatch, record_property):
     """the conv3 side of the layer-3 one-pass backward (pw_bwd_fused_split3e_kernel: 216 -> 96 behind a prologue; act' epilogue and the statistics of 216 channels in the
-    data-gradient waves) against the separate kernels: gx, gA, gB, gw; launched twice: identical bits"""
-    import cfn_hip
-    monkeypatch.setenv('CFN_PWF_L3E', '1')
+    data-gradient waves) against the separate kernels and the fp64 reference: gx, gA, gB, gw; launched twice: identical bits"""
+    pw_env(monkeypatch, {'CFN_PWF_L3E': '1'})
     N, Cin, Cout, T, H, W = cfg
-    f64 = lambda seed, *shape, scale=1.0: (rnd(seed, *shape) * scale).double().to(DEV)
-    gy, y, x = rnd(1, N, Cout, T, H, W).to(DEV), rnd(2, N, Cout, T, H, W).to(DEV), rnd(3, N, Cin, T, H, W).to(DEV)
-    w = (0.3 * rnd(4, Cout, Cin)).to(DEV)
-    gs, gq, gsc = f64(5, N, Cout, scale=0.05), f64(6, N, Cout, scale=0.01), 1.0 + f64(7, N, Cout, scale=0.3)
-    A, B = 1.0 + f64(8, N, Cin, scale=0.2), f64(9, N, Cin, scale=0.2)
-
-    def run(fused):
-        gx = torch.full_like(x, float('nan'))
-        gA, gB = (torch.zeros(N, Cin, dtype=torch.float64, device=DEV) for _ in range(2))
-        gw = torch.zeros(Cout, Cin, dtype=torch.float64, device=DEV)
-        if fused:
-            ok = cfn_hip.call_try('cfn_pwconv_bwd_fused', gy, y, gs, gq, w, x, A, B, act, gx, gA, gB, gw, N, Cin, Cout, T, H, W, None, 1, gsc)
-            assert ok, 'shape should be handled by the layer-3 conv3 split fused kernel'
-        else:
-            cfn_hip.call('cfn_pwconv_bwd_data_acc', gy, y, gs, gq, w, x, A, B, act, gx, gA, gB, N, Cin, Cout, T, H, W, 1, None, 1, gsc)
-            cfn_hip.call('cfn_pwconv_bwd_weight', gy, y, gs, gq, x, A, B, act, gw, N, Cin, Cout, T, H, W, 1, gsc)
-        return gx, gA, gB, gw
-
-    ref, got, again = run(False), run(True), run(True)
-    for name, r, g, g2 in zip(('gx', 'gA', 'gB', 'gw'), ref, got, again):
+    c = pw_bwd_inputs(N, Cin, Cout, T, H, W, act)
+    ref, got, again = pw_bwd_run(c, False), pw_bwd_run(c, True), pw_bwd_run(c, True)
+    for name, r, g, g2 in zip(PW_OUTS, ref, got, again):
         assert relerr(g, r) <= 2e-5, (name, relerr(g, r))
         assert torch.equal(g, g2), name
+    pw_check_fp64(c, got, ref, record_property)
+
+
+# the kernel instances cfn_pwconv_bwd_fused launches: route -> (switches, Cin, Cout, act, takes `acc`).  The last four are opt-in routes.
+PW_ROUTES = {
+    'pf21_relu': ({}, 24, 54, 1, True),                # pw_bwd_fused_kernel<2,1,RELU>: layer 1 block 0 conv1
+    'pf21': ({}, 24, 54, None, True),                  # <2,1,-1>: layer 1 blocks 1+ conv1
+    'pf12_swish': ({}, 54, 24, 2, True),               # <1,2,SWISH>: layer 1 conv3
+    'pf11': ({}, 20, 12, 0, True),                     # <1,1,NONE>: Cin, Cout <= 32
+    'pfs42': ({}, 48, 108, None, True),                # pw_bwd_fused_split_kernel<4,2,-1>: layer 2 conv1
+    'pfs41': ({}, 24, 108, None, True),                # <4,1,-1>: layer 2 block 0 conv1
+    'pf3_73': ({}, 96, 216, None, True),               # pw_bwd_fused_split3_kernel<7,3>: layer 3 conv1
+    'pf3_72': ({}, 48, 216, None, True),               # <7,2>: layer 3 block 0 conv1
+    'pfs42_relu': ({'CFN_PWF_SPLIT': '2'}, 48, 108, 1, True),
+    'pfs41_none': ({'CFN_PWF_SPLIT': '2'}, 24, 108, 0, True),
+    'pfs24_swish': ({'CFN_PWF_SPLIT': '2'}, 108, 48, 2, True),
+    'pf3e_swish': ({'CFN_PWF_L3E': '1'}, 216, 96, 2, False),   # pw_bwd_fused_split3e_kernel<3,7,SWISH>: layer 3 conv3
+}
+
+
+def _pw_fp64_case(monkeypatch, record, env, N, Cin, Cout, T, H, W, act, acc_s, terms, edge=None):
+    pw_env(monkeypatch, env)
+    c = pw_bwd_inputs(N, Cin, Cout, T, H, W, act, acc_s, terms, edge)
+    got = pw_bwd_run(c, True, prefill=True)
+    assert not torch.isnan(got[0]).any(), 'gx not written everywhere'
+    pw_check_fp64(c, got, pw_bwd_run(c, False), record)
+
+
+PW_OPTIONS = [(route, terms, acc_s) for route, (_, _, _, _, takes_acc) in PW_ROUTES.items() for terms in PW_TERMS for acc_s in ((0, 2) if takes_acc else (0,))]
+
+
+@pytest.mark.parametrize('route,terms,acc_s', PW_OPTIONS)
+def test_pwconv_bwd_fused_fp64_optional_arguments(route, terms, acc_s, monkeypatch, record_property):
+    """every kernel instance of cfn_pwconv_bwd_fused with each combination of the optional arguments (gs, gq, gscale: all / none -- the eval-mode
+    and frozen-BN backward -- / gs only / gscale only; with and without the compact shortcut gradient where the route takes it) against the fp64
+    reference.  gw, gA, gB start from a non-zero pattern (the kernels add into them), gx from NaN"""
+    env, Cin, Cout, act, _ = PW_ROUTES[route]
+    _pw_fp64_case(monkeypatch, record_property, env, 2, Cin, Cout, 2, 10, 10, act, acc_s, terms)
+
+
+# the channel corners of every window the entry point takes: (window, switches, prologues, takes `acc`, [(Cin, Cout), ...]); the option
+# combinations, the prologues and `acc` cycle over a window's corners
+PW_WINDOWS = [
+    ('wide_m', {}, (None,) * 4, True, [(33, 65), (33, 128), (64, 65), (64, 128)]),                  # split <4,2>
+    ('thin_k', {}, (None,) * 4, True, [(16, 65), (16, 128), (32, 65), (32, 128)]),                  # split <4,1>
+    ('split3_72', {}, (None,) * 4, True, [(33, 193), (33, 224), (64, 193), (64, 224)]),
+    ('split3_73', {}, (None,) * 4, True, [(65, 193), (65, 224), (96, 193), (96, 224)]),
+    ('split3e', {'CFN_PWF_L3E': '1'}, (1, 2, 0, 2), False, [(193, 65), (193, 96), (224, 65), (224, 96)]),
+    ('wide_k', {'CFN_PWF_SPLIT': '2'}, (2, 1, 0, 2), True, [(65, 33), (65, 64), (128, 33), (128, 64)]),     # split <2,4>
+    ('fp32_21', {}, (1, None, 2, 0), True, [(32, 64), (3, 33), (32, 33), (1, 64)]),
+    ('fp32_12', {}, (2, None, 1, 0), True, [(64, 32), (33, 3), (33, 32), (64, 1)]),
+    ('fp32_11', {}, (0, None, 1, 2), True, [(32, 32), (1, 1), (3, 32), (32, 2)]),
+]
+PW_CORNERS = [('%s-%dx%d' % (name, ci, co), env, acts[i], ci, co, list(PW_TERMS)[i], 2 if takes_acc and i in (1, 2) else 0)
+              for name, env, acts, takes_acc, corners in PW_WINDOWS for i, (ci, co) in enumerate(corners)]
+
+
+@pytest.mark.parametrize('case', PW_CORNERS, ids=[c[0] for c in PW_CORNERS])
+def test_pwconv_bwd_fused_fp64_channel_corners(case, monkeypatch, record_property):
+    """the lowest and highest Cin and Cout of every window of cfn_pwconv_bwd_fused (pwfs_try_launch's wide_m / thin_k / wide_k / layer-3
+    windows, the fp32 kernel's three), each option combination once per window, against the fp64 reference"""
+    _, env, act, Cin, Cout, terms, acc_s = case
+    _pw_fp64_case(monkeypatch, record_property, env, 2, Cin, Cout, 1, 6, 10, act, acc_s, terms)
+
+
+# position and batch edges: stage = 64 positions (pwfused / pwfuseds), 32 (split3); a strip = 4 stages at these batch sizes
+def _pos_cases(route, stage, acc_s):
+    qs = [(1, 2, 2), (1, 6, (stage - 4) // 6) if (stage - 4) % 6 == 0 else (1, 4, (stage - 4) // 4), (1, 8, stage // 8), (1, 4, stage // 4 + 1),
+          (1, 4, 3 * stage + 1)]
+    return [(route, n, t, h, w, acc_s) for (t, h, w), n in zip(qs, (1, 3, 8, 1, 3))]
+
+
+PW_POSITIONS = (_pos_cases('pf21_relu', 64, 2) + _pos_cases('pf12_swish', 64, 0) + _pos_cases('pfs42', 64, 0) + _pos_cases('pfs41', 64, 2)
+                + _pos_cases('pf3_73', 32, 0) + _pos_cases('pf3_72', 32, 2) + _pos_cases('pfs24_swish', 64, 0) + _pos_cases('pf3e_swish', 32, 0)
+                # more samples than the route's workgroup target (512 / 256 split, 1536 / 1024 fp32): one strip per sample, the want < 1 clamp
+                + [('pfs42', 520, 1, 2, 2, 0), ('pf3_73', 520, 1, 2, 2, 0), ('pf21', 1600, 1, 2, 2, 0), ('pf12_swish', 1100, 1, 2, 2, 0)])
+
+
+@pytest.mark.parametrize('case', PW_POSITIONS)
+def test_pwconv_bwd_fused_fp64_position_edges(case, monkeypatch, record_property):
+    """T*H*W in {4, stage - 4, stage, stage + 4, several strips + 4}, N in {1, 3, 8}, and N beyond the workgroup target, against the fp64
+    reference"""
+    route, N, T, H, W, acc_s = case
+    env, Cin, Cout, act, _ = PW_ROUTES[route]
+    _pw_fp64_case(monkeypatch, record_property, env, N, Cin, Cout, T, H, W, act, acc_s, 'all')
+
+
+@pytest.mark.parametrize('edge', ['relu0', 'swish90'])
+@pytest.mark.parametrize('route', ['pf21_relu', 'pf12_swish', 'pfs42_relu', 'pfs24_swish', 'pf3e_swish'])
+def test_pwconv_bwd_fused_fp64_prologue_edges(route, edge, monkeypatch, record_property):
+    """ReLU prologue with A x + B == 0 exactly in some channels (act'(0) = 0 on both sides) and swish with |A x + B| up to ~90 (no inf / NaN),
+    against the fp64 reference"""
+    env, Cin, Cout, _, takes_acc = PW_ROUTES[route]
+    act = 1 if edge == 'relu0' else 2
+    _pw_fp64_case(monkeypatch, record_property, env, 2, Cin, Cout, 2, 6, 6, act, 2 if takes_acc else 0, 'all', edge)
+
+
+def _misaligned(t):
+    """a copy of t that starts 4 bytes past a 16-byte boundary (a view at element offset 1)"""
+    buf = torch.empty(t.numel() + 4, dtype=t.dtype, device=t.device)
+    v = buf[1:1 + t.numel()].view(t.shape)
+    v.copy_(t)
+    assert v.data_ptr() % 16 == 4
+    return v
+
+
+# shapes cfn_pwconv_bwd_fused must decline: (id, switches, N, Cin, Cout, T, H, W, act, acc_s, misaligned tensor)
+PW_DECLINES = [
+    ('q%4-fp32', {}, 1, 24, 54, 65, 7, 7, None, 0, None),              # the coarse stream's 65 x 7 x 7
+    ('q%4-fp32-relu', {}, 1, 24, 54, 65, 7, 7, 1, 2, None),
+    ('q%4-split', {}, 1, 48, 108, 65, 7, 7, None, 0, None),
+    ('q%4-split-pro', {'CFN_PWF_SPLIT': '2'}, 1, 108, 48, 65, 7, 7, 2, 0, None),
+    ('q%4-l3', {}, 1, 96, 216, 65, 7, 7, None, 0, None),
+    ('q%4-l3e', {'CFN_PWF_L3E': '1'}, 1, 216, 96, 65, 7, 7, 2, 0, None),
+    ('gy+4-fp32', {}, 2, 24, 54, 2, 8, 8, 1, 0, 'gy'),
+    ('x+4-fp32', {}, 2, 24, 54, 2, 8, 8, 1, 0, 'x'),
+    ('y+4-fp32', {}, 2, 54, 24, 2, 8, 8, 2, 0, 'y'),
+    ('gy+4-split', {}, 2, 48, 108, 2, 8, 8, None, 0, 'gy'),
+    ('x+4-split', {}, 2, 24, 108, 2, 8, 8, None, 0, 'x'),
+    ('y+4-split', {'CFN_PWF_SPLIT': '2'}, 2, 108, 48, 2, 8, 8, 2, 0, 'y'),
+    ('gy+4-l3', {}, 1, 96, 216, 2, 8, 8, None, 0, 'gy'),
+    ('x+4-l3', {}, 1, 48, 216, 2, 8, 8, None, 0, 'x'),
+    ('y+4-l3', {}, 1, 96, 216, 2, 8, 8, None, 0, 'y'),
+    ('y+4-l3e', {'CFN_PWF_L3E': '1'}, 1, 216, 96, 2, 8, 8, 2, 0, 'y'),
+    ('sigmoid-fp32', {}, 2, 24, 54, 2, 8, 8, 3, 0, None),
+    ('sigmoid-split', {'CFN_PWF_SPLIT': '2'}, 2, 48, 108, 2, 8, 8, 3, 0, None),
+    ('sigmoid-l3e', {'CFN_PWF_L3E': '1'}, 1, 216, 96, 2, 8, 8, 3, 0, None),
+    ('l2-prologue-default', {}, 2, 48, 108, 2, 8, 8, 1, 0, None),       # layer-2 shapes with a prologue: only under CFN_PWF_SPLIT=2
+    ('l2-conv3-default', {}, 2, 108, 48, 2, 8, 8, 2, 0, None),
+    ('l3-prologue', {}, 1, 96, 216, 2, 8, 8, 1, 0, None),
+    ('l3e-acc', {'CFN_PWF_L3E': '1'}, 1, 216, 96, 2, 8, 8, 2, 2, None),
+    ('l3e-default', {}, 1, 216, 96, 2, 8, 8, 2, 0, None),
+    ('33x33', {}, 2, 33, 33, 2, 8, 8, None, 0, None),                  # fp32: not both > 32
+    ('65x16', {}, 2, 65, 16, 2, 8, 8, None, 0, None),
+    ('16x65-pro', {}, 2, 16, 65, 2, 8, 8, 1, 0, None),
+    ('15x100', {}, 2, 15, 100, 2, 8, 8, None, 0, None),                # thin_k starts at 16
+    ('33x129', {}, 2, 33, 129, 2, 8, 8, None, 0, None),                # wide_m ends at 128
+    ('65x65', {}, 2, 65, 65, 2, 8, 8, None, 0, None),
+    ('129x48', {'CFN_PWF_SPLIT': '2'}, 2, 129, 48, 2, 8, 8, 2, 0, None),   # wide_k ends at 128
+    ('65x32', {'CFN_PWF_SPLIT': '2'}, 2, 65, 32, 2, 8, 8, 2, 0, None),     # wide_k starts above 32
+    ('32x216', {}, 1, 32, 216, 2, 8, 8, None, 0, None),                # split3 starts above 32
+    ('97x216', {}, 1, 97, 216, 2, 8, 8, None, 0, None),
+    ('96x192', {}, 1, 96, 192, 2, 8, 8, None, 0, None),
+    ('96x225', {}, 1, 96, 225, 2, 8, 8, None, 0, None),
+    ('192x96', {'CFN_PWF_L3E': '1'}, 1, 192, 96, 2, 8, 8, 2, 0, None),
+    ('225x96', {'CFN_PWF_L3E': '1'}, 1, 225, 96, 2, 8, 8, 2, 0, None),
+    ('216x64', {'CFN_PWF_L3E': '1'}, 1, 216, 64, 2, 8, 8, 2, 0, None),
+    ('216x97', {'CFN_PWF_L3E': '1'}, 1, 216, 97, 2, 8, 8, 2, 0, None),
+]
+
+
+@pytest.mark.parametrize('case', PW_DECLINES, ids=[d[0] for d in PW_DECLINES])
+def test_pwconv_bwd_fused_declines_without_launching(case, monkeypatch):
+    """a shape / alignment / activation cfn_pwconv_bwd_fused does not take returns -1 and launches nothing: gx still NaN bit for bit, gw, gA, gB
+    still their pre-fill (ops.py then runs the separate kernels, which would add on top of anything a declined call had added)"""
+    import cfn_hip
+    _, env, N, Cin, Cout, T, H, W, act, acc_s, mis = case
+    pw_env(monkeypatch, env)
+    c = pw_bwd_inputs(N, Cin, Cout, T, H, W, act if act != 3 else 0, acc_s)
+    if mis:
+        c[mis] = _misaligned(c[mis])
+    gx = torch.full_like(c['x'], float('nan'))
+    nan_bits = gx.view(torch.int32).clone()
+    gA = gB = None
+    if c['A'] is not None:
+        gA, gB = pw_prefill(N, Cin), pw_prefill(N, Cin)
+    gw = pw_prefill(Cout, Cin)
+    ok = cfn_hip.call_try('cfn_pwconv_bwd_fused', c['gy'], c['y'], c['gs'], c['gq'], c['w'], c['x'], c['A'], c['B'], act or 0, gx, gA, gB, gw,
+                          N, Cin, Cout, T, H, W, c['acc'], acc_s or 1, c['gsc'])
+    torch.cuda.synchronize()
+    assert ok is False
+    assert torch.equal(gx.view(torch.int32), nan_bits)
+    assert torch.equal(gw, pw_prefill(Cout, Cin))
+    if gA is not None:
+        assert torch.equal(gA, pw_prefill(N, Cin)) and torch.equal(gB, pw_prefill(N, Cin))
 
 
 @pytest.mark.parametrize('cfg', [(4, 48, 108, 16, 28, 28, 1), (2, 24, 108, 8, 56, 56, None), (8, 96, 216, 8, 14, 14, None), (2, 48, 216, 8, 28, 28, None), (2, 108, 48, 8, 28, 28, 2)])

@@ -41,7 +41,7 @@ def header_prototypes(path=HEADER):
                     at.append(ctypes.c_void_p)
                     base = a.replace('const', '').split('*')[0].strip()
                     dt[-1] = {'float': torch.float32, 'double': torch.float64, 'long': torch.int64, 'int': torch.int32,
-                               'unsigned short': torch.bfloat16}.get(base)
+                               'unsigned short': torch.bfloat16, 'unsigned char': torch.uint8}.get(base)
                 elif a.startswith('long'):
                     at.append(ctypes.c_long)
                 elif a.startswith('double'):

@@ -55,9 +55,15 @@ class GraphedStep(object):
         self._graphs = {}       # shape signature -> (graph, static inputs, static outputs, lr signature)
 
     @staticmethod
+    def _is_nt(a):
+        """a namedtuple of tensors (cfn_hip.u8clips.U8Clips: uint8 frames + per-clip lengths)"""
+        return isinstance(a, tuple) and hasattr(a, '_fields')
+
+    @staticmethod
     def _sig(args):
         return tuple((tuple(a.shape), a.dtype, a.device) if torch.is_tensor(a) else
-                     tuple(sorted((k, tuple(v.shape)) for k, v in a.items())) if isinstance(a, dict) else a for a in args)
+                     tuple(sorted((k, tuple(v.shape)) for k, v in a.items())) if isinstance(a, dict) else
+                     (type(a).__name__,) + GraphedStep._sig(tuple(a)) if GraphedStep._is_nt(a) else a for a in args)
 
     @staticmethod
     def _clone(a):
@@ -65,6 +71,8 @@ class GraphedStep(object):
             return a.clone()
         if isinstance(a, dict):
             return {k: v.clone() for k, v in a.items()}
+        if GraphedStep._is_nt(a):
+            return type(a)(*[GraphedStep._clone(v) for v in a])
         return a
 
     @staticmethod
@@ -74,13 +82,17 @@ class GraphedStep(object):
         elif isinstance(dst, dict):
             for k in dst:
                 dst[k].copy_(src[k], non_blocking=True)
+        elif GraphedStep._is_nt(dst):
+            for d, s in zip(dst, src):
+                GraphedStep._copy(d, s)
 
     def _side_stream(self, args):
         """Autograd remembers the stream an AccumulateGrad node was created on and synchronises with it in every later
         backward; a node born on the default stream would drag the (uncapturable) default stream into the capture.  So the
         eager first steps run on the same side stream the captures use."""
         if self.stream is None:
-            dev = next(a.device for a in args if torch.is_tensor(a)) if any(torch.is_tensor(a) for a in args) else None
+            has_dev = lambda a: torch.is_tensor(a) or (self._is_nt(a) and hasattr(a, 'device'))
+            dev = next(a.device for a in args if has_dev(a)) if any(has_dev(a) for a in args) else None
             self.stream = torch.cuda.Stream(device=dev)
         return self.stream
 

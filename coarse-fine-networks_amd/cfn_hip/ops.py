@@ -587,6 +587,71 @@ def stem_conv(x, w):
     return _StemConv.apply(x, w)
 
 
+# ---- uint8 frames: normalised on the GPU (csrc/stem_u8.hip) -------------------------------------------------------------------
+from .u8clips import clip_lut  # noqa: E402,F401  (host-built (3, 256) table, the reference's op order)
+
+
+def _u8_args(frames, lengths, lut):
+    """frames (N, T, H, W, 3) uint8, lengths (N) int32 or None, lut (3, 256) fp32: checked here, the C ABI sees pointers only"""
+    if frames.dtype != torch.uint8 or frames.dim() != 5 or frames.shape[4] != 3:
+        raise RuntimeError('uint8 frames of shape (N, T, H, W, 3) expected, got %s %s' % (frames.dtype, tuple(frames.shape)))
+    if lut.dtype != torch.float32 or lut.numel() != 3 * 256:
+        raise RuntimeError('a (3, 256) fp32 table expected (ops.clip_lut), got %s %s' % (lut.dtype, tuple(lut.shape)))
+    if lengths is not None:
+        if lengths.numel() != frames.shape[0]:
+            raise RuntimeError('one length per clip expected: %d clips, lengths %s' % (frames.shape[0], tuple(lengths.shape)))
+        lengths = lengths.to(torch.int32).contiguous()
+    return frames.contiguous(), lengths, lut.contiguous()
+
+
+def clip_u8_to_f32(frames, lut, lengths=None):
+    """(N, T, H, W, 3) uint8 -> the normalised fp32 clip (N, 3, T, H, W); frames t >= lengths[n] are zero"""
+    frames, lengths, lut = _u8_args(frames, lengths, lut)
+    N, T, H, W, _ = frames.shape
+    x = torch.empty(N, 3, T, H, W, dtype=torch.float32, device=frames.device)
+    call('cfn_clip_u8_to_f32', frames, lut, lengths, x, N, T, H, W)
+    return x
+
+
+class _StemConvU8(Function):
+    """conv1_s on uint8 frames.  Shapes the fused kernels decline run as convert + the fp32 entry point."""
+
+    @staticmethod
+    def forward(ctx, frames, lengths, lut, w):
+        frames, lengths, lut = _u8_args(frames, lengths, lut)
+        N, T, H, W, Ci = frames.shape
+        Co = w.shape[0]
+        Ho, Wo = (H + 2 - 3) // 2 + 1, (W + 2 - 3) // 2 + 1
+        y = torch.empty(N, Co, T, Ho, Wo, dtype=torch.float32, device=frames.device)
+        w2 = w.reshape(Co, Ci * 9).contiguous()
+        if not call_try('cfn_stem_conv_u8_fwd', frames, lut, lengths, w2, y, N, Ci, Co, T, H, W):
+            call('cfn_stem_conv_fwd', clip_u8_to_f32(frames, lut, lengths), w2, y, N, Ci, Co, T, H, W)
+        ctx.save_for_backward(frames, lengths, lut)
+        ctx.wshape = tuple(w.shape)
+        ctx.wparam = w
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        frames, lengths, lut = ctx.saved_tensors
+        N, T, H, W, Ci = frames.shape
+        Co = ctx.wshape[0]
+        gw = None
+        if ctx.needs_input_grad[3]:
+            g64, fin = _gw_buffers(ctx.wparam, Co, Ci * 9, frames.device)
+            gy = gy.contiguous()
+            if not call_try('cfn_stem_conv_u8_bwd_weight', gy, frames, lut, lengths, g64, N, Ci, Co, T, H, W):
+                call('cfn_stem_conv_bwd_weight', gy, clip_u8_to_f32(frames, lut, lengths), g64, N, Ci, Co, T, H, W)
+            gw = fin()
+        return None, None, None, gw
+
+
+def stem_conv_u8(frames, lengths, lut, w):
+    """stem_conv(clip_u8_to_f32(frames, lut, lengths), w) without the fp32 clip (bit-identical forward)"""
+    return _StemConvU8.apply(frames, lengths, lut, w)
+
+
 class _BnFold(Function):
     """(sum, sumsq) of a conv output -> per-(n,c) prologue (A, B); optional fused SE gate.  cfn_bn_fold_*."""
 

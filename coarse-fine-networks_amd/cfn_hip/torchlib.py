@@ -29,7 +29,7 @@ _lib = 'cfn'
 
 # Native registration (csrc/torch/cfn_torch.cpp -> cfn_hip/libcfn_torch.so, built by __graft_entry__.build()): ALL 16 forward + 16 backward
 # operators of the set are defined and implemented by TORCH_LIBRARY inside a shared library (round 5: dwconv3d / pwconv /
-# time_sample, round 6: the other 13 pairs).  When it is present the Python definitions below are skipped; their fake implementations and
+# time_sample, round 6: the other 13 pairs; the uint8 input path adds stem_conv_u8 + its backward, clip_u8_to_f32 and the host-side clip_lut).  When it is present the Python definitions below are skipped; their fake implementations and
 # autograd formulas are attached to the native operators.  CFN_NATIVE_OPS=0: Python custom_op definitions over ctypes for everything (the
 # round-3/4 route; also what serves 16-bit tensors through bn_add_relu / pool_hw / dwconv_t5 -- the native operators are fp32).
 NATIVE_LIB = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'libcfn_torch.so')
@@ -383,6 +383,63 @@ def _(gy, x, w):
 
 stem_conv.register_autograd(lambda ctx, gy: (None, torch.ops.cfn.stem_conv_backward(gy, *ctx.saved_tensors)),
                             setup_context=lambda ctx, inputs, output: ctx.save_for_backward(*inputs))
+
+
+# ---- uint8 frames, normalised on the GPU: the table (host), the converter, conv1_s on the bytes (no clip gradient) ----------------
+if not NATIVE:      # (no tensor argument: one composite kernel for every dispatch key; the native library defines it the same way)
+    _frag = torch.library.Library(_lib, 'FRAGMENT')
+    _frag.define('clip_lut(float[] mean, float[] std, float norm_value=255.) -> Tensor')
+    _frag.impl('clip_lut', lambda mean, std, norm_value=255.: _ops.clip_lut(mean, std, norm_value), 'CompositeImplicitAutograd')
+
+
+@_op('clip_u8_to_f32')
+def clip_u8_to_f32(frames: torch.Tensor, lut: torch.Tensor, lengths: Optional[torch.Tensor] = None) -> torch.Tensor:
+    return _ops.clip_u8_to_f32(frames, lut, lengths)
+
+
+@clip_u8_to_f32.register_fake
+def _(frames, lut, lengths=None):
+    N, T, H, W, _ = frames.shape
+    return frames.new_empty((N, 3, T, H, W), dtype=torch.float32)
+
+
+@_op('stem_conv_u8')
+def stem_conv_u8(frames: torch.Tensor, lengths: Optional[torch.Tensor], lut: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
+    return _ops._StemConvU8.forward(_Ctx(), frames, lengths, lut, w)
+
+
+@stem_conv_u8.register_fake
+def _(frames, lengths, lut, w):
+    N, T, H, W, _ = frames.shape
+    return w.new_empty((N, w.shape[0], T, (H - 1) // 2 + 1, (W - 1) // 2 + 1), dtype=torch.float32)
+
+
+@_op('stem_conv_u8_backward')
+def stem_conv_u8_backward(gy: torch.Tensor, frames: torch.Tensor, lengths: Optional[torch.Tensor], lut: torch.Tensor,
+                          w: torch.Tensor) -> torch.Tensor:
+    f, ln, lt = _ops._u8_args(frames, lengths, lut)
+    c = _Ctx((f, ln, lt), wshape=tuple(w.shape), wparam=w)
+    return _own(_ops._StemConvU8.backward(c, gy)[3], dtype=torch.float32).view(w.shape)
+
+
+@stem_conv_u8_backward.register_fake
+def _(gy, frames, lengths, lut, w):
+    return torch.empty_like(w, dtype=torch.float32)
+
+
+def _su8_setup(ctx, inputs, output):
+    frames, lengths, lut, w = inputs
+    ctx.has_len = lengths is not None
+    ctx.save_for_backward(*([frames, lut, w] + ([lengths] if ctx.has_len else [])))
+
+
+def _su8_backward(ctx, gy):
+    frames, lut, w = ctx.saved_tensors[:3]
+    lengths = ctx.saved_tensors[3] if ctx.has_len else None
+    return None, None, None, torch.ops.cfn.stem_conv_u8_backward(gy, frames, lengths, lut, w)
+
+
+stem_conv_u8.register_autograd(_su8_backward, setup_context=_su8_setup)
 
 
 # ---- dense conv3d (Grid Pool saliency convs) -------------------------------------------------------------------------------------
@@ -828,7 +885,9 @@ time_resize.register_autograd(lambda ctx, g: (torch.ops.cfn.time_resize_backward
 
 
 OPERATORS = ('dwconv3d', 'pwconv', 'time_sample', 'dwconv_t5', 'stem_conv', 'conv3d_dense', 'bn_fold', 'bn_add_relu', 'affine_act',
-             'pool_hw', 'interp1d', 'grid_cdf', 'gauss_align', 'fusion_gather', 'film', 'time_resize')
+             'pool_hw', 'interp1d', 'grid_cdf', 'gauss_align', 'fusion_gather', 'film', 'time_resize', 'stem_conv_u8')
+# the uint8 input path's operators without a gradient (the host-built table, the frames -> fp32 clip converter)
+INPUT_OPERATORS = ('clip_lut', 'clip_u8_to_f32')
 
 
 # ---------------------------------------------------------------------------------------------------------------------------

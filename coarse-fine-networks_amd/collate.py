@@ -11,9 +11,17 @@ structure the models and losses consume.
 Zero padding on the right along time, ``mask`` = 1 over each sample's own label length, fine features and their mask
 truncated to ``cap`` = 128 frames (the Gaussian-alignment tables of the fusion layers are sized for that).  Inputs may
 be numpy arrays or tensors; outputs are fp32 tensors (pin them and copy with non_blocking=True in the loader).
+
+``fine_collate_u8`` / ``coarse_collate_u8``: the same batches from samples whose clips are still uint8 frames
+(n, T, H, W, 3), channels last, as the decoder and the crop / flip transforms leave them.  The clip member becomes a
+``U8Clips(frames (B,n,Tmax,H,W,3) uint8, lengths (B,n) int32)``: a quarter of the bytes to pad, pin and copy, and no CPU
+normalisation (the reference's ToTensor + Normalize, spatial_transforms.py:46-85, :108-118) -- the stem conv normalises on the
+GPU (``model.set_input_norm``).  Labels, masks, features and meta are what the fp32 builders produce.
 """
 import numpy as np
 import torch
+
+from cfn_hip.u8clips import U8Clips, CHARADES_MEAN, CHARADES_STD  # noqa: F401
 
 
 def _t(a):
@@ -42,6 +50,22 @@ def _label_mask(labels, tl):
     return mask
 
 
+def _pad_time_u8(clips):
+    """uint8 clips (n, T_i, H, W, 3) -> U8Clips((B, n, Tmax, H, W, 3), lengths (B, n)); zero bytes behind each clip's own length"""
+    clips = [_t(c) for c in clips]
+    for c in clips:
+        if c.dtype != torch.uint8 or c.dim() != 5 or c.shape[4] != 3:
+            raise ValueError('uint8 clips of shape (n, T, H, W, 3) expected, got %s %s' % (c.dtype, tuple(c.shape)))
+    t_max = max(c.shape[1] for c in clips)
+    n, _, H, W, _ = clips[0].shape
+    frames = torch.zeros((len(clips), n, t_max, H, W, 3), dtype=torch.uint8)
+    lengths = torch.zeros((len(clips), n), dtype=torch.int32)
+    for i, c in enumerate(clips):
+        frames[i, :, :c.shape[1]] = c
+        lengths[i] = c.shape[1]
+    return U8Clips(frames, lengths)
+
+
 def fine_collate(batch):
     clips = [b[0] for b in batch]
     labels = [b[1] for b in batch]
@@ -50,12 +74,18 @@ def fine_collate(batch):
     return [_pad_time(clips, 2, t_max), _pad_time(labels, 1, tl_max), _label_mask(labels, tl_max), [b[2] for b in batch]]
 
 
-def coarse_collate(batch, cap=128):
-    clips = [b[0] for b in batch]
+def fine_collate_u8(batch):
+    """fine_collate for samples (uint8 clips (n,T,H,W,3), label (157,TL), vid)"""
+    labels = [b[1] for b in batch]
+    tl_max = max(_t(lb).shape[1] for lb in labels)
+    return [_pad_time_u8([b[0] for b in batch]), _pad_time(labels, 1, tl_max), _label_mask(labels, tl_max), [b[2] for b in batch]]
+
+
+def _coarse_rest(batch, cap):
+    """everything of a coarse batch but the clip: [label, mask, feat, feat_mask, meta, [vid...], dur]"""
     labels = [b[1] for b in batch]
     feats = [b[2] for b in batch]
     keys = list(feats[0].keys())
-    t_max = max(_t(c).shape[2] for c in clips)
     tl_max = max(_t(lb).shape[1] for lb in labels)
     tf_max = min(max(_t(f[keys[0]]).shape[1] for f in feats), cap)
     feat = {k: _pad_time([f[k] for f in feats], 1, tf_max) for k in keys}
@@ -64,5 +94,15 @@ def coarse_collate(batch, cap=128):
         feat_mask[i, :min(cap, _t(f[keys[0]]).shape[1])] = 1.0
     meta = torch.stack([_t(b[3]) for b in batch])
     dur = torch.as_tensor([float(b[5]) for b in batch], dtype=torch.float64)
-    return [_pad_time(clips, 2, t_max), _pad_time(labels, 1, tl_max), _label_mask(labels, tl_max), feat, feat_mask, meta,
-            [b[4] for b in batch], dur]
+    return [_pad_time(labels, 1, tl_max), _label_mask(labels, tl_max), feat, feat_mask, meta, [b[4] for b in batch], dur]
+
+
+def coarse_collate(batch, cap=128):
+    clips = [b[0] for b in batch]
+    t_max = max(_t(c).shape[2] for c in clips)
+    return [_pad_time(clips, 2, t_max)] + _coarse_rest(batch, cap)
+
+
+def coarse_collate_u8(batch, cap=128):
+    """coarse_collate for samples whose clips are uint8 (n,T,H,W,3)"""
+    return [_pad_time_u8([b[0] for b in batch])] + _coarse_rest(batch, cap)

@@ -11,6 +11,7 @@
 //   cfn::time_sample / _backward          Grid Pool resampler      x3d_coarse.py:393-403
 // round 6: the remaining 13 pairs of the section-8(b) set -- dwconv_t5, stem_conv, conv3d_dense, bn_fold, bn_add_relu, affine_act, pool_hw, interp1d,
 // grid_cdf, gauss_align, fusion_gather, film, time_resize (each with its _backward) -- see the second half of this file.
+// uint8 input path: clip_lut (host table), clip_u8_to_f32, stem_conv_u8 + stem_conv_u8_backward (csrc/stem_u8.hip).
 #include <ATen/ATen.h>
 // (a ROCm build of torch presents its HIP devices as "cuda": the masquerading guard / stream classes are the ones that accept them)
 #include <ATen/hip/impl/HIPGuardImplMasqueradingAsCUDA.h>
@@ -318,6 +319,77 @@ Tensor stem_conv_backward(const Tensor& gy_, const Tensor& x_, const Tensor& w) 
     const Tensor x = x_.contiguous(), gy = gy_.contiguous();
     Tensor gw = f64({Co, Ci * 9}, x);
     ok(cfn_stem_conv_bwd_weight(gy.data_ptr<float>(), x.data_ptr<float>(), gw.data_ptr<double>(), (int)N, (int)Ci, (int)Co, (int)T, (int)H, (int)W, stream_of(x)), "cfn_stem_conv_bwd_weight");
+    return gw.to(at::kFloat).view(w.sizes());
+}
+
+// ---- uint8 frames, normalised on the GPU (spatial_transforms.py:46-85, :108-118; charades_fine.py:170-173) --------------------------------
+// the (3, 256) table of normalised byte values: the reference's operations in the reference's order, on the host
+Tensor clip_lut(c10::ArrayRef<double> mean, c10::ArrayRef<double> std, double norm_value) {
+    TORCH_CHECK(mean.size() == 3 && std.size() == 3, "cfn::clip_lut: mean and std of the 3 image channels expected");
+    Tensor lut = at::arange(256, at::TensorOptions().dtype(at::kByte)).view({1, 256}).repeat({3, 1}).to(at::kFloat).div(at::Scalar(norm_value));
+    for (int c = 0; c < 3; ++c) lut.select(0, c).sub_(at::Scalar(mean[c])).div_(at::Scalar(std[c]));
+    return lut;
+}
+
+struct U8In { Tensor frames, lut, len; int64_t N, T, H, W; };
+inline U8In u8_in(const Tensor& frames, OptT lengths, const Tensor& lut, const char* op) {
+    TORCH_CHECK(frames.is_cuda(), op, ": device tensors only (there is no CPU path)");
+    TORCH_CHECK(frames.scalar_type() == at::kByte && frames.dim() == 5 && frames.size(4) == 3, op, ": uint8 frames (N, T, H, W, 3) expected, got ", frames.scalar_type(), " ", frames.sizes());
+    TORCH_CHECK(lut.scalar_type() == at::kFloat && lut.numel() == 3 * 256 && lut.device() == frames.device(), op, ": a (3, 256) fp32 table on the frames' device expected, got ", lut.scalar_type(), " ", lut.sizes());
+    U8In r{frames.contiguous(), lut.contiguous(), Tensor(), frames.size(0), frames.size(1), frames.size(2), frames.size(3)};
+    if (lengths.has_value() && lengths->defined()) {
+        TORCH_CHECK(lengths->numel() == r.N && lengths->device() == frames.device(), op, ": one length per clip on the frames' device expected, got ", lengths->sizes());
+        r.len = lengths->to(at::kInt).contiguous();
+    }
+    return r;
+}
+inline const int* iptr(const Tensor& t) { return t.defined() ? t.data_ptr<int>() : nullptr; }
+
+Tensor clip_u8_to_f32_t(const U8In& u) {
+    Tensor x = at::empty({u.N, 3, u.T, u.H, u.W}, u.frames.options().dtype(at::kFloat));
+    ok(cfn_clip_u8_to_f32(u.frames.data_ptr<uint8_t>(), u.lut.data_ptr<float>(), iptr(u.len), x.data_ptr<float>(), (int)u.N, (int)u.T, (int)u.H, (int)u.W, stream_of(x)), "cfn_clip_u8_to_f32");
+    return x;
+}
+
+Tensor clip_u8_to_f32(const Tensor& frames, const Tensor& lut, OptT lengths) {
+    const U8In u = u8_in(frames, lengths, lut, "cfn::clip_u8_to_f32");
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(frames.device());
+    return clip_u8_to_f32_t(u);
+}
+
+// shapes the fused kernels decline (-1): convert, then the fp32 entry point
+Tensor stem_conv_u8(const Tensor& frames, OptT lengths, const Tensor& lut, const Tensor& w) {
+    const U8In u = u8_in(frames, lengths, lut, "cfn::stem_conv_u8");
+    TORCH_CHECK(w.dim() >= 2 && w.numel() == w.size(0) * 27 && w.device() == frames.device(), "cfn::stem_conv_u8: w (Co, 3, 1, 3, 3) on the frames' device");
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(frames.device());
+    const int64_t Co = w.size(0);
+    const Tensor w2 = f32c(w.reshape({Co, 27}));
+    Tensor y = at::empty({u.N, Co, u.T, (u.H + 2 - 3) / 2 + 1, (u.W + 2 - 3) / 2 + 1}, w2.options());
+    const int rc = cfn_stem_conv_u8_fwd(u.frames.data_ptr<uint8_t>(), u.lut.data_ptr<float>(), iptr(u.len), w2.data_ptr<float>(), y.data_ptr<float>(), (int)u.N, 3, (int)Co,
+                                        (int)u.T, (int)u.H, (int)u.W, stream_of(y));
+    if (rc == -1) {
+        const Tensor x = clip_u8_to_f32_t(u);
+        ok(cfn_stem_conv_fwd(x.data_ptr<float>(), w2.data_ptr<float>(), y.data_ptr<float>(), (int)u.N, 3, (int)Co, (int)u.T, (int)u.H, (int)u.W, stream_of(y)), "cfn_stem_conv_fwd");
+    } else ok(rc, "cfn_stem_conv_u8_fwd");
+    return y;
+}
+
+Tensor stem_conv_u8_backward(const Tensor& gy_, const Tensor& frames, OptT lengths, const Tensor& lut, const Tensor& w) {
+    const U8In u = u8_in(frames, lengths, lut, "cfn::stem_conv_u8_backward");
+    check_f32(gy_, "cfn::stem_conv_u8_backward", "gy");
+    TORCH_CHECK(w.dim() >= 2 && w.numel() == w.size(0) * 27, "cfn::stem_conv_u8_backward: w (Co, 3, 1, 3, 3)");
+    const int64_t Co = w.size(0);
+    TORCH_CHECK(gy_.dim() == 5 && gy_.size(0) == u.N && gy_.size(1) == Co && gy_.size(2) == u.T && gy_.size(3) == (u.H + 2 - 3) / 2 + 1 && gy_.size(4) == (u.W + 2 - 3) / 2 + 1 &&
+                    gy_.device() == frames.device(), "cfn::stem_conv_u8_backward: gy ", gy_.sizes(), " is not the gradient of the stem conv of frames ", frames.sizes());
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(frames.device());
+    const Tensor gy = gy_.contiguous();
+    Tensor gw = f64({Co, 27}, gy);
+    const int rc = cfn_stem_conv_u8_bwd_weight(gy.data_ptr<float>(), u.frames.data_ptr<uint8_t>(), u.lut.data_ptr<float>(), iptr(u.len), gw.data_ptr<double>(), (int)u.N, 3, (int)Co,
+                                               (int)u.T, (int)u.H, (int)u.W, stream_of(gy));
+    if (rc == -1) {
+        const Tensor x = clip_u8_to_f32_t(u);
+        ok(cfn_stem_conv_bwd_weight(gy.data_ptr<float>(), x.data_ptr<float>(), gw.data_ptr<double>(), (int)u.N, 3, (int)Co, (int)u.T, (int)u.H, (int)u.W, stream_of(gy)), "cfn_stem_conv_bwd_weight");
+    } else ok(rc, "cfn_stem_conv_u8_bwd_weight");
     return gw.to(at::kFloat).view(w.sizes());
 }
 
@@ -801,6 +873,10 @@ TORCH_LIBRARY_FRAGMENT(cfn, m) {
     m.def("dwconv_t5_backward(Tensor gy, Tensor gs, Tensor gq, Tensor x, Tensor w, Tensor y) -> (Tensor, Tensor)");
     m.def("stem_conv(Tensor x, Tensor w) -> Tensor");
     m.def("stem_conv_backward(Tensor gy, Tensor x, Tensor w) -> Tensor");
+    m.def("clip_lut(float[] mean, float[] std, float norm_value=255.) -> Tensor", clip_lut);      // (host table, no tensor argument: one kernel for every key)
+    m.def("clip_u8_to_f32(Tensor frames, Tensor lut, Tensor? lengths=None) -> Tensor");
+    m.def("stem_conv_u8(Tensor frames, Tensor? lengths, Tensor lut, Tensor w) -> Tensor");
+    m.def("stem_conv_u8_backward(Tensor gy, Tensor frames, Tensor? lengths, Tensor lut, Tensor w) -> Tensor");
     m.def("conv3d_dense(Tensor x, Tensor w, SymInt[] kernel, SymInt[] stride, SymInt[] padding, Tensor? A=None, Tensor? B=None, SymInt act=0) -> (Tensor, Tensor, Tensor)");
     m.def("conv3d_dense_backward(Tensor gy, Tensor gs, Tensor gq, Tensor x, Tensor w, Tensor y, SymInt[] kernel, SymInt[] stride, SymInt[] padding, Tensor? A=None, Tensor? B=None, SymInt act=0) -> (Tensor, Tensor, Tensor, Tensor)");
     m.def("bn_fold(Tensor? s, Tensor? q, Tensor? gamma, Tensor? beta, Tensor run_mean, Tensor run_var, Tensor nbt, bool training, SymInt N, SymInt C, SymInt S, float count, float eps, float momentum, Tensor? w1=None, Tensor? b1=None, Tensor? w2=None, Tensor? b2=None, float pool_count=1.) -> Tensor[]");
@@ -836,6 +912,9 @@ TORCH_LIBRARY_IMPL(cfn, CUDA, m) {      // (the HIP backend of a ROCm build of t
     m.impl("dwconv_t5_backward", dwconv_t5_backward);
     m.impl("stem_conv", stem_conv);
     m.impl("stem_conv_backward", stem_conv_backward);
+    m.impl("clip_u8_to_f32", clip_u8_to_f32);
+    m.impl("stem_conv_u8", stem_conv_u8);
+    m.impl("stem_conv_u8_backward", stem_conv_u8_backward);
     m.impl("conv3d_dense", conv3d_dense);
     m.impl("conv3d_dense_backward", conv3d_dense_backward);
     m.impl("bn_fold", bn_fold);

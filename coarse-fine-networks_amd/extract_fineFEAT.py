@@ -19,11 +19,15 @@ import x3d_fine                                   # noqa: E402
 FEAT_KEYS = ('layer1', 'layer2', 'layer3', 'layer4', 'conv5')
 
 
-def build_tower(device, ckpt=None, n_classes=157):
+def build_tower(device, ckpt=None, n_classes=157, input_norm=None):
+    """input_norm = (mean, std[, norm_value]): extract() then also takes videos as uint8 frames (cfn_hip.u8clips.U8Clips, frames
+    (1, T, H, W, 3)), normalised in the stem conv -- the reference's Normalize(CHARADES_MEAN, CHARADES_STD), extract_fineFEAT.py:78"""
     net = x3d_fine.generate_model('M', n_classes=n_classes, n_input_channels=3, task='loc', dropout=0.5,
                                   base_bn_splits=1, global_tower=True)
     if ckpt and os.path.exists(ckpt):
         net.load_state_dict(torch.load(ckpt, map_location='cpu')['model_state_dict'])
+    if input_norm is not None:
+        net.set_input_norm(*input_norm)
     net.to(device).train(False)
     net.aggregate_sub_bn_stats()          # extract_fineFEAT.py:136-139
     return net

@@ -27,7 +27,8 @@ import x3d_coarse                                 # noqa: E402
 from cfn_hip import staging                       # noqa: E402
 from cfn_hip import dist as cdist                 # noqa: E402
 from apmeter import APMeter                       # noqa: E402
-from train_fine import lr_warmup                  # noqa: E402
+from train_fine import lr_warmup, flatten_clips   # noqa: E402
+from cfn_hip.u8clips import U8Clips, CHARADES_MEAN, CHARADES_STD   # noqa: E402,F401
 
 BS = 6
 BS_UPSCALE = 1
@@ -80,8 +81,10 @@ def detection_loss(per_frame_logits, labels, masks, group=None, crops=1, local_n
     return _loss(per_frame_logits, labels, masks, False, group, crops, local_norm)
 
 
-def build_model(device, n_classes=NUM_CLASSES, pretrained=None, dropout=0.5, act_dtype=None):
-    """act_dtype 'bf16' / 'fp16': 16-bit stem + layer 1 (x3d_coarse.ResNet); None / 'f32': the reference's fp32"""
+def build_model(device, n_classes=NUM_CLASSES, pretrained=None, dropout=0.5, act_dtype=None, input_norm=None):
+    """act_dtype 'bf16' / 'fp16': 16-bit stem + layer 1 (x3d_coarse.ResNet); None / 'f32': the reference's fp32.
+    input_norm = (mean, std[, norm_value]): the net also takes uint8 frames (collate.coarse_collate_u8), normalised in the stem conv --
+    the reference's Normalize(CHARADES_MEAN, CHARADES_STD), train_coarse_fineFEAT.py:82-85"""
     net = x3d_coarse.generate_model(x3d_version=X3D_VERSION, n_classes=400, n_input_channels=3, feat_depth=FEAT_DEPTH,
                                     task='loc', dropout=dropout, base_bn_splits=1, learnedMixing=True, isMixing=True,
                                     t_pool='grid', act_dtype=act_dtype)
@@ -91,6 +94,8 @@ def build_model(device, n_classes=NUM_CLASSES, pretrained=None, dropout=0.5, act
         state.update(ckpt['model_state_dict'])
         net.load_state_dict(state)
     net.replace_logits(n_classes)
+    if input_norm is not None:
+        net.set_input_norm(*input_norm)
     return net.to(device)
 
 
@@ -103,13 +108,14 @@ def param_groups(net, lr):
 
 
 def forward_video(net, inputs, feat, feat_masks, i, meta, t_lim=1000):
-    """whole-video inference with the reference's chunking of long videos (:215-224)"""
+    """whole-video inference with the reference's chunking of long videos (:215-224); inputs: fp32 clip or U8Clips"""
     if inputs.shape[2] < t_lim + 5:
         return net([inputs, feat, feat_masks, i, meta])
     outs = []
     meta = meta.clone()
     for t_ind in range(0, inputs.shape[2] // t_lim + 1):
-        chunk = inputs[:, :, t_ind * t_lim:min(inputs.shape[2], (t_ind + 1) * t_lim)].contiguous()
+        t0, t1 = t_ind * t_lim, min(inputs.shape[2], (t_ind + 1) * t_lim)
+        chunk = inputs.time_slice(t0, t1) if isinstance(inputs, U8Clips) else inputs[:, :, t0:t1].contiguous()
         outs.append(net([chunk, feat, feat_masks, i, meta]))
         meta[:, 0] += t_lim
     return torch.cat(outs, dim=2)
@@ -150,7 +156,8 @@ def localize_rows(probs, labels, valid_t, names, dur):
 def run(init_lr=INIT_LR, warmup_steps=0, max_epochs=200, mode='rgb', root=None, train_split=None,
         batch_size=BS * BS_UPSCALE, frames=80 * 4, dataloaders=None, max_steps=None,
         save_model='models/coarse_fineFEAT_charades_', pretrained='models/x3d_multigrid_kinetics_fb_pretrained.pt',
-        csv_path='localize_corr_v1.csv', log=print, phase_hook=None):
+        csv_path='localize_corr_v1.csv', log=print, phase_hook=None, input_norm=None):
+    """input_norm: see build_model -- needed when the loaders collate uint8 frames (collate.coarse_collate_u8)."""
     rank, world, dev = cdist.init_from_env()
     gamma_tau = 5
     clip_frames = frames * 2 // (gamma_tau * 2)
@@ -159,7 +166,7 @@ def run(init_lr=INIT_LR, warmup_steps=0, max_epochs=200, mode='rgb', root=None, 
     if dataloaders is None:
         dataloaders = {'train': SyntheticCoarse(local_bs, iters, clip_frames, seed=rank),
                        'val': SyntheticCoarse(1, CHARADES_VAL_SIZE // world, clip_frames, seed=1000 + rank)}
-    net = build_model(dev, pretrained=pretrained)
+    net = build_model(dev, pretrained=pretrained, input_norm=input_norm)
     cdist.sync_module(net)   # rw2-6, mix2-5, pool_1 and the new fc2 are not in the checkpoint: rank 0's draw everywhere
     optimizer = optim.SGD(param_groups(net, init_lr), lr=init_lr, momentum=0.9, weight_decay=1e-5)
     lr_sched = optim.lr_scheduler.MultiStepLR(optimizer, [15, 25, 35])
@@ -191,7 +198,7 @@ def run(init_lr=INIT_LR, warmup_steps=0, max_epochs=200, mode='rgb', root=None, 
                     if not (cdist.all_agree(ok, dev) if world > 1 else ok):
                         continue
                 b, n = inputs.shape[:2]            # n crops per video at validation time (:198-201)
-                inputs = inputs.view((b * n,) + tuple(inputs.shape[2:])).to(dev, non_blocking=True)
+                inputs = flatten_clips(inputs, dev)
                 labels, masks, feat_masks, meta = labels.to(dev), masks.to(dev), feat_masks.to(dev), meta.to(dev)
                 feat = {k: v.to(dev) for k, v in feat.items()}
                 valid_t = masks.sum(1).int()

@@ -27,6 +27,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import x3d_fine                                   # noqa: E402
 from cfn_hip import dist as cdist                 # noqa: E402
 from cfn_hip import staging                       # noqa: E402
+from cfn_hip.u8clips import U8Clips, CHARADES_MEAN, CHARADES_STD   # noqa: E402,F401
 from apmeter import APMeter                       # noqa: E402
 
 BS = 8
@@ -101,7 +102,9 @@ def lr_warmup(init_lr, cur_steps, warmup_steps, opt):
             pg['lr'] = lr_scale * init_lr
 
 
-def build_model(device, n_classes=NUM_CLASSES, pretrained=None, dropout=0.5, act_dtype=None):
+def build_model(device, n_classes=NUM_CLASSES, pretrained=None, dropout=0.5, act_dtype=None, input_norm=None):
+    """input_norm = (mean, std[, norm_value]): the net also takes uint8 frames (collate.fine_collate_u8) and normalises them in the stem
+    conv, e.g. (CHARADES_MEAN, CHARADES_STD) -- the reference's Normalize(CHARADES_MEAN, CHARADES_STD), train_fine.py:77-80"""
     net = x3d_fine.generate_model(x3d_version=X3D_VERSION, n_classes=400, n_input_channels=3, task='loc',
                                   dropout=dropout, base_bn_splits=1, t_downsample=False, extract_feat=False,
                                   act_dtype=act_dtype)
@@ -111,7 +114,17 @@ def build_model(device, n_classes=NUM_CLASSES, pretrained=None, dropout=0.5, act
         state.update(ckpt['model_state_dict'])
         net.load_state_dict(state)
     net.replace_logits(n_classes)
+    if input_norm is not None:
+        net.set_input_norm(*input_norm)
     return net.to(device)
+
+
+def flatten_clips(inputs, dev):
+    """(b, n crops, ...) -> (b * n, ...) on `dev`: an fp32 clip tensor (b, n, 3, T, H, W) or a U8Clips batch"""
+    if isinstance(inputs, U8Clips):
+        return inputs.flatten_crops().to(dev, non_blocking=True)
+    b, n = inputs.shape[:2]
+    return inputs.view((b * n,) + tuple(inputs.shape[2:])).to(dev, non_blocking=True)
 
 
 def forward_backward(net, inputs, labels, masks, gamma_tau=5, mask_total=None):
@@ -232,7 +245,8 @@ def _ap_rows(probs, labels, valid_t):
 
 def run(init_lr=INIT_LR, warmup_steps=0, max_epochs=200, mode='rgb', root=None, train_split=None,
         batch_size=BS * BS_UPSCALE, frames=80 * 4, dataloaders=None, max_steps=None, save_model='models/fine_charades_',
-        pretrained='models/x3d_multigrid_kinetics_fb_pretrained.pt', log=print, phase_hook=None):
+        pretrained='models/x3d_multigrid_kinetics_fb_pretrained.pt', log=print, phase_hook=None, input_norm=None):
+    """input_norm: see build_model -- needed when the loaders collate uint8 frames (collate.fine_collate_u8)."""
     rank, world, dev = cdist.init_from_env()
     gamma_tau = {'S': 6, 'M': 5, 'XL': 5}[X3D_VERSION]
     crop = {'S': 160, 'M': 224, 'XL': 312}[X3D_VERSION]
@@ -244,7 +258,7 @@ def run(init_lr=INIT_LR, warmup_steps=0, max_epochs=200, mode='rgb', root=None, 
     if dataloaders is None:
         dataloaders = {'train': SyntheticCharades(local_bs, iters, clip_frames, crop, gamma_tau * 2, seed=rank),
                        'val': SyntheticCharades(val_bs, val_iters, clip_frames, crop, gamma_tau * 2, seed=1000 + rank)}
-    net = build_model(dev, pretrained=pretrained)
+    net = build_model(dev, pretrained=pretrained, input_norm=input_norm)
     cdist.sync_module(net)        # one model on every rank (DataParallel replicates rank 0's; fc2 was just re-drawn)
     optimizer = optim.SGD(net.parameters(), lr=init_lr, momentum=0.9, weight_decay=1e-5)
     lr_sched = optim.lr_scheduler.MultiStepLR(optimizer, [15, 20, 25])
@@ -274,7 +288,7 @@ def run(init_lr=INIT_LR, warmup_steps=0, max_epochs=200, mode='rgb', root=None, 
                 if not ok:
                     continue
                 b, n = inputs.shape[:2]          # n crops per video (1 in training, train_fine.py:176-185)
-                inputs = inputs.view((b * n,) + tuple(inputs.shape[2:])).to(dev, non_blocking=True)
+                inputs = flatten_clips(inputs, dev)
                 labels, masks = labels.to(dev), masks.to(dev)
                 valid_t = masks.sum(1).int()
                 n_it += 1

@@ -53,11 +53,12 @@ class SyntheticJoint(object):
             yield x, labels, torch.ones(self.bs, tl)
 
 
-def build_models(device, pretrained_fine=None, pretrained_coarse=None, dropout=0.5, fine_act_dtype=None, coarse_act_dtype=None):
+def build_models(device, pretrained_fine=None, pretrained_coarse=None, dropout=0.5, fine_act_dtype=None, coarse_act_dtype=None, input_norm=None):
     """(fine tower, coarse net).  The tower has no classifier of its own on this path (fc1 / fc2 get no gradient).
     fine_act_dtype='fp16' / 'bf16': the Fine stream -- 2/3 of the joint step's bytes and flops -- stores its activations as IEEE half / bf16 and
     runs its pointwise convs on v_mfma_f32_32x32x16_{f16,bf16} (BASELINE configs[4] "fp16 MFMA pointwise"; both kinds run at the same MFMA rate
-    on CDNA4; fp16 adds a static loss scale, train_step); its pooled feature maps are fp32, so the Coarse stream and the fusion are unchanged."""
+    on CDNA4; fp16 adds a static loss scale, train_step); its pooled feature maps are fp32, so the Coarse stream and the fusion are unchanged.
+    input_norm = (mean, std[, norm_value]): both nets also take the clip as uint8 frames (cfn_hip.u8clips.U8Clips), normalised in their stem convs."""
     fine = x3d_fine.generate_model(x3d_version='M', n_classes=NUM_CLASSES, n_input_channels=3, task='loc', dropout=dropout,
                                    base_bn_splits=1, global_tower=True, act_dtype=fine_act_dtype)
     if pretrained_fine:
@@ -66,7 +67,9 @@ def build_models(device, pretrained_fine=None, pretrained_coarse=None, dropout=0
         fine.load_state_dict(state)
     # coarse_act_dtype: the stem + layer 1 of the Coarse stream in 16 bits as well (x3d_coarse.ResNet) -- the joint step then runs 16-bit in both
     # trunks wherever a tensor has the clip's full frame count
-    coarse = tc.build_model(device, pretrained=pretrained_coarse, dropout=dropout, act_dtype=coarse_act_dtype)
+    coarse = tc.build_model(device, pretrained=pretrained_coarse, dropout=dropout, act_dtype=coarse_act_dtype, input_norm=input_norm)
+    if input_norm is not None:
+        fine.set_input_norm(*input_norm)
     return fine.to(device), coarse
 
 
@@ -75,6 +78,8 @@ def coarse_window(clip, coarse_frames=None, start=None):
     tf = clip.shape[2]
     tcn = coarse_frames or tf // 2
     s = (tf - tcn) // 2 if start is None else start
+    if isinstance(clip, tc.U8Clips):
+        return clip.time_slice(s, s + tcn), s
     return clip[:, :, s:s + tcn].contiguous(), s
 
 

@@ -23,6 +23,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from cfn_hip import ops, ACT_NONE, ACT_RELU, ACT_SWISH
+from cfn_hip.u8clips import U8Clips
 
 # CFN_USE_TORCH_OPS=1 (or x3d_fine.USE_TORCH_OPS = True): Bottleneck runs through the registered dispatcher operators
 # torch.ops.cfn.* (cfn_hip/torchlib.py) with plain semantics -- the same kernels, visible to torch.compile / torch.export as opaque
@@ -363,10 +364,32 @@ class ResNet(nn.Module):
                 count += 1
         return count
 
+    def set_input_norm(self, mean, std, norm_value=255):
+        """Accept uint8 frames (cfn_hip.u8clips.U8Clips) as the clip: conv1_s normalises them while it loads them, with the
+        reference's ToTensor(norm_value) + Normalize(mean, std) (spatial_transforms.py:46-85, :108-118) as a (3, 256) table.
+        (An addition to the reference's surface.)  The table is a NON-persistent buffer: it follows .to() and the state_dict keys
+        stay the reference's."""
+        lut = ops.clip_lut(mean, std, norm_value).to(self.conv1_s.weight.device)
+        self.register_buffer('input_lut', lut, persistent=False)
+        return self
+
     # -- pieces shared with x3d_coarse ---------------------------------------------------------------
+    def _conv1_s(self, x):
+        """fp32 clip (N, 3, T, H, W), or uint8 frames normalised at load time"""
+        if not isinstance(x, U8Clips):
+            return ops.stem_conv(x, self.conv1_s.weight)
+        lut = getattr(self, 'input_lut', None)
+        if lut is None:
+            raise RuntimeError('the model was handed uint8 frames (U8Clips) but does not know how to normalise them: call '
+                               'set_input_norm(mean, std) first (e.g. CHARADES_MEAN / CHARADES_STD)')
+        if x.frames.dim() != 5:
+            raise RuntimeError('U8Clips of shape (N, T, H, W, 3) expected (flatten_crops() a collated batch), got %s'
+                               % (tuple(x.frames.shape),))
+        return ops.stem_conv_u8(x.frames, x.lengths, lut, self.conv1_s.weight)
+
     def _stem(self, x):
         """conv1_s -> conv1_t -> bn1 -> relu (x3d_fine.py:334-337); bn1+relu stay deferred."""
-        y = ops.stem_conv(x, self.conv1_s.weight)
+        y = self._conv1_s(x)
         y, s, q = ops.dwconv_t5(y, self.conv1_t.weight, stats=self.training, out_dtype=self.act_dtype)
         A, B = self.bn1.fold(s, q, _count(y), y.shape[0])
         return Deferred(y, A, B, ACT_RELU)

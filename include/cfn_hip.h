@@ -133,6 +133,22 @@ int cfn_stem_conv_fwd(const float* x, const float* w, float* y, int N, int Cimg,
 int cfn_stem_conv_bwd_weight(const float* gy, const float* x, double* gw, int N, int Cimg, int Cout, int T, int Hi, int Wi,
                              void* stream);
 
+/* ---- uint8 video frames, normalised on the GPU.  Replaces the host side ToTensor(255) + Normalize(mean, std) per frame
+ * (spatial_transforms.py:46-85, :108-118) and the stack + permute per clip (charades_fine.py:170-173).
+ * `unsigned char*` = uint8 tensor.  frames (N, T, H, W, 3) channels last, contiguous; lut (3, 256) fp32 = the normalised value of
+ * every byte per channel, built on the host with the reference's operations (the converted clip is bit-identical to the
+ * reference's); lengths (N) int32 or NULL (= all frames valid): frame t >= lengths[n] is zero padding and reads as 0.0.
+ *   cfn_clip_u8_to_f32: x (N, 3, T, H, W) fp32, any H and W.
+ *   cfn_stem_conv_u8_fwd / _bwd_weight: cfn_stem_conv_fwd / _bwd_weight of that clip without materialising it (Cimg must be 3;
+ *   the forward is bit-identical).  They return -1, with nothing launched, for a shape the fused kernels do not take (forward:
+ *   Cout > 32, W % 4, odd H; weight gradient: anything but 24 channels at 224 x 224): convert, then use the fp32 entry point. ---- */
+int cfn_clip_u8_to_f32(const unsigned char* frames, const float* lut, const int* lengths, float* x, int N, int T, int H, int W,
+                       void* stream);
+int cfn_stem_conv_u8_fwd(const unsigned char* frames, const float* lut, const int* lengths, const float* w, float* y, int N,
+                         int Cimg, int Cout, int T, int Hi, int Wi, void* stream);
+int cfn_stem_conv_u8_bwd_weight(const float* gy, const unsigned char* frames, const float* lut, const int* lengths, double* gw,
+                                int N, int Cimg, int Cout, int T, int Hi, int Wi, void* stream);
+
 /* ---- SubBatchNorm3d statistics -> (A,B) prologue, fused with the SE gate: SubBatchNorm3d.forward x3d_fine.py:51-62
  * (split groups, shared affine), nn.BatchNorm3d running-stat update, SE branch x3d_fine.py:157-163.
  * training: s,q (N,C) fp64 sums over `count` positions; run_mean/run_var = split_bn buffers (S*C) updated in place,

@@ -652,6 +652,63 @@ def stem_conv_u8(frames, lengths, lut, w):
     return _StemConvU8.apply(frames, lengths, lut, w)
 
 
+# ---- uint8 frames: crop, antialiased bilinear resize and flip on the GPU (csrc/aug_u8.hip; tables: cfn_hip/u8aug.py) -------------
+from . import u8aug  # noqa: E402
+
+_AUG_TABLES = {}                 # (crop extents of the batch, S, device) -> (bounds, coef) on the device
+_AUG_TABLES_MAX = 256
+
+
+def aug_tables(box, size, device):
+    """device tables (bounds (N, S, 2), coef (N, S, K) int32) of a batch whose crop extents are box[:, 2]; `box` is read on the host
+    (a device tensor costs one small copy back and a wait for it).  Cached per (extents, size, device): a dataset has a handful of
+    distinct crop extents."""
+    cs = tuple(int(v) for v in box.detach().reshape(-1, 4)[:, 2].cpu().tolist())
+    device = torch.device(device)
+    key = (cs, int(size), device.type, device.index)
+    hit = _AUG_TABLES.get(key)
+    if hit is None:
+        if any(c <= 0 or c > 4 * int(size) for c in cs):
+            raise RuntimeError('crop_resize_flip_u8: crop extents %s into %d: 1 <= c <= 4 * size expected (the kernel takes tables of up '
+                               'to %d taps; there is no CPU fallback)' % (sorted(set(cs)), size, u8aug.MAX_TAPS))
+        bounds, coef = u8aug.batch_tables(cs, size)
+        hit = (bounds.to(device), coef.to(device))
+        if len(_AUG_TABLES) >= _AUG_TABLES_MAX:
+            _AUG_TABLES.clear()
+        _AUG_TABLES[key] = hit
+    return hit
+
+
+def crop_resize_flip_u8(frames, lengths, box, size, out=None, tables=None):
+    """frames (N, T, Hs, Ws, 3) uint8 on the GPU, box (N, 4) int32 = x1, y1, c, flip per clip -> (N, T, size, size, 3) uint8: the
+    reference's PIL crop + resize(BILINEAR) + FLIP_LEFT_RIGHT, bit for bit; frames t >= lengths[n] are zero bytes.
+    tables = aug_tables(box, size, device) may be handed in (then `box` is not read on the host: no wait, capturable); with `out`,
+    a device `box` and cached or given tables nothing is allocated on the device."""
+    if frames.dtype != torch.uint8 or frames.dim() != 5 or frames.shape[4] != 3:
+        raise RuntimeError('uint8 frames of shape (N, T, Hs, Ws, 3) expected, got %s %s' % (frames.dtype, tuple(frames.shape)))
+    N, T, Hs, Ws, _ = frames.shape
+    S = int(size)
+    if box.numel() != 4 * N:
+        raise RuntimeError('one box (x1, y1, c, flip) per clip expected: %d clips, box %s' % (N, tuple(box.shape)))
+    if lengths is not None:
+        if lengths.numel() != N:
+            raise RuntimeError('one length per clip expected: %d clips, lengths %s' % (N, tuple(lengths.shape)))
+        lengths = lengths.to(torch.int32).contiguous()
+    bounds, coef = tables if tables is not None else aug_tables(box, S, frames.device)
+    if tuple(bounds.shape) != (N, S, 2) or coef.dim() != 3 or tuple(coef.shape[:2]) != (N, S):
+        raise RuntimeError('tables of %d clips into %d expected, got bounds %s coef %s' % (N, S, tuple(bounds.shape), tuple(coef.shape)))
+    box = box.reshape(N, 4).to(device=frames.device, dtype=torch.int32).contiguous()
+    if out is None:
+        out = torch.empty(N, T, S, S, 3, dtype=torch.uint8, device=frames.device)
+    elif out.dtype != torch.uint8 or tuple(out.shape) != (N, T, S, S, 3) or not out.is_contiguous():
+        raise RuntimeError('out: a contiguous uint8 tensor of shape %s expected, got %s %s' % ((N, T, S, S, 3), out.dtype, tuple(out.shape)))
+    if not call_try('cfn_crop_resize_flip_u8', frames.contiguous(), lengths, box, bounds.contiguous(), coef.contiguous(), out, N, T, Hs, Ws,
+                    S, int(coef.shape[2])):
+        raise RuntimeError('crop_resize_flip_u8: %d taps into size %d is beyond what the kernel was built for (c <= 4 * size, size <= 312 '
+                           'at 9 taps); there is no CPU fallback' % (int(coef.shape[2]), S))
+    return out
+
+
 class _BnFold(Function):
     """(sum, sumsq) of a conv output -> per-(n,c) prologue (A, B); optional fused SE gate.  cfn_bn_fold_*."""
 

@@ -884,10 +884,25 @@ def _tr_setup(ctx, inputs, output):
 time_resize.register_autograd(lambda ctx, g: (torch.ops.cfn.time_resize_backward(g, *ctx.meta), None, None), setup_context=_tr_setup)
 
 
+# ---- uint8 frames: crop + antialiased bilinear resize + flip on the GPU (csrc/aug_u8.hip; the tap tables: cfn_hip/u8aug.py) -------
+@_op('crop_resize_flip_u8')
+def crop_resize_flip_u8(frames: torch.Tensor, lengths: Optional[torch.Tensor], box: torch.Tensor, bounds: torch.Tensor, coef: torch.Tensor,
+                        size: int) -> torch.Tensor:
+    return _ops.crop_resize_flip_u8(frames, lengths, box, size, tables=(bounds, coef))
+
+
+@crop_resize_flip_u8.register_fake
+def _(frames, lengths, box, bounds, coef, size):
+    N, T = frames.shape[:2]
+    return frames.new_empty((N, T, size, size, 3), dtype=torch.uint8)
+
+
 OPERATORS = ('dwconv3d', 'pwconv', 'time_sample', 'dwconv_t5', 'stem_conv', 'conv3d_dense', 'bn_fold', 'bn_add_relu', 'affine_act',
              'pool_hw', 'interp1d', 'grid_cdf', 'gauss_align', 'fusion_gather', 'film', 'time_resize', 'stem_conv_u8')
 # the uint8 input path's operators without a gradient (the host-built table, the frames -> fp32 clip converter)
 INPUT_OPERATORS = ('clip_lut', 'clip_u8_to_f32')
+# spatial augmentation of uint8 frames on the GPU (no gradient)
+AUGMENT_OPERATORS = ('crop_resize_flip_u8',)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------

@@ -2,8 +2,10 @@
 them (cfn_hip.ops.stem_conv_u8, csrc/stem_u8.hip).
 
 The reference normalises on the CPU -- ToTensor(255) + Normalize(mean, std) per frame (spatial_transforms.py:46-85, :108-118),
-stack + permute per clip (charades_fine.py:170-173) -- and collates padded fp32 batches.  Decode, resize, crop and flip commute
-with the conversion and stay on the host, on uint8.
+stack + permute per clip (charades_fine.py:170-173) -- and collates padded fp32 batches.  Crop, resize and flip commute with the
+conversion and run on the GPU as well, on the bytes: a loader may hand over the frames as decoded, with one crop box per clip
+(RawU8Clips below; ops.crop_resize_flip_u8, csrc/aug_u8.hip, bit-exact to the reference's PIL transforms), or do that work itself
+and hand over U8Clips.  Only the decode stays on the host.
 """
 import collections
 
@@ -82,3 +84,59 @@ class U8Clips(collections.namedtuple('U8Clips', ['frames', 'lengths'])):
         x = torch.where(live.view(tuple(live.shape) + (1, 1, 1)), x, torch.zeros((), dtype=x.dtype, device=x.device))
         nd = x.dim()
         return x.permute(tuple(range(nd - 4)) + (nd - 1, nd - 4, nd - 3, nd - 2)).contiguous()
+
+
+class RawU8Clips(collections.namedtuple('RawU8Clips', ['frames', 'lengths', 'box'])):
+    """A batch of uint8 clips as DECODED, before the spatial transform: ``frames`` (..., T, Hs, Ws, 3) uint8, every clip's h x w picture
+    in the top-left corner of a common Hs x Ws and zero padded along time; ``lengths`` (...) int32; ``box`` (..., 4) int32 =
+    x1, y1, c, flip: the square crop window and whether the result is mirrored (cfn_hip.u8aug.train_crop_params / center_crop_params
+    draw them as the reference's MultiScaleRandomCropMultigrid + RandomHorizontalFlip / CenterCropScaled do).
+
+    ``transform(size)`` crops, resizes and flips on the frames' device and returns the U8Clips the models take.  A namedtuple, like
+    U8Clips: staging and pinning rebuild it around the moved tensors.  ``shape`` is the logical shape BEFORE the transform."""
+    __slots__ = ()
+
+    @property
+    def shape(self):
+        s = tuple(self.frames.shape)
+        return torch.Size(s[:-4] + (3,) + s[-4:-1])
+
+    @property
+    def device(self):
+        return self.frames.device
+
+    def size(self, dim=None):
+        return self.shape if dim is None else self.shape[dim]
+
+    def dim(self):
+        return len(self.shape)
+
+    def to(self, device, non_blocking=False):
+        """move all three members to `device`; the element types are part of the format, so a dtype is refused"""
+        if isinstance(device, torch.dtype) or not isinstance(device, (str, int, torch.device)):
+            raise TypeError('RawU8Clips.to() takes a device: frames stay uint8, lengths and box int32')
+        return RawU8Clips(*[m.to(device, non_blocking=non_blocking) for m in self])
+
+    def cuda(self, device=None, non_blocking=False):
+        return RawU8Clips(*[m.cuda(device, non_blocking=non_blocking) for m in self])
+
+    def flatten_crops(self):
+        """(B, n, T, Hs, Ws, 3) -> (B * n, T, Hs, Ws, 3); lengths and boxes follow"""
+        f = self.frames
+        return RawU8Clips(f.reshape((-1,) + tuple(f.shape[-4:])), self.lengths.reshape(-1), self.box.reshape(-1, 4))
+
+    def time_slice(self, t0, t1):
+        """frames [t0, t1) of every clip, as U8Clips.time_slice; the boxes stay"""
+        u = U8Clips(self.frames, self.lengths).time_slice(t0, t1)
+        return RawU8Clips(u.frames, u.lengths, self.box)
+
+    def transform(self, size, out=None):
+        """crop + antialiased bilinear resize to size x size + flip on the GPU, on the current stream of the frames' device
+        (ops.crop_resize_flip_u8): the U8Clips batch (..., T, size, size, 3) on the same device.  The crop extents box[..., 2] select
+        the tap tables on the host: a box that already lives on the device is copied back for that (16 bytes per clip)."""
+        from . import ops
+        f = self.frames
+        lead = tuple(f.shape[:-4])
+        flat = self.flatten_crops()
+        y = ops.crop_resize_flip_u8(flat.frames, flat.lengths, flat.box, size, out=out)
+        return U8Clips(y.view(lead + tuple(y.shape[1:])), self.lengths)

@@ -17,11 +17,18 @@ be numpy arrays or tensors; outputs are fp32 tensors (pin them and copy with non
 ``U8Clips(frames (B,n,Tmax,H,W,3) uint8, lengths (B,n) int32)``: a quarter of the bytes to pad, pin and copy, and no CPU
 normalisation (the reference's ToTensor + Normalize, spatial_transforms.py:46-85, :108-118) -- the stem conv normalises on the
 GPU (``model.set_input_norm``).  Labels, masks, features and meta are what the fp32 builders produce.
+
+``fine_collate_raw_u8`` / ``coarse_collate_raw_u8``: the clips are the frames AS DECODED, before any spatial transform -- the clip
+member of a sample is a pair ``(frames (n, T, h, w, 3) uint8, box (n, 4) int = x1, y1, c, flip)`` with h, w differing from sample
+to sample (cfn_hip.u8aug.train_crop_params / center_crop_params draw the boxes as the reference's transforms do).  The clip
+member of the batch becomes a ``RawU8Clips(frames (B,n,Tmax,Hmax,Wmax,3), lengths (B,n), box (B,n,4))``, every picture in the
+top-left corner of its zero-padded frame; crop, resize and flip run on the GPU (``RawU8Clips.transform``, which the training and
+extraction scripts call).
 """
 import numpy as np
 import torch
 
-from cfn_hip.u8clips import U8Clips, CHARADES_MEAN, CHARADES_STD  # noqa: F401
+from cfn_hip.u8clips import RawU8Clips, U8Clips, CHARADES_MEAN, CHARADES_STD  # noqa: F401
 
 
 def _t(a):
@@ -66,6 +73,37 @@ def _pad_time_u8(clips):
     return U8Clips(frames, lengths)
 
 
+def _pad_raw_u8(samples):
+    """[(frames (n, T_i, h_i, w_i, 3) uint8, box (n, 4) int)] -> RawU8Clips((B, n, Tmax, Hmax, Wmax, 3), lengths (B, n), box (B, n, 4)):
+    zero bytes right of and below each picture and behind each clip's own length"""
+    clips, boxes = [], []
+    for smp in samples:
+        if not isinstance(smp, (tuple, list)) or len(smp) != 2:
+            raise ValueError('a raw clip is a pair (frames (n, T, h, w, 3) uint8, box (n, 4) int)')
+        c, b = _t(smp[0]), _t(smp[1])
+        if c.dtype != torch.uint8 or c.dim() != 5 or c.shape[4] != 3:
+            raise ValueError('uint8 frames of shape (n, T, h, w, 3) expected, got %s %s' % (c.dtype, tuple(c.shape)))
+        if b.is_floating_point() or b.dtype == torch.bool or tuple(b.shape) != (c.shape[0], 4):
+            raise ValueError('integer boxes of shape (n, 4) = x1, y1, c, flip expected for %d clips, got %s %s' % (c.shape[0], b.dtype, tuple(b.shape)))
+        b = b.to(torch.int32)
+        h, w = c.shape[2], c.shape[3]
+        for x1, y1, cs, flip in b.tolist():
+            if cs <= 0 or x1 < 0 or y1 < 0 or x1 + cs > w or y1 + cs > h or flip not in (0, 1):
+                raise ValueError('box (x1, y1, c, flip) = %s does not lie inside the %d x %d frames' % ((x1, y1, cs, flip), h, w))
+        clips.append(c)
+        boxes.append(b)
+    n = clips[0].shape[0]
+    if any(c.shape[0] != n for c in clips):
+        raise ValueError('the same number of clips per sample expected, got %s' % [c.shape[0] for c in clips])
+    t_max, h_max, w_max = (max(c.shape[d] for c in clips) for d in (1, 2, 3))
+    frames = torch.zeros((len(clips), n, t_max, h_max, w_max, 3), dtype=torch.uint8)
+    lengths = torch.zeros((len(clips), n), dtype=torch.int32)
+    for i, c in enumerate(clips):
+        frames[i, :, :c.shape[1], :c.shape[2], :c.shape[3]] = c
+        lengths[i] = c.shape[1]
+    return RawU8Clips(frames, lengths, torch.stack(boxes))
+
+
 def fine_collate(batch):
     clips = [b[0] for b in batch]
     labels = [b[1] for b in batch]
@@ -79,6 +117,13 @@ def fine_collate_u8(batch):
     labels = [b[1] for b in batch]
     tl_max = max(_t(lb).shape[1] for lb in labels)
     return [_pad_time_u8([b[0] for b in batch]), _pad_time(labels, 1, tl_max), _label_mask(labels, tl_max), [b[2] for b in batch]]
+
+
+def fine_collate_raw_u8(batch):
+    """fine_collate for samples ((frames (n,T,h,w,3) uint8, box (n,4)), label (157,TL), vid): untransformed frames + crop boxes"""
+    labels = [b[1] for b in batch]
+    tl_max = max(_t(lb).shape[1] for lb in labels)
+    return [_pad_raw_u8([b[0] for b in batch]), _pad_time(labels, 1, tl_max), _label_mask(labels, tl_max), [b[2] for b in batch]]
 
 
 def _coarse_rest(batch, cap):
@@ -106,3 +151,8 @@ def coarse_collate(batch, cap=128):
 def coarse_collate_u8(batch, cap=128):
     """coarse_collate for samples whose clips are uint8 (n,T,H,W,3)"""
     return [_pad_time_u8([b[0] for b in batch])] + _coarse_rest(batch, cap)
+
+
+def coarse_collate_raw_u8(batch, cap=128):
+    """coarse_collate for samples whose clips are (frames (n,T,h,w,3) uint8, box (n,4)) pairs: untransformed frames + crop boxes"""
+    return [_pad_raw_u8([b[0] for b in batch])] + _coarse_rest(batch, cap)

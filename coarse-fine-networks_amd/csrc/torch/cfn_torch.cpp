@@ -11,7 +11,7 @@
 //   cfn::time_sample / _backward          Grid Pool resampler      x3d_coarse.py:393-403
 // round 6: the remaining 13 pairs of the section-8(b) set -- dwconv_t5, stem_conv, conv3d_dense, bn_fold, bn_add_relu, affine_act, pool_hw, interp1d,
 // grid_cdf, gauss_align, fusion_gather, film, time_resize (each with its _backward) -- see the second half of this file.
-// uint8 input path: clip_lut (host table), clip_u8_to_f32, stem_conv_u8 + stem_conv_u8_backward (csrc/stem_u8.hip).
+// uint8 input path: clip_lut (host table), clip_u8_to_f32, stem_conv_u8 + stem_conv_u8_backward (csrc/stem_u8.hip); crop_resize_flip_u8 (csrc/aug_u8.hip).
 #include <ATen/ATen.h>
 // (a ROCm build of torch presents its HIP devices as "cuda": the masquerading guard / stream classes are the ones that accept them)
 #include <ATen/hip/impl/HIPGuardImplMasqueradingAsCUDA.h>
@@ -355,6 +355,34 @@ Tensor clip_u8_to_f32(const Tensor& frames, const Tensor& lut, OptT lengths) {
     const U8In u = u8_in(frames, lengths, lut, "cfn::clip_u8_to_f32");
     c10::hip::HIPGuardMasqueradingAsCUDA guard(frames.device());
     return clip_u8_to_f32_t(u);
+}
+
+// crop + antialiased bilinear resize + flip of uint8 frames (csrc/aug_u8.hip); the tap tables come from cfn_hip/u8aug.py.  A geometry the
+// kernel declines (-1) is an error: there is no other route.
+Tensor crop_resize_flip_u8(const Tensor& frames, OptT lengths, const Tensor& box, const Tensor& bounds, const Tensor& coef, int64_t size) {
+    const char* op = "cfn::crop_resize_flip_u8";
+    TORCH_CHECK(frames.is_cuda(), op, ": device tensors only (there is no CPU path)");
+    TORCH_CHECK(frames.scalar_type() == at::kByte && frames.dim() == 5 && frames.size(4) == 3, op, ": uint8 frames (N, T, Hs, Ws, 3) expected, got ", frames.scalar_type(), " ", frames.sizes());
+    const int64_t N = frames.size(0), T = frames.size(1), Hs = frames.size(2), Ws = frames.size(3), S = size;
+    TORCH_CHECK(S > 0, op, ": a positive output size expected, got ", S);
+    TORCH_CHECK(box.scalar_type() == at::kInt && box.numel() == 4 * N && box.device() == frames.device(), op, ": box (N, 4) int32 on the frames' device expected, got ", box.scalar_type(), " ", box.sizes());
+    TORCH_CHECK(bounds.scalar_type() == at::kInt && bounds.dim() == 3 && bounds.size(0) == N && bounds.size(1) == S && bounds.size(2) == 2 && bounds.device() == frames.device(),
+                op, ": bounds (N, size, 2) int32 on the frames' device expected, got ", bounds.scalar_type(), " ", bounds.sizes());
+    TORCH_CHECK(coef.scalar_type() == at::kInt && coef.dim() == 3 && coef.size(0) == N && coef.size(1) == S && coef.size(2) > 0 && coef.device() == frames.device(),
+                op, ": coef (N, size, K) int32 on the frames' device expected, got ", coef.scalar_type(), " ", coef.sizes());
+    Tensor len;
+    if (lengths.has_value() && lengths->defined()) {
+        TORCH_CHECK(lengths->numel() == N && lengths->device() == frames.device(), op, ": one length per clip on the frames' device expected, got ", lengths->sizes());
+        len = lengths->to(at::kInt).contiguous();
+    }
+    const Tensor f = frames.contiguous(), b = box.contiguous(), bd = bounds.contiguous(), cf = coef.contiguous();
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(frames.device());
+    Tensor out = at::empty({N, T, S, S, 3}, f.options());
+    const int rc = cfn_crop_resize_flip_u8(f.data_ptr<uint8_t>(), iptr(len), b.data_ptr<int>(), bd.data_ptr<int>(), cf.data_ptr<int>(), out.data_ptr<uint8_t>(), (int)N, (int)T, (int)Hs,
+                                           (int)Ws, (int)S, (int)coef.size(2), stream_of(out));
+    TORCH_CHECK(rc != -1, op, ": ", coef.size(2), " taps into size ", S, " is beyond what the kernel was built for (c <= 4 * size); there is no CPU fallback");
+    ok(rc, "cfn_crop_resize_flip_u8");
+    return out;
 }
 
 // shapes the fused kernels decline (-1): convert, then the fp32 entry point
@@ -875,6 +903,7 @@ TORCH_LIBRARY_FRAGMENT(cfn, m) {
     m.def("stem_conv_backward(Tensor gy, Tensor x, Tensor w) -> Tensor");
     m.def("clip_lut(float[] mean, float[] std, float norm_value=255.) -> Tensor", clip_lut);      // (host table, no tensor argument: one kernel for every key)
     m.def("clip_u8_to_f32(Tensor frames, Tensor lut, Tensor? lengths=None) -> Tensor");
+    m.def("crop_resize_flip_u8(Tensor frames, Tensor? lengths, Tensor box, Tensor bounds, Tensor coef, int size) -> Tensor");
     m.def("stem_conv_u8(Tensor frames, Tensor? lengths, Tensor lut, Tensor w) -> Tensor");
     m.def("stem_conv_u8_backward(Tensor gy, Tensor frames, Tensor? lengths, Tensor lut, Tensor w) -> Tensor");
     m.def("conv3d_dense(Tensor x, Tensor w, SymInt[] kernel, SymInt[] stride, SymInt[] padding, Tensor? A=None, Tensor? B=None, SymInt act=0) -> (Tensor, Tensor, Tensor)");
@@ -913,6 +942,7 @@ TORCH_LIBRARY_IMPL(cfn, CUDA, m) {      // (the HIP backend of a ROCm build of t
     m.impl("stem_conv", stem_conv);
     m.impl("stem_conv_backward", stem_conv_backward);
     m.impl("clip_u8_to_f32", clip_u8_to_f32);
+    m.impl("crop_resize_flip_u8", crop_resize_flip_u8);
     m.impl("stem_conv_u8", stem_conv_u8);
     m.impl("stem_conv_u8_backward", stem_conv_u8_backward);
     m.impl("conv3d_dense", conv3d_dense);

@@ -7,7 +7,9 @@ charades_coarse_fineFEAT.py:84-87):
 
 ``x3d_fine.generate_model(..., global_tower=True)`` produces them with the HIP path (adaptive (None,7,7)
 average pooling of every stage output, x3d_fine.py:339-363).  ``extract(videos)`` takes any iterable of
-(vid, clip (1,3,T,224,224)); the Charades frame reader itself is out of scope."""
+(vid, clip (1,3,T,224,224)); the Charades frame reader itself is out of scope.  A clip may also be uint8 frames:
+U8Clips (1,T,224,224,3), or RawU8Clips -- the frames as decoded plus a crop box (cfn_hip.u8aug.center_crop_params), cropped and
+resized on the GPU as the reference's CenterCropScaled does on the CPU (extract_fineFEAT.py:76)."""
 import os
 import sys
 
@@ -15,6 +17,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import x3d_fine                                   # noqa: E402
+from cfn_hip.u8clips import RawU8Clips            # noqa: E402
 
 FEAT_KEYS = ('layer1', 'layer2', 'layer3', 'layer4', 'conv5')
 
@@ -34,12 +37,15 @@ def build_tower(device, ckpt=None, n_classes=157, input_norm=None):
 
 
 @torch.no_grad()
-def extract(net, videos, save_dir, device='cuda'):
+def extract(net, videos, save_dir, device='cuda', crop=224):
     for k in FEAT_KEYS:
         os.makedirs(os.path.join(save_dir, k), exist_ok=True)
     n = 0
     for vid, clip in videos:
-        feat, _ = net([clip.to(device), None])
+        clip = clip.to(device)
+        if isinstance(clip, RawU8Clips):
+            clip = clip.transform(crop)
+        feat, _ = net([clip, None])
         for k in FEAT_KEYS:
             torch.save(feat[k].data.cpu(), os.path.join(save_dir, k, vid))
         n += 1

@@ -28,7 +28,7 @@ from cfn_hip import staging                       # noqa: E402
 from cfn_hip import dist as cdist                 # noqa: E402
 from apmeter import APMeter                       # noqa: E402
 from train_fine import lr_warmup, flatten_clips   # noqa: E402
-from cfn_hip.u8clips import U8Clips, CHARADES_MEAN, CHARADES_STD   # noqa: E402,F401
+from cfn_hip.u8clips import RawU8Clips, U8Clips, CHARADES_MEAN, CHARADES_STD   # noqa: E402,F401
 
 BS = 6
 BS_UPSCALE = 1
@@ -107,15 +107,23 @@ def param_groups(net, lr):
     return [{'params': base}, {'params': rw, 'lr': lr * 10}]
 
 
-def forward_video(net, inputs, feat, feat_masks, i, meta, t_lim=1000):
-    """whole-video inference with the reference's chunking of long videos (:215-224); inputs: fp32 clip or U8Clips"""
+CROP = 224                      # the X3D-M crop the coarse net runs at (train_coarse_fineFEAT.py:79-85)
+
+
+def forward_video(net, inputs, feat, feat_masks, i, meta, t_lim=1000, crop=CROP):
+    """whole-video inference with the reference's chunking of long videos (:215-224); inputs: fp32 clip, U8Clips, or RawU8Clips
+    (untransformed frames + crop boxes on the device: every chunk is cropped / resized to `crop` / flipped when its turn comes, so
+    the transformed video is never resident as a whole)"""
+    raw = isinstance(inputs, RawU8Clips)
     if inputs.shape[2] < t_lim + 5:
-        return net([inputs, feat, feat_masks, i, meta])
+        return net([inputs.transform(crop) if raw else inputs, feat, feat_masks, i, meta])
     outs = []
     meta = meta.clone()
     for t_ind in range(0, inputs.shape[2] // t_lim + 1):
         t0, t1 = t_ind * t_lim, min(inputs.shape[2], (t_ind + 1) * t_lim)
-        chunk = inputs.time_slice(t0, t1) if isinstance(inputs, U8Clips) else inputs[:, :, t0:t1].contiguous()
+        chunk = inputs.time_slice(t0, t1) if isinstance(inputs, (U8Clips, RawU8Clips)) else inputs[:, :, t0:t1].contiguous()
+        if raw:
+            chunk = chunk.transform(crop)
         outs.append(net([chunk, feat, feat_masks, i, meta]))
         meta[:, 0] += t_lim
     return torch.cat(outs, dim=2)
@@ -157,7 +165,8 @@ def run(init_lr=INIT_LR, warmup_steps=0, max_epochs=200, mode='rgb', root=None, 
         batch_size=BS * BS_UPSCALE, frames=80 * 4, dataloaders=None, max_steps=None,
         save_model='models/coarse_fineFEAT_charades_', pretrained='models/x3d_multigrid_kinetics_fb_pretrained.pt',
         csv_path='localize_corr_v1.csv', log=print, phase_hook=None, input_norm=None):
-    """input_norm: see build_model -- needed when the loaders collate uint8 frames (collate.coarse_collate_u8)."""
+    """input_norm: see build_model -- needed when the loaders collate uint8 frames (collate.coarse_collate_u8, or coarse_collate_raw_u8:
+    untransformed frames + crop boxes, transformed on the GPU -- per training batch, and per chunk of a validation video)."""
     rank, world, dev = cdist.init_from_env()
     gamma_tau = 5
     clip_frames = frames * 2 // (gamma_tau * 2)
@@ -198,7 +207,7 @@ def run(init_lr=INIT_LR, warmup_steps=0, max_epochs=200, mode='rgb', root=None, 
                     if not (cdist.all_agree(ok, dev) if world > 1 else ok):
                         continue
                 b, n = inputs.shape[:2]            # n crops per video at validation time (:198-201)
-                inputs = flatten_clips(inputs, dev)
+                inputs = flatten_clips(inputs, dev, CROP if train else None)      # validation: forward_video transforms chunk by chunk
                 labels, masks, feat_masks, meta = labels.to(dev), masks.to(dev), feat_masks.to(dev), meta.to(dev)
                 feat = {k: v.to(dev) for k, v in feat.items()}
                 valid_t = masks.sum(1).int()

@@ -27,7 +27,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import x3d_fine                                   # noqa: E402
 from cfn_hip import dist as cdist                 # noqa: E402
 from cfn_hip import staging                       # noqa: E402
-from cfn_hip.u8clips import U8Clips, CHARADES_MEAN, CHARADES_STD   # noqa: E402,F401
+from cfn_hip.u8clips import RawU8Clips, U8Clips, CHARADES_MEAN, CHARADES_STD   # noqa: E402,F401
 from apmeter import APMeter                       # noqa: E402
 
 BS = 8
@@ -119,8 +119,13 @@ def build_model(device, n_classes=NUM_CLASSES, pretrained=None, dropout=0.5, act
     return net.to(device)
 
 
-def flatten_clips(inputs, dev):
-    """(b, n crops, ...) -> (b * n, ...) on `dev`: an fp32 clip tensor (b, n, 3, T, H, W) or a U8Clips batch"""
+def flatten_clips(inputs, dev, crop=None):
+    """(b, n crops, ...) -> (b * n, ...) on `dev`: an fp32 clip tensor (b, n, 3, T, H, W), a U8Clips batch, or a RawU8Clips batch
+    (frames as decoded + crop boxes, collate.fine_collate_raw_u8), which is cropped, resized to `crop` x `crop` and flipped on `dev`, on
+    the current stream, into the U8Clips batch the net takes (crop=None: handed on as it is)"""
+    if isinstance(inputs, RawU8Clips):
+        raw = inputs.flatten_crops().to(dev, non_blocking=True)
+        return raw if crop is None else raw.transform(crop)
     if isinstance(inputs, U8Clips):
         return inputs.flatten_crops().to(dev, non_blocking=True)
     b, n = inputs.shape[:2]
@@ -246,7 +251,8 @@ def _ap_rows(probs, labels, valid_t):
 def run(init_lr=INIT_LR, warmup_steps=0, max_epochs=200, mode='rgb', root=None, train_split=None,
         batch_size=BS * BS_UPSCALE, frames=80 * 4, dataloaders=None, max_steps=None, save_model='models/fine_charades_',
         pretrained='models/x3d_multigrid_kinetics_fb_pretrained.pt', log=print, phase_hook=None, input_norm=None):
-    """input_norm: see build_model -- needed when the loaders collate uint8 frames (collate.fine_collate_u8)."""
+    """input_norm: see build_model -- needed when the loaders collate uint8 frames (collate.fine_collate_u8, or fine_collate_raw_u8:
+    untransformed frames + crop boxes, cropped / resized to the model's crop size / flipped on the GPU in front of the step)."""
     rank, world, dev = cdist.init_from_env()
     gamma_tau = {'S': 6, 'M': 5, 'XL': 5}[X3D_VERSION]
     crop = {'S': 160, 'M': 224, 'XL': 312}[X3D_VERSION]
@@ -288,7 +294,7 @@ def run(init_lr=INIT_LR, warmup_steps=0, max_epochs=200, mode='rgb', root=None, 
                 if not ok:
                     continue
                 b, n = inputs.shape[:2]          # n crops per video (1 in training, train_fine.py:176-185)
-                inputs = flatten_clips(inputs, dev)
+                inputs = flatten_clips(inputs, dev, crop)
                 labels, masks = labels.to(dev), masks.to(dev)
                 valid_t = masks.sum(1).int()
                 n_it += 1

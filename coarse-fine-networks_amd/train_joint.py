@@ -121,12 +121,16 @@ def train_step(fine, coarse, reducer, optimizer, clip, labels, masks, pre_step=N
 
 
 def run(init_lr=INIT_LR, warmup_steps=0, max_steps=None, batch_size=BS, fine_frames=128, coarse_frames=64, dataloader=None,
-        pretrained_fine=None, pretrained_coarse=None, save_model='models/joint_charades_', log=print, fine_act_dtype=None, coarse_act_dtype=None):
+        pretrained_fine=None, pretrained_coarse=None, save_model='models/joint_charades_', log=print, fine_act_dtype=None, coarse_act_dtype=None,
+        input_norm=None, crop=tc.CROP):
+    """input_norm: see build_models -- needed when the loader yields the clip as uint8 frames: U8Clips, or RawU8Clips (untransformed
+    frames + crop boxes), which is cropped / resized to `crop` / flipped on the GPU in front of the step."""
     rank, world, dev = cdist.init_from_env()
     local_bs = max(batch_size // world, 1)
     if dataloader is None:
         dataloader = SyntheticJoint(local_bs, tc.CHARADES_TR_SIZE // batch_size, fine_frames, coarse_frames, seed=rank)
-    fine, coarse = build_models(dev, pretrained_fine, pretrained_coarse, fine_act_dtype=fine_act_dtype, coarse_act_dtype=coarse_act_dtype)
+    fine, coarse = build_models(dev, pretrained_fine, pretrained_coarse, fine_act_dtype=fine_act_dtype, coarse_act_dtype=coarse_act_dtype,
+                                input_norm=input_norm)
     cdist.sync_module(fine)
     cdist.sync_module(coarse)
     groups = param_groups(fine, coarse, init_lr)
@@ -141,7 +145,10 @@ def run(init_lr=INIT_LR, warmup_steps=0, max_steps=None, batch_size=BS, fine_fra
         if not (cdist.all_agree(ok, dev) if world > 1 else ok):
             continue
         warm = (lambda: lr_warmup(init_lr, steps, warmup_steps, optimizer))
-        cls_loss, loc_loss, _ = train_step(fine, coarse, reducer, optimizer, clip.to(dev), labels.to(dev), masks.to(dev), warm)
+        clip = clip.to(dev)
+        if isinstance(clip, tc.RawU8Clips):
+            clip = clip.transform(crop)
+        cls_loss, loc_loss, _ = train_step(fine, coarse, reducer, optimizer, clip, labels.to(dev), masks.to(dev), warm)
         steps += 1
         if steps % 50 == 0 or max_steps is not None:
             m_loc, m_cls = cdist.mean_over_ranks([float(loc_loss), float(cls_loss)], dev)

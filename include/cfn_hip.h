@@ -405,6 +405,23 @@ int cfn_pool_hw_fwd_f16(const unsigned short* x, const double* A, const double* 
 int cfn_pool_hw_bwd_f16(const float* gout, const unsigned short* x, const double* A, const double* B, int act,
                          unsigned short* gx, double* gA, double* gB, long NC, int T, int H, int W, int OH, int OW, void* stream);
 
+/* =====================================================================================================================
+ * Spatial augmentation of uint8 frames on the GPU (csrc/aug_u8.hip): square crop, antialiased bilinear resize and horizontal
+ * flip, bit-exact to PIL's 8-bit Image.resize(BILINEAR).  Replaces the reference's per-frame CPU transforms
+ * MultiScaleRandomCropMultigrid + RandomHorizontalFlip (train_fine.py:74-77, train_coarse_fineFEAT.py:79-82;
+ * transforms/spatial_transforms.py:480-510, :339-357) and CenterCropScaled (train_fine.py:78, extract_fineFEAT.py:76;
+ * spatial_transforms.py:201-230).
+ *   src (N,T,Hs,Ws,3) uint8, each clip's picture in the top-left corner; box (N,4) = x1, y1, c, flip; bounds (N,S,2) = xmin, n and
+ *   coef (N,S,K) = 22-bit fixed-point taps of the c -> S resize, zero behind n (cfn_hip/u8aug.py builds them on the host; one table
+ *   serves both axes); dst (N,T,S,S,3); lengths (N) or NULL: frames t >= lengths[n] are written as zero bytes.
+ * Horizontal pass first, rounded to uint8, then the vertical pass on those bytes; int32 accumulators.  One launch on `stream`, no
+ * allocation (capturable).  Every source read is checked against the extent of src: a bad box gives wrong bytes, never a fault.
+ * Returns 1 for null pointers / non-positive sizes, -1 with nothing launched for K > 9 (c > 4 * S) or an S too wide for the
+ * kernel's LDS image (64 KB: S <= 312 at K = 9).
+ * ===================================================================================================================== */
+int cfn_crop_resize_flip_u8(const unsigned char* src, const int* lengths, const int* box, const int* bounds, const int* coef,
+                            unsigned char* dst, int N, int T, int Hs, int Ws, int S, int K, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

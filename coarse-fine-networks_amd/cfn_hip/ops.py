@@ -709,6 +709,81 @@ def crop_resize_flip_u8(frames, lengths, box, size, out=None, tables=None):
     return out
 
 
+# ---- per-class average precision on the GPU (csrc/apmeter.hip; the meter: apmeter.DeviceAPMeter) -----------------------------------
+AP_SORT_TILE = 8192              # rows per tile of cfn_ap_sort (cfn_ap_sort_tile(); tests place sizes on its edges)
+AP_FLAG_NONBINARY, AP_FLAG_OVERFLOW = 1, 2
+
+
+def _ap_stores(scores, targets, count, what):
+    for name, x in (('scores', scores), ('targets', targets), ('count', count)):
+        if not torch.is_tensor(x) or not x.is_cuda:
+            raise RuntimeError('%s: %s must be a device tensor; there is no CPU path' % (what, name))
+    if scores.dtype != torch.float32 or scores.dim() != 2 or targets.dtype != torch.uint8 or tuple(targets.shape) != tuple(scores.shape):
+        raise RuntimeError('%s: class-major stores expected, scores (K, cap) fp32 and targets (K, cap) uint8; got %s %s, %s %s'
+                           % (what, scores.dtype, tuple(scores.shape), targets.dtype, tuple(targets.shape)))
+    if count.dtype != torch.int32 or count.numel() != 1:
+        raise RuntimeError('%s: count must be one int32 on the device, got %s %s' % (what, count.dtype, tuple(count.shape)))
+    if scores.shape[0] < 1 or scores.shape[1] < 1:
+        raise RuntimeError('%s: empty stores %s' % (what, tuple(scores.shape)))
+    return int(scores.shape[0]), int(scores.shape[1])
+
+
+def ap_append(probs, labels, valid, scores, targets, count, flags):
+    """Append a batch to class-major AP stores, in place, without reading anything back: probs / labels (B, K, TL) fp32 on the device,
+    valid (B,) int32 on the device or None (every frame); video b contributes its first min(valid[b], TL) frames, videos in batch
+    order (train_fine._ap_rows).  scores (K, cap) fp32, targets (K, cap) uint8, count and flags one int32 each, all on the device.
+    A batch that does not fit sets AP_FLAG_OVERFLOW in flags and writes nothing; a label other than 0 / 1 sets AP_FLAG_NONBINARY."""
+    K, cap = _ap_stores(scores, targets, count, 'ap_append')
+    for name, x in (('probs', probs), ('labels', labels), ('flags', flags)):
+        if not torch.is_tensor(x) or not x.is_cuda:
+            raise RuntimeError('ap_append: %s must be a device tensor; there is no CPU path' % name)
+    if probs.dim() != 3 or probs.shape[1] != K or tuple(labels.shape) != tuple(probs.shape):
+        raise RuntimeError('ap_append: probs and labels (B, %d, TL) expected, got %s and %s' % (K, tuple(probs.shape), tuple(labels.shape)))
+    if flags.dtype != torch.int32 or flags.numel() != 1:
+        raise RuntimeError('ap_append: flags must be one int32 on the device')
+    B, _, TL = probs.shape
+    if valid is not None:
+        if valid.numel() != B:
+            raise RuntimeError('ap_append: one valid length per video expected: %d videos, valid %s' % (B, tuple(valid.shape)))
+        valid = valid.to(torch.int32).contiguous()
+    call('cfn_ap_append', probs.float().contiguous(), labels.float().contiguous(), valid, scores, targets, count, flags, B, K, TL, cap)
+
+
+def ap_sort(scores, targets, count, out=None):
+    """Stable descending sort of rows 0 .. count - 1 of every class: scores (K, cap) fp32, targets (K, cap) uint8, count one int32
+    on the device -> (sorted_scores, sorted_targets) of the same shapes; rows behind count are not written.  The sorted scores are
+    canonical (+0.0 for -0.0, one NaN pattern for every NaN).  out = (sorted_scores, sorted_targets, tmp_keys int32, tmp_targets):
+    buffers to reuse; allocated with torch otherwise."""
+    K, cap = _ap_stores(scores, targets, count, 'ap_sort')
+    if out is None:
+        out = (torch.empty_like(scores), torch.empty_like(targets), torch.empty(K, cap, dtype=torch.int32, device=scores.device),
+               torch.empty_like(targets))
+    ss, st, tk, tt = out
+    for x, ref, dt in ((ss, scores, torch.float32), (st, targets, torch.uint8), (tk, scores, torch.int32), (tt, targets, torch.uint8)):
+        if tuple(x.shape) != tuple(ref.shape) or x.dtype != dt or x.device != ref.device:
+            raise RuntimeError('ap_sort: out buffers of shape %s (fp32, uint8, int32, uint8) on %s expected' % (tuple(ref.shape), ref.device))
+    call('cfn_ap_sort', scores, targets, count, ss, st, tk, tt, K, cap)
+    return ss, st
+
+
+def ap_reduce(sorted_targets, count):
+    """(K, cap) uint8 sorted target bytes -> (K,) fp32 AP over the first count rows (a class without a positive: 0)"""
+    if not sorted_targets.is_cuda or not count.is_cuda:
+        raise RuntimeError('ap_reduce: device tensors only; there is no CPU path')
+    if sorted_targets.dtype != torch.uint8 or sorted_targets.dim() != 2 or count.dtype != torch.int32 or count.numel() != 1:
+        raise RuntimeError('ap_reduce: sorted targets (K, cap) uint8 and one int32 count expected')
+    K, cap = sorted_targets.shape
+    ap = torch.empty(K, dtype=torch.float32, device=sorted_targets.device)
+    call('cfn_ap_reduce', sorted_targets, count, ap, K, cap)
+    return ap
+
+
+def average_precision(scores, targets, count, out=None):
+    """(K,) fp32 per-class AP of the first count rows of class-major stores, on the device: ap_sort + ap_reduce (nothing is read back)"""
+    _, st = ap_sort(scores, targets, count, out=out)
+    return ap_reduce(st, count)
+
+
 class _BnFold(Function):
     """(sum, sumsq) of a conv output -> per-(n,c) prologue (A, B); optional fused SE gate.  cfn_bn_fold_*."""
 

@@ -897,12 +897,46 @@ def _(frames, lengths, box, bounds, coef, size):
     return frames.new_empty((N, T, size, size, 3), dtype=torch.uint8)
 
 
+# ---- per-class average precision on the GPU (csrc/apmeter.hip): class-major stores on the device, no gradient ------------------------------
+@_op('ap_append', mutates_args=('scores', 'targets', 'count', 'flags'))
+def ap_append(probs: torch.Tensor, labels: torch.Tensor, valid: Optional[torch.Tensor], scores: torch.Tensor, targets: torch.Tensor,
+              count: torch.Tensor, flags: torch.Tensor) -> None:
+    _ops.ap_append(probs, labels, valid, scores, targets, count, flags)
+
+
+@ap_append.register_fake
+def _(probs, labels, valid, scores, targets, count, flags):
+    return None
+
+
+@_op('ap_sort')
+def ap_sort(scores: torch.Tensor, targets: torch.Tensor, count: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    return _ops.ap_sort(scores, targets, count)
+
+
+@ap_sort.register_fake
+def _(scores, targets, count):
+    return torch.empty_like(scores), torch.empty_like(targets)
+
+
+@_op('average_precision')
+def average_precision(scores: torch.Tensor, targets: torch.Tensor, count: torch.Tensor) -> torch.Tensor:
+    return _ops.average_precision(scores, targets, count)
+
+
+@average_precision.register_fake
+def _(scores, targets, count):
+    return scores.new_empty((scores.shape[0],), dtype=torch.float32)
+
+
 OPERATORS = ('dwconv3d', 'pwconv', 'time_sample', 'dwconv_t5', 'stem_conv', 'conv3d_dense', 'bn_fold', 'bn_add_relu', 'affine_act',
              'pool_hw', 'interp1d', 'grid_cdf', 'gauss_align', 'fusion_gather', 'film', 'time_resize', 'stem_conv_u8')
 # the uint8 input path's operators without a gradient (the host-built table, the frames -> fp32 clip converter)
 INPUT_OPERATORS = ('clip_lut', 'clip_u8_to_f32')
 # spatial augmentation of uint8 frames on the GPU (no gradient)
 AUGMENT_OPERATORS = ('crop_resize_flip_u8',)
+# device-resident average precision (no gradient; ap_append mutates its stores)
+METRIC_OPERATORS = ('ap_append', 'ap_sort', 'average_precision')
 
 
 # ---------------------------------------------------------------------------------------------------------------------------

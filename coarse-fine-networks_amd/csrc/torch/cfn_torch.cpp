@@ -12,6 +12,7 @@
 // round 6: the remaining 13 pairs of the section-8(b) set -- dwconv_t5, stem_conv, conv3d_dense, bn_fold, bn_add_relu, affine_act, pool_hw, interp1d,
 // grid_cdf, gauss_align, fusion_gather, film, time_resize (each with its _backward) -- see the second half of this file.
 // uint8 input path: clip_lut (host table), clip_u8_to_f32, stem_conv_u8 + stem_conv_u8_backward (csrc/stem_u8.hip); crop_resize_flip_u8 (csrc/aug_u8.hip).
+// metrics: ap_append (mutates its stores), ap_sort, average_precision (csrc/apmeter.hip) -- no gradients.
 #include <ATen/ATen.h>
 // (a ROCm build of torch presents its HIP devices as "cuda": the masquerading guard / stream classes are the ones that accept them)
 #include <ATen/hip/impl/HIPGuardImplMasqueradingAsCUDA.h>
@@ -383,6 +384,56 @@ Tensor crop_resize_flip_u8(const Tensor& frames, OptT lengths, const Tensor& box
     TORCH_CHECK(rc != -1, op, ": ", coef.size(2), " taps into size ", S, " is beyond what the kernel was built for (c <= 4 * size); there is no CPU fallback");
     ok(rc, "cfn_crop_resize_flip_u8");
     return out;
+}
+
+// ---- per-class average precision on the GPU (csrc/apmeter.hip; apmeter.DeviceAPMeter) ----------------------------------------------------------
+// class-major stores scores (K, cap) fp32 / targets (K, cap) uint8, the row count and the flag word one int32 each ON THE DEVICE: nothing is read back
+struct ApStores { int64_t K, cap; };
+inline ApStores ap_stores(const Tensor& scores, const Tensor& targets, const Tensor& count, const char* op) {
+    TORCH_CHECK(scores.is_cuda(), op, ": device tensors only (there is no CPU path)");
+    TORCH_CHECK(scores.scalar_type() == at::kFloat && scores.dim() == 2 && scores.size(0) > 0 && scores.size(1) > 0 && scores.is_contiguous(), op,
+                ": scores must be a contiguous (K, cap) fp32 store, got ", scores.scalar_type(), " ", scores.sizes());
+    TORCH_CHECK(targets.scalar_type() == at::kByte && targets.sizes() == scores.sizes() && targets.is_contiguous() && targets.device() == scores.device(), op,
+                ": targets must be a contiguous uint8 store of the shape of scores on its device, got ", targets.scalar_type(), " ", targets.sizes());
+    TORCH_CHECK(count.scalar_type() == at::kInt && count.numel() == 1 && count.device() == scores.device(), op, ": count must be one int32 on the stores' device");
+    return {scores.size(0), scores.size(1)};
+}
+
+void ap_append(const Tensor& probs, const Tensor& labels, OptT valid, Tensor scores, Tensor targets, Tensor count, Tensor flags) {
+    const char* op = "cfn::ap_append";
+    const ApStores s = ap_stores(scores, targets, count, op);
+    TORCH_CHECK(flags.scalar_type() == at::kInt && flags.numel() == 1 && flags.device() == scores.device(), op, ": flags must be one int32 on the stores' device");
+    TORCH_CHECK(probs.dim() == 3 && probs.size(0) > 0 && probs.size(1) == s.K && probs.size(2) > 0 && probs.scalar_type() == at::kFloat && probs.device() == scores.device(), op,
+                ": probs (B, ", s.K, ", TL) fp32 on the stores' device expected, got ", probs.scalar_type(), " ", probs.sizes());
+    check_like(labels, probs, op, "labels", "probs");
+    const int64_t B = probs.size(0), TL = probs.size(2);
+    Tensor v;
+    if (valid.has_value() && valid->defined()) {
+        TORCH_CHECK(valid->numel() == B && valid->device() == scores.device(), op, ": one valid length per video on the stores' device expected, got ", valid->sizes());
+        v = valid->to(at::kInt).contiguous();
+    }
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(scores.device());
+    const Tensor p = probs.contiguous(), l = labels.contiguous();
+    ok(cfn_ap_append(p.data_ptr<float>(), l.data_ptr<float>(), iptr(v), scores.data_ptr<float>(), targets.data_ptr<uint8_t>(), count.data_ptr<int>(), flags.data_ptr<int>(),
+                     (int)B, (int)s.K, (int)TL, (long)s.cap, stream_of(scores)), "cfn_ap_append");
+}
+
+std::tuple<Tensor, Tensor> ap_sort(const Tensor& scores, const Tensor& targets, const Tensor& count) {
+    const ApStores s = ap_stores(scores, targets, count, "cfn::ap_sort");
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(scores.device());
+    Tensor ss = at::empty_like(scores), st = at::empty_like(targets), tk = at::empty({s.K, s.cap}, scores.options().dtype(at::kInt)), tt = at::empty_like(targets);
+    ok(cfn_ap_sort(scores.data_ptr<float>(), targets.data_ptr<uint8_t>(), count.data_ptr<int>(), ss.data_ptr<float>(), st.data_ptr<uint8_t>(), tk.data_ptr<int>(),
+                   tt.data_ptr<uint8_t>(), (int)s.K, (long)s.cap, stream_of(scores)), "cfn_ap_sort");
+    return {ss, st};
+}
+
+Tensor average_precision(const Tensor& scores, const Tensor& targets, const Tensor& count) {
+    const ApStores s = ap_stores(scores, targets, count, "cfn::average_precision");
+    const auto sorted = ap_sort(scores, targets, count);
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(scores.device());
+    Tensor ap = at::empty({s.K}, scores.options());
+    ok(cfn_ap_reduce(std::get<1>(sorted).data_ptr<uint8_t>(), count.data_ptr<int>(), ap.data_ptr<float>(), (int)s.K, (long)s.cap, stream_of(scores)), "cfn_ap_reduce");
+    return ap;
 }
 
 // shapes the fused kernels decline (-1): convert, then the fp32 entry point
@@ -904,6 +955,9 @@ TORCH_LIBRARY_FRAGMENT(cfn, m) {
     m.def("clip_lut(float[] mean, float[] std, float norm_value=255.) -> Tensor", clip_lut);      // (host table, no tensor argument: one kernel for every key)
     m.def("clip_u8_to_f32(Tensor frames, Tensor lut, Tensor? lengths=None) -> Tensor");
     m.def("crop_resize_flip_u8(Tensor frames, Tensor? lengths, Tensor box, Tensor bounds, Tensor coef, int size) -> Tensor");
+    m.def("ap_append(Tensor probs, Tensor labels, Tensor? valid, Tensor(a!) scores, Tensor(b!) targets, Tensor(c!) count, Tensor(d!) flags) -> ()");
+    m.def("ap_sort(Tensor scores, Tensor targets, Tensor count) -> (Tensor, Tensor)");
+    m.def("average_precision(Tensor scores, Tensor targets, Tensor count) -> Tensor");
     m.def("stem_conv_u8(Tensor frames, Tensor? lengths, Tensor lut, Tensor w) -> Tensor");
     m.def("stem_conv_u8_backward(Tensor gy, Tensor frames, Tensor? lengths, Tensor lut, Tensor w) -> Tensor");
     m.def("conv3d_dense(Tensor x, Tensor w, SymInt[] kernel, SymInt[] stride, SymInt[] padding, Tensor? A=None, Tensor? B=None, SymInt act=0) -> (Tensor, Tensor, Tensor)");
@@ -943,6 +997,9 @@ TORCH_LIBRARY_IMPL(cfn, CUDA, m) {      // (the HIP backend of a ROCm build of t
     m.impl("stem_conv_backward", stem_conv_backward);
     m.impl("clip_u8_to_f32", clip_u8_to_f32);
     m.impl("crop_resize_flip_u8", crop_resize_flip_u8);
+    m.impl("ap_append", ap_append);
+    m.impl("ap_sort", ap_sort);
+    m.impl("average_precision", average_precision);
     m.impl("stem_conv_u8", stem_conv_u8);
     m.impl("stem_conv_u8_backward", stem_conv_u8_backward);
     m.impl("conv3d_dense", conv3d_dense);

@@ -27,6 +27,7 @@ import x3d_coarse                                 # noqa: E402
 from cfn_hip import staging                       # noqa: E402
 from cfn_hip import dist as cdist                 # noqa: E402
 from apmeter import APMeter                       # noqa: E402
+from cfn_hip import metrics                       # noqa: E402
 from train_fine import lr_warmup, flatten_clips   # noqa: E402
 from cfn_hip.u8clips import RawU8Clips, U8Clips, CHARADES_MEAN, CHARADES_STD   # noqa: E402,F401
 
@@ -164,9 +165,10 @@ def localize_rows(probs, labels, valid_t, names, dur):
 def run(init_lr=INIT_LR, warmup_steps=0, max_epochs=200, mode='rgb', root=None, train_split=None,
         batch_size=BS * BS_UPSCALE, frames=80 * 4, dataloaders=None, max_steps=None,
         save_model='models/coarse_fineFEAT_charades_', pretrained='models/x3d_multigrid_kinetics_fb_pretrained.pt',
-        csv_path='localize_corr_v1.csv', log=print, phase_hook=None, input_norm=None):
+        csv_path='localize_corr_v1.csv', log=print, phase_hook=None, input_norm=None, device_ap=False):
     """input_norm: see build_model -- needed when the loaders collate uint8 frames (collate.coarse_collate_u8, or coarse_collate_raw_u8:
-    untransformed frames + crop boxes, transformed on the GPU -- per training batch, and per chunk of a validation video)."""
+    untransformed frames + crop boxes, transformed on the GPU -- per training batch, and per chunk of a validation video).
+    device_ap: the training phases keep their AP rows and loss totals on the GPU (cfn_hip.metrics.StepMetrics): no read-back per step."""
     rank, world, dev = cdist.init_from_env()
     gamma_tau = 5
     clip_frames = frames * 2 // (gamma_tau * 2)
@@ -180,7 +182,7 @@ def run(init_lr=INIT_LR, warmup_steps=0, max_epochs=200, mode='rgb', root=None, 
     optimizer = optim.SGD(param_groups(net, init_lr), lr=init_lr, momentum=0.9, weight_decay=1e-5)
     lr_sched = optim.lr_scheduler.MultiStepLR(optimizer, [15, 25, 35])
     reducer = cdist.GradReducer(net.parameters())
-    tr_apm, val_apm = APMeter(), APMeter()
+    tr, val_apm = metrics.StepMetrics(device_ap, dev), APMeter()
     writer = write_file = None
     if rank == 0 and csv_path:
         write_file = open(csv_path, 'w', newline='\n')
@@ -201,6 +203,7 @@ def run(init_lr=INIT_LR, warmup_steps=0, max_epochs=200, mode='rgb', root=None, 
             tot_loc = tot_cls = 0.0
             n_it = 0
             val_rows = []
+            tr.start_phase()
             for i, (inputs, labels, masks, feat, feat_masks, meta, name, dur) in enumerate(stager.stage(dataloaders[phase]) if stager else dataloaders[phase]):
                 if train:     # collective skip of a short last batch (:193-194)
                     ok = inputs.shape[0] == local_bs
@@ -217,22 +220,21 @@ def run(init_lr=INIT_LR, warmup_steps=0, max_epochs=200, mode='rgb', root=None, 
                     cls_loss, loc_loss, probs = train_step(net, reducer, optimizer, inputs, labels, masks, feat, feat_masks, meta,
                                                            i, pre_step=warm)
                     steps += 1
-                    for bb in range(labels.shape[0]):
-                        v = int(valid_t[bb])
-                        tr_apm.add(probs[bb][:, :v].transpose(0, 1).cpu().numpy(), labels[bb][:, :v].transpose(0, 1).cpu().numpy())
+                    tr.update(cls_loss, loc_loss, probs, labels, valid_t)
                 else:
                     with torch.no_grad():
                         logits = forward_video(net, inputs, feat, feat_masks, i, meta)
                         cls_loss, loc_loss, probs = detection_loss(logits, labels, masks, crops=n, local_norm=True)
                     val_rows.extend(localize_rows(probs, labels, valid_t, name, dur))
-                tot_cls += float(cls_loss)
-                tot_loc += float(loc_loss)
+                    tot_cls += float(cls_loss)
+                    tot_loc += float(loc_loss)
                 if train and steps % max(iters // 2, 1) == 0:
-                    m_loc, m_cls = cdist.mean_over_ranks([tot_loc / n_it, tot_cls / n_it], dev)
+                    t_loc, t_cls = tr.totals()
+                    m_loc, m_cls = cdist.mean_over_ranks([t_loc / n_it, t_cls / n_it], dev)
                     if rank == 0:
                         log(' Epoch:{} {} steps: {} Loc Loss: {:.4f} Cls Loss: {:.4f} mAP: {:.4f}'.format(
-                            epochs, phase, steps, m_loc, m_cls, _mean_ap(tr_apm)))
-                    tr_apm.reset()
+                            epochs, phase, steps, m_loc, m_cls, tr.mean_ap()))
+                    tr.reset_ap()
                 if train and steps % 1000 == 0 and rank == 0:
                     os.makedirs(os.path.dirname(save_model) or '.', exist_ok=True)
                     torch.save({'model_state_dict': net.state_dict(), 'optimizer_state_dict': optimizer.state_dict(),
@@ -270,6 +272,7 @@ if __name__ == '__main__':
     parser.add_argument('-gpu', default='0', type=str)
     parser.add_argument('--max-steps', type=int, default=None)
     parser.add_argument('--batch-size', type=int, default=BS * BS_UPSCALE)
+    parser.add_argument('--device-ap', action='store_true', help='training AP rows and loss totals stay on the GPU')
     args = parser.parse_args()
     if 'RANK' not in os.environ and len(args.gpu.split(',')) > 1:
         from train_fine import _spawn
@@ -279,7 +282,7 @@ if __name__ == '__main__':
         sys.exit(subprocess.call([sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', str(n),
                                   '--master-addr', '127.0.0.1', '--master-port', os.environ.get('MASTER_PORT', '29512'),
                                   os.path.abspath(__file__), '--batch-size', str(args.batch_size)] +
-                                 (['--max-steps', str(args.max_steps)] if args.max_steps else []), env=env))
+                                 (['--max-steps', str(args.max_steps)] if args.max_steps else []) + (['--device-ap'] if args.device_ap else []), env=env))
     if 'RANK' not in os.environ:
         os.environ['CUDA_VISIBLE_DEVICES'] = args.gpu
-    run(batch_size=args.batch_size, max_steps=args.max_steps)
+    run(batch_size=args.batch_size, max_steps=args.max_steps, device_ap=args.device_ap)

@@ -29,6 +29,7 @@ from cfn_hip import dist as cdist                 # noqa: E402
 from cfn_hip import staging                       # noqa: E402
 from cfn_hip.u8clips import RawU8Clips, U8Clips, CHARADES_MEAN, CHARADES_STD   # noqa: E402,F401
 from apmeter import APMeter                       # noqa: E402
+from cfn_hip import metrics                       # noqa: E402
 
 BS = 8
 BS_UPSCALE = 1
@@ -239,20 +240,17 @@ def train_step(net, reducer, optimizer, inputs, labels, masks, gamma_tau=5, pre_
     return cls_loss, loc_loss, probs
 
 
-def _ap_rows(probs, labels, valid_t):
-    """per video: (scores (v,157), targets (v,157)) numpy over the valid frames -- what APMeter.add takes"""
-    rows = []
-    for i in range(labels.shape[0]):
-        v = int(valid_t[i])
-        rows.append((probs[i][:, :v].transpose(0, 1).cpu().numpy(), labels[i][:, :v].transpose(0, 1).cpu().numpy()))
-    return rows
+_ap_rows = metrics.ap_rows      # per video: (scores (v,157), targets (v,157)) numpy over the valid frames -- what APMeter.add takes
 
 
 def run(init_lr=INIT_LR, warmup_steps=0, max_epochs=200, mode='rgb', root=None, train_split=None,
         batch_size=BS * BS_UPSCALE, frames=80 * 4, dataloaders=None, max_steps=None, save_model='models/fine_charades_',
-        pretrained='models/x3d_multigrid_kinetics_fb_pretrained.pt', log=print, phase_hook=None, input_norm=None):
+        pretrained='models/x3d_multigrid_kinetics_fb_pretrained.pt', log=print, phase_hook=None, input_norm=None,
+        device_ap=False):
     """input_norm: see build_model -- needed when the loaders collate uint8 frames (collate.fine_collate_u8, or fine_collate_raw_u8:
-    untransformed frames + crop boxes, cropped / resized to the model's crop size / flipped on the GPU in front of the step)."""
+    untransformed frames + crop boxes, cropped / resized to the model's crop size / flipped on the GPU in front of the step).
+    device_ap: the training phases keep their AP rows and loss totals on the GPU (cfn_hip.metrics.StepMetrics, apmeter.DeviceAPMeter):
+    no read-back per step, the host waits for the device only where a line is logged."""
     rank, world, dev = cdist.init_from_env()
     gamma_tau = {'S': 6, 'M': 5, 'XL': 5}[X3D_VERSION]
     crop = {'S': 160, 'M': 224, 'XL': 312}[X3D_VERSION]
@@ -269,7 +267,7 @@ def run(init_lr=INIT_LR, warmup_steps=0, max_epochs=200, mode='rgb', root=None, 
     optimizer = optim.SGD(net.parameters(), lr=init_lr, momentum=0.9, weight_decay=1e-5)
     lr_sched = optim.lr_scheduler.MultiStepLR(optimizer, [15, 20, 25])
     reducer = cdist.GradReducer(net.parameters())
-    tr_apm, val_apm = APMeter(), APMeter()
+    tr, val_apm = metrics.StepMetrics(device_ap, dev), APMeter()
     # batches reach HBM through a pinned slab on a copy stream, one batch ahead of the step (the reference: a synchronous `.cuda()` per tensor
     # in front of every step, train_fine.py:184-197); the `.to(dev)` calls below are no-ops on staged batches
     stager = staging.HostStager(dev) if dev.type == 'cuda' else None
@@ -286,6 +284,7 @@ def run(init_lr=INIT_LR, warmup_steps=0, max_epochs=200, mode='rgb', root=None, 
             tot_loc = tot_cls = 0.0
             n_it = 0
             val_rows = []
+            tr.start_phase()
             for inputs, labels, masks, _name in (stager.stage(dataloaders[phase]) if stager else dataloaders[phase]):
                 want = local_bs if train else val_bs
                 ok = inputs.shape[0] == want
@@ -302,21 +301,21 @@ def run(init_lr=INIT_LR, warmup_steps=0, max_epochs=200, mode='rgb', root=None, 
                     warm = (lambda: lr_warmup(init_lr, steps, warmup_steps, optimizer))
                     cls_loss, loc_loss, probs = train_step(net, reducer, optimizer, inputs, labels, masks, gamma_tau, pre_step=warm)
                     steps += 1
-                    for sc, tg in _ap_rows(probs, labels, valid_t):
-                        tr_apm.add(sc, tg)
+                    tr.update(cls_loss, loc_loss, probs, labels, valid_t)
                 else:
                     with torch.no_grad():
                         logits = net([inputs, masks[:, ::gamma_tau * 2]])
                         cls_loss, loc_loss, probs = detection_loss(logits, labels, masks, True, crops=n, local_norm=True)
                     val_rows.extend(_ap_rows(probs, labels, valid_t))
-                tot_cls += float(cls_loss)
-                tot_loc += float(loc_loss)
+                    tot_cls += float(cls_loss)
+                    tot_loc += float(loc_loss)
                 if train and steps % max(iters // 2, 1) == 0:
-                    m_loc, m_cls = cdist.mean_over_ranks([tot_loc / n_it, tot_cls / n_it], dev)
+                    t_loc, t_cls = tr.totals()
+                    m_loc, m_cls = cdist.mean_over_ranks([t_loc / n_it, t_cls / n_it], dev)
                     if rank == 0:
                         log(' Epoch:{} {} steps: {} Loc Loss: {:.4f} Cls Loss: {:.4f} mAP: {:.4f}'.format(
-                            epochs, phase, steps, m_loc, m_cls, _mean_ap(tr_apm)))
-                    tr_apm.reset()
+                            epochs, phase, steps, m_loc, m_cls, tr.mean_ap()))
+                    tr.reset_ap()
                 if train and steps % 1000 == 0 and rank == 0:
                     os.makedirs(os.path.dirname(save_model) or '.', exist_ok=True)
                     torch.save({'model_state_dict': net.state_dict(), 'optimizer_state_dict': optimizer.state_dict(),
@@ -358,10 +357,11 @@ if __name__ == '__main__':
     parser.add_argument('-gpu', default='0', type=str)
     parser.add_argument('--max-steps', type=int, default=None)
     parser.add_argument('--batch-size', type=int, default=BS * BS_UPSCALE)
+    parser.add_argument('--device-ap', action='store_true', help='training AP rows and loss totals stay on the GPU')
     args = parser.parse_args()
     if 'RANK' not in os.environ and len(args.gpu.split(',')) > 1:
         sys.exit(_spawn(args.gpu, ['--batch-size', str(args.batch_size)] +
-                        (['--max-steps', str(args.max_steps)] if args.max_steps else [])))
+                        (['--max-steps', str(args.max_steps)] if args.max_steps else []) + (['--device-ap'] if args.device_ap else [])))
     if 'RANK' not in os.environ:
         os.environ['CUDA_VISIBLE_DEVICES'] = args.gpu
-    run(batch_size=args.batch_size, max_steps=args.max_steps)
+    run(batch_size=args.batch_size, max_steps=args.max_steps, device_ap=args.device_ap)

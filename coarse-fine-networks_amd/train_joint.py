@@ -27,6 +27,7 @@ import train_coarse_fineFEAT as tc
 import train_fine                # noqa: E402
 from cfn_hip import staging                       # noqa: E402
 from cfn_hip import dist as cdist                 # noqa: E402
+from cfn_hip import metrics                       # noqa: E402
 from train_fine import lr_warmup                  # noqa: E402
 
 BS = 8
@@ -122,9 +123,12 @@ def train_step(fine, coarse, reducer, optimizer, clip, labels, masks, pre_step=N
 
 def run(init_lr=INIT_LR, warmup_steps=0, max_steps=None, batch_size=BS, fine_frames=128, coarse_frames=64, dataloader=None,
         pretrained_fine=None, pretrained_coarse=None, save_model='models/joint_charades_', log=print, fine_act_dtype=None, coarse_act_dtype=None,
-        input_norm=None, crop=tc.CROP):
+        input_norm=None, crop=tc.CROP, device_ap=False):
     """input_norm: see build_models -- needed when the loader yields the clip as uint8 frames: U8Clips, or RawU8Clips (untransformed
-    frames + crop boxes), which is cropped / resized to `crop` / flipped on the GPU in front of the step."""
+    frames + crop boxes), which is cropped / resized to `crop` / flipped on the GPU in front of the step.
+    device_ap: this loop reads its losses back only where it logs and keeps no AP meter; with device_ap the training rows of every step
+    go to a device-resident meter as well (cfn_hip.metrics.StepMetrics, no read-back per step) and the logged lines carry the mAP of
+    the steps since the last one."""
     rank, world, dev = cdist.init_from_env()
     local_bs = max(batch_size // world, 1)
     if dataloader is None:
@@ -139,6 +143,7 @@ def run(init_lr=INIT_LR, warmup_steps=0, max_steps=None, batch_size=BS, fine_fra
     fine.train(True)
     coarse.train(True)
     steps = 0
+    tr = metrics.StepMetrics(True, dev) if device_ap else None
     # (the clip, labels and masks reach HBM one batch ahead of the step, on a copy stream: cfn_hip/staging.py)
     for clip, labels, masks in staging.stage(dataloader, dev):
         ok = clip.shape[0] == local_bs
@@ -148,12 +153,18 @@ def run(init_lr=INIT_LR, warmup_steps=0, max_steps=None, batch_size=BS, fine_fra
         clip = clip.to(dev)
         if isinstance(clip, tc.RawU8Clips):
             clip = clip.transform(crop)
-        cls_loss, loc_loss, _ = train_step(fine, coarse, reducer, optimizer, clip, labels.to(dev), masks.to(dev), warm)
+        labels, masks = labels.to(dev), masks.to(dev)
+        cls_loss, loc_loss, probs = train_step(fine, coarse, reducer, optimizer, clip, labels, masks, warm)
         steps += 1
+        if tr is not None:
+            tr.update(cls_loss, loc_loss, probs, labels, masks.sum(1).int())
         if steps % 50 == 0 or max_steps is not None:
             m_loc, m_cls = cdist.mean_over_ranks([float(loc_loss), float(cls_loss)], dev)
             if rank == 0:
-                log(' joint steps: {} Loc Loss: {:.4f} Cls Loss: {:.4f}'.format(steps, m_loc, m_cls))
+                log(' joint steps: {} Loc Loss: {:.4f} Cls Loss: {:.4f}'.format(steps, m_loc, m_cls)
+                    + ('' if tr is None else ' mAP: {:.4f}'.format(tr.mean_ap())))
+            if tr is not None:
+                tr.reset_ap()
         if steps % 1000 == 0 and rank == 0:
             os.makedirs(os.path.dirname(save_model) or '.', exist_ok=True)
             torch.save({'fine_state_dict': fine.state_dict(), 'model_state_dict': coarse.state_dict(),
@@ -168,6 +179,7 @@ if __name__ == '__main__':
     parser.add_argument('-gpu', default='0', type=str)
     parser.add_argument('--max-steps', type=int, default=None)
     parser.add_argument('--batch-size', type=int, default=BS)
+    parser.add_argument('--device-ap', action='store_true', help='training AP rows on the GPU, mAP in the logged lines')
     args = parser.parse_args()
     if 'RANK' not in os.environ and len(args.gpu.split(',')) > 1:
         import subprocess
@@ -176,7 +188,7 @@ if __name__ == '__main__':
         sys.exit(subprocess.call([sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', str(n),
                                   '--master-addr', '127.0.0.1', '--master-port', os.environ.get('MASTER_PORT', '29513'),
                                   os.path.abspath(__file__), '--batch-size', str(args.batch_size)] +
-                                 (['--max-steps', str(args.max_steps)] if args.max_steps else []), env=env))
+                                 (['--max-steps', str(args.max_steps)] if args.max_steps else []) + (['--device-ap'] if args.device_ap else []), env=env))
     if 'RANK' not in os.environ:
         os.environ['CUDA_VISIBLE_DEVICES'] = args.gpu
-    run(batch_size=args.batch_size, max_steps=args.max_steps)
+    run(batch_size=args.batch_size, max_steps=args.max_steps, device_ap=args.device_ap)

@@ -422,6 +422,33 @@ int cfn_pool_hw_bwd_f16(const float* gout, const unsigned short* x, const double
 int cfn_crop_resize_flip_u8(const unsigned char* src, const int* lengths, const int* box, const int* bounds, const int* coef,
                             unsigned char* dst, int N, int T, int Hs, int Ws, int S, int K, void* stream);
 
+/* =====================================================================================================================
+ * Per-class average precision on the GPU (csrc/apmeter.hip): the device-resident form of apmeter.APMeter (reference
+ * apmeter.py:22-136).  Per class: a STABLE descending sort of the scores in insertion order (numpy's order on special values:
+ * +0.0 and -0.0 tie, denormals are distinct, every NaN sorts behind -inf), AP = (sum over the positive ranks r of tp_r / r) /
+ * max(npos, 1).
+ *   scores (K, cap) fp32 and targets (K, cap) uint8: class-major stores, row i of class k at k * cap + i (64-bit offsets);
+ *   count: ONE int on the device, the rows held; flags: one int on the device, bit 0 = a label that is neither 0 nor 1 was
+ *   appended, bit 1 = a batch did not fit into cap (nothing of it was written, count unchanged).
+ * No entry point reads count on the host; no grid size depends on it; each is capturable (no allocation, no synchronisation,
+ * also in deterministic mode: nothing here accumulates in floating point across workgroups).  Results are bit-identical from
+ * run to run.
+ *   cfn_ap_append: probs, labels (B, K, TL) fp32; valid (B) int32 or NULL (= TL frames each).  Video b contributes frames
+ *     0 .. min(valid[b], TL) - 1 of every class, videos in batch order, frames ascending; target byte = label != 0.
+ *   cfn_ap_sort: rows 0 .. count - 1 of every class of scores / targets -> sorted_scores / sorted_targets (K, cap), the rows
+ *     behind count untouched; tmp_keys (K, cap) int32 and tmp_targets (K, cap) uint8 are scratch.  LSD radix sort, 8-bit digits,
+ *     one workgroup per class.  The sorted scores are canonical: +0.0 for -0.0, one NaN pattern for every NaN.
+ *   cfn_ap_reduce: sorted target bytes -> ap (K) fp32; a class without a positive gives 0.  fp64 sums in a fixed order.
+ *   cfn_ap_sort_tile: rows per tile of the sort (host only).
+ * Return 1 for null pointers and for K, cap, TL, B <= 0 (cap must be below 2^31 less one tile; K, B <= 65535).
+ * ===================================================================================================================== */
+int cfn_ap_append(const float* probs, const float* labels, const int* valid, float* scores, unsigned char* targets, int* count,
+                  int* flags, int B, int K, int TL, long cap, void* stream);
+int cfn_ap_sort(const float* scores, const unsigned char* targets, const int* count, float* sorted_scores,
+                unsigned char* sorted_targets, int* tmp_keys, unsigned char* tmp_targets, int K, long cap, void* stream);
+int cfn_ap_reduce(const unsigned char* sorted_targets, const int* count, float* ap, int K, long cap, void* stream);
+int cfn_ap_sort_tile(void);
+
 #ifdef __cplusplus
 }
 #endif

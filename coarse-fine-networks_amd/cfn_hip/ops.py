@@ -1184,6 +1184,82 @@ def time_resize(x, L, align_corners=True):
     return _TimeResize.apply(x, L, align_corners)
 
 
+def _detloss_args(logits, labels, masks, crops):
+    """device fp32 tensors of matching shapes, contiguous -> (logits, labels, masks, B, C, T, TL)"""
+    for name, v in (('logits', logits), ('labels', labels), ('masks', masks)):
+        if not v.is_cuda or v.dtype != torch.float32:
+            raise RuntimeError('detection_loss: %s must be a device fp32 tensor, got %s on %s (there is no CPU path)' % (name, v.dtype, v.device))
+        if v.device != logits.device:
+            raise RuntimeError('detection_loss: %s lives on %s, the logits on %s' % (name, v.device, logits.device))
+    crops = int(crops)
+    if logits.dim() != 3 or labels.dim() != 3 or masks.dim() != 2 or crops < 1:
+        raise RuntimeError('detection_loss: logits (B*crops, C, T), labels (B, C, TL), masks (B, TL), crops >= 1')
+    B, C, TL = labels.shape
+    if logits.shape[0] != B * crops or logits.shape[1] != C or tuple(masks.shape) != (B, TL) or 0 in logits.shape or 0 in labels.shape:
+        raise RuntimeError('detection_loss: logits %s, labels %s, masks %s do not belong together at %d crop(s)'
+                           % (tuple(logits.shape), tuple(labels.shape), tuple(masks.shape), crops))
+    return logits.contiguous(), labels.contiguous(), masks.contiguous(), B, C, logits.shape[2], TL
+
+
+def detection_loss_fwd(logits, labels, masks, align_corners=True, crops=1, norm=None, world=1.0, want_probs=True):
+    """cfn_detloss_fwd -> (cls (), loc (), probs (B, C, TL) or None, jstar (B*C) int32, ymax (B*C), norm_used (1) fp64); the last three are
+    what cfn_detloss_bwd needs beside the inputs"""
+    logits, labels, masks, B, C, T, TL = _detloss_args(logits, labels, masks, crops)
+    dev = logits.device
+    if norm is not None:
+        if not norm.is_cuda or norm.device != dev or norm.numel() != 1:
+            raise RuntimeError('detection_loss: norm must be a one-element tensor on the device of the logits')
+        norm = norm.detach().to(torch.float32).reshape(1)
+    cls = torch.empty((), dtype=torch.float32, device=dev)
+    loc = torch.empty((), dtype=torch.float32, device=dev)
+    probs = torch.empty(B, C, TL, dtype=torch.float32, device=dev) if want_probs else None
+    jstar = torch.empty(B * C, dtype=torch.int32, device=dev)
+    ymax = torch.empty(B * C, dtype=torch.float32, device=dev)
+    rows = torch.empty(2 * B * C, dtype=torch.float64, device=dev)
+    norm_used = torch.empty(1, dtype=torch.float64, device=dev)
+    call('cfn_detloss_fwd', logits, labels, masks, norm, float(world), probs, cls, loc, jstar, ymax, rows, norm_used, B, C, T, TL, int(crops),
+         int(bool(align_corners)))
+    return cls, loc, probs, jstar, ymax, norm_used
+
+
+def detection_loss_bwd(g_cls, g_loc, logits, labels, masks, jstar, ymax, norm_used, align_corners=True, crops=1, world=1.0):
+    """cfn_detloss_bwd -> the gradient of g_cls * cls + g_loc * loc at the logits; g_cls / g_loc are device scalars"""
+    logits, labels, masks, B, C, T, TL = _detloss_args(logits, labels, masks, crops)
+    if jstar.numel() != B * C or ymax.numel() != B * C or norm_used.numel() != 1:
+        raise RuntimeError('detection_loss_bwd: jstar / ymax / norm_used are not the ones the forward returned for these shapes')
+    g_cls, g_loc = (g.detach().to(torch.float32).reshape(1) for g in (g_cls, g_loc))
+    gx = torch.empty_like(logits)
+    call('cfn_detloss_bwd', g_cls, g_loc, logits, labels, masks, jstar.contiguous(), ymax.contiguous(), norm_used, float(world), gx, B, C, T, TL,
+         int(crops), int(bool(align_corners)))
+    return gx
+
+
+class _DetectionLoss(Function):
+    """the detection loss of both training scripts in one forward and one backward kernel (csrc/detloss.hip)"""
+
+    @staticmethod
+    def forward(ctx, logits, labels, masks, align_corners, crops, norm, world, want_probs):
+        cls, loc, probs, jstar, ymax, norm_used = detection_loss_fwd(logits, labels, masks, align_corners, crops, norm, world, want_probs)
+        ctx.save_for_backward(logits, labels, masks, jstar, ymax, norm_used)
+        ctx.meta = (bool(align_corners), int(crops), float(world))
+        if probs is not None:
+            ctx.mark_non_differentiable(probs)
+        return cls, loc, probs
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_cls, g_loc, _g_probs):
+        gx = detection_loss_bwd(g_cls, g_loc, *ctx.saved_tensors, *ctx.meta) if ctx.needs_input_grad[0] else None
+        return gx, None, None, None, None, None, None, None
+
+
+def detection_loss(logits, labels, masks, align_corners, crops=1, norm=None, world=1.0, want_probs=True):
+    """cls + loc loss of train_fine.py:199-213 / train_coarse_fineFEAT.py:226-240 -> (cls, loc, probs).  logits (B*crops, C, T), labels
+    (B, C, TL), masks (B, TL): device fp32.  norm: the loc normaliser as a device scalar (None: C * sum(masks) of this call); world: the
+    factor on loc.  probs carries no gradient (the training loops log it); want_probs=False skips its store and returns None."""
+    return _DetectionLoss.apply(logits, labels, masks, align_corners, crops, norm, world, want_probs)
+
+
 def _geom(kernel, stride, padding):
     return (ctypes.c_int * 9)(*(tuple(kernel) + tuple(stride) + tuple(padding)))
 

@@ -884,6 +884,49 @@ def _tr_setup(ctx, inputs, output):
 time_resize.register_autograd(lambda ctx, g: (torch.ops.cfn.time_resize_backward(g, *ctx.meta), None, None), setup_context=_tr_setup)
 
 
+# ---- detection loss of both training scripts, one forward + one backward kernel (csrc/detloss.hip; opt-in: CFN_FUSED_LOSS / --fused-loss) ------
+@_op('detection_loss')
+def detection_loss(logits: torch.Tensor, labels: torch.Tensor, masks: torch.Tensor, align_corners: bool, crops: int = 1,
+                   norm: Optional[torch.Tensor] = None, world: float = 1.0,
+                   want_probs: bool = True) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """-> (cls, loc, probs, jstar, ymax, norm_used): the last three are what the backward operator takes; probs is a 1-element placeholder
+    when it is not wanted"""
+    cls, loc, probs, jstar, ymax, norm_used = _ops.detection_loss_fwd(logits, labels, masks, align_corners, crops, norm, world, want_probs)
+    return cls, loc, (_z(logits) if probs is None else probs), jstar, ymax, norm_used
+
+
+@detection_loss.register_fake
+def _(logits, labels, masks, align_corners, crops=1, norm=None, world=1.0, want_probs=True):
+    B, C, TL = labels.shape
+    return (logits.new_empty((), dtype=torch.float32), logits.new_empty((), dtype=torch.float32),
+            logits.new_empty((B, C, TL) if want_probs else (1,), dtype=torch.float32), logits.new_empty((B * C,), dtype=torch.int32),
+            logits.new_empty((B * C,), dtype=torch.float32), logits.new_empty((1,), dtype=torch.float64))
+
+
+@_op('detection_loss_backward')
+def detection_loss_backward(g_cls: torch.Tensor, g_loc: torch.Tensor, logits: torch.Tensor, labels: torch.Tensor, masks: torch.Tensor,
+                            jstar: torch.Tensor, ymax: torch.Tensor, norm_used: torch.Tensor, align_corners: bool, crops: int,
+                            world: float) -> torch.Tensor:
+    return _ops.detection_loss_bwd(g_cls, g_loc, logits, labels, masks, jstar, ymax, norm_used, align_corners, crops, world)
+
+
+@detection_loss_backward.register_fake
+def _(g_cls, g_loc, logits, labels, masks, jstar, ymax, norm_used, align_corners, crops, world):
+    return logits.new_empty(logits.shape, dtype=torch.float32)
+
+
+def _dl_setup(ctx, inputs, output):
+    ctx.save_for_backward(inputs[0], inputs[1], inputs[2], output[3], output[4], output[5])
+    ctx.meta = (inputs[3], inputs[4], inputs[6])
+
+
+def _dl_backward(ctx, g_cls, g_loc, *_rest):      # (probs and the saved statistics carry no gradient)
+    return (torch.ops.cfn.detection_loss_backward(g_cls, g_loc, *ctx.saved_tensors, *ctx.meta),) + (None,) * 7
+
+
+detection_loss.register_autograd(_dl_backward, setup_context=_dl_setup)
+
+
 # ---- uint8 frames: crop + antialiased bilinear resize + flip on the GPU (csrc/aug_u8.hip; the tap tables: cfn_hip/u8aug.py) -------
 @_op('crop_resize_flip_u8')
 def crop_resize_flip_u8(frames: torch.Tensor, lengths: Optional[torch.Tensor], box: torch.Tensor, bounds: torch.Tensor, coef: torch.Tensor,
@@ -930,7 +973,7 @@ def _(scores, targets, count):
 
 
 OPERATORS = ('dwconv3d', 'pwconv', 'time_sample', 'dwconv_t5', 'stem_conv', 'conv3d_dense', 'bn_fold', 'bn_add_relu', 'affine_act',
-             'pool_hw', 'interp1d', 'grid_cdf', 'gauss_align', 'fusion_gather', 'film', 'time_resize', 'stem_conv_u8')
+             'pool_hw', 'interp1d', 'grid_cdf', 'gauss_align', 'fusion_gather', 'film', 'time_resize', 'stem_conv_u8', 'detection_loss')
 # the uint8 input path's operators without a gradient (the host-built table, the frames -> fp32 clip converter)
 INPUT_OPERATORS = ('clip_lut', 'clip_u8_to_f32')
 # spatial augmentation of uint8 frames on the GPU (no gradient)
@@ -992,6 +1035,11 @@ class TorchOps(object):
     @staticmethod
     def film(x, m, c, f):
         return torch.ops.cfn.film(x, m, c, f)
+
+    @staticmethod
+    def detection_loss(logits, labels, masks, align_corners, crops=1, norm=None, world=1.0, want_probs=True):
+        cls, loc, probs = torch.ops.cfn.detection_loss(logits, labels, masks, align_corners, crops, norm, world, want_probs)[:3]
+        return cls, loc, (probs if want_probs else None)
 
     @staticmethod
     def interp1d(x, y, xnew):

@@ -6,6 +6,7 @@
 // i0 = floor(i_t) is reproduced bit-exactly: same fp32 operation order, FMA contraction disabled
 // in the index helpers.  Kernels are pure streaming (two input planes -> one output plane).
 #include "cfn_common.h"
+#include "resize_src.h"
 
 typedef float __attribute__((ext_vector_type(4))) f4v;
 
@@ -209,26 +210,8 @@ __global__ void interp1d_bwd_kernel(const float* __restrict__ g, const float* __
     }
 }
 
-// ---- temporal linear resize: align_corners=True (F.interpolate 'linear' x3d_coarse.py:725 and the t-axis of
-// 'trilinear' :449 when h,w keep their size) or half-pixel centres (align_corners=False: the loss upsampling of
-// train_coarse_fineFEAT.py:226) -- ATen's area_pixel_compute_scale / _source_index in the same operation order
-__device__ __forceinline__ void resize_src(int j, int Kin, int Lout, int ac, int& i0, int& i1, float& l0, float& l1) {
-#pragma clang fp contract(off)
-    float src;
-    if (ac) {
-        const float scale = Lout > 1 ? (float)(Kin - 1) / (float)(Lout - 1) : 0.0f;
-        src = scale * (float)j;
-    } else {
-        const float scale = (float)Kin / (float)Lout;
-        src = fmaf(scale, (float)j + 0.5f, -0.5f);   // ATen's CPU build contracts this expression into one FMA (checked
-        if (src < 0.0f) src = 0.0f;                  // against F.interpolate: 2e-7 with, 1e-5 without)
-    }
-    i0 = (int)src;
-    i1 = i0 + (i0 < Kin - 1 ? 1 : 0);
-    l1 = src - (float)i0;
-    l0 = 1.0f - l1;
-}
-
+// ---- temporal linear resize (F.interpolate mode='linear', both align_corners conventions): the index arithmetic resize_src() and the gather
+// range of the backward live in resize_src.h, shared with the fused detection loss (detloss.hip)
 // one thread per output element (bc, j, p), p fastest
 __global__ __launch_bounds__(256) void time_resize_fwd_kernel(const float* __restrict__ x, float* __restrict__ out, int Kin,
                                                               int Lout, long P, long total, int ac) {
@@ -244,7 +227,7 @@ __global__ __launch_bounds__(256) void time_resize_fwd_kernel(const float* __res
 }
 
 // one thread per input element (bc, k, p): gathers the few outputs j whose source interval touches k
-// (src(j) = j*(Kin-1)/(Lout-1) in [k-1, k+1]  =>  j in [(k-1)/scale, (k+1)/scale], checked exactly)
+// (resize_gather_range, then i0 / i1 of every candidate checked exactly)
 __global__ __launch_bounds__(256) void time_resize_bwd_kernel(const float* __restrict__ g, float* __restrict__ gx, int Kin,
                                                               int Lout, long P, long total, int ac) {
     const long e = (long)blockIdx.x * 256 + threadIdx.x;
@@ -252,20 +235,8 @@ __global__ __launch_bounds__(256) void time_resize_bwd_kernel(const float* __res
     const long p = e % P, r = e / P;
     const int k = (int)(r % Kin);
     const long bc = r / Kin;
-    int jlo = 0, jhi = Lout - 1;
-    if (!ac) {              // src(j) = (j + 0.5) * Kin / Lout - 0.5 (clamped at 0) within [k-1, k+1]
-        const double inv = (double)Lout / (double)Kin;
-        jlo = k == 0 ? 0 : (int)floor((k - 0.5) * inv - 0.5) - 1;
-        jhi = (int)ceil((k + 1.5) * inv - 0.5) + 1;
-        if (jlo < 0) jlo = 0;
-        if (jhi > Lout - 1) jhi = Lout - 1;
-    } else if (Kin > 1 && Lout > 1) {
-        const double inv = (double)(Lout - 1) / (double)(Kin - 1);
-        jlo = (int)floor((k - 1) * inv) - 1;
-        jhi = (int)ceil((k + 1) * inv) + 1;
-        if (jlo < 0) jlo = 0;
-        if (jhi > Lout - 1) jhi = Lout - 1;
-    }
+    int jlo, jhi;
+    resize_gather_range(k, Kin, Lout, ac, jlo, jhi);
     float acc = 0.f;
     for (int j = jlo; j <= jhi; ++j) {
         int i0, i1; float l0, l1;

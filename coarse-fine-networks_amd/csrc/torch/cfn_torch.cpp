@@ -13,6 +13,7 @@
 // grid_cdf, gauss_align, fusion_gather, film, time_resize (each with its _backward) -- see the second half of this file.
 // uint8 input path: clip_lut (host table), clip_u8_to_f32, stem_conv_u8 + stem_conv_u8_backward (csrc/stem_u8.hip); crop_resize_flip_u8 (csrc/aug_u8.hip).
 // metrics: ap_append (mutates its stores), ap_sort, average_precision (csrc/apmeter.hip) -- no gradients.
+// loss: detection_loss + detection_loss_backward (csrc/detloss.hip), the opt-in fused detection loss of the three training scripts.
 #include <ATen/ATen.h>
 // (a ROCm build of torch presents its HIP devices as "cuda": the masquerading guard / stream classes are the ones that accept them)
 #include <ATen/hip/impl/HIPGuardImplMasqueradingAsCUDA.h>
@@ -939,6 +940,62 @@ Tensor time_resize_backward(const Tensor& g_, at::IntArrayRef shape, int64_t L, 
     return gx;
 }
 
+// ---- detection loss of both training scripts as one forward + one backward kernel (csrc/detloss.hip; train_fine.py:199-213,
+// train_coarse_fineFEAT.py:226-240) -> (cls, loc, probs, jstar, ymax, norm_used): the last three feed detection_loss_backward -----------------
+void detloss_shapes(const Tensor& logits, const Tensor& labels, const Tensor& masks, int64_t crops, const char* op) {
+    check_f32(logits, op, "logits");
+    check_f32(labels, op, "labels");
+    check_f32(masks, op, "masks");
+    TORCH_CHECK(logits.dim() == 3 && labels.dim() == 3 && masks.dim() == 2 && crops >= 1, op, ": logits (B*crops, C, T), labels (B, C, TL), masks (B, TL), crops >= 1");
+    TORCH_CHECK(logits.size(0) == labels.size(0) * crops && logits.size(1) == labels.size(1) && masks.size(0) == labels.size(0) && masks.size(1) == labels.size(2) &&
+                    logits.numel() > 0 && labels.numel() > 0,
+                op, ": logits ", logits.sizes(), ", labels ", labels.sizes(), ", masks ", masks.sizes(), " do not belong together at ", crops, " crop(s)");
+    TORCH_CHECK(labels.device() == logits.device() && masks.device() == logits.device(), op, ": labels / masks live on another device than the logits");
+}
+
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> detection_loss(const Tensor& logits_, const Tensor& labels_, const Tensor& masks_, bool align_corners,
+                                                                          int64_t crops, OptT norm_, double world, bool want_probs) {
+    detloss_shapes(logits_, labels_, masks_, crops, "cfn::detection_loss");
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(logits_.device());
+    const Tensor logits = logits_.contiguous(), labels = labels_.contiguous(), masks = masks_.contiguous();
+    Tensor norm;
+    if (norm_.has_value() && norm_->defined()) {
+        TORCH_CHECK(norm_->is_cuda() && norm_->device() == logits.device() && norm_->numel() == 1, "cfn::detection_loss: norm must be a one-element tensor on the device of the logits");
+        norm = norm_->to(at::kFloat).reshape({1});
+    }
+    const int64_t B = labels.size(0), C = labels.size(1), TL = labels.size(2), T = logits.size(2);
+    Tensor cls = at::empty({}, logits.options()), loc = at::empty({}, logits.options());
+    Tensor probs = want_probs ? at::empty({B, C, TL}, logits.options()) : at::zeros({1}, logits.options());
+    Tensor jstar = at::empty({B * C}, logits.options().dtype(at::kInt)), ymax = at::empty({B * C}, logits.options());
+    Tensor rows = at::empty({2 * B * C}, logits.options().dtype(at::kDouble)), norm_used = at::empty({1}, logits.options().dtype(at::kDouble));
+    ok(cfn_detloss_fwd(logits.data_ptr<float>(), labels.data_ptr<float>(), masks.data_ptr<float>(), norm.defined() ? norm.data_ptr<float>() : nullptr, world,
+                       want_probs ? probs.data_ptr<float>() : nullptr, cls.data_ptr<float>(), loc.data_ptr<float>(), jstar.data_ptr<int>(), ymax.data_ptr<float>(),
+                       rows.data_ptr<double>(), norm_used.data_ptr<double>(), (int)B, (int)C, (int)T, (int)TL, (int)crops, (int)align_corners, stream_of(logits)),
+       "cfn_detloss_fwd");
+    return {cls, loc, probs, jstar, ymax, norm_used};
+}
+
+Tensor detection_loss_backward(const Tensor& g_cls_, const Tensor& g_loc_, const Tensor& logits_, const Tensor& labels_, const Tensor& masks_, const Tensor& jstar_,
+                               const Tensor& ymax_, const Tensor& norm_used_, bool align_corners, int64_t crops, double world) {
+    detloss_shapes(logits_, labels_, masks_, crops, "cfn::detection_loss_backward");
+    const int64_t B = labels_.size(0), C = labels_.size(1), TL = labels_.size(2), T = logits_.size(2);
+    TORCH_CHECK(jstar_.scalar_type() == at::kInt && jstar_.numel() == B * C && ymax_.scalar_type() == at::kFloat && ymax_.numel() == B * C &&
+                    norm_used_.scalar_type() == at::kDouble && norm_used_.numel() == 1,
+                "cfn::detection_loss_backward: jstar / ymax / norm_used are not the ones the forward returned for these shapes");
+    TORCH_CHECK(g_cls_.numel() == 1 && g_loc_.numel() == 1, "cfn::detection_loss_backward: g_cls and g_loc are scalars");
+    for (const Tensor* t : {&g_cls_, &g_loc_, &jstar_, &ymax_, &norm_used_})
+        TORCH_CHECK(t->is_cuda() && t->device() == logits_.device(), "cfn::detection_loss_backward: every tensor lives on the device of the logits");
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(logits_.device());
+    const Tensor logits = logits_.contiguous(), labels = labels_.contiguous(), masks = masks_.contiguous(), jstar = jstar_.contiguous(), ymax = ymax_.contiguous();
+    const Tensor g_cls = g_cls_.to(at::kFloat).reshape({1}), g_loc = g_loc_.to(at::kFloat).reshape({1});
+    Tensor gx = at::empty_like(logits);
+    ok(cfn_detloss_bwd(g_cls.data_ptr<float>(), g_loc.data_ptr<float>(), logits.data_ptr<float>(), labels.data_ptr<float>(), masks.data_ptr<float>(), jstar.data_ptr<int>(),
+                       ymax.data_ptr<float>(), norm_used_.data_ptr<double>(), world, gx.data_ptr<float>(), (int)B, (int)C, (int)T, (int)TL, (int)crops, (int)align_corners,
+                       stream_of(logits)),
+       "cfn_detloss_bwd");
+    return gx;
+}
+
 }  // namespace
 
 TORCH_LIBRARY_FRAGMENT(cfn, m) {
@@ -982,6 +1039,8 @@ TORCH_LIBRARY_FRAGMENT(cfn, m) {
     m.def("film_backward(Tensor g, Tensor x, Tensor m, SymInt f) -> (Tensor, Tensor, Tensor)");
     m.def("time_resize(Tensor x, SymInt L, bool align_corners=True) -> Tensor");
     m.def("time_resize_backward(Tensor g, SymInt[] shape, SymInt L, bool align_corners) -> Tensor");
+    m.def("detection_loss(Tensor logits, Tensor labels, Tensor masks, bool align_corners, SymInt crops=1, Tensor? norm=None, float world=1., bool want_probs=True) -> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)");
+    m.def("detection_loss_backward(Tensor g_cls, Tensor g_loc, Tensor logits, Tensor labels, Tensor masks, Tensor jstar, Tensor ymax, Tensor norm_used, bool align_corners, SymInt crops, float world) -> Tensor");
 }
 
 TORCH_LIBRARY_IMPL(cfn, CUDA, m) {      // (the HIP backend of a ROCm build of torch dispatches on the CUDA key)
@@ -1024,4 +1083,6 @@ TORCH_LIBRARY_IMPL(cfn, CUDA, m) {      // (the HIP backend of a ROCm build of t
     m.impl("film_backward", film_backward);
     m.impl("time_resize", time_resize);
     m.impl("time_resize_backward", time_resize_backward);
+    m.impl("detection_loss", detection_loss);
+    m.impl("detection_loss_backward", detection_loss_backward);
 }

@@ -75,11 +75,11 @@ def _mean_ap(apm):
     return float(v.mean()) if torch.is_tensor(v) else float(v)
 
 
-def detection_loss(per_frame_logits, labels, masks, group=None, crops=1, local_norm=False):
-    """train_coarse_fineFEAT.py:226-240 (F.interpolate WITHOUT align_corners); multi-crop / normaliser conventions as in
-    train_fine.detection_loss"""
+def detection_loss(per_frame_logits, labels, masks, group=None, crops=1, local_norm=False, fused=None):
+    """train_coarse_fineFEAT.py:226-240 (F.interpolate WITHOUT align_corners); multi-crop / normaliser conventions and the `fused`
+    switch as in train_fine.detection_loss"""
     from train_fine import detection_loss as _loss
-    return _loss(per_frame_logits, labels, masks, False, group, crops, local_norm)
+    return _loss(per_frame_logits, labels, masks, False, group, crops, local_norm, fused=fused)
 
 
 def build_model(device, n_classes=NUM_CLASSES, pretrained=None, dropout=0.5, act_dtype=None, input_norm=None):
@@ -130,9 +130,9 @@ def forward_video(net, inputs, feat, feat_masks, i, meta, t_lim=1000, crop=CROP)
     return torch.cat(outs, dim=2)
 
 
-def train_step(net, reducer, optimizer, inputs, labels, masks, feat, feat_masks, meta, i=0, pre_step=None):
+def train_step(net, reducer, optimizer, inputs, labels, masks, feat, feat_masks, meta, i=0, pre_step=None, fused=None):
     logits = net([inputs, feat, feat_masks, i, meta])
-    cls_loss, loc_loss, probs = detection_loss(logits, labels, masks)
+    cls_loss, loc_loss, probs = detection_loss(logits, labels, masks, fused=fused)
     from train_fine import loss_scaler, unscale_grads
     scaler = loss_scaler(net)      # fp16 stem + layer 1: device-side loss scale (train_fine.LossScaler); None otherwise
     loss = (cls_loss + loc_loss) / 2
@@ -165,10 +165,14 @@ def localize_rows(probs, labels, valid_t, names, dur):
 def run(init_lr=INIT_LR, warmup_steps=0, max_epochs=200, mode='rgb', root=None, train_split=None,
         batch_size=BS * BS_UPSCALE, frames=80 * 4, dataloaders=None, max_steps=None,
         save_model='models/coarse_fineFEAT_charades_', pretrained='models/x3d_multigrid_kinetics_fb_pretrained.pt',
-        csv_path='localize_corr_v1.csv', log=print, phase_hook=None, input_norm=None, device_ap=False):
+        csv_path='localize_corr_v1.csv', log=print, phase_hook=None, input_norm=None, device_ap=False,
+        fused_loss=False):
     """input_norm: see build_model -- needed when the loaders collate uint8 frames (collate.coarse_collate_u8, or coarse_collate_raw_u8:
     untransformed frames + crop boxes, transformed on the GPU -- per training batch, and per chunk of a validation video).
-    device_ap: the training phases keep their AP rows and loss totals on the GPU (cfn_hip.metrics.StepMetrics): no read-back per step."""
+    device_ap: the training phases keep their AP rows and loss totals on the GPU (cfn_hip.metrics.StepMetrics): no read-back per step.
+    fused_loss: the loss runs as one forward and one backward kernel (train_fine.detection_loss(fused=True)); False leaves the choice to
+    CFN_FUSED_LOSS."""
+    fused = True if fused_loss else None
     rank, world, dev = cdist.init_from_env()
     gamma_tau = 5
     clip_frames = frames * 2 // (gamma_tau * 2)
@@ -218,13 +222,13 @@ def run(init_lr=INIT_LR, warmup_steps=0, max_epochs=200, mode='rgb', root=None, 
                 if train:
                     warm = (lambda: lr_warmup(init_lr, steps, warmup_steps, optimizer))
                     cls_loss, loc_loss, probs = train_step(net, reducer, optimizer, inputs, labels, masks, feat, feat_masks, meta,
-                                                           i, pre_step=warm)
+                                                           i, pre_step=warm, fused=fused)
                     steps += 1
                     tr.update(cls_loss, loc_loss, probs, labels, valid_t)
                 else:
                     with torch.no_grad():
                         logits = forward_video(net, inputs, feat, feat_masks, i, meta)
-                        cls_loss, loc_loss, probs = detection_loss(logits, labels, masks, crops=n, local_norm=True)
+                        cls_loss, loc_loss, probs = detection_loss(logits, labels, masks, crops=n, local_norm=True, fused=fused)
                     val_rows.extend(localize_rows(probs, labels, valid_t, name, dur))
                     tot_cls += float(cls_loss)
                     tot_loc += float(loc_loss)
@@ -273,6 +277,7 @@ if __name__ == '__main__':
     parser.add_argument('--max-steps', type=int, default=None)
     parser.add_argument('--batch-size', type=int, default=BS * BS_UPSCALE)
     parser.add_argument('--device-ap', action='store_true', help='training AP rows and loss totals stay on the GPU')
+    parser.add_argument('--fused-loss', action='store_true', help='the detection loss as one forward and one backward HIP kernel')
     args = parser.parse_args()
     if 'RANK' not in os.environ and len(args.gpu.split(',')) > 1:
         from train_fine import _spawn
@@ -282,7 +287,8 @@ if __name__ == '__main__':
         sys.exit(subprocess.call([sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', str(n),
                                   '--master-addr', '127.0.0.1', '--master-port', os.environ.get('MASTER_PORT', '29512'),
                                   os.path.abspath(__file__), '--batch-size', str(args.batch_size)] +
-                                 (['--max-steps', str(args.max_steps)] if args.max_steps else []) + (['--device-ap'] if args.device_ap else []), env=env))
+                                 (['--max-steps', str(args.max_steps)] if args.max_steps else []) + (['--device-ap'] if args.device_ap else []) +
+                                 (['--fused-loss'] if args.fused_loss else []), env=env))
     if 'RANK' not in os.environ:
         os.environ['CUDA_VISIBLE_DEVICES'] = args.gpu
-    run(batch_size=args.batch_size, max_steps=args.max_steps, device_ap=args.device_ap)
+    run(batch_size=args.batch_size, max_steps=args.max_steps, device_ap=args.device_ap, fused_loss=args.fused_loss)

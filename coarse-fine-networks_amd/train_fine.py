@@ -61,7 +61,15 @@ class SyntheticCharades(object):
             yield x, labels, masks, ['synthetic_%d' % i] * self.bs
 
 
-def detection_loss(per_frame_logits, labels, masks, align_corners=True, group=None, crops=1, local_norm=False, mask_total=None):
+def fused_loss_enabled(fused=None):
+    """the opt-in switch of the fused detection loss (cfn_hip.ops.detection_loss): an explicit True / False, or None = the environment
+    variable CFN_FUSED_LOSS, read at every call (default off)"""
+    if fused is None:
+        return os.environ.get('CFN_FUSED_LOSS', '0') not in ('', '0')
+    return bool(fused)
+
+
+def detection_loss(per_frame_logits, labels, masks, align_corners=True, group=None, crops=1, local_norm=False, mask_total=None, fused=None):
     """cls + loc loss of train_fine.py:199-213 for one rank's shard.
 
     ``loc_loss`` is normalised by the GLOBAL sum(masks) and multiplied by the world size, so that the
@@ -69,7 +77,21 @@ def detection_loss(per_frame_logits, labels, masks, align_corners=True, group=No
     crops = n > 1: validation-time multi-crop, logits are (b*n, C, T) against (b, ...) labels / masks; the per-frame
     probability is the max over the n crops of a video (train_fine.py:204-207).  local_norm=True (evaluation): this
     rank's own sum(masks) and no world factor -- no collective, ranks may hold different numbers of videos.
-    mask_total: the global sum(masks) computed beforehand (cfn_hip.graph.GraphedDPStep takes the collective out of the captured part)."""
+    mask_total: the global sum(masks) computed beforehand (cfn_hip.graph.GraphedDPStep takes the collective out of the captured part).
+    fused (see fused_loss_enabled): device fp32 logits go through ONE forward and ONE backward kernel (cfn_hip.ops.detection_loss)
+    instead of the operator chain below; anything else (CPU tensors, other dtypes) takes the chain as before."""
+    if fused_loss_enabled(fused) and per_frame_logits.is_cuda and per_frame_logits.dtype == torch.float32:
+        from cfn_hip import ops
+        world = 1
+        if not local_norm and torch.distributed.is_initialized():
+            world = torch.distributed.get_world_size(group)
+        if mask_total is not None:
+            norm = mask_total * labels.shape[1]
+        elif world > 1:                              # the normaliser is global: one collective, as below
+            norm = cdist.global_mask_count(masks, group) * labels.shape[1]
+        else:
+            norm = None                              # the kernel sums this shard's masks itself
+        return ops.detection_loss(per_frame_logits, labels, masks, align_corners, crops, norm, float(world), True)
     tl = labels.size(2)
     if per_frame_logits.is_cuda:
         from cfn_hip import ops
@@ -133,14 +155,14 @@ def flatten_clips(inputs, dev, crop=None):
     return inputs.view((b * n,) + tuple(inputs.shape[2:])).to(dev, non_blocking=True)
 
 
-def forward_backward(net, inputs, labels, masks, gamma_tau=5, mask_total=None):
+def forward_backward(net, inputs, labels, masks, gamma_tau=5, mask_total=None, fused=None):
     """forward + loss + backward of one shard (no collective when mask_total is given, no optimizer): the capturable part of a
     data-parallel step (cfn_hip.graph.GraphedDPStep).  With fp16 activations the loss is multiplied by the net's loss scale:
     EVERY caller runs `post_reduce(net)` between the gradient reduction and the optimizer (train_step below does; GraphedDPStep takes it
-    as its `post_reduce` hook and captures it in front of the optimizer graph)."""
+    as its `post_reduce` hook and captures it in front of the optimizer graph).  fused: see detection_loss."""
     masks_clip = masks[:, ::gamma_tau * 2]
     logits = net([inputs, masks_clip])
-    cls_loss, loc_loss, probs = detection_loss(logits, labels, masks, True, mask_total=mask_total)
+    cls_loss, loc_loss, probs = detection_loss(logits, labels, masks, True, mask_total=mask_total, fused=fused)
     loss = (cls_loss + loc_loss) / 2
     scaler = loss_scaler(net)
     (loss if scaler is None else scaler.scale_loss(loss)).backward()
@@ -225,12 +247,12 @@ def post_reduce(net):
     unscale_grads(net.parameters(), loss_scaler(net))
 
 
-def train_step(net, reducer, optimizer, inputs, labels, masks, gamma_tau=5, pre_step=None):
+def train_step(net, reducer, optimizer, inputs, labels, masks, gamma_tau=5, pre_step=None, fused=None):
     """one optimisation step on this rank's shard; returns (cls_loss, loc_loss, probs).  pre_step() runs between the
     gradient reduction and optimizer.step() -- where the reference adjusts the warm-up learning rate
-    (train_fine.py:241-244)."""
+    (train_fine.py:241-244).  fused: see detection_loss."""
     reducer.begin_pass()
-    cls_loss, loc_loss, probs = forward_backward(net, inputs, labels, masks, gamma_tau)
+    cls_loss, loc_loss, probs = forward_backward(net, inputs, labels, masks, gamma_tau, fused=fused)
     reducer.finish()
     post_reduce(net)
     if pre_step is not None:
@@ -246,11 +268,14 @@ _ap_rows = metrics.ap_rows      # per video: (scores (v,157), targets (v,157)) n
 def run(init_lr=INIT_LR, warmup_steps=0, max_epochs=200, mode='rgb', root=None, train_split=None,
         batch_size=BS * BS_UPSCALE, frames=80 * 4, dataloaders=None, max_steps=None, save_model='models/fine_charades_',
         pretrained='models/x3d_multigrid_kinetics_fb_pretrained.pt', log=print, phase_hook=None, input_norm=None,
-        device_ap=False):
+        device_ap=False, fused_loss=False):
     """input_norm: see build_model -- needed when the loaders collate uint8 frames (collate.fine_collate_u8, or fine_collate_raw_u8:
     untransformed frames + crop boxes, cropped / resized to the model's crop size / flipped on the GPU in front of the step).
     device_ap: the training phases keep their AP rows and loss totals on the GPU (cfn_hip.metrics.StepMetrics, apmeter.DeviceAPMeter):
-    no read-back per step, the host waits for the device only where a line is logged."""
+    no read-back per step, the host waits for the device only where a line is logged.
+    fused_loss: the loss of every step and of validation runs as one forward and one backward kernel (detection_loss(fused=True)); False leaves
+    the choice to CFN_FUSED_LOSS."""
+    fused = True if fused_loss else None
     rank, world, dev = cdist.init_from_env()
     gamma_tau = {'S': 6, 'M': 5, 'XL': 5}[X3D_VERSION]
     crop = {'S': 160, 'M': 224, 'XL': 312}[X3D_VERSION]
@@ -299,13 +324,13 @@ def run(init_lr=INIT_LR, warmup_steps=0, max_epochs=200, mode='rgb', root=None, 
                 n_it += 1
                 if train:
                     warm = (lambda: lr_warmup(init_lr, steps, warmup_steps, optimizer))
-                    cls_loss, loc_loss, probs = train_step(net, reducer, optimizer, inputs, labels, masks, gamma_tau, pre_step=warm)
+                    cls_loss, loc_loss, probs = train_step(net, reducer, optimizer, inputs, labels, masks, gamma_tau, pre_step=warm, fused=fused)
                     steps += 1
                     tr.update(cls_loss, loc_loss, probs, labels, valid_t)
                 else:
                     with torch.no_grad():
                         logits = net([inputs, masks[:, ::gamma_tau * 2]])
-                        cls_loss, loc_loss, probs = detection_loss(logits, labels, masks, True, crops=n, local_norm=True)
+                        cls_loss, loc_loss, probs = detection_loss(logits, labels, masks, True, crops=n, local_norm=True, fused=fused)
                     val_rows.extend(_ap_rows(probs, labels, valid_t))
                     tot_cls += float(cls_loss)
                     tot_loc += float(loc_loss)
@@ -358,10 +383,12 @@ if __name__ == '__main__':
     parser.add_argument('--max-steps', type=int, default=None)
     parser.add_argument('--batch-size', type=int, default=BS * BS_UPSCALE)
     parser.add_argument('--device-ap', action='store_true', help='training AP rows and loss totals stay on the GPU')
+    parser.add_argument('--fused-loss', action='store_true', help='the detection loss as one forward and one backward HIP kernel')
     args = parser.parse_args()
     if 'RANK' not in os.environ and len(args.gpu.split(',')) > 1:
         sys.exit(_spawn(args.gpu, ['--batch-size', str(args.batch_size)] +
-                        (['--max-steps', str(args.max_steps)] if args.max_steps else []) + (['--device-ap'] if args.device_ap else [])))
+                        (['--max-steps', str(args.max_steps)] if args.max_steps else []) + (['--device-ap'] if args.device_ap else []) +
+                        (['--fused-loss'] if args.fused_loss else [])))
     if 'RANK' not in os.environ:
         os.environ['CUDA_VISIBLE_DEVICES'] = args.gpu
-    run(batch_size=args.batch_size, max_steps=args.max_steps, device_ap=args.device_ap)
+    run(batch_size=args.batch_size, max_steps=args.max_steps, device_ap=args.device_ap, fused_loss=args.fused_loss)

@@ -105,9 +105,10 @@ def param_groups(fine, coarse, lr):
     return groups
 
 
-def train_step(fine, coarse, reducer, optimizer, clip, labels, masks, pre_step=None):
+def train_step(fine, coarse, reducer, optimizer, clip, labels, masks, pre_step=None, fused=None):
+    """fused: the switch of the fused detection loss, see train_fine.detection_loss"""
     logits, _ = joint_forward(fine, coarse, clip)
-    cls_loss, loc_loss, probs = tc.detection_loss(logits, labels, masks)
+    cls_loss, loc_loss, probs = tc.detection_loss(logits, labels, masks, fused=fused)
     scaler = train_fine.loss_scaler(fine, coarse)  # fp16 fine tower / fp16 coarse layer 1 (BASELINE configs[4]): device-side loss scale, see train_fine.LossScaler
     loss = (cls_loss + loc_loss) / 2
     reducer.begin_pass()
@@ -123,12 +124,15 @@ def train_step(fine, coarse, reducer, optimizer, clip, labels, masks, pre_step=N
 
 def run(init_lr=INIT_LR, warmup_steps=0, max_steps=None, batch_size=BS, fine_frames=128, coarse_frames=64, dataloader=None,
         pretrained_fine=None, pretrained_coarse=None, save_model='models/joint_charades_', log=print, fine_act_dtype=None, coarse_act_dtype=None,
-        input_norm=None, crop=tc.CROP, device_ap=False):
+        input_norm=None, crop=tc.CROP, device_ap=False, fused_loss=False):
     """input_norm: see build_models -- needed when the loader yields the clip as uint8 frames: U8Clips, or RawU8Clips (untransformed
     frames + crop boxes), which is cropped / resized to `crop` / flipped on the GPU in front of the step.
     device_ap: this loop reads its losses back only where it logs and keeps no AP meter; with device_ap the training rows of every step
     go to a device-resident meter as well (cfn_hip.metrics.StepMetrics, no read-back per step) and the logged lines carry the mAP of
-    the steps since the last one."""
+    the steps since the last one.
+    fused_loss: the loss runs as one forward and one backward kernel (train_fine.detection_loss(fused=True)); False leaves the choice to
+    CFN_FUSED_LOSS."""
+    fused = True if fused_loss else None
     rank, world, dev = cdist.init_from_env()
     local_bs = max(batch_size // world, 1)
     if dataloader is None:
@@ -154,7 +158,7 @@ def run(init_lr=INIT_LR, warmup_steps=0, max_steps=None, batch_size=BS, fine_fra
         if isinstance(clip, tc.RawU8Clips):
             clip = clip.transform(crop)
         labels, masks = labels.to(dev), masks.to(dev)
-        cls_loss, loc_loss, probs = train_step(fine, coarse, reducer, optimizer, clip, labels, masks, warm)
+        cls_loss, loc_loss, probs = train_step(fine, coarse, reducer, optimizer, clip, labels, masks, warm, fused=fused)
         steps += 1
         if tr is not None:
             tr.update(cls_loss, loc_loss, probs, labels, masks.sum(1).int())
@@ -180,6 +184,7 @@ if __name__ == '__main__':
     parser.add_argument('--max-steps', type=int, default=None)
     parser.add_argument('--batch-size', type=int, default=BS)
     parser.add_argument('--device-ap', action='store_true', help='training AP rows on the GPU, mAP in the logged lines')
+    parser.add_argument('--fused-loss', action='store_true', help='the detection loss as one forward and one backward HIP kernel')
     args = parser.parse_args()
     if 'RANK' not in os.environ and len(args.gpu.split(',')) > 1:
         import subprocess
@@ -188,7 +193,8 @@ if __name__ == '__main__':
         sys.exit(subprocess.call([sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', str(n),
                                   '--master-addr', '127.0.0.1', '--master-port', os.environ.get('MASTER_PORT', '29513'),
                                   os.path.abspath(__file__), '--batch-size', str(args.batch_size)] +
-                                 (['--max-steps', str(args.max_steps)] if args.max_steps else []) + (['--device-ap'] if args.device_ap else []), env=env))
+                                 (['--max-steps', str(args.max_steps)] if args.max_steps else []) + (['--device-ap'] if args.device_ap else []) +
+                                 (['--fused-loss'] if args.fused_loss else []), env=env))
     if 'RANK' not in os.environ:
         os.environ['CUDA_VISIBLE_DEVICES'] = args.gpu
-    run(batch_size=args.batch_size, max_steps=args.max_steps, device_ap=args.device_ap)
+    run(batch_size=args.batch_size, max_steps=args.max_steps, device_ap=args.device_ap, fused_loss=args.fused_loss)

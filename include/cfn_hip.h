@@ -272,6 +272,21 @@ int cfn_interp1d_bwd(const float* g, const float* x, const float* y, const float
 int cfn_time_resize_fwd(const float* x, float* out, long BC, int Kin, int Lout, long P, int align_corners, void* stream);
 int cfn_time_resize_bwd(const float* g, float* gx, long BC, int Kin, int Lout, long P, int align_corners, void* stream);
 
+/* ---- detection loss, fused (opt-in; csrc/detloss.hip): train_fine.py:199-213 (align_corners=1) / train_coarse_fineFEAT.py:226-240
+ * (align_corners=0), n = crops per video (train_fine.py:204-207: max over the crops' sigmoids).
+ * logits (B*n,C,T), labels (B,C,TL), masks (B,TL) fp32 -> probs (B,C,TL) = max_n sigmoid(resize(logits)) * masks (NULL: not stored),
+ * cls = mean_BC BCE(max_t probs, max_t labels), loc = sum BCE(probs, labels) / norm * world; norm: device scalar, NULL = C * sum(masks).
+ * BCE as ATen: on the fp32 probability, logs clamped at -100.  Kept for the backward: jstar (BC) first frame of the row maximum,
+ * ymax (BC) = max_t labels, norm_used (1); rows (2*BC) is scratch.  Fixed-order fp64 sums, no atomics: bit-reproducible.
+ * bwd: g_cls, g_loc device scalars (the fp16 path's loss scale lives on the device); recomputes the probabilities from the logits and
+ * overwrites all of gx (B*n,C,T); a crop that never held the maximum gets zeros.  n*T <= 6144. ---- */
+int cfn_detloss_fwd(const float* logits, const float* labels, const float* masks, const float* norm, double world, float* probs,
+                    float* cls, float* loc, int* jstar, float* ymax, double* rows, double* norm_used, int B, int C, int T, int TL,
+                    int n, int align_corners, void* stream);
+int cfn_detloss_bwd(const float* g_cls, const float* g_loc, const float* logits, const float* labels, const float* masks,
+                    const int* jstar, const float* ymax, const double* norm_used, double world, float* gx, int B, int C, int T,
+                    int TL, int n, int align_corners, void* stream);
+
 /* =====================================================================================================================
  * bf16 activation path (BASELINE.json configs[1] "X3D-M fwd+bwd bf16"; the reference itself is fp32 only: these entry
  * points are the same call sites with activations and activation gradients stored as bf16 in HBM).

@@ -311,8 +311,15 @@ class _PwConv(Function):
                 # conv1's data gradient consumes it
                 Ho, Wo = y.shape[3], y.shape[4]
                 da = torch.empty(N, Cin, T, Ho, Wo, dtype=torch.float32, device=x.device)
-                call('cfn_pwconv_bwd_data_acc', gy, y, gs, gq, w2, None, None, None, ACT_NONE, da, None, None, N, Cin, Cout, T,
-                     Ho, Wo, 1, None, 1, gsc)
+                # stride 2 and a weight gradient wanted: both products in one pass over gy, y and the lattice of x
+                # (csrc/pwshort.hip; CFN_PW_SHORT=0, read per call, declines it)
+                if ctx.needs_input_grad[3]:
+                    g64, fin = _gw_buffers(ctx.wparam, Cout, Cin, x.device)
+                    fused = call_try('cfn_pwconv_short_bwd', gy, y, gs, gq, gsc, w2, x, A, B, act, da, g64, N, Cin, Cout, T, H, W,
+                                     stride)
+                if not fused:
+                    call('cfn_pwconv_bwd_data_acc', gy, y, gs, gq, w2, None, None, None, ACT_NONE, da, None, None, N, Cin, Cout, T,
+                         Ho, Wo, 1, None, 1, gsc)
                 token.acc, token.acc_stride = da, stride
             else:
                 gx = torch.zeros_like(x) if stride != 1 else torch.empty_like(x)

@@ -126,6 +126,18 @@ int cfn_pwconv_bwd_fused(const float* gy, const float* y, const double* gsum, co
                          double* gw, int N, int Cin, int Cout, int T, int Hi, int Wi, const float* acc, int acc_stride,
                          const double* gscale, void* stream);
 
+/* Backward of the spatially strided shortcut conv of a stage-first block (x3d_fine.py:284-287) in ONE pass over gy, y and the stride
+ * lattice of x (pwshort.hip, fp32 MFMA): with g' = gscale*gy + gsum + 2*y*gsumsq on the output grid (Ho, Wo) = ((Hi-1)/2+1, (Wi-1)/2+1)
+ *   da (N,Cin,T,Ho,Wo) = W^T g'        the COMPACT data gradient (no act' epilogue, no statistics: the `acc` of cfn_pwconv_bwd_data_acc /
+ *                                      cfn_pwconv_bwd_fused, which conv1's backward adds on the lattice);
+ *   gw (Cout,Cin) fp64 += g' a^T       a = act(A x + B) at (t, 2 oh, 2 ow); A, B (N,Cin) may be NULL; act none / ReLU.
+ * gsum, gsumsq, gscale may each be NULL (y only with gsumsq).  The same results as cfn_pwconv_bwd_data_acc on the output grid +
+ * cfn_pwconv_bwd_weight(stride 2).  Cout <= 192, Cin <= 96, any plane size.  Returns -1 WITHOUT launching (nothing is written) for any
+ * other stride, width or activation, and when CFN_PW_SHORT=0 (read per call): callers then use the two separate entry points. */
+int cfn_pwconv_short_bwd(const float* gy, const float* y, const double* gsum, const double* gsumsq, const double* gscale,
+                         const float* w, const float* x, const double* A, const double* B, int act, float* da, double* gw,
+                         int N, int Cin, int Cout, int T, int Hi, int Wi, int stride, void* stream);
+
 /* ---- stem 1x3x3 stride (1,2,2) pad (0,1,1) dense conv: conv1_s x3d_fine.py:210-215 (im2col view on MFMA);
  * gw is fp64 (Cout, Cimg*9), zero-filled by caller.  The clip needs no gradient. ---- */
 int cfn_stem_conv_fwd(const float* x, const float* w, float* y, int N, int Cimg, int Cout, int T, int Hi, int Wi,

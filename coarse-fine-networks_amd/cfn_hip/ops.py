@@ -1428,3 +1428,74 @@ class _GridCdf(Function):
 
 def grid_cdf(g, bias=None):
     return _GridCdf.apply(g, bias)
+
+
+# ---- packed 16-bit fine features (csrc/featpack.hip; the record format and the batch type: cfn_hip/featpack.py) ---------------------------
+FEAT_POSITIONS = 49
+
+
+def _feat_channels(channels, what):
+    channels = tuple(int(c) for c in channels)
+    if len(channels) != 5 or any(c <= 0 or c % 8 for c in channels):
+        raise RuntimeError('%s: five channel counts that are positive multiples of 8 expected, got %s' % (what, channels))
+    return channels
+
+
+def _feat_sfx(dtype, what):
+    if dtype not in (torch.float16, torch.bfloat16):
+        raise RuntimeError('%s: fp16 or bf16 data expected, got %s' % (what, dtype))
+    return '_f16' if dtype == torch.float16 else '_bf16'
+
+
+def feat_unpack(data, offsets, lengths, channels, t_max, out=None):
+    """data: 1-D fp16 / bf16 on the GPU; offsets (B, 5) int64 = first element of every video's five time-major blocks (length, C_k, 49),
+    multiples of 8; lengths (B,) int32 -> the five fp32 maps (B, C_k, t_max, 7, 7), zero behind each video's own length.  One launch;
+    offsets and lengths are read on the device only (no wait, capturable); `t_max` is a host int.  out: five preallocated maps."""
+    channels = _feat_channels(channels, 'feat_unpack')
+    sfx = _feat_sfx(data.dtype, 'feat_unpack')
+    t_max = int(t_max)
+    if data.dim() != 1 or not data.is_contiguous():
+        raise RuntimeError('feat_unpack: a flat contiguous buffer expected, got %s' % (tuple(data.shape),))
+    if offsets.dtype != torch.int64 or offsets.dim() != 2 or offsets.shape[1] != 5 or offsets.shape[0] < 1:
+        raise RuntimeError('feat_unpack: offsets (B, 5) int64 expected, got %s %s' % (offsets.dtype, tuple(offsets.shape)))
+    B = int(offsets.shape[0])
+    if lengths.dtype != torch.int32 or lengths.numel() != B:
+        raise RuntimeError('feat_unpack: lengths (%d,) int32 expected, got %s %s' % (B, lengths.dtype, tuple(lengths.shape)))
+    if t_max < 1:
+        raise RuntimeError('feat_unpack: t_max >= 1 expected, got %d' % t_max)
+    if out is None:
+        out = [torch.empty(B, c, t_max, 7, 7, dtype=torch.float32, device=data.device) for c in channels]
+    else:
+        out = list(out)
+        if len(out) != 5:
+            raise RuntimeError('feat_unpack: out: five maps expected, got %d' % len(out))
+        for y, c in zip(out, channels):
+            if y.dtype != torch.float32 or tuple(y.shape) != (B, c, t_max, 7, 7) or not y.is_contiguous():
+                raise RuntimeError('feat_unpack: out: five contiguous fp32 maps (%d, C_k, %d, 7, 7) with C_k = %s expected, got %s %s'
+                                   % (B, t_max, channels, y.dtype, tuple(y.shape)))
+    call('cfn_feat_unpack' + sfx, data, offsets.contiguous(), lengths.contiguous(), *out, B, t_max, *channels, int(data.numel()))
+    return out
+
+
+def feat_pack(feat, dtype, out=None):
+    """feat: the five fp32 maps (C_k, T', 7, 7) (or (1, C_k, T', 7, 7)) of ONE video on the GPU, in key order -> its record payload: a
+    1-D fp16 / bf16 tensor, the five time-major blocks (T', C_k, 49) back to back; round to nearest even, as tensor.to(dtype) on the CPU"""
+    sfx = _feat_sfx(dtype, 'feat_pack')
+    xs = []
+    for x in feat:
+        if x.dim() == 5 and x.shape[0] == 1:
+            x = x[0]
+        if x.dtype != torch.float32 or x.dim() != 4 or x.shape[2] * x.shape[3] != FEAT_POSITIONS:
+            raise RuntimeError('feat_pack: fp32 maps (C, T, 7, 7) expected, got %s %s' % (x.dtype, tuple(x.shape)))
+        xs.append(x.contiguous())
+    if len(xs) != 5 or any(x.shape[1] != xs[0].shape[1] for x in xs):
+        raise RuntimeError('feat_pack: five maps of one frame count expected, got %s' % [tuple(x.shape) for x in xs])
+    channels = _feat_channels([x.shape[0] for x in xs], 'feat_pack')
+    T = int(xs[0].shape[1])
+    n = T * sum(channels) * FEAT_POSITIONS
+    if out is None:
+        out = torch.empty(n, dtype=dtype, device=xs[0].device)
+    elif out.dtype != dtype or out.dim() != 1 or out.numel() != n or not out.is_contiguous():
+        raise RuntimeError('feat_pack: out: a flat %s tensor of %d elements expected, got %s %s' % (dtype, n, out.dtype, tuple(out.shape)))
+    call('cfn_feat_pack' + sfx, *xs, out, T, *channels)
+    return out

@@ -17,7 +17,7 @@ with plain semantics:
 
 No CPU implementation is registered: calling them with CPU tensors fails in the dispatcher.
 """
-from typing import Optional, Tuple
+from typing import List, Optional, Sequence, Tuple
 
 import torch
 
@@ -972,6 +972,30 @@ def _(scores, targets, count):
     return scores.new_empty((scores.shape[0],), dtype=torch.float32)
 
 
+# ---- packed 16-bit fine features (csrc/featpack.hip; the record format and the batch type: cfn_hip/featpack.py), no gradient ------------------
+@_op('feat_unpack')
+def feat_unpack(data: torch.Tensor, offsets: torch.Tensor, lengths: torch.Tensor, channels: Sequence[int], t_max: int) -> List[torch.Tensor]:
+    return _ops.feat_unpack(data, offsets, lengths, channels, t_max)
+
+
+@feat_unpack.register_fake
+def _(data, offsets, lengths, channels, t_max):
+    return [data.new_empty((offsets.shape[0], c, t_max, 7, 7), dtype=torch.float32) for c in channels]
+
+
+@_op('feat_pack')
+def feat_pack(feat: Sequence[torch.Tensor], dtype: torch.dtype) -> torch.Tensor:
+    return _ops.feat_pack(feat, dtype)
+
+
+@feat_pack.register_fake
+def _(feat, dtype):
+    n = 0
+    for f in feat:
+        n = n + f.shape[-4] * f.shape[-3] * 49
+    return feat[0].new_empty((n,), dtype=dtype)
+
+
 OPERATORS = ('dwconv3d', 'pwconv', 'time_sample', 'dwconv_t5', 'stem_conv', 'conv3d_dense', 'bn_fold', 'bn_add_relu', 'affine_act',
              'pool_hw', 'interp1d', 'grid_cdf', 'gauss_align', 'fusion_gather', 'film', 'time_resize', 'stem_conv_u8', 'detection_loss')
 # the uint8 input path's operators without a gradient (the host-built table, the frames -> fp32 clip converter)
@@ -980,6 +1004,8 @@ INPUT_OPERATORS = ('clip_lut', 'clip_u8_to_f32')
 AUGMENT_OPERATORS = ('crop_resize_flip_u8',)
 # device-resident average precision (no gradient; ap_append mutates its stores)
 METRIC_OPERATORS = ('ap_append', 'ap_sort', 'average_precision')
+# packed 16-bit fine features: widen + pad a batch, round + transpose one video's maps (no gradient)
+FEATURE_OPERATORS = ('feat_unpack', 'feat_pack')
 
 
 # ---------------------------------------------------------------------------------------------------------------------------

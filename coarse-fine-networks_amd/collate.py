@@ -24,11 +24,17 @@ to sample (cfn_hip.u8aug.train_crop_params / center_crop_params draw the boxes a
 member of the batch becomes a ``RawU8Clips(frames (B,n,Tmax,Hmax,Wmax,3), lengths (B,n), box (B,n,4))``, every picture in the
 top-left corner of its zero-padded frame; crop, resize and flip run on the GPU (``RawU8Clips.transform``, which the training and
 extraction scripts call).
+
+``coarse_collate_packed`` / ``_packed_u8`` / ``_packed_raw_u8``: the feature member of a sample is a ``cfn_hip.featpack.Record`` -- the
+memory-mapped 16-bit record of the video (one file instead of five fp32 ones).  Member 3 of the batch becomes a ``PackedFeats``: the first
+min(T', cap) frames of every block copied, unpadded and still 16-bit, into one flat buffer (five contiguous copies per sample, no zero
+fill); ``PackedFeats.unpack()`` widens and pads on the GPU.  The other seven members are what ``coarse_collate*`` builds.
 """
 import numpy as np
 import torch
 
 from cfn_hip.u8clips import RawU8Clips, U8Clips, CHARADES_MEAN, CHARADES_STD  # noqa: F401
+from cfn_hip.featpack import PackedFeats, Record, collate_records  # noqa: F401
 
 
 def _t(a):
@@ -156,3 +162,30 @@ def coarse_collate_u8(batch, cap=128):
 def coarse_collate_raw_u8(batch, cap=128):
     """coarse_collate for samples whose clips are (frames (n,T,h,w,3) uint8, box (n,4)) pairs: untransformed frames + crop boxes"""
     return [_pad_raw_u8([b[0] for b in batch])] + _coarse_rest(batch, cap)
+
+
+def _coarse_rest_packed(batch, cap):
+    """_coarse_rest for samples whose feature member is a Record: [label, mask, PackedFeats, feat_mask, meta, [vid...], dur]"""
+    labels = [b[1] for b in batch]
+    tl_max = max(_t(lb).shape[1] for lb in labels)
+    feat, feat_mask = collate_records([b[2] for b in batch], cap)
+    meta = torch.stack([_t(b[3]) for b in batch])
+    dur = torch.as_tensor([float(b[5]) for b in batch], dtype=torch.float64)
+    return [_pad_time(labels, 1, tl_max), _label_mask(labels, tl_max), feat, feat_mask, meta, [b[4] for b in batch], dur]
+
+
+def coarse_collate_packed(batch, cap=128):
+    """coarse_collate for samples (clips, label, Record, meta, vid, dur): the features stay 16-bit and unpadded (PackedFeats)"""
+    clips = [b[0] for b in batch]
+    t_max = max(_t(c).shape[2] for c in clips)
+    return [_pad_time(clips, 2, t_max)] + _coarse_rest_packed(batch, cap)
+
+
+def coarse_collate_packed_u8(batch, cap=128):
+    """coarse_collate_packed for samples whose clips are uint8 (n,T,H,W,3)"""
+    return [_pad_time_u8([b[0] for b in batch])] + _coarse_rest_packed(batch, cap)
+
+
+def coarse_collate_packed_raw_u8(batch, cap=128):
+    """coarse_collate_packed for samples whose clips are (frames (n,T,h,w,3) uint8, box (n,4)) pairs"""
+    return [_pad_raw_u8([b[0] for b in batch])] + _coarse_rest_packed(batch, cap)

@@ -14,6 +14,7 @@
 // uint8 input path: clip_lut (host table), clip_u8_to_f32, stem_conv_u8 + stem_conv_u8_backward (csrc/stem_u8.hip); crop_resize_flip_u8 (csrc/aug_u8.hip).
 // metrics: ap_append (mutates its stores), ap_sort, average_precision (csrc/apmeter.hip) -- no gradients.
 // loss: detection_loss + detection_loss_backward (csrc/detloss.hip), the opt-in fused detection loss of the three training scripts.
+// packed 16-bit fine features: feat_unpack, feat_pack (csrc/featpack.hip) -- no gradients.
 #include <ATen/ATen.h>
 // (a ROCm build of torch presents its HIP devices as "cuda": the masquerading guard / stream classes are the ones that accept them)
 #include <ATen/hip/impl/HIPGuardImplMasqueradingAsCUDA.h>
@@ -996,6 +997,71 @@ Tensor detection_loss_backward(const Tensor& g_cls_, const Tensor& g_loc_, const
     return gx;
 }
 
+// ---- packed 16-bit fine features (csrc/featpack.hip; cfn_hip/featpack.py) -- no gradients: features from disk carry none ----------------------
+inline void feat_channels(at::IntArrayRef channels, const char* op, int* C) {
+    TORCH_CHECK(channels.size() == 5, op, ": five channel counts expected, got ", channels.size());
+    for (int k = 0; k < 5; ++k) {
+        TORCH_CHECK(channels[k] > 0 && channels[k] % 8 == 0 && channels[k] < (1 << 24), op, ": channel counts must be positive multiples of 8, got ", channels);
+        C[k] = (int)channels[k];
+    }
+}
+
+// data: flat fp16 / bf16; offsets (B, 5) int64; lengths (B) int32; -> the five fp32 maps (B, C_k, t_max, 7, 7).  offsets and lengths stay on the device.
+std::vector<Tensor> feat_unpack(const Tensor& data, const Tensor& offsets, const Tensor& lengths, at::IntArrayRef channels, int64_t t_max) {
+    const char* op = "cfn::feat_unpack";
+    TORCH_CHECK(data.is_cuda(), op, ": device tensors only (there is no CPU path)");
+    TORCH_CHECK((data.scalar_type() == at::kHalf || data.scalar_type() == at::kBFloat16) && data.dim() == 1 && data.is_contiguous(), op,
+                ": a flat contiguous fp16 / bf16 buffer expected, got ", data.scalar_type(), " ", data.sizes());
+    TORCH_CHECK(offsets.scalar_type() == at::kLong && offsets.dim() == 2 && offsets.size(0) >= 1 && offsets.size(1) == 5 && offsets.device() == data.device(), op,
+                ": offsets (B, 5) int64 on the data's device expected, got ", offsets.scalar_type(), " ", offsets.sizes());
+    const int64_t B = offsets.size(0);
+    TORCH_CHECK(lengths.scalar_type() == at::kInt && lengths.numel() == B && lengths.device() == data.device(), op,
+                ": lengths (B) int32 on the data's device expected, got ", lengths.scalar_type(), " ", lengths.sizes());
+    TORCH_CHECK(t_max >= 1 && t_max < (1 << 24) && B < (1 << 24), op, ": 1 <= t_max expected, got ", t_max);
+    int C[5];
+    feat_channels(channels, op, C);
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(data.device());
+    const Tensor off = offsets.contiguous(), len = lengths.contiguous();
+    std::vector<Tensor> out;
+    for (int k = 0; k < 5; ++k) out.push_back(at::empty({B, C[k], t_max, 7, 7}, data.options().dtype(at::kFloat)));
+    auto fn = data.scalar_type() == at::kHalf ? cfn_feat_unpack_f16 : cfn_feat_unpack_bf16;
+    ok(fn((const unsigned short*)data.data_ptr(), (const long*)off.data_ptr<int64_t>(), len.data_ptr<int>(), out[0].data_ptr<float>(), out[1].data_ptr<float>(),
+          out[2].data_ptr<float>(), out[3].data_ptr<float>(), out[4].data_ptr<float>(), (int)B, (int)t_max, C[0], C[1], C[2], C[3], C[4], (long)data.numel(),
+          stream_of(data)),
+       "cfn_feat_unpack");
+    return out;
+}
+
+// feat: the five fp32 maps (C_k, T, 7, 7) or (1, C_k, T, 7, 7) of one video -> its payload, flat fp16 / bf16
+Tensor feat_pack(at::TensorList feat, at::ScalarType dtype) {
+    const char* op = "cfn::feat_pack";
+    TORCH_CHECK(dtype == at::kHalf || dtype == at::kBFloat16, op, ": fp16 or bf16 expected, got ", dtype);
+    TORCH_CHECK(feat.size() == 5, op, ": five feature maps expected, got ", feat.size());
+    std::vector<Tensor> x;
+    std::vector<int64_t> channels;
+    for (const Tensor& f_ : feat) {
+        TORCH_CHECK(f_.is_cuda(), op, ": device tensors only (there is no CPU path)");
+        const Tensor f = f_.dim() == 5 && f_.size(0) == 1 ? f_.select(0, 0) : f_;
+        TORCH_CHECK(f.scalar_type() == at::kFloat && f.dim() == 4 && f.size(2) * f.size(3) == 49, op, ": fp32 maps (C, T, 7, 7) expected, got ", f.scalar_type(), " ", f.sizes());
+        TORCH_CHECK(f.device() == feat[0].device() && (x.empty() || f.size(1) == x[0].size(1)), op, ": five maps of one frame count on one device expected");
+        x.push_back(f.contiguous());
+        channels.push_back(f.size(0));
+    }
+    const int64_t T = x[0].size(1);
+    TORCH_CHECK(T >= 1 && T < (1 << 24), op, ": at least one frame expected, got ", T);
+    int C[5];
+    feat_channels(channels, op, C);
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(x[0].device());
+    int64_t n = 0;
+    for (int k = 0; k < 5; ++k) n += T * C[k] * 49;
+    Tensor out = at::empty({n}, x[0].options().dtype(dtype));
+    auto fn = dtype == at::kHalf ? cfn_feat_pack_f16 : cfn_feat_pack_bf16;
+    ok(fn(x[0].data_ptr<float>(), x[1].data_ptr<float>(), x[2].data_ptr<float>(), x[3].data_ptr<float>(), x[4].data_ptr<float>(), (unsigned short*)out.data_ptr(), (int)T,
+          C[0], C[1], C[2], C[3], C[4], stream_of(out)),
+       "cfn_feat_pack");
+    return out;
+}
+
 }  // namespace
 
 TORCH_LIBRARY_FRAGMENT(cfn, m) {
@@ -1041,6 +1107,8 @@ TORCH_LIBRARY_FRAGMENT(cfn, m) {
     m.def("time_resize_backward(Tensor g, SymInt[] shape, SymInt L, bool align_corners) -> Tensor");
     m.def("detection_loss(Tensor logits, Tensor labels, Tensor masks, bool align_corners, SymInt crops=1, Tensor? norm=None, float world=1., bool want_probs=True) -> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)");
     m.def("detection_loss_backward(Tensor g_cls, Tensor g_loc, Tensor logits, Tensor labels, Tensor masks, Tensor jstar, Tensor ymax, Tensor norm_used, bool align_corners, SymInt crops, float world) -> Tensor");
+    m.def("feat_unpack(Tensor data, Tensor offsets, Tensor lengths, SymInt[] channels, SymInt t_max) -> Tensor[]");
+    m.def("feat_pack(Tensor[] feat, ScalarType dtype) -> Tensor");
 }
 
 TORCH_LIBRARY_IMPL(cfn, CUDA, m) {      // (the HIP backend of a ROCm build of torch dispatches on the CUDA key)
@@ -1085,4 +1153,6 @@ TORCH_LIBRARY_IMPL(cfn, CUDA, m) {      // (the HIP backend of a ROCm build of t
     m.impl("time_resize_backward", time_resize_backward);
     m.impl("detection_loss", detection_loss);
     m.impl("detection_loss_backward", detection_loss_backward);
+    m.impl("feat_unpack", feat_unpack);
+    m.impl("feat_pack", feat_pack);
 }

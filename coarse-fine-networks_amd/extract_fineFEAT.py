@@ -9,7 +9,10 @@ charades_coarse_fineFEAT.py:84-87):
 average pooling of every stage output, x3d_fine.py:339-363).  ``extract(videos)`` takes any iterable of
 (vid, clip (1,3,T,224,224)); the Charades frame reader itself is out of scope.  A clip may also be uint8 frames:
 U8Clips (1,T,224,224,3), or RawU8Clips -- the frames as decoded plus a crop box (cfn_hip.u8aug.center_crop_params), cropped and
-resized on the GPU as the reference's CenterCropScaled does on the CPU (extract_fineFEAT.py:76)."""
+resized on the GPU as the reference's CenterCropScaled does on the CPU (extract_fineFEAT.py:76).
+
+``extract(..., feat_dtype='fp16' | 'bf16')`` writes ONE packed 16-bit record per video instead, ``<save_dir>/packed/<vid>.cff``
+(cfn_hip/featpack.py): the five maps are rounded and laid out time-major on the GPU (ops.feat_pack) and read back in one copy."""
 import os
 import sys
 
@@ -18,6 +21,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import x3d_fine                                   # noqa: E402
 from cfn_hip.u8clips import RawU8Clips            # noqa: E402
+from cfn_hip import featpack                      # noqa: E402
 
 FEAT_KEYS = ('layer1', 'layer2', 'layer3', 'layer4', 'conv5')
 
@@ -37,17 +41,27 @@ def build_tower(device, ckpt=None, n_classes=157, input_norm=None):
 
 
 @torch.no_grad()
-def extract(net, videos, save_dir, device='cuda', crop=224):
-    for k in FEAT_KEYS:
-        os.makedirs(os.path.join(save_dir, k), exist_ok=True)
+def extract(net, videos, save_dir, device='cuda', crop=224, feat_dtype=None):
+    """feat_dtype None: the reference's five fp32 files per video; 'fp16' / 'bf16': one packed record per video"""
+    dt = None if feat_dtype is None else featpack.feat_dtype(feat_dtype)
+    if dt is None:
+        for k in FEAT_KEYS:
+            os.makedirs(os.path.join(save_dir, k), exist_ok=True)
+    else:
+        from cfn_hip import ops
     n = 0
     for vid, clip in videos:
         clip = clip.to(device)
         if isinstance(clip, RawU8Clips):
             clip = clip.transform(crop)
         feat, _ = net([clip, None])
-        for k in FEAT_KEYS:
-            torch.save(feat[k].data.cpu(), os.path.join(save_dir, k, vid))
+        if dt is None:
+            for k in FEAT_KEYS:
+                torch.save(feat[k].data.cpu(), os.path.join(save_dir, k, vid))
+        else:
+            maps = [feat[k].data for k in FEAT_KEYS]
+            payload = ops.feat_pack(maps, dt).cpu()            # one read-back per video
+            featpack.write_record(featpack.record_path(save_dir, vid), payload, dt, maps[0].shape[-3], [m.shape[-4] for m in maps])
         n += 1
     return n
 
@@ -59,8 +73,10 @@ if __name__ == '__main__':
     ap.add_argument('--save-dir', default='fine_feat')
     ap.add_argument('--ckpt', default='models/fine_charades_039000_SAVE.pt')
     ap.add_argument('--synthetic', type=int, default=2, help='number of synthetic videos to run')
+    ap.add_argument('--feat-dtype', default=None, choices=['fp16', 'bf16'],
+                    help='write one packed 16-bit record per video (<save-dir>/packed/<vid>.cff) instead of five fp32 files')
     a = ap.parse_args()
     os.environ.setdefault('CUDA_VISIBLE_DEVICES', a.gpu)
     g = torch.Generator().manual_seed(0)
     vids = (('synthetic_%03d' % i, torch.randn(1, 3, 64, 224, 224, generator=g)) for i in range(a.synthetic))
-    print('wrote', extract(build_tower('cuda', a.ckpt), vids, a.save_dir), 'videos to', a.save_dir)
+    print('wrote', extract(build_tower('cuda', a.ckpt), vids, a.save_dir, feat_dtype=a.feat_dtype), 'videos to', a.save_dir)

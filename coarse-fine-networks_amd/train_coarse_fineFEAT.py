@@ -30,6 +30,7 @@ from apmeter import APMeter                       # noqa: E402
 from cfn_hip import metrics                       # noqa: E402
 from train_fine import lr_warmup, flatten_clips   # noqa: E402
 from cfn_hip.u8clips import RawU8Clips, U8Clips, CHARADES_MEAN, CHARADES_STD   # noqa: E402,F401
+from cfn_hip.featpack import PackedFeats          # noqa: E402
 
 BS = 6
 BS_UPSCALE = 1
@@ -111,11 +112,20 @@ def param_groups(net, lr):
 CROP = 224                      # the X3D-M crop the coarse net runs at (train_coarse_fineFEAT.py:79-85)
 
 
+def unpack_feat(feat, device=None):
+    """the fine features as the dict {k: (B, C_k, T', 7, 7) fp32} the net takes: a PackedFeats batch (collate.coarse_collate_packed: 16-bit,
+    unpadded) is widened and padded by one kernel on its device; a dict passes through"""
+    if isinstance(feat, PackedFeats):
+        return (feat if device is None else feat.to(device)).unpack()
+    return feat if device is None else {k: v.to(device) for k, v in feat.items()}
+
+
 def forward_video(net, inputs, feat, feat_masks, i, meta, t_lim=1000, crop=CROP):
     """whole-video inference with the reference's chunking of long videos (:215-224); inputs: fp32 clip, U8Clips, or RawU8Clips
     (untransformed frames + crop boxes on the device: every chunk is cropped / resized to `crop` / flipped when its turn comes, so
-    the transformed video is never resident as a whole)"""
+    the transformed video is never resident as a whole).  feat: the dict, or a PackedFeats, unpacked ONCE for all chunks"""
     raw = isinstance(inputs, RawU8Clips)
+    feat = unpack_feat(feat)
     if inputs.shape[2] < t_lim + 5:
         return net([inputs.transform(crop) if raw else inputs, feat, feat_masks, i, meta])
     outs = []
@@ -131,6 +141,7 @@ def forward_video(net, inputs, feat, feat_masks, i, meta, t_lim=1000, crop=CROP)
 
 
 def train_step(net, reducer, optimizer, inputs, labels, masks, feat, feat_masks, meta, i=0, pre_step=None, fused=None):
+    feat = unpack_feat(feat)       # (a PackedFeats batch; a dict is taken as it is)
     logits = net([inputs, feat, feat_masks, i, meta])
     cls_loss, loc_loss, probs = detection_loss(logits, labels, masks, fused=fused)
     from train_fine import loss_scaler, unscale_grads
@@ -170,6 +181,7 @@ def run(init_lr=INIT_LR, warmup_steps=0, max_epochs=200, mode='rgb', root=None, 
     """input_norm: see build_model -- needed when the loaders collate uint8 frames (collate.coarse_collate_u8, or coarse_collate_raw_u8:
     untransformed frames + crop boxes, transformed on the GPU -- per training batch, and per chunk of a validation video).
     device_ap: the training phases keep their AP rows and loss totals on the GPU (cfn_hip.metrics.StepMetrics): no read-back per step.
+    The loaders may collate packed 16-bit fine features (collate.coarse_collate_packed*: member 3 is a PackedFeats); nothing changes for dicts.
     fused_loss: the loss runs as one forward and one backward kernel (train_fine.detection_loss(fused=True)); False leaves the choice to
     CFN_FUSED_LOSS."""
     fused = True if fused_loss else None
@@ -216,7 +228,7 @@ def run(init_lr=INIT_LR, warmup_steps=0, max_epochs=200, mode='rgb', root=None, 
                 b, n = inputs.shape[:2]            # n crops per video at validation time (:198-201)
                 inputs = flatten_clips(inputs, dev, CROP if train else None)      # validation: forward_video transforms chunk by chunk
                 labels, masks, feat_masks, meta = labels.to(dev), masks.to(dev), feat_masks.to(dev), meta.to(dev)
-                feat = {k: v.to(dev) for k, v in feat.items()}
+                feat = unpack_feat(feat, dev)      # a PackedFeats batch (coarse_collate_packed): unpacked once per batch / validation video
                 valid_t = masks.sum(1).int()
                 n_it += 1
                 if train:

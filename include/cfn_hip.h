@@ -476,6 +476,31 @@ int cfn_ap_sort(const float* scores, const unsigned char* targets, const int* co
 int cfn_ap_reduce(const unsigned char* sorted_targets, const int* count, float* ap, int K, long cap, void* stream);
 int cfn_ap_sort_tile(void);
 
+/* =====================================================================================================================
+ * Packed 16-bit fine features (csrc/featpack.hip; the record format and the batch type: cfn_hip/featpack.py).  The five feature
+ * maps of the Fine stream (reference extract_fineFEAT.py:153-173, read back by charades_coarse_fineFEAT.py:84-87) are stored
+ * and moved as fp16 (_f16) or bf16 (_bf16), unpadded and time-major: per video and key a block (T', C_k, 49).
+ *   cfn_feat_unpack: data = `total` 16-bit elements starting on a 16-byte boundary; offsets (B, 5) = first element of every
+ *     block, multiples of 8; lengths (B).  out_k (B, C_k, t_max, 49) fp32:
+ *       out_k[b, c, t, p] = t < lengths[b] ? widen(data[offsets[b, k] + (t * C_k + c) * 49 + p]) : 0.0f
+ *     EVERY element of the five outputs is written; widening is exact (fp16 subnormals included).  offsets and lengths are read
+ *     on the device only: a length is clamped to [0, t_max], an offset is rounded down to a multiple of 8 and every read is
+ *     checked against `total` (a bad offset gives wrong values, never a fault).
+ *   cfn_feat_pack: x_k (C_k, T, 49) fp32, the maps of ONE video -> dst = its payload, the five blocks (T, C_k, 49) back to
+ *     back in key order, starting on a 16-byte boundary.  Round to nearest even, bit-identical to the CPU's tensor.to(dtype)
+ *     for every finite value (fp16 overflow -> inf); a NaN stays a NaN.
+ * One launch each on `stream`, no allocation, no synchronisation (capturable).  Return 1 for null pointers, B < 1, t_max / T < 1,
+ * a channel count that is not a positive multiple of 8, or a misaligned 16-bit buffer.
+ * ===================================================================================================================== */
+int cfn_feat_unpack_f16(const unsigned short* data, const long* offsets, const int* lengths, float* out0, float* out1, float* out2,
+                        float* out3, float* out4, int B, int t_max, int c0, int c1, int c2, int c3, int c4, long total, void* stream);
+int cfn_feat_unpack_bf16(const unsigned short* data, const long* offsets, const int* lengths, float* out0, float* out1, float* out2,
+                         float* out3, float* out4, int B, int t_max, int c0, int c1, int c2, int c3, int c4, long total, void* stream);
+int cfn_feat_pack_f16(const float* x0, const float* x1, const float* x2, const float* x3, const float* x4, unsigned short* dst, int T,
+                      int c0, int c1, int c2, int c3, int c4, void* stream);
+int cfn_feat_pack_bf16(const float* x0, const float* x1, const float* x2, const float* x3, const float* x4, unsigned short* dst, int T,
+                       int c0, int c1, int c2, int c3, int c4, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1499,3 +1499,55 @@ def feat_pack(feat, dtype, out=None):
         raise RuntimeError('feat_pack: out: a flat %s tensor of %d elements expected, got %s %s' % (dtype, n, out.dtype, tuple(out.shape)))
     call('cfn_feat_pack' + sfx, *xs, out, T, *channels)
     return out
+
+
+# ---- baseline JPEG frames decoded on the GPU (csrc/jpegdec.hip; the host side and the batch type: cfn_hip/jpegdec.py) ------------------------
+def jpeg_workspace_bytes(rows, slots, lanes, blocks_max):
+    """bytes of workspace cfn_jpeg_decode_u8 needs for `rows` frames into `slots` = clips x Tmax frame slots"""
+    n = int(query('cfn_jpeg_workspace_bytes', int(rows), int(slots), int(lanes), int(blocks_max)))
+    if n < 0:
+        raise RuntimeError('jpeg_decode_u8: bad sizes (%d frames, %d slots, %d lanes, %d blocks)' % (rows, slots, lanes, blocks_max))
+    return n
+
+
+def jpeg_decode_u8(jpeg_clips, out=None, status=None, workspace=None):
+    """a cfn_hip.jpegdec.JpegClips batch on the GPU -> its frames (N, Tmax, Hmax, Wmax, 3) uint8, N = all clips of the batch: what PIL
+    decodes, bit for bit, each picture in the top-left corner, zero bytes elsewhere (RawU8Clips.frames as collate._pad_raw_u8 builds
+    them).  On the current stream; nothing is read back: sizes come from the batch's host-side `dims`.
+    out: preallocated frames, every byte is written.  status: (R,) int32, one word per row of `frames`, zeroed and set by the kernels
+    (0 = decoded; jpegdec.check_status raises on anything else); with status=None the words are dropped -- pass one to learn of a bad
+    frame.  workspace: a uint8 device buffer of at least jpeg_workspace_bytes(...) (allocated per call otherwise).  No CPU path."""
+    jc = jpeg_clips
+    if not (hasattr(jc, '_fields') and jc._fields[:6] == ('data', 'frames', 'tables', 'geom', 'lengths', 'box')):
+        raise RuntimeError('jpeg_decode_u8: a JpegClips batch expected, got %s' % type(jc).__name__)
+    data, frames, tables = jc.data, jc.frames, jc.tables
+    geom, lengths = jc.geom.reshape(-1, 4), jc.lengths.reshape(-1)
+    T, H, W, lanes, blocks_max = (int(d) for d in jc.dims)
+    if data.dtype != torch.uint8 or data.dim() != 1 or data.numel() < 1:
+        raise RuntimeError('jpeg_decode_u8: data: a flat uint8 buffer expected, got %s %s' % (data.dtype, tuple(data.shape)))
+    if frames.dim() != 2 or frames.shape[1] != 8 or frames.shape[0] < 1:
+        raise RuntimeError('jpeg_decode_u8: frames (R, 8) int32 expected, got %s %s' % (frames.dtype, tuple(frames.shape)))
+    if tables.dim() != 2 or tables.shape[1] != 3456 or tables.shape[0] < 1:
+        raise RuntimeError('jpeg_decode_u8: tables (S, 3456) int32 expected, got %s %s' % (tables.dtype, tuple(tables.shape)))
+    N, R = int(lengths.numel()), int(frames.shape[0])
+    if geom.shape[0] != N:
+        raise RuntimeError('jpeg_decode_u8: one geometry per clip expected: %d clips, geom %s' % (N, tuple(jc.geom.shape)))
+    dev = data.device
+    if out is None:
+        out = torch.empty(N, T, H, W, 3, dtype=torch.uint8, device=dev)
+    elif out.dtype != torch.uint8 or out.numel() != N * T * H * W * 3 or tuple(out.shape[-4:]) != (T, H, W, 3) or not out.is_contiguous():
+        raise RuntimeError('jpeg_decode_u8: out: a contiguous uint8 tensor (..., %d, %d, %d, 3) of %d clips expected, got %s %s'
+                           % (T, H, W, N, out.dtype, tuple(out.shape)))
+    if status is None:
+        status = torch.empty(R, dtype=torch.int32, device=dev)
+    elif status.dtype != torch.int32 or status.numel() != R or not status.is_contiguous():
+        raise RuntimeError('jpeg_decode_u8: status: %d contiguous int32 words expected, got %s %s' % (R, status.dtype, tuple(status.shape)))
+    need = jpeg_workspace_bytes(R, N * T, lanes, blocks_max)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+    elif workspace.dtype != torch.uint8 or workspace.numel() < need or not workspace.is_contiguous():
+        raise RuntimeError('jpeg_decode_u8: workspace: a contiguous uint8 buffer of at least %d bytes expected, got %s %s'
+                           % (need, workspace.dtype, tuple(workspace.shape)))
+    call('cfn_jpeg_decode_u8', data.contiguous(), frames.contiguous(), tables.contiguous(), geom.contiguous(), lengths.contiguous(), out, status,
+         workspace, int(workspace.numel()), int(data.numel()), R, int(tables.shape[0]), N, T, H, W, lanes, blocks_max)
+    return out.view(N, T, H, W, 3)

@@ -996,6 +996,23 @@ def _(feat, dtype):
     return feat[0].new_empty((n,), dtype=dtype)
 
 
+# ---- baseline JPEG frames decoded on the GPU (csrc/jpegdec.hip; the batch type: cfn_hip/jpegdec.py), no gradient ----------------------------
+@_op('jpeg_decode_u8')
+def jpeg_decode_u8(data: torch.Tensor, frames: torch.Tensor, tables: torch.Tensor, geom: torch.Tensor, lengths: torch.Tensor,
+                   dims: Sequence[int]) -> Tuple[torch.Tensor, torch.Tensor]:
+    """the members of a JpegClips batch -> (frames (N, Tmax, Hmax, Wmax, 3) uint8, status (R,) int32)"""
+    from .jpegdec import JpegClips
+    status = torch.empty(frames.shape[0], dtype=torch.int32, device=data.device)
+    box = torch.zeros(lengths.numel(), 4, dtype=torch.int32, device=data.device)
+    return _ops.jpeg_decode_u8(JpegClips(data, frames, tables, geom, lengths, box, tuple(dims)), status=status), status
+
+
+@jpeg_decode_u8.register_fake
+def _(data, frames, tables, geom, lengths, dims):
+    return (data.new_empty((lengths.numel(), dims[0], dims[1], dims[2], 3), dtype=torch.uint8),
+            data.new_empty((frames.shape[0],), dtype=torch.int32))
+
+
 OPERATORS = ('dwconv3d', 'pwconv', 'time_sample', 'dwconv_t5', 'stem_conv', 'conv3d_dense', 'bn_fold', 'bn_add_relu', 'affine_act',
              'pool_hw', 'interp1d', 'grid_cdf', 'gauss_align', 'fusion_gather', 'film', 'time_resize', 'stem_conv_u8', 'detection_loss')
 # the uint8 input path's operators without a gradient (the host-built table, the frames -> fp32 clip converter)
@@ -1006,6 +1023,8 @@ AUGMENT_OPERATORS = ('crop_resize_flip_u8',)
 METRIC_OPERATORS = ('ap_append', 'ap_sort', 'average_precision')
 # packed 16-bit fine features: widen + pad a batch, round + transpose one video's maps (no gradient)
 FEATURE_OPERATORS = ('feat_unpack', 'feat_pack')
+# baseline JPEG frames -> uint8 frames on the GPU (no gradient)
+DECODE_OPERATORS = ('jpeg_decode_u8',)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------

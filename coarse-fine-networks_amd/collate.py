@@ -29,12 +29,18 @@ extraction scripts call).
 memory-mapped 16-bit record of the video (one file instead of five fp32 ones).  Member 3 of the batch becomes a ``PackedFeats``: the first
 min(T', cap) frames of every block copied, unpadded and still 16-bit, into one flat buffer (five contiguous copies per sample, no zero
 fill); ``PackedFeats.unpack()`` widens and pads on the GPU.  The other seven members are what ``coarse_collate*`` builds.
+
+``fine_collate_jpeg`` / ``coarse_collate_jpeg`` / ``coarse_collate_packed_jpeg``: the samples of ``*_collate_raw_u8`` with the frames still ENCODED --
+the clip member of a sample is a pair ``(n lists of T_i baseline JPEG frames (bytes), box (n, 4) int)``.  The clip member of the batch becomes a
+``cfn_hip.jpegdec.JpegClips``: the entropy-coded segments in one flat buffer plus the decoder tables; ``JpegClips.decode()`` makes the RawU8Clips
+batch on the GPU, bit for bit what PIL decodes (the training and extraction scripts call it).  All frames of a clip share size and sampling.
 """
 import numpy as np
 import torch
 
 from cfn_hip.u8clips import RawU8Clips, U8Clips, CHARADES_MEAN, CHARADES_STD  # noqa: F401
 from cfn_hip.featpack import PackedFeats, Record, collate_records  # noqa: F401
+from cfn_hip.jpegdec import JpegClips, collate_jpeg  # noqa: F401
 
 
 def _t(a):
@@ -189,3 +195,20 @@ def coarse_collate_packed_u8(batch, cap=128):
 def coarse_collate_packed_raw_u8(batch, cap=128):
     """coarse_collate_packed for samples whose clips are (frames (n,T,h,w,3) uint8, box (n,4)) pairs"""
     return [_pad_raw_u8([b[0] for b in batch])] + _coarse_rest_packed(batch, cap)
+
+
+def fine_collate_jpeg(batch):
+    """fine_collate_raw_u8 for samples ((n lists of encoded frames, box (n,4)), label (157,TL), vid): the frames stay JPEG (JpegClips)"""
+    labels = [b[1] for b in batch]
+    tl_max = max(_t(lb).shape[1] for lb in labels)
+    return [collate_jpeg([b[0] for b in batch]), _pad_time(labels, 1, tl_max), _label_mask(labels, tl_max), [b[2] for b in batch]]
+
+
+def coarse_collate_jpeg(batch, cap=128):
+    """coarse_collate_raw_u8 for samples whose clips are (n lists of encoded frames, box (n,4)) pairs"""
+    return [collate_jpeg([b[0] for b in batch])] + _coarse_rest(batch, cap)
+
+
+def coarse_collate_packed_jpeg(batch, cap=128):
+    """coarse_collate_packed_raw_u8 for samples whose clips are (n lists of encoded frames, box (n,4)) pairs"""
+    return [collate_jpeg([b[0] for b in batch])] + _coarse_rest_packed(batch, cap)

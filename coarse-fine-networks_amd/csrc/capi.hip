@@ -187,3 +187,32 @@ extern "C" int cfn_prof_collect(int family, double* total_ms, long* launches, do
     if (total_bytes) *total_bytes = by;
     return CFN_OK;
 }
+
+// ---- baseline JPEG decode (csrc/jpegdec.hip) -----------------------------------------------------------------------------------------
+#include "jpegdec.h"
+
+extern "C" long cfn_jpeg_workspace_bytes(int rows, long slots, int lanes, int blocks_max) {
+    if (rows < 1 || slots < 1 || lanes < 1 || blocks_max < 1) return -1;
+    JpegLayout l;
+    jpeg_workspace_layout(rows, slots, lanes, blocks_max, &l);
+    return l.total;
+}
+
+extern "C" int cfn_jpeg_decode_u8(const unsigned char* data, const int* frames, const int* tables, const int* geom, const int* lengths,
+                                  unsigned char* out, int* status, void* ws, long ws_bytes, long data_bytes, int rows, int sets, int N,
+                                  int Tmax, int Hmax, int Wmax, int lanes, int blocks_max, void* stream) {
+    CFN_REQUIRE(data && frames && tables && geom && lengths && out && status && ws, "cfn_jpeg_decode_u8: null tensor");
+    CFN_REQUIRE(rows >= 1 && sets >= 1 && N >= 1 && Tmax >= 1 && Hmax >= 1 && Wmax >= 1 && lanes >= 1 && blocks_max >= 1 && data_bytes >= 1,
+                "cfn_jpeg_decode_u8: bad shape (%d frames, %d table sets, %d clips of %d x %d x %d, %d lanes, %d blocks, %ld bytes)", rows, sets, N,
+                Tmax, Hmax, Wmax, lanes, blocks_max, data_bytes);
+    CFN_REQUIRE(data_bytes < (1L << 31), "cfn_jpeg_decode_u8: %ld bytes of data: offsets are 32-bit", data_bytes);
+    CFN_REQUIRE(((uintptr_t)data & 3) == 0 && ((uintptr_t)out & 3) == 0 && ((uintptr_t)ws & 15) == 0,
+                "cfn_jpeg_decode_u8: data and out must start on a 4-byte boundary, the workspace on a 16-byte boundary");
+    const long need = cfn_jpeg_workspace_bytes(rows, (long)N * Tmax, lanes, blocks_max);
+    CFN_REQUIRE(ws_bytes >= need, "cfn_jpeg_decode_u8: a workspace of %ld bytes is needed, %ld given", need, ws_bytes);
+    JpegArgs a = {};
+    a.data = data; a.frames = frames; a.tables = tables; a.geom = geom; a.lengths = lengths; a.out = out; a.status = status;
+    a.data_bytes = data_bytes; a.rows = rows; a.sets = sets; a.N = N; a.T = Tmax; a.H = Hmax; a.W = Wmax; a.lanes = lanes;
+    a.blocks_max = blocks_max;
+    return jpeg_decode_launch(a, ws, stream);
+}

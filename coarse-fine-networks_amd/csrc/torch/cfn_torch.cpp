@@ -15,6 +15,7 @@
 // metrics: ap_append (mutates its stores), ap_sort, average_precision (csrc/apmeter.hip) -- no gradients.
 // loss: detection_loss + detection_loss_backward (csrc/detloss.hip), the opt-in fused detection loss of the three training scripts.
 // packed 16-bit fine features: feat_unpack, feat_pack (csrc/featpack.hip) -- no gradients.
+// baseline JPEG frames -> uint8 frames: jpeg_decode_u8 (csrc/jpegdec.hip) -- no gradient.
 #include <ATen/ATen.h>
 // (a ROCm build of torch presents its HIP devices as "cuda": the masquerading guard / stream classes are the ones that accept them)
 #include <ATen/hip/impl/HIPGuardImplMasqueradingAsCUDA.h>
@@ -1062,6 +1063,38 @@ Tensor feat_pack(at::TensorList feat, at::ScalarType dtype) {
     return out;
 }
 
+// ---- baseline JPEG frames decoded on the GPU (csrc/jpegdec.hip; cfn_hip/jpegdec.py) -- no gradient ---------------------------------------------
+// the members of a JpegClips batch; dims = (Tmax, Hmax, Wmax, decoder lanes, most blocks of a frame) -> (frames (N, Tmax, Hmax, Wmax, 3) uint8, status (R) int32)
+std::tuple<Tensor, Tensor> jpeg_decode_u8(const Tensor& data, const Tensor& frames, const Tensor& tables, const Tensor& geom, const Tensor& lengths,
+                                          at::IntArrayRef dims) {
+    const char* op = "cfn::jpeg_decode_u8";
+    TORCH_CHECK(data.is_cuda(), op, ": device tensors only (there is no CPU path)");
+    TORCH_CHECK(data.scalar_type() == at::kByte && data.dim() == 1 && data.numel() >= 1, op, ": data: a flat uint8 buffer expected, got ", data.scalar_type(), " ", data.sizes());
+    TORCH_CHECK(frames.scalar_type() == at::kInt && frames.dim() == 2 && frames.size(0) >= 1 && frames.size(1) == 8, op, ": frames (R, 8) int32 expected, got ",
+                frames.scalar_type(), " ", frames.sizes());
+    TORCH_CHECK(tables.scalar_type() == at::kInt && tables.dim() == 2 && tables.size(0) >= 1 && tables.size(1) == 3456, op, ": tables (S, 3456) int32 expected, got ",
+                tables.scalar_type(), " ", tables.sizes());
+    const int64_t N = lengths.numel(), R = frames.size(0);
+    TORCH_CHECK(lengths.scalar_type() == at::kInt && N >= 1 && geom.scalar_type() == at::kInt && geom.numel() == 4 * N, op,
+                ": lengths (N) and geom (N, 4) int32 expected, got ", lengths.sizes(), " and ", geom.sizes());
+    for (const Tensor* t : {&frames, &tables, &geom, &lengths}) TORCH_CHECK(t->device() == data.device(), op, ": all members on the data's device expected");
+    TORCH_CHECK(dims.size() == 5, op, ": dims = (Tmax, Hmax, Wmax, lanes, blocks) expected, got ", dims);
+    for (int64_t d : dims) TORCH_CHECK(d >= 1 && d < (1LL << 31), op, ": positive dims expected, got ", dims);
+    TORCH_CHECK(N * dims[0] < (1LL << 31) && R < (1LL << 31), op, ": too many frames");
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(data.device());
+    const Tensor d = data.contiguous(), f = frames.contiguous(), tb = tables.contiguous(), g = geom.contiguous(), len = lengths.contiguous();
+    const long need = cfn_jpeg_workspace_bytes((int)R, (long)(N * dims[0]), (int)dims[3], (int)dims[4]);
+    TORCH_CHECK(need > 0, op, ": bad sizes");
+    Tensor ws = at::empty({(int64_t)need}, data.options());
+    Tensor out = at::empty({N, dims[0], dims[1], dims[2], 3}, data.options());
+    Tensor status = at::empty({R}, data.options().dtype(at::kInt));
+    ok(cfn_jpeg_decode_u8(d.data_ptr<uint8_t>(), f.data_ptr<int>(), tb.data_ptr<int>(), g.data_ptr<int>(), len.data_ptr<int>(), out.data_ptr<uint8_t>(),
+                          status.data_ptr<int>(), ws.data_ptr(), need, (long)d.numel(), (int)R, (int)tb.size(0), (int)N, (int)dims[0], (int)dims[1], (int)dims[2],
+                          (int)dims[3], (int)dims[4], stream_of(out)),
+       "cfn_jpeg_decode_u8");
+    return std::make_tuple(out, status);
+}
+
 }  // namespace
 
 TORCH_LIBRARY_FRAGMENT(cfn, m) {
@@ -1109,6 +1142,7 @@ TORCH_LIBRARY_FRAGMENT(cfn, m) {
     m.def("detection_loss_backward(Tensor g_cls, Tensor g_loc, Tensor logits, Tensor labels, Tensor masks, Tensor jstar, Tensor ymax, Tensor norm_used, bool align_corners, SymInt crops, float world) -> Tensor");
     m.def("feat_unpack(Tensor data, Tensor offsets, Tensor lengths, SymInt[] channels, SymInt t_max) -> Tensor[]");
     m.def("feat_pack(Tensor[] feat, ScalarType dtype) -> Tensor");
+    m.def("jpeg_decode_u8(Tensor data, Tensor frames, Tensor tables, Tensor geom, Tensor lengths, SymInt[] dims) -> (Tensor, Tensor)");
 }
 
 TORCH_LIBRARY_IMPL(cfn, CUDA, m) {      // (the HIP backend of a ROCm build of torch dispatches on the CUDA key)
@@ -1155,4 +1189,5 @@ TORCH_LIBRARY_IMPL(cfn, CUDA, m) {      // (the HIP backend of a ROCm build of t
     m.impl("detection_loss_backward", detection_loss_backward);
     m.impl("feat_unpack", feat_unpack);
     m.impl("feat_pack", feat_pack);
+    m.impl("jpeg_decode_u8", jpeg_decode_u8);
 }

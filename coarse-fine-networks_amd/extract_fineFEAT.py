@@ -21,6 +21,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import x3d_fine                                   # noqa: E402
 from cfn_hip.u8clips import RawU8Clips            # noqa: E402
+from cfn_hip.jpegdec import JpegClips, decode_checked   # noqa: E402
 from cfn_hip import featpack                      # noqa: E402
 
 FEAT_KEYS = ('layer1', 'layer2', 'layer3', 'layer4', 'conv5')
@@ -51,6 +52,8 @@ def extract(net, videos, save_dir, device='cuda', crop=224, feat_dtype=None):
         from cfn_hip import ops
     n = 0
     for vid, clip in videos:
+        if isinstance(clip, JpegClips):            # frames still JPEG: decoded on the device into the RawU8Clips batch (one status read-back)
+            clip = decode_checked(clip, device, [vid]).flatten_crops()
         clip = clip.to(device)
         if isinstance(clip, RawU8Clips):
             clip = clip.transform(crop)

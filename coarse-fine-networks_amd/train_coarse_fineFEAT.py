@@ -226,7 +226,7 @@ def run(init_lr=INIT_LR, warmup_steps=0, max_epochs=200, mode='rgb', root=None, 
                     if not (cdist.all_agree(ok, dev) if world > 1 else ok):
                         continue
                 b, n = inputs.shape[:2]            # n crops per video at validation time (:198-201)
-                inputs = flatten_clips(inputs, dev, CROP if train else None)      # validation: forward_video transforms chunk by chunk
+                inputs = flatten_clips(inputs, dev, CROP if train else None, names=name)      # validation: forward_video transforms chunk by chunk
                 labels, masks, feat_masks, meta = labels.to(dev), masks.to(dev), feat_masks.to(dev), meta.to(dev)
                 feat = unpack_feat(feat, dev)      # a PackedFeats batch (coarse_collate_packed): unpacked once per batch / validation video
                 valid_t = masks.sum(1).int()

@@ -28,6 +28,7 @@ import x3d_fine                                   # noqa: E402
 from cfn_hip import dist as cdist                 # noqa: E402
 from cfn_hip import staging                       # noqa: E402
 from cfn_hip.u8clips import RawU8Clips, U8Clips, CHARADES_MEAN, CHARADES_STD   # noqa: E402,F401
+from cfn_hip.jpegdec import JpegClips, decode_checked        # noqa: E402
 from apmeter import APMeter                       # noqa: E402
 from cfn_hip import metrics                       # noqa: E402
 
@@ -142,10 +143,14 @@ def build_model(device, n_classes=NUM_CLASSES, pretrained=None, dropout=0.5, act
     return net.to(device)
 
 
-def flatten_clips(inputs, dev, crop=None):
+def flatten_clips(inputs, dev, crop=None, names=None):
     """(b, n crops, ...) -> (b * n, ...) on `dev`: an fp32 clip tensor (b, n, 3, T, H, W), a U8Clips batch, or a RawU8Clips batch
     (frames as decoded + crop boxes, collate.fine_collate_raw_u8), which is cropped, resized to `crop` x `crop` and flipped on `dev`, on
-    the current stream, into the U8Clips batch the net takes (crop=None: handed on as it is)"""
+    the current stream, into the U8Clips batch the net takes (crop=None: handed on as it is).  A JpegClips batch (frames still JPEG,
+    collate.fine_collate_jpeg) is first decoded on `dev`, on the current stream, into that RawU8Clips batch; its status words are read
+    back once, and a frame that did not decode raises, naming the video (names: one per video of the batch)."""
+    if isinstance(inputs, JpegClips):
+        inputs = decode_checked(inputs, dev, names)
     if isinstance(inputs, RawU8Clips):
         raw = inputs.flatten_crops().to(dev, non_blocking=True)
         return raw if crop is None else raw.transform(crop)
@@ -318,7 +323,7 @@ def run(init_lr=INIT_LR, warmup_steps=0, max_epochs=200, mode='rgb', root=None, 
                 if not ok:
                     continue
                 b, n = inputs.shape[:2]          # n crops per video (1 in training, train_fine.py:176-185)
-                inputs = flatten_clips(inputs, dev, crop)
+                inputs = flatten_clips(inputs, dev, crop, names=_name)
                 labels, masks = labels.to(dev), masks.to(dev)
                 valid_t = masks.sum(1).int()
                 n_it += 1

@@ -28,6 +28,7 @@ import train_fine                # noqa: E402
 from cfn_hip import staging                       # noqa: E402
 from cfn_hip import dist as cdist                 # noqa: E402
 from cfn_hip import metrics                       # noqa: E402
+from cfn_hip.jpegdec import JpegClips, decode_checked   # noqa: E402
 from train_fine import lr_warmup                  # noqa: E402
 
 BS = 8
@@ -154,6 +155,8 @@ def run(init_lr=INIT_LR, warmup_steps=0, max_steps=None, batch_size=BS, fine_fra
         if not (cdist.all_agree(ok, dev) if world > 1 else ok):
             continue
         warm = (lambda: lr_warmup(init_lr, steps, warmup_steps, optimizer))
+        if isinstance(clip, JpegClips):            # frames still JPEG (collate_jpeg): decoded on the device, one status read-back per batch
+            clip = decode_checked(clip, dev).flatten_crops()
         clip = clip.to(dev)
         if isinstance(clip, tc.RawU8Clips):
             clip = clip.transform(crop)

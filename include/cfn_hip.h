@@ -501,6 +501,36 @@ int cfn_feat_pack_f16(const float* x0, const float* x1, const float* x2, const f
 int cfn_feat_pack_bf16(const float* x0, const float* x1, const float* x2, const float* x3, const float* x4, unsigned short* dst, int T,
                        int c0, int c1, int c2, int c3, int c4, void* stream);
 
+/* =====================================================================================================================
+ * Baseline JPEG frames decoded on the GPU (csrc/jpegdec.hip; the host side and the batch type: cfn_hip/jpegdec.py), bit for bit
+ * what PIL with libjpeg gives.  Replaces the reference's per-frame host decode Image.open(f).convert('RGB') in pil_loader /
+ * video_loader of charades_fine.py and charades_coarse_fineFEAT.py.  Baseline sequential DCT, 8 bit, one interleaved scan; gray
+ * or YCbCr 4:4:4 / 4:2:2 / 4:2:0; restart intervals.
+ *   data: `data_bytes` bytes, every frame's entropy-coded segment (stuffed zeros and RSTn kept), each on a 4-byte boundary and
+ *     followed by >= 8 zero bytes.  frames (rows, 8) int32 per frame: clip, t, offset, bytes, table set, restart interval, first
+ *     decoder lane, decoder lanes (= restart intervals).  tables (sets, 3456) int32: 2 quantisation tables in natural order
+ *     (component 0; components 1 and 2), then DC0, DC1, AC0, AC1 as look[512] (9-bit lookahead: length << 8 | symbol), maxcode[32],
+ *     valoff[32] (both indexed by code length), huffval[256].  geom (N, 4) int32 per clip: h, w, luma sampling (h << 4 | v),
+ *     components.  lengths (N) int32.
+ *   out (N, Tmax, Hmax, Wmax, 3) uint8: EVERY byte is written -- the h x w picture of frame (clip, t) in the top-left corner,
+ *     zero bytes beside and below it and in frames no row of `frames` names.  status (rows) int32, zeroed by the call: 0 = decoded,
+ *     bit 0 = the frame's record disagrees with the batch, bit 1 = ran out of data / a restart marker is missing, bit 2 = invalid
+ *     Huffman code.  Such a frame stops where it is; every other frame is unaffected.
+ *   ws: cfn_jpeg_workspace_bytes(rows, N * Tmax, lanes, blocks_max) bytes on a 16-byte boundary (lanes = sum of the frames' decoder
+ *     lanes, blocks_max = most 8 x 8 blocks of one frame): int16 coefficients [frame][component][block row][block column][64],
+ *     planar 8-bit samples, interval starts.  The library keeps no state; the caller owns the buffer until the stream has passed.
+ * Entropy decode runs one lane per (frame, restart interval); dequantise + jidctint ("islow", int32) one lane per block; "fancy"
+ * upsampling + YCbCr -> RGB one lane per 4 pixels.  Records, tables and geometry are DATA read on the device: every index derived
+ * from them is checked or masked, every loop bound is independent of the bit stream (a bad batch sets status, never faults or
+ * spins).  3 memsets + 4 launches on `stream`, no allocation, no synchronisation.  Returns 1 for null pointers, non-positive
+ * sizes, data of 2 GiB or more, misaligned buffers or a workspace that is too small; cfn_jpeg_workspace_bytes -1 for
+ * non-positive sizes.
+ * ===================================================================================================================== */
+long cfn_jpeg_workspace_bytes(int rows, long slots, int lanes, int blocks_max);
+int cfn_jpeg_decode_u8(const unsigned char* data, const int* frames, const int* tables, const int* geom, const int* lengths,
+                       unsigned char* out, int* status, void* ws, long ws_bytes, long data_bytes, int rows, int sets, int N,
+                       int Tmax, int Hmax, int Wmax, int lanes, int blocks_max, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -495,8 +495,7 @@ static inline bool ew_vec4(long vol, const void* p0, const void* p1 = nullptr, c
 }
 // flat elementwise kernels: one buffer descriptor per channel (< 2 GB), a 1-D grid
 static inline bool ew_flat_ok(long vol, long NC) {
-    static const int on = getenv("CFN_EW_FLAT") ? atoi(getenv("CFN_EW_FLAT")) : 1;
-    return on && vol * 4 < 0x7ffffff0L && NC * (long)cfn_cdiv(vol, 256L * EW_ITEMS * 4) < 0x7fffffffL && NC < 0x7fffffffL;
+    return vol * 4 < 0x7ffffff0L && NC * (long)cfn_cdiv(vol, 256L * EW_ITEMS * 4) < 0x7fffffffL && NC < 0x7fffffffL;
 }
 #define CFN_NC_CHECK(NC) CFN_REQUIRE((NC) > 0 && cfn_split_nc_ok(NC), "N*C = %ld has no grid factorisation", (long)(NC))
 

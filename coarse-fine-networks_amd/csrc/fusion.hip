@@ -551,8 +551,7 @@ extern "C" int cfn_fusion_gather_fwd(const float* x, const float* at_raw, const 
     const long total = (long)B * crops * C * K * P;
     hipStream_t st = (hipStream_t)stream;
     CfnProfScope prof(CFN_K_FUSION, st, 4.0 * B * ((double)C * Tf * P + (double)crops * C * K * P));
-    static const int tiled = getenv("CFN_FUSION_TILED") ? atoi(getenv("CFN_FUSION_TILED")) : 1;
-    if (tiled && P <= 256) {
+    if (P <= 256) {
         // k tile: 13 (K = 65: T = 256), 9 (K = 17: T = 64) or 8 -- the one that wastes the fewest slots
         const int G = 256 / P, CT = 4;
         const int w13 = cfn_cdiv(K, 13) * 13 - K, w9 = cfn_cdiv(K, 9) * 9 - K, w8 = cfn_cdiv(K, 8) * 8 - K;
@@ -584,11 +583,10 @@ extern "C" int cfn_fusion_gather_bwd(const float* gz, const float* z, const floa
     }
     if (gat || gGX) {
         const long total = (long)B * crops * Tf * K * P;
-        static const int tiled = getenv("CFN_FUSION_TILED") ? atoi(getenv("CFN_FUSION_TILED")) : 1;
         const int G = P <= 256 ? 256 / P : 0;
         const int kgroups = cfn_cdiv(K, 8), tgroups = cfn_cdiv(Tf, 8);
         const long nblk = G ? cfn_cdiv((long)B * crops * kgroups * tgroups, G) : 0;
-        if (tiled && G && nblk < 0x7fffffffL)
+        if (G && nblk < 0x7fffffffL)
             hipLaunchKernelGGL((fusion_gather_bwd_w_tiled_kernel<8, 8>), dim3((unsigned)nblk), dim3(256), 0, st, gz, z, den, x, dw,
                                crops, C, Tf, K, P, kgroups, tgroups, B * crops);
         else

@@ -572,8 +572,7 @@ extern "C" int H16N(cfn_pwconv_bwd_weight)(const uint16_t* gy, const uint16_t* y
     a.kblocks = cfn_cdiv(Cin, 32 * NTW);
     const long groups = (long)N * a.mblocks * a.kblocks;
     const int nsteps = (int)((Q + 15) / 16);
-    static const int wgs_env = getenv("CFN_PWB_WG_WGS") ? atoi(getenv("CFN_PWB_WG_WGS")) : 0;
-    long strips = ((wgs_env > 0 ? wgs_env : 1024) + groups - 1) / groups;
+    long strips = (1024 + groups - 1) / groups;
     const long maxs = cfn_cdiv(nsteps, PWB_WAVES * 4);
     if (strips > maxs) strips = maxs;
     if (strips < 1) strips = 1;

@@ -653,11 +653,10 @@ extern "C" int cfn_pwconv_bwd_data_acc(const float* gy, const float* y, const do
     if (acc && !A) {
         // no act' epilogue: contraction on a split-bf16 kernel (those decline the compact shortcut gradient), lattice add behind it
         // (stage-first conv1 of layers 3 / 4, 8 clips x 256 frames: 0.77 ms on pw_deep_kernel with the in-kernel lattice loads)
-        static const int lat = getenv("CFN_PW_LATTICE") ? atoi(getenv("CFN_PW_LATTICE")) : 1;
         PwArgs a2 = a;
         a2.acc = nullptr;
-        int rc = lat ? pwk_try_launch(a2, PW_DGRAD, false, st) : -1;
-        if (rc < 0 && lat) rc = pwt_try_launch(a2, PW_DGRAD, false, st);
+        int rc = pwk_try_launch(a2, PW_DGRAD, false, st);
+        if (rc < 0) rc = pwt_try_launch(a2, PW_DGRAD, false, st);
         if (rc > 0) return rc;
         if (rc == 0) {
             const long total = (long)N * Cin * T * a.acc_Ho * a.acc_Wo;

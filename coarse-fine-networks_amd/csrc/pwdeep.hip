@@ -340,7 +340,6 @@ static int pwd_act(const PwArgs& a, int MT, int NW, unsigned blocks, size_t lds,
 
 int pwd_try_launch(PwArgs& a, int mode, bool stats, hipStream_t st) {
     if (a.stem || a.stride != 1 || a.K < 48 || a.M <= 32) return -1;
-    { const char* e = getenv("CFN_PWD_OFF"); if (e && atoi(e)) return -1; }
     if (a.act != CFN_ACT_NONE && a.act != CFN_ACT_RELU && a.act != CFN_ACT_SWISH) return -1;
     const int Kpad = (a.K + PW_UNIT - 1) / PW_UNIT * PW_UNIT;
     int mt_max = (120 * 1024 / 4 / Kpad) / 32;            // resident weight image <= 120 KiB

@@ -322,7 +322,6 @@ extern "C" int cfn_pwconv_bwd_fused(const float* gy, const float* y, const doubl
     if ((long)Cout * Ql * 4 >= 0x7ffffff0L || (long)Cin * Ql * 4 >= 0x7ffffff0L) return -1;   // 32-bit buffer offsets per sample
     if (A && act != CFN_ACT_NONE && act != CFN_ACT_RELU && act != CFN_ACT_SWISH) return -1;
     if ((((uintptr_t)gy | (uintptr_t)x | (uintptr_t)(y ? y : gy)) & 15) != 0) return -1;
-    { const char* e = getenv("CFN_PWF_OFF"); if (e && atoi(e)) return -1; }
     PfArgs a = {};
     a.gy = gy; a.y = gsumsq ? y : nullptr; a.gs = gsum; a.gq = gsumsq; a.gsc = gscale; a.w = w; a.x = x; a.pa = A; a.pb = B;
     a.gx = gx; a.gA = gA; a.gB = gB; a.gw = gw;
@@ -334,8 +333,7 @@ extern "C" int cfn_pwconv_bwd_fused(const float* gy, const float* y, const doubl
     // whole rounds of the chip: 2 workgroups per CU are resident with a prologue (3 without), so 1024 (1536) workgroups
     // are 2 full rounds; 640 (= 1.25 rounds) cost 4.56 instead of 3.83 ms on 24->54 @112
     const bool epi = A != nullptr;
-    static const int wgs_env = getenv("CFN_PWF_WGS") ? atoi(getenv("CFN_PWF_WGS")) : 0;      // (measurement switch: workgroups per launch)
-    long want = (wgs_env > 0 ? wgs_env : (epi ? 1024 : 1536)) / N;
+    long want = (epi ? 1024 : 1536) / N;
     if (want < 1) want = 1;
     long stages = cfn_cdiv(nst, want);
     if (stages < 4) stages = 4;

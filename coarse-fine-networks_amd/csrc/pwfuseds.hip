@@ -1024,13 +1024,14 @@ static int pf3_launch(const float* gy, const float* y, const double* gsum, const
     a.acc = acc; a.acc_s = acc ? acc_stride : 1; a.Hi = Hi; a.Wi = Wi; a.T = T;
     a.acc_Ho = (Hi - 1) / a.acc_s + 1; a.acc_Wo = (Wi - 1) / a.acc_s + 1;
     a.N = N; a.M = Cout; a.K = Cin; a.Q = (int)Ql;
+#ifdef CFN_PWFS_KNOCKOUTS      // tools/pwfs_knockouts.sh builds a library of its own with this; a.dbg stays 0 otherwise
     { const char* e = getenv("CFN_PWFS_DBG"); a.dbg = e ? atoi(e) : 0; }
+#endif
     const long nst = cfn_cdiv(Ql, PF3_PT);
     // whole rounds of the chip (one workgroup per CU is resident) and few of them: every workgroup pays the W^T load and M x K fp64 atomics once; measured at 96 -> 216,
     // 8 clips x 256 frames x 14 x 14: 256 / 512 / 1024 workgroups = 0.301 / 0.333 / 0.395 ms, 320 / 384 (partial rounds) 0.416 / 0.376.  One round; two where a workgroup
     // would otherwise walk more than ~100 stages (the first block of layer 3 at 28 x 28)
-    static const int wgs_env = getenv("CFN_PWF3_WGS") ? atoi(getenv("CFN_PWF3_WGS")) : 0;
-    const long wgs = wgs_env > 0 ? wgs_env : ((long)N * nst > 256L * 100 ? 512 : 256);
+    const long wgs = (long)N * nst > 256L * 100 ? 512 : 256;
     long want = wgs / N;
     if (want < 1) want = 1;
     long stages = cfn_cdiv(nst, want);
@@ -1058,8 +1059,7 @@ static int pf3e_try_launch(const float* gy, const float* y, const double* gsum, 
     a.gx = gx; a.gA = gA; a.gB = gB; a.gw = gw;
     a.N = N; a.M = Cout; a.K = Cin; a.Q = (int)Ql;
     const long nst = cfn_cdiv(Ql, PF3_PT);
-    static const int wgs = getenv("CFN_PWF3_WGS") ? atoi(getenv("CFN_PWF3_WGS")) : 256;
-    long want = wgs / N;
+    long want = 256 / N;                      // one round of the chip
     if (want < 1) want = 1;
     long stages = cfn_cdiv(nst, want);
     if (stages < 4) stages = 4;
@@ -1088,17 +1088,14 @@ int pwfs_try_launch(const float* gy, const float* y, const double* gsum, const d
     const char* env_on = getenv("CFN_PWF_SPLIT");      // read per call: tests and A/B harnesses switch it inside one process
     const int on = env_on ? atoi(env_on) : 1;          // default 1: the no-prologue shapes (measured in the step: -1.3 .. -1.9 ms; level 2 loses 0.5 ms of it)
     if (!on || pws_terms_now() != 6) return -1;
-    // CFN_PWF_SPLIT: 1 = the shapes WITHOUT a prologue (conv1 of the layer-2 blocks, whose input is a materialised block output), 2 = also the
-    // shapes with one (conv3: BN2 + swish in front)
+    // CFN_PWF_SPLIT: 1 = the shapes WITHOUT a prologue (conv1 of the layer-2 blocks, whose input is a materialised block output), 2 (or more) = also
+    // the shapes with one (conv3: BN2 + swish in front)
     const bool wide_m = Cout > 64 && Cout <= 128 && Cin > 32 && Cin <= 64;          // conv1 of layer 2: 48 -> 108
     const bool thin_k = Cout > 64 && Cout <= 128 && Cin >= 16 && Cin <= 32;         // conv1 of the first block of layer 2: 24 -> 108
     const bool wide_k = Cin > 64 && Cin <= 128 && Cout > 32 && Cout <= 64;          // conv3 of layer 2: 108 -> 48
-    // layer-1 widths (24 <-> 54), served by the fp32 kernel of pwfused.hip unless CFN_PWF_SPLIT >= 3 (measurement switch)
-    const bool l1_m = on >= 3 && Cout > 32 && Cout <= 64 && Cin >= 16 && Cin <= 32;      // conv1 of layer 1: 24 -> 54
-    const bool l1_k = on >= 3 && Cin > 32 && Cin <= 64 && Cout >= 16 && Cout <= 32;      // conv3 of layer 1: 54 -> 24
-    // layer 3's conv1 (96 -> 216, no prologue, no shortcut gradient): the variant with W^T resident in the data-gradient waves' registers (CFN_PWF_L3=0 switches it off alone)
-    static const int l3_on = getenv("CFN_PWF_L3") ? atoi(getenv("CFN_PWF_L3")) : 1;
-    if (on >= 1 && l3_on && A == nullptr && Cout > 192 && Cout <= 224 && Cin > 32 && Cin <= 96) {
+    // (the layer-1 widths, 24 <-> 54, stay on the fp32 kernel of pwfused.hip)
+    // layer 3's conv1 (96 -> 216, no prologue, no shortcut gradient): the variant with W^T resident in the data-gradient waves' registers
+    if (on >= 1 && A == nullptr && Cout > 192 && Cout <= 224 && Cin > 32 && Cin <= 96) {
         const long Ql3 = (long)T * Hi * Wi;
         if (Ql3 % 4 == 0 && Ql3 < (1L << 30) && (long)Cout * Ql3 * 4 < 0x7ffffff0L && ((((uintptr_t)gy | (uintptr_t)x | (uintptr_t)(y ? y : gy)) & 15) == 0) &&
             (acc == nullptr || acc_stride >= 1)) {
@@ -1115,7 +1112,7 @@ int pwfs_try_launch(const float* gy, const float* y, const double* gsum, const d
             (act == CFN_ACT_NONE || act == CFN_ACT_RELU || act == CFN_ACT_SWISH))
             return pf3e_try_launch(gy, y, gsum, gsumsq, w, x, A, B, act, gx, gA, gB, gw, N, Cin, Cout, Ql3, gscale, st);
     }
-    if (!wide_m && !wide_k && !thin_k && !l1_m && !l1_k) return -1;
+    if (!wide_m && !wide_k && !thin_k) return -1;
     if (A != nullptr && on < 2) return -1;
     const long Ql = (long)T * Hi * Wi;
     if (Ql % 4 != 0 || Ql >= (1L << 30)) return -1;
@@ -1128,12 +1125,13 @@ int pwfs_try_launch(const float* gy, const float* y, const double* gsum, const d
     a.acc = acc; a.acc_s = acc ? acc_stride : 1; a.Hi = Hi; a.Wi = Wi; a.T = T;
     a.acc_Ho = (Hi - 1) / a.acc_s + 1; a.acc_Wo = (Wi - 1) / a.acc_s + 1;
     a.N = N; a.M = Cout; a.K = Cin; a.Q = (int)Ql;
+#ifdef CFN_PWFS_KNOCKOUTS      // tools/pwfs_knockouts.sh builds a library of its own with this; a.dbg stays 0 otherwise
     { const char* e = getenv("CFN_PWFS_DBG"); a.dbg = e ? atoi(e) : 0; }
+#endif
     const long nst = cfn_cdiv(Ql, PFS_PT);
     // one workgroup per CU is resident: whole rounds of the chip, and few of them (a workgroup splits W^T once and ends with M x K fp64 atomics): measured, 48 -> 108 at
     // 8 clips x 256 frames: 256 / 512 / 768 / 1024 / 2048 workgroups = 0.495 / 0.471-0.481 / 0.491 / 0.504 / 0.553 ms; 320 (1.25 rounds) 0.619
-    static const int wgs = getenv("CFN_PWFS_WGS") ? atoi(getenv("CFN_PWFS_WGS")) : 512;
-    long want = wgs / N;
+    long want = 512 / N;
     if (want < 1) want = 1;
     long stages = cfn_cdiv(nst, want);
     if (stages < 4) stages = 4;
@@ -1144,7 +1142,5 @@ int pwfs_try_launch(const float* gy, const float* y, const double* gsum, const d
     const bool epi = A != nullptr;
     if (wide_m) return pfs_launch<4, 2>(a, act, epi, blocks, st);
     if (thin_k) return pfs_launch<4, 1>(a, act, epi, blocks, st);
-    if (l1_m) return pfs_launch<2, 1>(a, act, epi, blocks, st);
-    if (l1_k) return pfs_launch<1, 2>(a, act, epi, blocks, st);
     return pfs_launch<2, 4>(a, act, epi, blocks, st);
 }

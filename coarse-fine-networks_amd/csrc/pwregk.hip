@@ -391,7 +391,6 @@ static int pwk_go(const PwArgs& a, int mode, bool stats, unsigned blocks, size_t
 
 // returns -1 when the shape is not handled.  DGRAD: only without the act' epilogue (stats == false) and without the compact shortcut gradient
 int pwk_try_launch(PwArgs& a, int mode, bool stats, hipStream_t st) {
-    static const int on = getenv("CFN_PWK") ? atoi(getenv("CFN_PWK")) : 15;             // bit 0: forward (two k slices), bit 1: data gradient, bit 2: forward (one slice), bit 3: data gradient with act' epilogue
     if (pws_terms_now() != 6 || a.stem || a.stride != 1 || a.acc) return -1;
     if (mode == PW_DGRAD && stats && !(a.ea && a.ex && a.s1)) return -1;
     if (a.Q & 3) return -1;
@@ -400,7 +399,6 @@ int pwk_try_launch(PwArgs& a, int mode, bool stats, hipStream_t st) {
     if (a.K > 128 && a.K <= 224 && a.M > 32 && a.M <= 128 && !(nkb & 1)) KS = 2;        // two equal slices
     else if (a.K >= 48 && a.K <= (a.M > 256 ? 192 : 112) && a.M > 128 && a.M <= 512 && (mode == PW_FWD || stats)) KS = 1;   // deep + many rows: two slabs
     else return -1;
-    if (mode == PW_DGRAD ? !(on & (stats ? 8 : 2)) : !(on & (KS == 2 ? 1 : 4))) return -1;
     if (mode == PW_DGRAD && stats && (KS != 1 || a.M > 256)) return -1;     // act' epilogue: one-slice shapes without slabs (192 -> 432 rows: 256 VGPRs + 63 spilled
                                                                             // dwords, 0.256 vs 0.260 ms for pw_deep_kernel: not instantiated)
     if (mode == PW_DGRAD && stats && (((uintptr_t)a.ex) & 15)) return -1;
@@ -416,8 +414,7 @@ int pwk_try_launch(PwArgs& a, int mode, bool stats, hipStream_t st) {
     const int slabs = KS == 1 ? cfn_cdiv(nrt, 8) : 1, rts = cfn_cdiv(nrt, slabs);       // row tiles per slab (<= 8)
     b.mtiles = slabs; b.kres = KS == 1 ? 32 * rts : a.M;
     const int ntiles = cfn_cdiv(a.Q, 32);
-    static const int wg_env = getenv("CFN_PWK_WGS") ? atoi(getenv("CFN_PWK_WGS")) : 0;
-    long wgs = cfn_cdiv(wg_env > 0 ? wg_env : 256, (long)a.N * slabs);      // one workgroup per CU (128 / 192 / 256 / 384 / 512: 0.30 / 0.22 / 0.176 / 0.23 / 0.185 ms)
+    long wgs = cfn_cdiv(256, (long)a.N * slabs);      // one workgroup per CU (128 / 192 / 256 / 384 / 512: 0.30 / 0.22 / 0.176 / 0.23 / 0.185 ms)
     if (wgs > ntiles) wgs = ntiles;
     if (wgs < 1) wgs = 1;
     b.nstrips = (int)wgs;

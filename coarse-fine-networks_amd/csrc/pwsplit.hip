@@ -34,18 +34,19 @@ static int pws_go_mt(const PwArgs& a, int MT, int NP, unsigned blocks, size_t ld
         if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
         hipLaunchKernelGGL(k, dim3(blocks), dim3(64 * PWS_WAVES), lds, st, a);                                             \
     } while (0)
+    // pws_try_launch's plan reaches exactly these tiles.  64 positions (NP = 2): one slab of more than 32 rows, or two slabs of more than
+    // 32 * mt2 rows together, so MT >= 2.  32 positions (NP = 1) are chosen only where they save a slab over NP = 2: with one staged tensor
+    // that takes more than 96 rows (MT >= 4), with two more than 64 (MT >= 3).
     if (NP == 1) {      // 32-position tiles: the many-row slabs
         if constexpr (MODE == PW_DGRAD && TWO) {
             switch (MT) { case 3: PWS_GO(3, 1); break; case 4: PWS_GO(4, 1); break; case 5: PWS_GO(5, 1); break; default: PWS_GO(6, 1); break; }
         } else {
-            switch (MT) { case 3: PWS_GO(3, 1); break; case 4: PWS_GO(4, 1); break; case 5: PWS_GO(5, 1); break; case 6: PWS_GO(6, 1); break; default: PWS_GO(7, 1); break; }
+            switch (MT) { case 4: PWS_GO(4, 1); break; case 5: PWS_GO(5, 1); break; case 6: PWS_GO(6, 1); break; default: PWS_GO(7, 1); break; }
         }
     } else if constexpr (MODE == PW_DGRAD && TWO) {
-        if (MT == 1) PWS_GO(1, 2); else PWS_GO(2, 2);
-    } else if constexpr (MODE == PW_DGRAD) {
-        switch (MT) { case 1: PWS_GO(1, 2); break; case 2: PWS_GO(2, 2); break; default: PWS_GO(3, 2); break; }
+        PWS_GO(2, 2);
     } else {
-        switch (MT) { case 1: PWS_GO(1, 2); break; case 2: PWS_GO(2, 2); break; default: PWS_GO(3, 2); break; }
+        if (MT == 2) PWS_GO(2, 2); else PWS_GO(3, 2);
     }
 #undef PWS_GO
     return cfn_check_launch("pwconv(split bf16)");
@@ -84,8 +85,7 @@ int pws_try_launch(PwArgs& a, int mode, bool stats, hipStream_t st) {
     // time per product: measured (8 clips, T = 256, profiles/r03_microbench_b8.txt) it wins up to K = 108 (layer 2 both convs,
     // layer 3 conv1 forward 0.18 vs 0.21 ms, conv3 data gradient 0.24 vs 0.33 ms) and loses from K = 216 on (layer 3 conv3
     // forward 0.22-0.26 vs 0.20 ms): those stay on the fp32-MFMA kernel
-    static const int maxk_env = getenv("CFN_PWS_MAXK") ? atoi(getenv("CFN_PWS_MAXK")) : 128;
-    if (a.K > maxk_env) return -1;
+    if (a.K > 128) return -1;
     if ((long)a.K * a.Q * 4 >= 0x3ffffff0L || (long)a.M * a.Q * 4 >= 0x3ffffff0L) return -1;
     if (((uintptr_t)a.src | (uintptr_t)a.dst | (uintptr_t)(a.src2 ? a.src2 : a.src) | (uintptr_t)(a.ex ? a.ex : a.src)) & 15) return -1;
     const int NS = terms == 3 ? 2 : 3;
@@ -101,9 +101,8 @@ int pws_try_launch(PwArgs& a, int mode, bool stats, hipStream_t st) {
     auto fit = [&](int mt) { while (mt > 0 && pws_lds(32 * mt, b.Kpad, b.kres, NS) > 160 * 1024) --mt; return mt; };
     const int mt2 = fit(mode == PW_FWD ? 3 : (a.src2 ? 2 : 3)), mt1 = fit(mode == PW_DGRAD && a.src2 ? 6 : 7);
     if (mt2 < 1) return -1;
-    static const int np_env = getenv("CFN_PWS_NP") ? atoi(getenv("CFN_PWS_NP")) : 0;
     int NP = 2, mt_max = mt2;
-    if (mt1 >= 3 && (cfn_cdiv(a.M, 32 * mt1) < cfn_cdiv(a.M, 32 * mt2) || np_env == 1) && np_env != 2) { NP = 1; mt_max = mt1; }
+    if (mt1 >= 3 && cfn_cdiv(a.M, 32 * mt1) < cfn_cdiv(a.M, 32 * mt2)) { NP = 1; mt_max = mt1; }
     int slabs = cfn_cdiv(a.M, 32 * mt_max);
     const int per = cfn_cdiv(a.M, slabs);
     int MT = cfn_cdiv(per, 32);
@@ -111,14 +110,12 @@ int pws_try_launch(PwArgs& a, int mode, bool stats, hipStream_t st) {
     slabs = cfn_cdiv(a.M, 32 * MT);
     // three or more slabs (X3D layer 4: the weight images of 432 x 192 do not fit LDS in fewer) re-read every activation that
     // often: measured slower than the fp32-MFMA kernel with its 4-byte weight image (0.19-0.31 vs 0.20-0.24 ms) -- declined
-    static const int slab_env = getenv("CFN_PWS_MAXSLABS") ? atoi(getenv("CFN_PWS_MAXSLABS")) : 2;
-    if (slabs > slab_env) return -1;
+    if (slabs > 2) return -1;
     b.mtiles = slabs;
     const size_t lds = pws_lds(32 * MT, b.Kpad, b.kres, NS);
     const int ntiles = cfn_cdiv(a.Q, 32 * NP);
     const long groups = (long)a.N * slabs;
-    static const int wg_env = getenv("CFN_PWS_WGS") ? atoi(getenv("CFN_PWS_WGS")) : 0;
-    long wgs = cfn_cdiv(wg_env > 0 ? wg_env : 256, groups);              // one 8-wave workgroup per CU (up to 256 VGPRs)
+    long wgs = cfn_cdiv(256, groups);              // one 8-wave workgroup per CU (up to 256 VGPRs)
     const long maxw = cfn_cdiv(ntiles, PWS_WAVES);
     if (wgs > maxw) wgs = maxw;
     if (wgs < 1) wgs = 1;

@@ -103,16 +103,12 @@ static int pwt_go_act(const PwArgs& a, int MT, unsigned blocks, size_t lds, hipS
 
 // returns -1 when the shape is not handled.  DGRAD: stats == (ea != nullptr), i.e. with the act' epilogue
 int pwt_try_launch(PwArgs& a, int mode, bool stats, hipStream_t st) {
-    static const int on = getenv("CFN_PWT") ? atoi(getenv("CFN_PWT")) : 7;               // bit 0: forward, bit 1: data gradient without act' epilogue, bit 2: with
-    static const int mink = getenv("CFN_PWT_MINK") ? atoi(getenv("CFN_PWT_MINK")) : 400;
-    static const int mink_epi = getenv("CFN_PWT_MINK_EPI") ? atoi(getenv("CFN_PWT_MINK_EPI")) : 160;
     if (pws_terms_now() != 6 || a.stem || a.stride != 1 || a.acc) return -1;
-    if (!(on & (mode == PW_FWD ? 1 : (stats ? 4 : 2)))) return -1;
     // K >= 400: every mode (measured, 8 clips x 256 frames @7x7, against pw_deep_kernel: forward 432 -> 192 0.223 -> 0.142 ms, data gradient with
     // two staged operands 0.229 -> 0.161, 432 rows 0.50 -> 0.31, 96 rows @14x14 0.54 -> 0.37); the data gradient WITH the act' epilogue into more
     // than 256 rows also from K = 160 (layer-4 conv3: contraction over 192, 432 rows in three slabs: 0.273 -> 0.223 ms; pwk_kernel takes the
     // shapes of up to 256 rows first)
-    const bool deep = a.K >= mink, epi = mode == PW_DGRAD && stats && a.K >= mink_epi && a.M > 256;
+    const bool deep = a.K >= 400, epi = mode == PW_DGRAD && stats && a.K >= 160 && a.M > 256;
     // whole 16-byte groups per row (Q % 4 == 0) are only needed by the forward's transposed epilogue (16-byte stores); the data gradient moves 4-byte
     // elements both ways -- the coarse stream's layer 4 (65 x 7 x 7 = 3,185 positions per row) runs its data gradients here
     if (!(deep || epi) || a.M <= 32 || (mode == PW_FWD && (a.Q & 3))) return -1;
@@ -140,8 +136,7 @@ int pwt_try_launch(PwArgs& a, int mode, bool stats, hipStream_t st) {
     b.kres = PWT_ROWB;
     const int ntiles = cfn_cdiv(a.Q, 32);
     const long groups = (long)a.N * slabs;
-    static const int wg_env = getenv("CFN_PWT_WGS") ? atoi(getenv("CFN_PWT_WGS")) : 0;
-    long wgs = (wg_env > 0 ? wg_env : 256) / groups;                        // one 8-wave workgroup per CU, never more than one round of the chip
+    long wgs = 256 / groups;                        // one 8-wave workgroup per CU, never more than one round of the chip
     const long maxw = cfn_cdiv(ntiles, PWS_WAVES);
     if (wgs > maxw) wgs = maxw;
     if (wgs < 1) wgs = 1;

@@ -237,8 +237,7 @@ static int wd_launch(WdArgs& a, hipStream_t st) {
     // four workgroups per CU
     // (re-measured with the round-2 kernels, 8 clips: 2x2 / 2x3 tiles everywhere lose 3-12 % against the shapes chosen below;
     //  two workgroups per CU gain 5-6 % for the 2x4 / 4x2 groups of layer 2 and nothing elsewhere)
-    static const int wg_env = getenv("CFN_PWD_WGS") ? atoi(getenv("CFN_PWD_WGS")) : 0;
-    long strips = (wg_env > 0 ? wg_env : (WD_T == 1 ? 1024 : (WD_T == 8 ? 512 : 256))) / groups;
+    long strips = (WD_T == 1 ? 1024 : (WD_T == 8 ? 512 : 256)) / groups;
     if (strips < 1) strips = 1;
     const long g8 = cfn_cdiv(a.Q, 8);
     if (strips > cfn_cdiv(g8, WD_WAVES * 4)) strips = cfn_cdiv(g8, WD_WAVES * 4);   // >= 4 position groups per wave
@@ -256,9 +255,7 @@ static bool wd_common_ok(const float* gy, const float* y, const float* x, int ac
     if (Q % 4 != 0) return false;
     if (act != CFN_ACT_NONE && act != CFN_ACT_RELU && act != CFN_ACT_SWISH) return false;
     if (((uintptr_t)gy | (uintptr_t)(y ? y : gy)) & 15) return false;
-    if ((long)M * Q * 4 >= (1L << 31) - 64) return false;
-    const char* e = getenv("CFN_PWD_OFF");
-    return !(e && atoi(e));
+    return (long)M * Q * 4 < (1L << 31) - 64;
 }
 
 // contiguous pointwise conv (stride 1): M, K >= 48 (smaller layers are HBM bound and stay on the LDS-staged kernel)

@@ -209,10 +209,6 @@ __global__ __launch_bounds__(256, NT == 4 ? 1 : 2) void sal_fwd_kernel(const Sal
     }
 }
 
-// environment switches are read ONCE per process (getenv on every launch); INT_MIN = not set
-static int sal_env_raw(const char* name) { const char* e = getenv(name); return e ? atoi(e) : -2147483647 - 1; }
-#define SAL_ENV(name, dflt) ([&]() { static const int v_ = sal_env_raw(name); return v_ == -2147483647 - 1 ? (dflt) : v_; }())
-
 // -1 = shape not handled (the caller runs the implicit GEMM)
 int sal_fwd_try_launch(const float* x, const double* A, const double* B, int act, const float* w, float* y, double* sum,
                        double* sumsq, int N, int Cin, int Cout, int T, int Hi, int Wi, const int* g, hipStream_t st) {
@@ -221,16 +217,14 @@ int sal_fwd_try_launch(const float* x, const double* A, const double* B, int act
     if (Cin != SAL_CIN || Cout > 32 || (Wi != 56 && Wi != 28) || (Hi & 1) || Hi < 2 || ((uintptr_t)x & 15)) return -1;
     if (A && act != CFN_ACT_RELU) return -1;
     if (!A && act != CFN_ACT_NONE) return -1;
-    if (SAL_ENV("CFN_SAL_OFF", 0)) return -1;
     if ((long)SAL_CW * T * Hi * Wi * 4 >= 0x7fff0000L) return -1;
     SalArgs a = {x, A, B, w, y, sum, sumsq, N, Cout, T, (T - 1) / 2 + 1, Hi, Hi / 2};
-    const int NT = SAL_ENV("CFN_SAL_NT", 1);
-    if (NT != 1 && NT != 4) return -1;
+    constexpr int NT = 1;                            // 32-position tiles per wave
     const int WO = Wi / 2, TR = 32 / WO, RB = NT * TR, RIN = 2 * RB + 1, PITCH = Wi + 4;
     a.bands = cfn_cdiv(a.Ho, RB);
     // chunk length: whole rounds of one workgroup per CU where possible (a 1.25-round grid costs a full second round)
     int cus = 256;
-    const int per_cu = NT == 4 ? 1 : 2;              // resident workgroups per CU (LDS / registers)
+    const int per_cu = 2;                            // resident workgroups per CU (LDS / registers)
     { int dev = 0; hipDeviceProp_t pr; if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess) cus = pr.multiProcessorCount; }
     int best = 4; double bestc = 1e30;
     for (int to = 2; to <= 16; ++to) {
@@ -239,8 +233,7 @@ int sal_fwd_try_launch(const float* x, const double* A, const double* B, int act
         const double cost = rounds * (3.0 * to + 1.0);          // MFMA sets per block: 3 per output frame + the halo frame's one
         if (cost < bestc - 1e-9) { bestc = cost; best = to; }
     }
-    a.TO = SAL_ENV("CFN_SAL_TO", best);
-    if (a.TO < 1) a.TO = 1;
+    a.TO = best;
     a.nchunks = cfn_cdiv(a.To, a.TO);
     const long blocks = (long)N * a.bands * a.nchunks;
     if (blocks >= (1L << 31)) return -1;
@@ -252,9 +245,7 @@ int sal_fwd_try_launch(const float* x, const double* A, const double* B, int act
         hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(256), lds, st, a);                                          \
     } while (0)
 #define SAL_GO2(WIV, NTV) do { if (A) SAL_GO(WIV, NTV, true); else SAL_GO(WIV, NTV, false); } while (0)
-#define SAL_GO3(WIV) do { if (NT == 1) SAL_GO2(WIV, 1); else SAL_GO2(WIV, 4); } while (0)
-    if (Wi == 56) SAL_GO3(56); else SAL_GO3(28);
-#undef SAL_GO3
+    if (Wi == 56) SAL_GO2(56, NT); else SAL_GO2(28, NT);
 #undef SAL_GO2
 #undef SAL_GO
     return cfn_check_launch("sal_conv_fwd");
@@ -480,7 +471,6 @@ int sal_dgrad_try_launch(const float* gy, const float* y, const double* gs, cons
     if (Cin != SAL_CIN || Cout != 24 || (Wi != 56 && Wi != 28) || (Hi & 1) || Hi < 2) return -1;
     if (A && act != CFN_ACT_RELU) return -1;
     if (!A && act != CFN_ACT_NONE) return -1;
-    if (SAL_ENV("CFN_SAL_OFF", 0) || SAL_ENV("CFN_SAL_DGRAD_OFF", 0)) return -1;
     if ((long)24 * T * Hi * Wi * 4 >= 0x7fff0000L) return -1;
     SalBwdArgs a = {};
     a.gy = gy; a.y = gq ? y : nullptr; a.gs = gs; a.gq = gq; a.w = w; a.x = x; a.pa = A; a.pb = B; a.gx = gx; a.gA = gA; a.gB = gB;
@@ -498,9 +488,7 @@ int sal_dgrad_try_launch(const float* gy, const float* y, const double* gs, cons
         const double cost = rounds * (ch + 1.5);                // + the workgroup's start-up (weights, two frames) in steps
         if (cost < bestc - 1e-9) { bestc = cost; best = ch; }
     }
-    a.CH = SAL_ENV("CFN_SAL_DG_CH", best);
-    if (a.CH < 2) a.CH = 2;
-    a.CH &= ~1;
+    a.CH = best;
     a.nchunks = cfn_cdiv(NU, a.CH);
     const long groups = (long)N * a.bands * a.nchunks;
     if (groups >= (1L << 30)) return -1;
@@ -707,7 +695,6 @@ int sal_wgrad_try_launch(const float* gy, const float* y, const double* gs, cons
     if (Cin != SAL_CIN || Cout != 24 || (Wi != 56 && Wi != 28) || (Hi & 1) || Hi < 2 || ((uintptr_t)x & 15)) return -1;
     if (A && act != CFN_ACT_RELU) return -1;
     if (!A && act != CFN_ACT_NONE) return -1;
-    if (SAL_ENV("CFN_SAL_OFF", 0) || SAL_ENV("CFN_SAL_WGRAD_OFF", 0)) return -1;
     if ((long)24 * T * Hi * Wi * 4 >= 0x7fff0000L) return -1;
     SalBwdArgs a = {};
     a.gy = gy; a.y = gq ? y : nullptr; a.gs = gs; a.gq = gq; a.x = x; a.pa = A; a.pb = B; a.gw = gw;
@@ -724,9 +711,7 @@ int sal_wgrad_try_launch(const float* gy, const float* y, const double* gs, cons
         const double cost = per * (ch + 0.75);
         if (cost < bestc - 1e-9) { bestc = cost; best = ch; }
     }
-    a.CH = SAL_ENV("CFN_SAL_WG_CH", best);
-    if (a.CH < 2) a.CH = 2;
-    a.CH &= ~1;
+    a.CH = best;
     a.nchunks = cfn_cdiv(a.To, a.CH);
     const long items = (long)N * a.bands * a.nchunks;
     if (items >= (1L << 30)) return -1;

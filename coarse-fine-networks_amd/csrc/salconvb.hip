@@ -248,7 +248,7 @@ __global__ __launch_bounds__(256, 2) void sal_fwdb_kernel(const SalBArgs a) {
     }
 }
 
-// -1 = shape not handled / switched off (the caller runs the exact-fp32 kernel of salconv.hip); same contract as sal_fwd_try_launch
+// -1 = shape not handled, or cfn_pw_split_terms != 6 (the caller runs the exact-fp32 kernel of salconv.hip); same contract as sal_fwd_try_launch
 int salb_fwd_try_launch(const float* x, const double* A, const double* B, int act, const float* w, float* y, double* sum, double* sumsq, int N, int Cin, int Cout,
                         int T, int Hi, int Wi, const int* g, hipStream_t st) {
     static const int want[9] = {3, 3, 3, 2, 2, 2, 1, 1, 1};
@@ -256,8 +256,7 @@ int salb_fwd_try_launch(const float* x, const double* A, const double* B, int ac
     if (Cin != SALB_CIN || Cout > 32 || (Wi != 56 && Wi != 28) || (Hi & 1) || Hi < 2 || ((uintptr_t)x & 15)) return -1;
     if (A && act != CFN_ACT_RELU) return -1;
     if (!A && act != CFN_ACT_NONE) return -1;
-    static const int on = getenv("CFN_SAL_BF16") ? atoi(getenv("CFN_SAL_BF16")) : 1;
-    if (!on || pws_terms_now() != 6) return -1;                       // the arithmetic setting of the pointwise contractions governs this one as well
+    if (pws_terms_now() != 6) return -1;                              // the arithmetic setting of the pointwise contractions governs this one as well
     if ((long)SALB_CIN * T * Hi * Wi * 4 >= 0x7fff0000L) return -1;
     SalBArgs a = {x, A, B, w, y, sum, sumsq, N, Cout, T, (T - 1) / 2 + 1, Hi, Hi / 2};
     const int WO = Wi / 2, TR = 32 / WO, RIN = 2 * TR + 1, PITCHC = Wi + 1;
@@ -272,8 +271,7 @@ int salb_fwd_try_launch(const float* x, const double* A, const double* B, int ac
         const double cost = rounds * (3.0 * to + 1.0);               // MFMA sets per block: 3 per output frame + the halo frame's one
         if (cost < bestc - 1e-9) { bestc = cost; best = to; }
     }
-    static const int to_env = getenv("CFN_SALB_TO") ? atoi(getenv("CFN_SALB_TO")) : 0;
-    a.TO = to_env > 0 ? to_env : best;
+    a.TO = best;
     a.nchunks = cfn_cdiv(a.To, a.TO);
     const long blocks = (long)N * a.bands * a.nchunks;
     if (blocks >= (1L << 31)) return -1;

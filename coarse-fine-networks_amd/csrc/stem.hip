@@ -92,7 +92,6 @@ __global__ __launch_bounds__(256) void stem_fwd_kernel(const StemArgs a) {
 // -1 = shape not handled (the caller uses the implicit-GEMM path)
 int stem_fwd_try_launch(const float* x, const float* w, float* y, int N, int Cimg, int Cout, int T, int Hi, int Wi, hipStream_t st) {
     if (Cimg != 3 || Cout > 32 || (Wi & 3) || (Hi & 1) || ((uintptr_t)x & 15)) return -1;
-    { const char* e = getenv("CFN_STEM_OFF"); if (e && atoi(e)) return -1; }
     StemArgs a = {x, w, y, N, Cout, T, Hi, Wi, Hi / 2, Wi / 2};
     a.RB = (a.Ho % 8 == 0) ? 8 : 4;
     a.RIN = 2 * a.RB + 1;
@@ -229,15 +228,13 @@ __global__ __launch_bounds__(512, 2) void stem_wgrad_kernel(const StemWgArgs a) 
 // -1 = shape not handled (the caller uses the implicit-GEMM path); probe: 0 = handled, nothing launched
 int stem_wgrad_try_launch(const float* gy, const float* x, double* gw, int N, int Cimg, int Cout, int T, int Hi, int Wi, hipStream_t st, bool probe) {
     if (Cimg != 3 || Cout != 24 || Hi != 224 || Wi != 224 || (((uintptr_t)x | (uintptr_t)gy) & 15)) return -1;
-    { const char* e = getenv("CFN_STEM_WG_OFF"); if (e && atoi(e)) return -1; }
     if ((long)24 * T * 112 * 112 * 4 >= 0x7fff0000L) return -1;
     const long items = (long)N * T * 28;
     if (items >= (1L << 30)) return -1;
     if (probe) return 0;
     static int cus = 0;
     if (!cus) { int dev = 0; hipDeviceProp_t pr; cus = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess) ? pr.multiProcessorCount : 256; }
-    static const int bpc = getenv("CFN_STEM_WG_BPC") ? atoi(getenv("CFN_STEM_WG_BPC")) : 2;     // persistent workgroups per CU (8 x 256 x 224 x 224: 1: 726 us, 2: 655 us; gather-form kernel 1346)
-    long blocks = (long)cus * (bpc > 0 ? bpc : 1);
+    long blocks = (long)cus * 2;      // persistent workgroups per CU (8 x 256 x 224 x 224: 1: 726 us, 2: 655 us; gather-form kernel 1346)
     if (blocks > items) blocks = items;
     const long per = (items + blocks - 1) / blocks;
     blocks = (items + per - 1) / per;

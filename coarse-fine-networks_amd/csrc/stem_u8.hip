@@ -215,8 +215,6 @@ extern "C" int cfn_stem_conv_u8_fwd(const unsigned char* frames, const float* lu
     CFN_REQUIRE(N > 0 && Cout > 0 && T > 0 && Hi > 0 && Wi > 0, "cfn_stem_conv_u8_fwd: bad shape");
     CFN_REQUIRE(Cimg == 3, "cfn_stem_conv_u8_fwd: uint8 frames have 3 interleaved channels, got Cimg = %d", Cimg);
     if (Cout > 32 || (Wi & 3) || (Hi & 1) || ((uintptr_t)frames & 3)) return -1;
-    static const bool off = getenv("CFN_STEM_U8_FWD_OFF") && atoi(getenv("CFN_STEM_U8_FWD_OFF"));      // A/B switch: convert + cfn_stem_conv_fwd
-    if (off) return -1;
     StemU8Args a = {frames, lut, lengths, w, y, N, Cout, T, Hi, Wi, Hi / 2, Wi / 2};
     a.RB = (a.Ho % 8 == 0) ? 8 : 4;
     a.RIN = 2 * a.RB + 1;
@@ -360,8 +358,6 @@ extern "C" int cfn_stem_conv_u8_bwd_weight(const float* gy, const unsigned char*
     CFN_REQUIRE(N > 0 && Cout > 0 && T > 0 && Hi > 0 && Wi > 0, "cfn_stem_conv_u8_bwd_weight: bad shape");
     CFN_REQUIRE(Cimg == 3, "cfn_stem_conv_u8_bwd_weight: uint8 frames have 3 interleaved channels, got Cimg = %d", Cimg);
     if (Cout != 24 || Hi != 224 || Wi != 224 || ((uintptr_t)gy & 15) || ((uintptr_t)frames & 3)) return -1;
-    static const bool off = getenv("CFN_STEM_U8_WG_OFF") && atoi(getenv("CFN_STEM_U8_WG_OFF"));        // A/B switch: convert + cfn_stem_conv_bwd_weight
-    if (off) return -1;
     if ((long)24 * T * 112 * 112 * 4 >= 0x7fff0000L) return -1;
     const long items = (long)N * T * 28;
     if (items >= (1L << 30)) return -1;

@@ -68,3 +68,21 @@ def test_product_modules_keep_reference_state_dict_keys():
     m2 = x3d_fine.generate_model('M', n_classes=157, task='loc', base_bn_splits=2)
     ref2 = {k: tuple(s) for k, s in json.loads(str(z['fine_s2']))}
     assert {k: tuple(v.shape) for k, v in m2.state_dict().items()} == ref2
+
+
+def test_library_reads_only_the_documented_switches():
+    """the library's environment variables are the six that INTEGRATION.md lists; the knock-out mask CFN_PWFS_DBG is read only by
+    a -DCFN_PWFS_KNOCKOUTS build (tools/pwfs_knockouts.sh) and is not in the product library"""
+    cfn_hip = _lib()
+    kept = {'CFN_PW_SPLIT', 'CFN_DET_RECORDS', 'CFN_PWF_SPLIT', 'CFN_PWF_L3E', 'CFN_PW_SHORT', 'CFN_BNFOLD_PS'}
+    read = set()
+    csrc = os.path.join(PKG, 'csrc')
+    for f in os.listdir(csrc):
+        if f.endswith('.hip') or f.endswith('.h'):
+            read |= set(re.findall(r'getenv\s*\(\s*"(CFN_\w+)"', open(os.path.join(csrc, f)).read()))
+    assert read == kept | {'CFN_PWFS_DBG'}, sorted(read ^ (kept | {'CFN_PWFS_DBG'}))
+    doc = open(os.path.join(ROOT, 'INTEGRATION.md')).read()
+    for name in sorted(kept):
+        assert name in doc, name
+    with open(cfn_hip.LIB_PATH, 'rb') as fh:
+        assert b'CFN_PWFS_DBG' not in fh.read()

@@ -393,7 +393,7 @@ def test_pwconv_bwd_fused_full_size_fp64(case, monkeypatch, record_property):
     1.7e-6 (<4,2> @28, 3136 positions per workgroup: 1.2e-6 against 2.6e-6).  Inside the ceiling; the factor for that case is 3"""
     import cfn_hip
     from pw_ref64 import pw_ref64
-    for k in ('CFN_PWF_SPLIT', 'CFN_PWF_L3E', 'CFN_PWF_OFF'):
+    for k in ('CFN_PWF_SPLIT', 'CFN_PWF_L3E'):
         monkeypatch.delenv(k, raising=False)
     _, Cin, Cout, H, act, acc_s, gw_factor = case
     N = 8

@@ -372,7 +372,7 @@ def pw_check_fp64(c, got, sep, record=None, ceil=PW_CEIL):
 
 def pw_env(monkeypatch, env):
     """the routing switches of cfn_pwconv_bwd_fused at their product defaults, then `env` on top"""
-    for k in ('CFN_PWF_SPLIT', 'CFN_PWF_L3E', 'CFN_PWF_OFF'):
+    for k in ('CFN_PWF_SPLIT', 'CFN_PWF_L3E'):
         monkeypatch.delenv(k, raising=False)
     for k, v in env.items():
         monkeypatch.setenv(k, v)

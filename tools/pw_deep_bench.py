@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Device time of the layer-4 deep contractions (K = 432) at the benchmark's size: forward 432 -> 192 (Swish prologue, statistics) and the
-data gradient of a 192 -> 432 conv (contraction over its 432 outputs, g' = gy + gs + 2 gq y).  Run once per setting of CFN_PWT
-(0 = pw_deep_kernel, 3 = pws_kernel with streamed weights) on the same box:  for v in 0 3; do CFN_PWT=$v python tools/pw_deep_bench.py; done"""
+data gradient of a 192 -> 432 conv (contraction over its 432 outputs, g' = gy + gs + 2 gq y): pws_kernel with streamed weights (csrc/pwstream.hip).  Another build of
+the library (tools/variant_lib.sh) on the same box:  CFN_LIB=coarse-fine-networks_amd/cfn_hip/variants/libcfn_hip_NAME.so python tools/pw_deep_bench.py"""
 import os
 import sys
 
@@ -51,8 +51,8 @@ def main():
         gs, gq = (torch.randn(s.shape, generator=g) * 0.01).to(DEV).to(s.dtype), (torch.randn(q.shape, generator=g) * 0.001).to(DEV).to(q.dtype)
         t_b2 = timeit(lambda: torch.autograd.grad((y, s, q), (xi,), (gy, gs, gq), retain_graph=True), 'pwconv_bwd')
         t_b1 = timeit(lambda: torch.autograd.grad((y, s), (xi,), (gy, gs), retain_graph=True), 'pwconv_bwd')
-        print('CFN_PWT=%s  K=%d M=%d @%dx%d N=%d T=%d: forward %.1f us [its data gradient with the act-prime epilogue, %d -> %d rows: %.1f us], data gradient (two operands) %.1f us, (one operand) %.1f us'
-              % (os.environ.get('CFN_PWT', 'default') + ' ' + os.path.basename(os.environ.get('CFN_LIB', '')), K, M, H, H, N, T, t_f, M, K, t_e, t_b2, t_b1), flush=True)
+        print('%s  K=%d M=%d @%dx%d N=%d T=%d: forward %.1f us [its data gradient with the act-prime epilogue, %d -> %d rows: %.1f us], data gradient (two operands) %.1f us, (one operand) %.1f us'
+              % (os.path.basename(os.environ.get('CFN_LIB', '')) or 'default', K, M, H, H, N, T, t_f, M, K, t_e, t_b2, t_b1), flush=True)
         del x, w, xi, wi, y, gy
 
 

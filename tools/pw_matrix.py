@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Forward-time matrix of one pointwise layer shape over (statistics on/off) x (prologue activation) -- where the time of the
-split-bf16 forward kernel goes.  env CFN_PW_SPLIT / CFN_PWS_NP select the kernel.  usage: pw_matrix.py Cin Cout H [T] [B]"""
+split-bf16 forward kernel goes.  env CFN_PW_SPLIT selects the arithmetic.  usage: pw_matrix.py Cin Cout H [T] [B]"""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, 'coarse-fine-networks_amd'))
@@ -26,4 +26,4 @@ for stats in (True, False):
         torch.cuda.synchronize()
         cfn_hip.prof_enable('pwconv_fwd', False)
         ms, n, _ = cfn_hip.prof_collect('pwconv_fwd')
-        print('split=%s np=%s stats=%d act=%d  %.3f ms  %.0f GB/s' % (os.environ.get('CFN_PW_SPLIT', '-'), os.environ.get('CFN_PWS_NP', '-'), stats, act, ms / n, gb / (ms / n) * 1e3))
+        print('split=%s stats=%d act=%d  %.3f ms  %.0f GB/s' % (os.environ.get('CFN_PW_SPLIT', '-'), stats, act, ms / n, gb / (ms / n) * 1e3))

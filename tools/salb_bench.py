@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Forward of the Grid Pool saliency convs (24 -> 24, 3x3x3, stride 2; x3d_coarse.py:362-366) at the metric's shapes: the split-bf16 kernel of
-csrc/salconvb.hip (CFN_SAL_BF16=1, default) against the exact-fp32 MFMA kernel of csrc/salconv.hip (CFN_SAL_BF16=0), one setting per process
-(the library reads its switches once); device time by HIP events, results compared with each other and, on a small case, with fp64 on the CPU.
+csrc/salconvb.hip (default) against the exact-fp32 MFMA kernel of csrc/salconv.hip, which the convs run on when the pointwise arithmetic is not the
+6-term split (CFN_PW_SPLIT=0, read once per process: one setting per child); device time by HIP events, results compared with each other and, on a small case, with fp64 on the CPU.
 
     python tools/salb_bench.py [--batch 8] [--frames 256]"""
 import argparse
@@ -66,10 +66,10 @@ if __name__ == '__main__':
         child(a.child, a.batch, a.frames)
         sys.exit(0)
     outs = {}
-    for mode in ('0', '1'):
+    for mode in ('0', '1'):                 # 0: exact fp32 (CFN_PW_SPLIT=0), 1: split bf16 (CFN_PW_SPLIT=6)
         f = tempfile.mktemp(suffix='.pt')
         subprocess.check_call([sys.executable, os.path.abspath(__file__), '--child', f, '--batch', str(a.batch), '--frames', str(a.frames)],
-                              env=dict(os.environ, CFN_SAL_BF16=mode))
+                              env=dict(os.environ, CFN_PW_SPLIT='6' if mode == '1' else '0'))
         outs[mode] = torch.load(f)
         os.remove(f)
     print('# saliency conv forward, %d clips x %d frames; algorithmic bytes = 4 B x (input + output elements)' % (a.batch, a.frames))

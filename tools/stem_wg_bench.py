@@ -1,7 +1,6 @@
 #!/usr/bin/env python3
-"""Steady-state timing of the stem weight gradient (cfn_stem_conv_bwd_weight) at 8 x 3 x 256 x 224 x 224:
-    python tools/stem_wg_bench.py            # stem_wgrad_kernel
-    CFN_STEM_WG_OFF=1 python tools/stem_wg_bench.py   # implicit-GEMM path (pw_wgrad_direct_kernel)"""
+"""Steady-state timing of the stem weight gradient (cfn_stem_conv_bwd_weight, stem_wgrad_kernel) at 8 x 3 x 256 x 224 x 224:
+    python tools/stem_wg_bench.py"""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, 'coarse-fine-networks_amd'))

@@ -6,15 +6,13 @@
   3. staged fp32      a loader COLLATES every step (collate.fine_collate of per-video fp32 samples) -> HostStager -> step
   4. staged uint8     the same with collate.fine_collate_u8 of per-video uint8 samples
 
---ab: the resident legs again in fresh child processes with the fused forward, the fused weight gradient or both switched off
-(CFN_STEM_U8_FWD_OFF / CFN_STEM_U8_WG_OFF = convert + the fp32 kernels; the switches are read once per process), each child with its
-own resident fp32 leg as the same-process control: this is the A/B that decides which route is the default.
+(The A/B against convert + the fp32 kernels that made the fused forward and weight gradient the default: "routes" in profiles/u8_input.json.)
 
 Per leg: ms/step (median over the repeats, with min / max), host bytes per step; collate seconds per batch for the staged legs; the
 stem family's device time per step (cfn_prof_enable(6)) beside its algorithmic bytes for the resident legs.  One JSON document on
 stdout and in --out.
 
-    python tools/u8_input_bench.py --ab --out profiles/u8_input.json
+    python tools/u8_input_bench.py --out u8_input.json
 """
 import argparse
 import json
@@ -47,7 +45,6 @@ def main():
     ap.add_argument('--repeats', type=int, default=3)
     ap.add_argument('--out', default=None)
     ap.add_argument('--resident-only', action='store_true', help='skip the staged legs')
-    ap.add_argument('--ab', action='store_true', help='also measure the convert + fp32-kernel routes in child processes')
     a = ap.parse_args()
     assert torch.cuda.is_available(), 'this tool measures the HIP path; it needs a GPU'
     dev = torch.device('cuda:0')
@@ -132,28 +129,13 @@ def main():
         ms, n, by = cfn_hip.prof_collect('stem')
         return {'ms_per_step': round(ms / 3, 4), 'launches_per_step': n // 3, 'algorithmic_GB_per_step': round(by / 3 / 1e9, 4)}
 
-    off = lambda k: os.environ.get(k, '0') not in ('', '0')
-    out = {'shape': [B, T, S, S], 'route': {'forward': 'convert+fp32' if off('CFN_STEM_U8_FWD_OFF') else 'fused',
-                                            'weight_gradient': 'convert+fp32' if off('CFN_STEM_U8_WG_OFF') else 'fused'}, 'steps': a.steps, 'warmup': a.warmup, 'repeats': a.repeats,
+    out = {'shape': [B, T, S, S], 'steps': a.steps, 'warmup': a.warmup, 'repeats': a.repeats,
            'device': cfn_hip.device_info(), 'legs': {}}
     for name, _, _ in legs:
         ms = [r[0] for r in raw[name]]
         out['legs'][name] = {'ms_per_step': round(statistics.median(ms), 3), 'min': round(min(ms), 3), 'max': round(max(ms), 3),
                              'host_bytes_per_step': int(raw[name][-1][1]), 'collate_s_per_batch': round(raw[name][-1][2], 4)}
     out['stem_family'] = {'f32': stem_profile('f32'), 'u8': stem_profile('u8')}
-    if a.ab:
-        import subprocess
-        out['routes'] = {}
-        for name, env in (('forward_off', {'CFN_STEM_U8_FWD_OFF': '1'}), ('weight_gradient_off', {'CFN_STEM_U8_WG_OFF': '1'}),
-                          ('both_off', {'CFN_STEM_U8_FWD_OFF': '1', 'CFN_STEM_U8_WG_OFF': '1'})):
-            cmd = [sys.executable, os.path.abspath(__file__), '--resident-only', '--batch', str(B), '--frames', str(T), '--crop', str(S),
-                   '--steps', str(a.steps), '--warmup', str(a.warmup), '--repeats', str(a.repeats)]
-            r = subprocess.run(cmd, env=dict(os.environ, **env), capture_output=True, text=True, timeout=400)
-            if r.returncode != 0:
-                raise RuntimeError('route %s failed (%d): %s' % (name, r.returncode, r.stderr[-2000:]))
-            child = json.loads(r.stdout[r.stdout.index('{'):])
-            out['routes'][name] = {k: child[k] for k in ('route', 'legs', 'stem_family')}
-            print('route %s done' % name, file=sys.stderr, flush=True)
     txt = json.dumps(out, indent=1)
     print(txt)
     if a.out:

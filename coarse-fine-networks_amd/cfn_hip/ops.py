@@ -1501,6 +1501,40 @@ def feat_pack(feat, dtype, out=None):
     return out
 
 
+# ---- frame labels from annotation segments (csrc/seglabels.hip; the sample record and the batch type: cfn_hip/seglabels.py) ----------------
+def seg_labels(seg, offsets, fps, window, n_classes, t_max, out=None):
+    """seg (S, 3) fp64 rows [class, start_s, end_s] on the GPU; offsets (B + 1,) int32: sample b owns rows offsets[b]:offsets[b + 1];
+    fps (B,) fp64; window (B, 2) int32 = first frame, length -> (labels (B, n_classes, t_max) fp32, mask (B, t_max) fp32, valid_t (B,) int32):
+    labels[b, c, t] = 1 iff t < length and some segment (c, s, e) of sample b has (start + t) / fps > s and (start + t) / fps < e, in fp64
+    (charades_fine.py:110-117, :165, :214-220).  One launch that writes every element; the tensors are read on the device only (no wait,
+    capturable); `n_classes` and `t_max` are host ints.  out: the three preallocated tensors.  No gradient, no CPU path."""
+    n_classes, t_max = int(n_classes), int(t_max)
+    if seg.dtype != torch.float64 or seg.dim() != 2 or seg.shape[1] != 3 or seg.shape[0] < 1 or not seg.is_contiguous():
+        raise RuntimeError('seg_labels: seg: a contiguous (S, 3) float64 tensor with S >= 1 expected, got %s %s' % (seg.dtype, tuple(seg.shape)))
+    if offsets.dtype != torch.int32 or offsets.dim() != 1 or offsets.numel() < 2:
+        raise RuntimeError('seg_labels: offsets (B + 1,) int32 expected, got %s %s' % (offsets.dtype, tuple(offsets.shape)))
+    B = int(offsets.numel()) - 1
+    if fps.dtype != torch.float64 or tuple(fps.shape) != (B,):
+        raise RuntimeError('seg_labels: fps (%d,) float64 expected, got %s %s' % (B, fps.dtype, tuple(fps.shape)))
+    if window.dtype != torch.int32 or tuple(window.shape) != (B, 2):
+        raise RuntimeError('seg_labels: window (%d, 2) int32 = start, length expected, got %s %s' % (B, window.dtype, tuple(window.shape)))
+    if n_classes < 1 or t_max < 1:
+        raise RuntimeError('seg_labels: n_classes >= 1 and t_max >= 1 expected, got %d and %d' % (n_classes, t_max))
+    dev = seg.device
+    if out is None:
+        out = (torch.empty(B, n_classes, t_max, dtype=torch.float32, device=dev), torch.empty(B, t_max, dtype=torch.float32, device=dev),
+               torch.empty(B, dtype=torch.int32, device=dev))
+    else:
+        out = tuple(out)
+        want = ((torch.float32, (B, n_classes, t_max)), (torch.float32, (B, t_max)), (torch.int32, (B,)))
+        if len(out) != 3 or any(y.dtype != dt or tuple(y.shape) != shp or not y.is_contiguous() for y, (dt, shp) in zip(out, want)):
+            raise RuntimeError('seg_labels: out: contiguous labels %s fp32, mask %s fp32 and valid_t %s int32 expected, got %s'
+                               % (want[0][1], want[1][1], want[2][1], [(y.dtype, tuple(y.shape)) for y in out]))
+    call('cfn_seg_labels', seg, offsets.contiguous(), fps.contiguous(), window.contiguous(), out[0], out[1], out[2], B, n_classes, t_max,
+         int(seg.shape[0]))
+    return out
+
+
 # ---- baseline JPEG frames decoded on the GPU (csrc/jpegdec.hip; the host side and the batch type: cfn_hip/jpegdec.py) ------------------------
 def jpeg_workspace_bytes(rows, slots, lanes, blocks_max):
     """bytes of workspace cfn_jpeg_decode_u8 needs for `rows` frames into `slots` = clips x Tmax frame slots"""

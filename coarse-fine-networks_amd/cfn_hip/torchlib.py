@@ -1013,6 +1013,20 @@ def _(data, frames, tables, geom, lengths, dims):
             data.new_empty((frames.shape[0],), dtype=torch.int32))
 
 
+# ---- frame labels from annotation segments (csrc/seglabels.hip; the sample record and the batch type: cfn_hip/seglabels.py), no gradient ------
+@_op('seg_labels')
+def seg_labels(seg: torch.Tensor, offsets: torch.Tensor, fps: torch.Tensor, window: torch.Tensor, n_classes: int,
+               t_max: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    return _ops.seg_labels(seg, offsets, fps, window, n_classes, t_max)
+
+
+@seg_labels.register_fake
+def _(seg, offsets, fps, window, n_classes, t_max):
+    B = offsets.shape[0] - 1
+    return (seg.new_empty((B, n_classes, t_max), dtype=torch.float32), seg.new_empty((B, t_max), dtype=torch.float32),
+            seg.new_empty((B,), dtype=torch.int32))
+
+
 OPERATORS = ('dwconv3d', 'pwconv', 'time_sample', 'dwconv_t5', 'stem_conv', 'conv3d_dense', 'bn_fold', 'bn_add_relu', 'affine_act',
              'pool_hw', 'interp1d', 'grid_cdf', 'gauss_align', 'fusion_gather', 'film', 'time_resize', 'stem_conv_u8', 'detection_loss')
 # the uint8 input path's operators without a gradient (the host-built table, the frames -> fp32 clip converter)
@@ -1025,6 +1039,8 @@ METRIC_OPERATORS = ('ap_append', 'ap_sort', 'average_precision')
 FEATURE_OPERATORS = ('feat_unpack', 'feat_pack')
 # baseline JPEG frames -> uint8 frames on the GPU (no gradient)
 DECODE_OPERATORS = ('jpeg_decode_u8',)
+# annotation segments -> dense frame labels, mask and lengths on the GPU (no gradient)
+LABEL_OPERATORS = ('seg_labels',)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------

@@ -34,6 +34,12 @@ fill); ``PackedFeats.unpack()`` widens and pads on the GPU.  The other seven mem
 the clip member of a sample is a pair ``(n lists of T_i baseline JPEG frames (bytes), box (n, 4) int)``.  The clip member of the batch becomes a
 ``cfn_hip.jpegdec.JpegClips``: the entropy-coded segments in one flat buffer plus the decoder tables; ``JpegClips.decode()`` makes the RawU8Clips
 batch on the GPU, bit for bit what PIL decodes (the training and extraction scripts call it).  All frames of a clip share size and sampling.
+
+Segment labels: with EVERY builder above the label member of a sample may be a ``cfn_hip.seglabels.SegLabel`` -- the video's action segments
+[class, start_s, end_s] plus the label window (``SegLabel.training(...)`` / ``SegLabel.testing(...)``) -- instead of the dense (157, TL) array.  The
+label member of the batch is then a ``cfn_hip.seglabels.SegLabels`` (a few hundred bytes) and the mask member is ``None``; the batch keeps its 4 / 8
+members.  ``SegLabels.dense()`` writes labels (B, 157, TLmax), mask (B, TLmax) and the valid lengths on the GPU, bit for bit what the dense collate
+gives (``cfn_hip.seglabels.materialize``, which the training scripts call).  All samples of a batch carry the same kind of label; 'loc' task only.
 """
 import numpy as np
 import torch
@@ -41,6 +47,7 @@ import torch
 from cfn_hip.u8clips import RawU8Clips, U8Clips, CHARADES_MEAN, CHARADES_STD  # noqa: F401
 from cfn_hip.featpack import PackedFeats, Record, collate_records  # noqa: F401
 from cfn_hip.jpegdec import JpegClips, collate_jpeg  # noqa: F401
+from cfn_hip.seglabels import SegLabel, SegLabels, collate_seg  # noqa: F401
 
 
 def _t(a):
@@ -67,6 +74,14 @@ def _label_mask(labels, tl):
     for i, lb in enumerate(labels):
         mask[i, :_t(lb).shape[1]] = 1.0
     return mask
+
+
+def _labels(labels):
+    """the label and mask members of a batch: dense (B, C, TLmax) + (B, TLmax), or SegLabels + None when the samples carry SegLabel records"""
+    if any(isinstance(lb, SegLabel) for lb in labels):
+        return collate_seg(labels), None
+    tl_max = max(_t(lb).shape[1] for lb in labels)
+    return _pad_time(labels, 1, tl_max), _label_mask(labels, tl_max)
 
 
 def _pad_time_u8(clips):
@@ -118,32 +133,24 @@ def _pad_raw_u8(samples):
 
 def fine_collate(batch):
     clips = [b[0] for b in batch]
-    labels = [b[1] for b in batch]
     t_max = max(_t(c).shape[2] for c in clips)
-    tl_max = max(_t(lb).shape[1] for lb in labels)
-    return [_pad_time(clips, 2, t_max), _pad_time(labels, 1, tl_max), _label_mask(labels, tl_max), [b[2] for b in batch]]
+    return [_pad_time(clips, 2, t_max), *_labels([b[1] for b in batch]), [b[2] for b in batch]]
 
 
 def fine_collate_u8(batch):
     """fine_collate for samples (uint8 clips (n,T,H,W,3), label (157,TL), vid)"""
-    labels = [b[1] for b in batch]
-    tl_max = max(_t(lb).shape[1] for lb in labels)
-    return [_pad_time_u8([b[0] for b in batch]), _pad_time(labels, 1, tl_max), _label_mask(labels, tl_max), [b[2] for b in batch]]
+    return [_pad_time_u8([b[0] for b in batch]), *_labels([b[1] for b in batch]), [b[2] for b in batch]]
 
 
 def fine_collate_raw_u8(batch):
     """fine_collate for samples ((frames (n,T,h,w,3) uint8, box (n,4)), label (157,TL), vid): untransformed frames + crop boxes"""
-    labels = [b[1] for b in batch]
-    tl_max = max(_t(lb).shape[1] for lb in labels)
-    return [_pad_raw_u8([b[0] for b in batch]), _pad_time(labels, 1, tl_max), _label_mask(labels, tl_max), [b[2] for b in batch]]
+    return [_pad_raw_u8([b[0] for b in batch]), *_labels([b[1] for b in batch]), [b[2] for b in batch]]
 
 
 def _coarse_rest(batch, cap):
     """everything of a coarse batch but the clip: [label, mask, feat, feat_mask, meta, [vid...], dur]"""
-    labels = [b[1] for b in batch]
     feats = [b[2] for b in batch]
     keys = list(feats[0].keys())
-    tl_max = max(_t(lb).shape[1] for lb in labels)
     tf_max = min(max(_t(f[keys[0]]).shape[1] for f in feats), cap)
     feat = {k: _pad_time([f[k] for f in feats], 1, tf_max) for k in keys}
     feat_mask = torch.zeros(len(batch), tf_max, dtype=torch.float32)
@@ -151,7 +158,7 @@ def _coarse_rest(batch, cap):
         feat_mask[i, :min(cap, _t(f[keys[0]]).shape[1])] = 1.0
     meta = torch.stack([_t(b[3]) for b in batch])
     dur = torch.as_tensor([float(b[5]) for b in batch], dtype=torch.float64)
-    return [_pad_time(labels, 1, tl_max), _label_mask(labels, tl_max), feat, feat_mask, meta, [b[4] for b in batch], dur]
+    return [*_labels([b[1] for b in batch]), feat, feat_mask, meta, [b[4] for b in batch], dur]
 
 
 def coarse_collate(batch, cap=128):
@@ -172,12 +179,10 @@ def coarse_collate_raw_u8(batch, cap=128):
 
 def _coarse_rest_packed(batch, cap):
     """_coarse_rest for samples whose feature member is a Record: [label, mask, PackedFeats, feat_mask, meta, [vid...], dur]"""
-    labels = [b[1] for b in batch]
-    tl_max = max(_t(lb).shape[1] for lb in labels)
     feat, feat_mask = collate_records([b[2] for b in batch], cap)
     meta = torch.stack([_t(b[3]) for b in batch])
     dur = torch.as_tensor([float(b[5]) for b in batch], dtype=torch.float64)
-    return [_pad_time(labels, 1, tl_max), _label_mask(labels, tl_max), feat, feat_mask, meta, [b[4] for b in batch], dur]
+    return [*_labels([b[1] for b in batch]), feat, feat_mask, meta, [b[4] for b in batch], dur]
 
 
 def coarse_collate_packed(batch, cap=128):
@@ -199,9 +204,7 @@ def coarse_collate_packed_raw_u8(batch, cap=128):
 
 def fine_collate_jpeg(batch):
     """fine_collate_raw_u8 for samples ((n lists of encoded frames, box (n,4)), label (157,TL), vid): the frames stay JPEG (JpegClips)"""
-    labels = [b[1] for b in batch]
-    tl_max = max(_t(lb).shape[1] for lb in labels)
-    return [collate_jpeg([b[0] for b in batch]), _pad_time(labels, 1, tl_max), _label_mask(labels, tl_max), [b[2] for b in batch]]
+    return [collate_jpeg([b[0] for b in batch]), *_labels([b[1] for b in batch]), [b[2] for b in batch]]
 
 
 def coarse_collate_jpeg(batch, cap=128):

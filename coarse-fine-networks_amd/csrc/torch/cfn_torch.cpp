@@ -16,6 +16,7 @@
 // loss: detection_loss + detection_loss_backward (csrc/detloss.hip), the opt-in fused detection loss of the three training scripts.
 // packed 16-bit fine features: feat_unpack, feat_pack (csrc/featpack.hip) -- no gradients.
 // baseline JPEG frames -> uint8 frames: jpeg_decode_u8 (csrc/jpegdec.hip) -- no gradient.
+// annotation segments -> dense frame labels, mask and lengths: seg_labels (csrc/seglabels.hip) -- no gradient.
 #include <ATen/ATen.h>
 // (a ROCm build of torch presents its HIP devices as "cuda": the masquerading guard / stream classes are the ones that accept them)
 #include <ATen/hip/impl/HIPGuardImplMasqueradingAsCUDA.h>
@@ -1095,6 +1096,34 @@ std::tuple<Tensor, Tensor> jpeg_decode_u8(const Tensor& data, const Tensor& fram
     return std::make_tuple(out, status);
 }
 
+// ---- frame labels from annotation segments (csrc/seglabels.hip; cfn_hip/seglabels.py) -- no gradient: labels are targets ------------------------
+// seg (S, 3) fp64 [class, start_s, end_s]; offsets (B + 1) int32; fps (B) fp64; window (B, 2) int32 = first frame, length
+// -> (labels (B, n_classes, t_max) fp32, mask (B, t_max) fp32, valid_t (B) int32).  The tensors stay on the device.
+std::tuple<Tensor, Tensor, Tensor> seg_labels(const Tensor& seg, const Tensor& offsets, const Tensor& fps, const Tensor& window, int64_t n_classes, int64_t t_max) {
+    const char* op = "cfn::seg_labels";
+    TORCH_CHECK(seg.is_cuda(), op, ": device tensors only (there is no CPU path)");
+    TORCH_CHECK(seg.scalar_type() == at::kDouble && seg.dim() == 2 && seg.size(0) >= 1 && seg.size(1) == 3, op, ": seg (S, 3) float64 with S >= 1 expected, got ",
+                seg.scalar_type(), " ", seg.sizes());
+    TORCH_CHECK(offsets.scalar_type() == at::kInt && offsets.dim() == 1 && offsets.numel() >= 2 && offsets.device() == seg.device(), op,
+                ": offsets (B + 1) int32 on seg's device expected, got ", offsets.scalar_type(), " ", offsets.sizes());
+    const int64_t B = offsets.numel() - 1;
+    TORCH_CHECK(fps.scalar_type() == at::kDouble && fps.dim() == 1 && fps.numel() == B && fps.device() == seg.device(), op,
+                ": fps (B) float64 on seg's device expected, got ", fps.scalar_type(), " ", fps.sizes());
+    TORCH_CHECK(window.scalar_type() == at::kInt && window.dim() == 2 && window.size(0) == B && window.size(1) == 2 && window.device() == seg.device(), op,
+                ": window (B, 2) int32 on seg's device expected, got ", window.scalar_type(), " ", window.sizes());
+    TORCH_CHECK(n_classes >= 1 && n_classes < (1 << 19) && t_max >= 1 && t_max < (1 << 24) && B <= 65535, op, ": 1 <= n_classes < 2^19, 1 <= t_max < 2^24 and B <= 65535 expected, got ",
+                n_classes, ", ", t_max, " and ", B);
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(seg.device());
+    const Tensor sg = seg.contiguous(), off = offsets.contiguous(), fp = fps.contiguous(), win = window.contiguous();
+    Tensor labels = at::empty({B, n_classes, t_max}, seg.options().dtype(at::kFloat));
+    Tensor mask = at::empty({B, t_max}, seg.options().dtype(at::kFloat));
+    Tensor valid = at::empty({B}, seg.options().dtype(at::kInt));
+    ok(cfn_seg_labels(sg.data_ptr<double>(), off.data_ptr<int>(), fp.data_ptr<double>(), win.data_ptr<int>(), labels.data_ptr<float>(), mask.data_ptr<float>(),
+                      valid.data_ptr<int>(), (int)B, (int)n_classes, (int)t_max, (long)sg.size(0), stream_of(seg)),
+       "cfn_seg_labels");
+    return std::make_tuple(labels, mask, valid);
+}
+
 }  // namespace
 
 TORCH_LIBRARY_FRAGMENT(cfn, m) {
@@ -1143,6 +1172,7 @@ TORCH_LIBRARY_FRAGMENT(cfn, m) {
     m.def("feat_unpack(Tensor data, Tensor offsets, Tensor lengths, SymInt[] channels, SymInt t_max) -> Tensor[]");
     m.def("feat_pack(Tensor[] feat, ScalarType dtype) -> Tensor");
     m.def("jpeg_decode_u8(Tensor data, Tensor frames, Tensor tables, Tensor geom, Tensor lengths, SymInt[] dims) -> (Tensor, Tensor)");
+    m.def("seg_labels(Tensor seg, Tensor offsets, Tensor fps, Tensor window, SymInt n_classes, SymInt t_max) -> (Tensor, Tensor, Tensor)");
 }
 
 TORCH_LIBRARY_IMPL(cfn, CUDA, m) {      // (the HIP backend of a ROCm build of torch dispatches on the CUDA key)
@@ -1190,4 +1220,5 @@ TORCH_LIBRARY_IMPL(cfn, CUDA, m) {      // (the HIP backend of a ROCm build of t
     m.impl("feat_unpack", feat_unpack);
     m.impl("feat_pack", feat_pack);
     m.impl("jpeg_decode_u8", jpeg_decode_u8);
+    m.impl("seg_labels", seg_labels);
 }

@@ -28,6 +28,7 @@ from cfn_hip import staging                       # noqa: E402
 from cfn_hip import dist as cdist                 # noqa: E402
 from apmeter import APMeter                       # noqa: E402
 from cfn_hip import metrics                       # noqa: E402
+from cfn_hip.seglabels import materialize         # noqa: E402
 from train_fine import lr_warmup, flatten_clips   # noqa: E402
 from cfn_hip.u8clips import RawU8Clips, U8Clips, CHARADES_MEAN, CHARADES_STD   # noqa: E402,F401
 from cfn_hip.featpack import PackedFeats          # noqa: E402
@@ -227,7 +228,8 @@ def run(init_lr=INIT_LR, warmup_steps=0, max_epochs=200, mode='rgb', root=None, 
                         continue
                 b, n = inputs.shape[:2]            # n crops per video at validation time (:198-201)
                 inputs = flatten_clips(inputs, dev, CROP if train else None, names=name)      # validation: forward_video transforms chunk by chunk
-                labels, masks, feat_masks, meta = labels.to(dev), masks.to(dev), feat_masks.to(dev), meta.to(dev)
+                labels, masks = materialize(labels, masks, dev)      # dense tensors: .to(dev); a SegLabels batch (segment labels): one kernel
+                feat_masks, meta = feat_masks.to(dev), meta.to(dev)
                 feat = unpack_feat(feat, dev)      # a PackedFeats batch (coarse_collate_packed): unpacked once per batch / validation video
                 valid_t = masks.sum(1).int()
                 n_it += 1

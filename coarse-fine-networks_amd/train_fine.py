@@ -31,6 +31,7 @@ from cfn_hip.u8clips import RawU8Clips, U8Clips, CHARADES_MEAN, CHARADES_STD   #
 from cfn_hip.jpegdec import JpegClips, decode_checked        # noqa: E402
 from apmeter import APMeter                       # noqa: E402
 from cfn_hip import metrics                       # noqa: E402
+from cfn_hip.seglabels import materialize         # noqa: E402
 
 BS = 8
 BS_UPSCALE = 1
@@ -324,7 +325,7 @@ def run(init_lr=INIT_LR, warmup_steps=0, max_epochs=200, mode='rgb', root=None, 
                     continue
                 b, n = inputs.shape[:2]          # n crops per video (1 in training, train_fine.py:176-185)
                 inputs = flatten_clips(inputs, dev, crop, names=_name)
-                labels, masks = labels.to(dev), masks.to(dev)
+                labels, masks = materialize(labels, masks, dev)      # dense tensors: .to(dev); a SegLabels batch (segment labels): one kernel
                 valid_t = masks.sum(1).int()
                 n_it += 1
                 if train:

@@ -28,6 +28,7 @@ import train_fine                # noqa: E402
 from cfn_hip import staging                       # noqa: E402
 from cfn_hip import dist as cdist                 # noqa: E402
 from cfn_hip import metrics                       # noqa: E402
+from cfn_hip.seglabels import materialize         # noqa: E402
 from cfn_hip.jpegdec import JpegClips, decode_checked   # noqa: E402
 from train_fine import lr_warmup                  # noqa: E402
 
@@ -160,7 +161,7 @@ def run(init_lr=INIT_LR, warmup_steps=0, max_steps=None, batch_size=BS, fine_fra
         clip = clip.to(dev)
         if isinstance(clip, tc.RawU8Clips):
             clip = clip.transform(crop)
-        labels, masks = labels.to(dev), masks.to(dev)
+        labels, masks = materialize(labels, masks, dev)      # dense tensors: .to(dev); a SegLabels batch (segment labels): one kernel
         cls_loss, loc_loss, probs = train_step(fine, coarse, reducer, optimizer, clip, labels, masks, warm, fused=fused)
         steps += 1
         if tr is not None:

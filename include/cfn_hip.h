@@ -531,6 +531,27 @@ int cfn_jpeg_decode_u8(const unsigned char* data, const int* frames, const int* 
                        unsigned char* out, int* status, void* ws, long ws_bytes, long data_bytes, int rows, int sets, int N,
                        int Tmax, int Hmax, int Wmax, int lanes, int blocks_max, void* stream);
 
+/* =====================================================================================================================
+ * Frame labels from annotation segments (csrc/seglabels.hip; the sample record and the batch type: cfn_hip/seglabels.py).
+ * Replaces, on the GPU, the dense label array the reference builds per video in make_dataset (charades_fine.py:110-117,
+ * the same loop in charades_coarse_fineFEAT.py:115-122), slices per sample in Charades.__getitem__ (charades_fine.py:149-165,
+ * :188) and zero-pads per batch in mt_collate_fn (charades_fine.py:214-220) -- bit for bit.
+ *   seg (n_seg, 3) fp64 rows [class, start_s, end_s]; offsets (B + 1) int32: video b owns rows offsets[b] .. offsets[b + 1] - 1;
+ *   fps (B) fp64 = num_frames / duration as the host computed it; window (B, 2) int32 = first frame (start_f - 1), length.
+ *     len = clamp(window[b, 1], 0, t_max),  fr = window[b, 0] + t
+ *     labels[b, c, t] = t < len && exists (c, s, e) of video b: fr / fps[b] > s && fr / fps[b] < e   ? 1.0f : 0.0f     (B, C, t_max)
+ *     mask[b, t]      = t < len ? 1.0f : 0.0f                                                                           (B, t_max)
+ *     valid_t[b]      = len                                                                                             (B) int32
+ *   fr / fps is one correctly rounded fp64 division and both inequalities are strict, as in the reference.  EVERY element of the
+ *   three outputs is written.  Same-class segments may overlap, a video may own no row; rows no offset range covers are ignored.
+ *   Everything but B, C, t_max and n_seg is read on the device only: an offset range is clamped to [0, n_seg], and a class that is
+ *   not an integer of [0, C) selects no row (a bad batch gives wrong values, never a store outside the outputs).
+ * One launch on `stream`, no allocation, no synchronisation (capturable); nothing accumulates, so the deterministic mode changes
+ * nothing.  Returns 1 for null pointers, B, C or t_max < 1, n_seg < 0, B > 65535, C >= 2^19 or t_max >= 2^24.
+ * ===================================================================================================================== */
+int cfn_seg_labels(const double* seg, const int* offsets, const double* fps, const int* window, float* labels, float* mask,
+                   int* valid_t, int B, int C, int t_max, long n_seg, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

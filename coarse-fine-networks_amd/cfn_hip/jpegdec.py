@@ -11,6 +11,10 @@ components YCbCr with luma sampling 1x1 (4:4:4), 2x1 (4:2:2) or 2x2 (4:2:0) and 
 else is refused by ``parse`` with the reason.  All frames of one clip share size and sampling.  ``decode_reference`` states the same
 arithmetic in numpy and plain Python: it serves the CPU tests and debugging and is NOT a fallback of ``JpegClips.decode()``, which has
 no CPU path.
+
+The entropy stage has two modes with the same output: 'interval' (the default), one lane per (frame, restart interval), and 'sync'
+(``decode(entropy='sync')``, ``CFN_JPEG_ENTROPY=sync``), which decodes a frame WITHOUT restart markers with one lane per subsequence of
+``sub_bytes`` raw bytes; ``decode_coefficients_sync`` states its rounds in plain Python.
 """
 import collections
 
@@ -312,6 +316,192 @@ def decode_coefficients(buf, info=None, stats=None):
     return planes
 
 
+# ---- the 'sync' entropy mode, stated on the CPU (csrc/jpegdec.hip: jpeg_sub_decode, jpeg_entropy_sync_kernel) --------------------------------
+# Huffman-coded data self-synchronises: a decoder started at an arbitrary byte falls into step with the true decode after a few symbols
+# (Weissenberger & Schmidt, "Accelerating JPEG Decompression on GPUs").  A frame WITHOUT restart markers is cut into subsequences of
+# `sub_bytes` raw bytes (stuffed FF 00 included), one decoder lane each.  A decoder state at a symbol boundary is (p, b, u, zz): the raw
+# byte index and bit (0 = the most significant) of the next symbol's first bit -- a stuffed 00 never holds a bit --, the unit index inside
+# the MCU and the zigzag index (0 = a DC symbol is due).  The byte behind a data byte FF is skipped whatever it is, bytes behind the
+# segment's end read as 0: that makes a lane's decode a pure function of its entry state, which is all the rounds need to be exact.
+SYNC_SUB_BYTES = 128                                   # the default subsequence size
+SYNC_SUB_BYTES_RANGE = (16, 1024)                      # a multiple of 4: a symbol and its value (<= 31 bits, stuffing included) end inside the next subsequence
+SYNC_MAX_SUBS = 1536                                   # the kernel's ceiling: 32 bytes of LDS per subsequence
+SYNC_DEFAULT_MAX_SUBS = 192                            # 13,328 + 32 * 192 bytes of LDS: eight workgroups on a CU's 160 KiB
+ENTROPY_MODES = ('interval', 'sync')
+
+
+def entropy_mode(entropy=None):
+    """None -> CFN_JPEG_ENTROPY (read at call time; unset = 'interval', today's lane per restart interval); anything but the two modes raises"""
+    import os
+    if entropy is None:
+        entropy = os.environ.get('CFN_JPEG_ENTROPY') or 'interval'
+    if entropy not in ENTROPY_MODES:
+        raise ValueError("entropy: 'interval' or 'sync' expected, got %r" % (entropy,))
+    return entropy
+
+
+def check_sync_sizes(sub_bytes=None, max_subs=None):
+    """(sub_bytes, max_subs) with the defaults filled in; ValueError naming the argument that is out of range"""
+    sub_bytes = SYNC_SUB_BYTES if sub_bytes is None else sub_bytes
+    max_subs = SYNC_DEFAULT_MAX_SUBS if max_subs is None else max_subs
+    if not isinstance(sub_bytes, int) or isinstance(sub_bytes, bool) or sub_bytes % 4 or not SYNC_SUB_BYTES_RANGE[0] <= sub_bytes <= SYNC_SUB_BYTES_RANGE[1]:
+        raise ValueError('sub_bytes: a multiple of 4 in [%d, %d] expected, got %r' % (SYNC_SUB_BYTES_RANGE + (sub_bytes,)))
+    if not isinstance(max_subs, int) or isinstance(max_subs, bool) or not 1 <= max_subs <= SYNC_MAX_SUBS:
+        raise ValueError('max_subs: an integer in [1, %d] expected, got %r' % (SYNC_MAX_SUBS, max_subs))
+    return sub_bytes, max_subs
+
+
+def _sync_sub(seg, end, dc, ac, comp, entry, limit, sink=None):
+    """decode from `entry` = (p, b, u, zz) up to the first symbol whose first bit lies at or behind raw byte `limit` (or the segment's
+    `end`) -> (exit state or None = invalid, blocks completed, [sum of DC differences per component]).  sink = [planes locator, next
+    block, blocks of the frame, predictors]: the write pass, which also stops behind the frame's last block and raises on bad data."""
+    p, b, u, zz = entry
+    bpm = len(comp)
+    blocks, dcsum = 0, [0, 0, 0]
+
+    def bit():
+        nonlocal p, b
+        v = (int(seg[p]) >> (7 - b)) & 1 if p < end else 0
+        b += 1
+        if b == 8:
+            b = 0
+            p += 2 if p < end and seg[p] == 0xFF else 1
+        return v
+
+    def symbol(table):
+        code = 0
+        for l in range(1, 17):
+            code = (code << 1) | bit()
+            s = table.get((l, code))
+            if s is not None:
+                return s
+        return -1
+
+    def receive(n):
+        v = 0
+        for _ in range(n):
+            v = (v << 1) | bit()
+        return _extend(v, n)
+
+    def bad(why):
+        if sink is not None:
+            raise ValueError(why)
+        return None, blocks, dcsum
+
+    while p < limit and (sink is None or sink[1] < sink[2]):
+        c = comp[u]
+        if zz == 0:
+            s = symbol(dc[c])
+            if s < 0:
+                return bad('an invalid Huffman code')
+            d = receive(s & 15)
+            dcsum[c] += d
+            if sink is not None:
+                sink[3][c] += d
+                sink[0](sink[1])[0] = sink[3][c]
+            zz = 1
+            continue
+        rs = symbol(ac[c])
+        if rs < 0:
+            return bad('an invalid Huffman code')
+        run, s = rs >> 4, rs & 15
+        if s == 0:
+            zz = zz + 16 if run == 15 else 64          # ZRL, EOB
+        else:
+            zz += run
+            if zz > 63:
+                return bad('a coefficient index beyond 63')
+            v = receive(s)
+            if sink is not None:
+                sink[0](sink[1])[ZIGZAG[zz]] = v
+            zz += 1
+        if zz >= 64:
+            zz, u, blocks = 0, (u + 1) % bpm, blocks + 1
+            if sink is not None:
+                sink[1] += 1
+    if sink is not None and (p > end or (p == end and b > 0)):
+        raise ValueError('the entropy-coded segment ran out of data')
+    return (p, b, u, zz), blocks, dcsum
+
+
+def decode_coefficients_sync(buf, sub_bytes, max_rounds=None, stats=None):
+    """decode_coefficients by the rounds of the 'sync' entropy mode, in plain Python over raw byte positions (frames without restart
+    markers).  Round 0: every subsequence j is decoded, storing nothing, from its speculative start (byte j * sub_bytes, one on when the
+    byte in front is FF; u = zz = 0), subsequence 0 from the true state.  Round k: j is decoded again from the exit state j - 1 had after
+    round k - 1 (from its speculative start when that exit is invalid), unless that is the entry it last used.  After round k the first
+    k + 1 exits are the true ones, so at most n rounds are needed; the rounds stop as soon as one changes no exit.  A scan of the block
+    counts and DC sums gives every subsequence its first block and entry predictors, and a last pass from the true entries writes.
+    stats receives subsequences, rounds (those in which something was decoded, round 0 included), entries [(p, b, u, zz)],
+    first_blocks, predictors [[3]], invalid_exits (speculative decodes that ended in an invalid code) and stuffed_starts (subsequences
+    whose first byte is a stuffed 00).  The reference of the CPU tests and of the kernel's intermediate values, NOT a fallback."""
+    a = _bytes(buf)
+    info = parse(a)
+    if info.restart_interval:
+        raise ValueError('the sync entropy mode takes frames without restart markers (restart interval %d)' % info.restart_interval)
+    S, _ = check_sync_sizes(sub_bytes)
+    nc = len(info.components)
+    hs, vs, mx, my, nblocks = block_grid(info.height, info.width, nc, sampling_code(info))
+    fac = [(hs, vs)] + [(1, 1)] * (nc - 1)
+    planes = [np.zeros((my * v, mx * h, 64), dtype=np.int32) for h, v in fac]
+    dc = [_huff_lookup(*info.htables[(0, c[4])]) for c in info.components]
+    ac = [_huff_lookup(*info.htables[(1, c[5])]) for c in info.components]
+    comp = [0] * (hs * vs) + list(range(1, nc))        # unit of the MCU -> component
+    bpm = len(comp)
+    seg = a[info.scan_start:info.scan_end]
+    end = int(seg.size)
+    n = max(1, -(-end // S))
+    spec = [(0, 0, 0, 0)] + [(j * S + (1 if seg[j * S - 1] == 0xFF else 0), 0, 0, 0) for j in range(1, n)]
+    limit = [min((j + 1) * S, end) for j in range(n)]
+
+    def locate(k):
+        m, u = divmod(k, bpm)
+        r, c = divmod(m, mx)
+        if u < hs * vs:
+            return planes[0][r * vs + u // hs, c * hs + u % hs]
+        return planes[comp[u]][r, c]
+
+    rec = [_sync_sub(seg, end, dc, ac, comp, spec[j], limit[j]) for j in range(n)]                  # round 0
+    used = list(spec)
+    invalid = sum(1 for r in rec if r[0] is None)
+    rounds = 1
+    cap = n if max_rounds is None else min(n, max_rounds)
+    while rounds < cap:
+        prev = [r[0] for r in rec]
+        todo = [j for j in range(1, n) if (prev[j - 1] or spec[j]) != used[j]]
+        if not todo:
+            break
+        rounds += 1
+        changed = False
+        for j in todo:
+            used[j] = prev[j - 1] or spec[j]
+            new = _sync_sub(seg, end, dc, ac, comp, used[j], limit[j])
+            invalid += 1 if new[0] is None else 0
+            changed = changed or new[0] != rec[j][0]
+            rec[j] = new
+        if not changed:
+            break
+    first, preds, k, pr = [], [], 0, [0, 0, 0]
+    for j in range(n):                                 # the exclusive scan
+        first.append(k)
+        preds.append(list(pr))
+        k += rec[j][1]
+        pr = [x + y for x, y in zip(pr, rec[j][2])]
+    entries = [spec[0]] + [rec[j - 1][0] for j in range(1, n)]
+    done = 0
+    for j in range(n):                                 # the write pass
+        if entries[j] is None or first[j] >= nblocks:
+            continue
+        sink = [locate, first[j], nblocks, list(preds[j])]
+        _sync_sub(seg, end, dc, ac, comp, entries[j], limit[j], sink)
+        done = max(done, sink[1])
+    if done < nblocks:
+        raise ValueError('the entropy-coded segment ran out of data')
+    if stats is not None:
+        stats.update(subsequences=n, rounds=rounds, entries=entries, first_blocks=first, predictors=preds, invalid_exits=invalid,
+                     stuffed_starts=sum(1 for j in range(1, n) if spec[j][0] != j * S))
+    return planes
+
+
 def _idct_pass(i, shift):
     """one 1-D pass of libjpeg's jidctint over axis 0 of i (8, ...) int64"""
     i0, i1, i2, i3, i4, i5, i6, i7 = i
@@ -469,12 +659,19 @@ class JpegClips(collections.namedtuple('JpegClips', ['data', 'frames', 'tables',
         return JpegClips(self.data, self.frames, self.tables, self.geom.reshape(-1, 4), self.lengths.reshape(-1), self.box.reshape(-1, 4),
                          self.dims)
 
-    def decode(self, out=None, status=None):
+    def decode(self, out=None, status=None, entropy=None, sub_bytes=None):
         """the RawU8Clips batch these frames decode to, on the data's device and current stream (ops.jpeg_decode_u8; there is no CPU
         path).  out: preallocated frames (..., Tmax, Hmax, Wmax, 3), every byte of which is written; status: (R,) int32, one word per
-        row of `frames`, 0 = decoded (check_status raises on anything else)."""
+        row of `frames`, 0 = decoded (check_status raises on anything else).  entropy: 'interval' or 'sync' (ops.jpeg_decode_u8; the
+        same bytes), None = CFN_JPEG_ENTROPY, read at call time (unset: 'interval'); sub_bytes: the sync mode's subsequence size."""
         from . import ops
-        frames = ops.jpeg_decode_u8(self, out=out, status=status)
+        mode = entropy_mode(entropy)
+        if mode == 'sync':
+            frames = ops.jpeg_decode_u8(self, out=out, status=status, entropy='sync', sub_bytes=sub_bytes)
+        else:
+            if sub_bytes is not None:
+                raise ValueError("sub_bytes belongs to entropy='sync', got entropy=%r" % (mode,))
+            frames = ops.jpeg_decode_u8(self, out=out, status=status)
         return RawU8Clips(frames.view(tuple(self.lengths.shape) + tuple(frames.shape[-4:])), self.lengths, self.box)
 
 
@@ -495,12 +692,13 @@ def check_status(status, frames, names=None, crops=1):
         raise RuntimeError('JPEG decode failed for %d frame(s); first: frame %d of clip %d%s: %s' % (bad.numel(), t, clip, who, why))
 
 
-def decode_checked(jpeg_clips, device, names=None):
+def decode_checked(jpeg_clips, device, names=None, entropy=None):
     """JpegClips (on any device) -> the RawU8Clips batch on `device`, decoded there on the current stream; the status words are read back
-    once and a frame that did not decode raises, naming its video (names: one per video of the batch)"""
+    once and a frame that did not decode raises, naming its video (names: one per video of the batch).  entropy: as JpegClips.decode"""
+    mode = entropy_mode(entropy)
     jc = jpeg_clips.to(device, non_blocking=True)
     status = torch.empty(jc.frames.shape[0], dtype=torch.int32, device=jc.device)
-    raw = jc.decode(status=status)
+    raw = jc.decode(status=status, entropy=mode)
     check_status(status, jpeg_clips.frames, names, crops=jpeg_clips.lengths.shape[1] if jpeg_clips.lengths.dim() > 1 else 1)
     return raw
 

@@ -1536,21 +1536,37 @@ def seg_labels(seg, offsets, fps, window, n_classes, t_max, out=None):
 
 
 # ---- baseline JPEG frames decoded on the GPU (csrc/jpegdec.hip; the host side and the batch type: cfn_hip/jpegdec.py) ------------------------
-def jpeg_workspace_bytes(rows, slots, lanes, blocks_max):
-    """bytes of workspace cfn_jpeg_decode_u8 needs for `rows` frames into `slots` = clips x Tmax frame slots"""
+def jpeg_workspace_bytes(rows, slots, lanes, blocks_max, entropy=None, sub_bytes=None, max_subs=None):
+    """bytes of workspace cfn_jpeg_decode_u8 needs for `rows` frames into `slots` = clips x Tmax frame slots.  entropy, sub_bytes,
+    max_subs: as jpeg_decode_u8 takes them; they are checked, and the sync mode needs no more (its records live in LDS)"""
+    from . import jpegdec
+    if jpegdec.entropy_mode(entropy) == 'sync' or sub_bytes is not None or max_subs is not None:
+        jpegdec.check_sync_sizes(sub_bytes, max_subs)
     n = int(query('cfn_jpeg_workspace_bytes', int(rows), int(slots), int(lanes), int(blocks_max)))
     if n < 0:
         raise RuntimeError('jpeg_decode_u8: bad sizes (%d frames, %d slots, %d lanes, %d blocks)' % (rows, slots, lanes, blocks_max))
     return n
 
 
-def jpeg_decode_u8(jpeg_clips, out=None, status=None, workspace=None):
+def jpeg_decode_u8(jpeg_clips, out=None, status=None, workspace=None, entropy=None, sub_bytes=None, max_subs=None):
     """a cfn_hip.jpegdec.JpegClips batch on the GPU -> its frames (N, Tmax, Hmax, Wmax, 3) uint8, N = all clips of the batch: what PIL
     decodes, bit for bit, each picture in the top-left corner, zero bytes elsewhere (RawU8Clips.frames as collate._pad_raw_u8 builds
     them).  On the current stream; nothing is read back: sizes come from the batch's host-side `dims`.
     out: preallocated frames, every byte is written.  status: (R,) int32, one word per row of `frames`, zeroed and set by the kernels
     (0 = decoded; jpegdec.check_status raises on anything else); with status=None the words are dropped -- pass one to learn of a bad
-    frame.  workspace: a uint8 device buffer of at least jpeg_workspace_bytes(...) (allocated per call otherwise).  No CPU path."""
+    frame.  workspace: a uint8 device buffer of at least jpeg_workspace_bytes(...) (allocated per call otherwise).  No CPU path.
+    entropy: None / 'interval' = one lane per (frame, restart interval), cfn_jpeg_decode_u8; 'sync' = cfn_jpeg_decode_u8_sync: a frame
+    without restart markers that is longer than `sub_bytes` (a multiple of 4 in [16, 1024], default jpegdec.SYNC_SUB_BYTES) and has at
+    most `max_subs` (<= jpegdec.SYNC_MAX_SUBS, default jpegdec.SYNC_DEFAULT_MAX_SUBS) subsequences of that size is decoded by one workgroup, a lane per
+    subsequence; every other frame as before.  The same bytes either way.  The environment is NOT read here (JpegClips.decode does)."""
+    from . import jpegdec
+    if entropy not in (None,) + jpegdec.ENTROPY_MODES:
+        raise ValueError("jpeg_decode_u8: entropy: None, 'interval' or 'sync' expected, got %r" % (entropy,))
+    sync = entropy == 'sync'
+    if sync or sub_bytes is not None or max_subs is not None:
+        sub_bytes, max_subs = jpegdec.check_sync_sizes(sub_bytes, max_subs)
+        if not sync:
+            raise ValueError("jpeg_decode_u8: sub_bytes / max_subs belong to entropy='sync', got entropy=%r" % (entropy,))
     jc = jpeg_clips
     if not (hasattr(jc, '_fields') and jc._fields[:6] == ('data', 'frames', 'tables', 'geom', 'lengths', 'box')):
         raise RuntimeError('jpeg_decode_u8: a JpegClips batch expected, got %s' % type(jc).__name__)
@@ -1582,6 +1598,10 @@ def jpeg_decode_u8(jpeg_clips, out=None, status=None, workspace=None):
     elif workspace.dtype != torch.uint8 or workspace.numel() < need or not workspace.is_contiguous():
         raise RuntimeError('jpeg_decode_u8: workspace: a contiguous uint8 buffer of at least %d bytes expected, got %s %s'
                            % (need, workspace.dtype, tuple(workspace.shape)))
-    call('cfn_jpeg_decode_u8', data.contiguous(), frames.contiguous(), tables.contiguous(), geom.contiguous(), lengths.contiguous(), out, status,
-         workspace, int(workspace.numel()), int(data.numel()), R, int(tables.shape[0]), N, T, H, W, lanes, blocks_max)
+    args = (data.contiguous(), frames.contiguous(), tables.contiguous(), geom.contiguous(), lengths.contiguous(), out, status, workspace,
+            int(workspace.numel()), int(data.numel()), R, int(tables.shape[0]), N, T, H, W, lanes, blocks_max)
+    if sync:
+        call('cfn_jpeg_decode_u8_sync', *(args + (sub_bytes, max_subs)))
+    else:
+        call('cfn_jpeg_decode_u8', *args)
     return out.view(N, T, H, W, 3)

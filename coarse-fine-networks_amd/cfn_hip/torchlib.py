@@ -1013,6 +1013,23 @@ def _(data, frames, tables, geom, lengths, dims):
             data.new_empty((frames.shape[0],), dtype=torch.int32))
 
 
+@_op('jpeg_decode_sync_u8')
+def jpeg_decode_sync_u8(data: torch.Tensor, frames: torch.Tensor, tables: torch.Tensor, geom: torch.Tensor, lengths: torch.Tensor,
+                        dims: Sequence[int], sub_bytes: int, max_subs: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """jpeg_decode_u8 with the sync entropy mode (ops.jpeg_decode_u8(..., entropy='sync', sub_bytes, max_subs)): the same outputs"""
+    from .jpegdec import JpegClips
+    status = torch.empty(frames.shape[0], dtype=torch.int32, device=data.device)
+    box = torch.zeros(lengths.numel(), 4, dtype=torch.int32, device=data.device)
+    return _ops.jpeg_decode_u8(JpegClips(data, frames, tables, geom, lengths, box, tuple(dims)), status=status, entropy='sync',
+                               sub_bytes=sub_bytes, max_subs=max_subs), status
+
+
+@jpeg_decode_sync_u8.register_fake
+def _(data, frames, tables, geom, lengths, dims, sub_bytes, max_subs):
+    return (data.new_empty((lengths.numel(), dims[0], dims[1], dims[2], 3), dtype=torch.uint8),
+            data.new_empty((frames.shape[0],), dtype=torch.int32))
+
+
 # ---- frame labels from annotation segments (csrc/seglabels.hip; the sample record and the batch type: cfn_hip/seglabels.py), no gradient ------
 @_op('seg_labels')
 def seg_labels(seg: torch.Tensor, offsets: torch.Tensor, fps: torch.Tensor, window: torch.Tensor, n_classes: int,
@@ -1039,6 +1056,8 @@ METRIC_OPERATORS = ('ap_append', 'ap_sort', 'average_precision')
 FEATURE_OPERATORS = ('feat_unpack', 'feat_pack')
 # baseline JPEG frames -> uint8 frames on the GPU (no gradient)
 DECODE_OPERATORS = ('jpeg_decode_u8',)
+# the same decode with the sync entropy mode: parallel inside a frame without restart markers (no gradient)
+DECODE_SYNC_OPERATORS = ('jpeg_decode_sync_u8',)
 # annotation segments -> dense frame labels, mask and lengths on the GPU (no gradient)
 LABEL_OPERATORS = ('seg_labels',)
 

@@ -216,3 +216,28 @@ extern "C" int cfn_jpeg_decode_u8(const unsigned char* data, const int* frames, 
     a.blocks_max = blocks_max;
     return jpeg_decode_launch(a, ws, stream);
 }
+
+// the same decode with the sync entropy mode for the frames without restart markers (csrc/jpegdec.hip jpeg_entropy_sync_kernel)
+extern "C" int cfn_jpeg_decode_u8_sync(const unsigned char* data, const int* frames, const int* tables, const int* geom, const int* lengths,
+                                       unsigned char* out, int* status, void* ws, long ws_bytes, long data_bytes, int rows, int sets, int N,
+                                       int Tmax, int Hmax, int Wmax, int lanes, int blocks_max, int sub_bytes, int max_subs,
+                                       void* stream) {
+    CFN_REQUIRE(sub_bytes >= 16 && sub_bytes <= 1024 && (sub_bytes & 3) == 0,
+                "cfn_jpeg_decode_u8_sync: sub_bytes: a multiple of 4 in [16, 1024] expected, got %d", sub_bytes);
+    CFN_REQUIRE(max_subs >= 1 && max_subs <= JP_SYNC_MAX_SUBS, "cfn_jpeg_decode_u8_sync: max_subs: 1 .. %d expected, got %d", JP_SYNC_MAX_SUBS,
+                max_subs);
+    CFN_REQUIRE(data && frames && tables && geom && lengths && out && status && ws, "cfn_jpeg_decode_u8_sync: null tensor");
+    CFN_REQUIRE(rows >= 1 && sets >= 1 && N >= 1 && Tmax >= 1 && Hmax >= 1 && Wmax >= 1 && lanes >= 1 && blocks_max >= 1 && data_bytes >= 1,
+                "cfn_jpeg_decode_u8_sync: bad shape (%d frames, %d table sets, %d clips of %d x %d x %d, %d lanes, %d blocks, %ld bytes)", rows, sets, N,
+                Tmax, Hmax, Wmax, lanes, blocks_max, data_bytes);
+    CFN_REQUIRE(data_bytes < (1L << 31), "cfn_jpeg_decode_u8_sync: %ld bytes of data: offsets are 32-bit", data_bytes);
+    CFN_REQUIRE(((uintptr_t)data & 3) == 0 && ((uintptr_t)out & 3) == 0 && ((uintptr_t)ws & 15) == 0,
+                "cfn_jpeg_decode_u8_sync: data and out must start on a 4-byte boundary, the workspace on a 16-byte boundary");
+    const long need = cfn_jpeg_workspace_bytes(rows, (long)N * Tmax, lanes, blocks_max);
+    CFN_REQUIRE(ws_bytes >= need, "cfn_jpeg_decode_u8_sync: a workspace of %ld bytes is needed, %ld given", need, ws_bytes);
+    JpegArgs a = {};
+    a.data = data; a.frames = frames; a.tables = tables; a.geom = geom; a.lengths = lengths; a.out = out; a.status = status;
+    a.data_bytes = data_bytes; a.rows = rows; a.sets = sets; a.N = N; a.T = Tmax; a.H = Hmax; a.W = Wmax; a.lanes = lanes;
+    a.blocks_max = blocks_max;
+    return jpeg_decode_sync_launch(a, ws, stream, sub_bytes, max_subs);
+}

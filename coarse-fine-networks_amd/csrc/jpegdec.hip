@@ -14,6 +14,12 @@
 //            jdcolor, gray replication; writes EVERY byte of the RawU8Clips frames (N, Tmax, Hmax, Wmax, 3): the picture in the top-left
 //            corner, zero bytes outside h x w and in frames nothing was decoded into
 //
+// A second entry point (cfn_jpeg_decode_u8_sync) puts a fifth kernel between scan and entropy:
+//
+//   entropy, sync   one WORKGROUP per frame without restart markers, one lane per subsequence of S raw bytes: speculative decodes in rounds
+//            until no exit state changes, a scan of block counts and DC sums, one write pass (see the section in front of the host code);
+//            the frames it takes are struck from the owner list, every other frame is left to the entropy kernel above
+//
 // Everything the kernels index with is DATA (records, offsets, lengths, tables, geometry): every loop has a bound that does not depend on
 // the bit stream (<= 16 bits per code, <= 63 AC symbols per block, block and MCU counts from the checked geometry), every read of `data`
 // is clamped to the frame's own segment, every table index is masked, every workspace index is derived from the checked geometry.  A
@@ -394,6 +400,273 @@ __global__ __launch_bounds__(256) void jpeg_colour_kernel(const JpegArgs a) {
     }
 }
 
+// ---- entropy, 'sync' mode: parallel inside a frame without restart markers -------------------------------------------------------------------
+// Huffman-coded data self-synchronises (Weissenberger & Schmidt, "Accelerating JPEG Decompression on GPUs"); the rounds, and why n of
+// them always reach the true states, are stated in plain Python by cfn_hip/jpegdec.py decode_coefficients_sync.  One workgroup per frame
+// row.  A frame is taken when its record has restart interval 0 (one decoder lane), more than `S` bytes and at most `max_subs`
+// subsequences of S raw bytes; the workgroup then clears the frame's entry in the owner list, so that jpeg_entropy_kernel, launched
+// behind this kernel, passes over it and decodes every other frame as before.
+//
+// A decoder state is one 64-bit word: raw byte index << 32 | bit << 12 | unit of the MCU << 8 | zigzag index; bit 15 says "changed in
+// this round" and takes no part in comparisons.  The byte behind a data byte FF is skipped whatever it is and bytes behind the segment's
+// end read as 0, so a subsequence's decode is a pure function of its entry state.
+#define JP_SYNC_INVALID 0xFFFFFFFF00000000ul
+#define JP_SYNC_CHG 0x8000ul
+
+__device__ __forceinline__ unsigned long jpeg_sync_pack(int p, int b, int u, int zz) {
+    return ((unsigned long)(unsigned)p << 32) | (unsigned long)(unsigned)((b << 12) | (u << 8) | zz);
+}
+
+// the subsequences of a frame the sync mode takes, 0 for every other frame
+__device__ __forceinline__ int jpeg_sync_subs(const JpegRow& f, const JpegGrid& g, int S, int max_subs) {
+    if (!f.ok || !g.ok || f.ri != 0 || f.lanes != 1 || f.bytes <= S) return 0;
+    const long n = ((long)f.bytes + S - 1) / S;
+    return n <= max_subs ? (int)n : 0;
+}
+
+// the speculative entry of subsequence j < n: its first byte, one on when that is the stuffed 00 of an FF 00 pair; u = zz = 0
+__device__ __forceinline__ unsigned long jpeg_sync_start(const JpegArgs& a, const JpegRow& f, int j, int S) {
+    if (j <= 0) return 0ul;
+    const int p = j * S;
+    return jpeg_sync_pack(p + (a.data[(long)f.off + p - 1] == 0xFFu ? 1 : 0), 0, 0, 0);
+}
+
+// the bit reader of the sync mode: JpegBits' buffer, plus one flag per buffered byte (was it FF, i.e. two raw bytes) from which the raw
+// position of the next bit is recovered.  Raw bytes come from aligned dword loads (the segment starts on a 4-byte boundary, the row
+// check says so), in address order whatever the bytes hold, so the next dword is always on its way while the current one is used.
+struct JpegSyncBits {
+    const unsigned* w; int pos, end; unsigned q, nxt; int qn, wi; unsigned long acc; int cnt; unsigned ffm;
+    // dword i of the segment, bytes at or behind `end` zeroed; nothing is read at or behind end rounded up to 4
+    __device__ __forceinline__ unsigned dword(int i) const {
+        const int rest = end - 4 * i;
+        if (i < 0 || rest <= 0) return 0u;
+        const unsigned v = w[i];
+        return rest >= 4 ? v : (v & ((1u << (8 * rest)) - 1u));
+    }
+    __device__ __forceinline__ void start(const unsigned char* seg, int p0, int bytes) {      // 0 <= p0 <= bytes
+        w = reinterpret_cast<const unsigned*>(seg); pos = p0; end = bytes; acc = 0; cnt = 0; ffm = 0;
+        wi = p0 >> 2;
+        q = dword(wi) >> (8 * (p0 & 3)); qn = 4 - (p0 & 3);
+        nxt = dword(wi + 1);
+        wi += 2;
+    }
+    __device__ __forceinline__ unsigned byte() {             // raw byte `pos`; 0 behind the end
+        if (qn == 0) { q = nxt; qn = 4; nxt = dword(wi); ++wi; }
+        const unsigned b = q & 255u;
+        q >>= 8; --qn; ++pos;
+        return b;
+    }
+    __device__ __forceinline__ void refill() {               // at least 57 valid bits behind this
+#pragma unroll 1
+        for (int i = 0; i < 8; ++i) {
+            if (cnt > 56) break;
+            const unsigned b = byte();
+            const unsigned ff = b == 0xFFu ? 1u : 0u;
+            if (ff) byte();                                  // the byte behind FF is skipped whatever it is
+            acc = (acc << 8) | b;
+            ffm = (ffm << 1) | ff;
+            cnt += 8;
+        }
+    }
+    // the raw byte that holds the next bit, and the bit's index in it (cnt >= 1: call behind refill)
+    __device__ __forceinline__ int head_byte() const {
+        const int h = (cnt - 1) >> 3;
+        return pos - (h + 1) - __builtin_popcount(ffm & ((2u << h) - 1u));
+    }
+    __device__ __forceinline__ int head_bit() const { return (8 - (cnt & 7)) & 7; }
+    __device__ __forceinline__ unsigned peek16() const { return (unsigned)(acc >> (cnt - 16)) & 0xFFFFu; }
+    __device__ __forceinline__ int receive(int s) {
+        const int v = (int)((acc >> (cnt - s)) & ((1u << s) - 1u));
+        cnt -= s;
+        return (s == 0 || v >= (1 << (s - 1))) ? v : v - (1 << s) + 1;
+    }
+    __device__ __forceinline__ int symbol(const int* ht) {   // as JpegBits::symbol, the caller refills
+        const unsigned pk = peek16();
+        const int e = ht[pk >> (16 - JP_LOOK)];
+        int len = e >> 8, sym = e & 255;
+        if (len == 0) {
+            sym = -1;
+#pragma unroll 1
+            for (int l = JP_LOOK + 1; l <= 16; ++l) {
+                const int code = (int)(pk >> (16 - l));
+                if (code <= ht[JP_HT_MAXCODE + l]) { sym = ht[JP_HT_VAL + ((ht[JP_HT_VALOFF + l] + code) & 255)] & 255; len = l; break; }
+            }
+            if (sym < 0) return -1;
+        }
+        cnt -= len & 31;
+        return sym;
+    }
+};
+
+// what a lane keeps per subsequence: the exit state, the blocks it completed, the sum of its DC differences per component
+struct JpegSub { unsigned long exit; int blocks, dc0, dc1, dc2; };
+
+// block `k` of the frame in scan order (MCU by MCU, luma units row by row, then Cb, Cr) -> its 64 coefficients; k < g.nblocks
+__device__ __forceinline__ short* jpeg_scan_block(short* coef, const JpegGrid& g, int k) {
+    const int ny = g.hs * g.vs, bpm = ny + (g.ncomp == 3 ? 2 : 0);
+    const int m = k / bpm, u = k - m * bpm, my = m / g.mx, mx = m - my * g.mx;
+    int idx;
+    if (u < ny) {
+        const int by = u / g.hs, bx = u - by * g.hs;
+        idx = (my * g.vs + by) * g.bw0 + mx * g.hs + bx;
+    } else {
+        idx = (u == ny ? g.nb0 : g.nb0 + g.nbc) + my * g.mx + mx;
+    }
+    return coef + (long)idx * 64;
+}
+
+// One subsequence of frame `f` (row r): decode from `entry` up to the first symbol whose first bit lies at or behind raw byte `limit`
+// (<= f.bytes).  `huff`: the frame's four Huffman tables (DC0, DC1, AC0, AC1).  write = false: nothing is stored and no status is set;
+// an invalid code or a coefficient index beyond 63 gives the exit JP_SYNC_INVALID.  write = true: the lane continues block `first` of
+// the scan (at the entry's zigzag index) with the predictors pred0..2, writes absolute DC values and AC coefficients in natural order,
+// stops behind the frame's last block and returns the status bits of what it met.
+__device__ __forceinline__ int jpeg_sub_decode(const JpegArgs& a, const JpegRow& f, const JpegGrid& g, int r, const int* huff, unsigned long entry,
+                                               int limit, bool write, int first, int pred0, int pred1, int pred2, JpegSub* out) {
+    const int ny = g.hs * g.vs, bpm = ny + (g.ncomp == 3 ? 2 : 0);
+    short* coef = a.coef + (long)r * a.blocks_max * 64;
+    int u = (int)(entry >> 8) & 15, zz = (int)entry & 63, bidx = first;
+    if (write) u = bidx % bpm;
+    if (u >= bpm) u = 0;
+    int p0 = (int)(entry >> 32);
+    if (p0 < 0 || p0 > limit) p0 = limit;
+    const int budget = 8 * (limit - p0) + 64;                // every symbol takes a bit or more
+    JpegSyncBits br;
+    br.start(a.data + f.off, p0, f.bytes);
+    br.refill();
+    br.cnt -= (int)(entry >> 12) & 7;
+    int blocks = 0, dc0 = 0, dc1 = 0, dc2 = 0, err = 0;
+    short* blk = (write && bidx < g.nblocks) ? jpeg_scan_block(coef, g, bidx) : nullptr;
+#pragma unroll 1
+    for (int it = 0; it < budget; ++it) {
+        br.refill();
+        if ((br.pos >= limit && br.head_byte() >= limit) || (write && bidx >= g.nblocks)) break;      // (the head never lies behind pos)
+        const int c = u < ny ? 0 : u - ny + 1, slot = c ? 1 : 0;
+        if (zz == 0) {
+            const int s = br.symbol(huff + slot * JP_HT_WORDS);
+            if (s < 0) { err = JP_ST_CODE; break; }
+            const int d = br.receive(s & 15);
+            if (c == 0) { dc0 += d; pred0 += d; } else if (c == 1) { dc1 += d; pred1 += d; } else { dc2 += d; pred2 += d; }
+            if (write) blk[0] = (short)(c == 0 ? pred0 : (c == 1 ? pred1 : pred2));
+            zz = 1;
+            continue;
+        }
+        const int s = br.symbol(huff + (2 + slot) * JP_HT_WORDS);
+        if (s < 0) { err = JP_ST_CODE; break; }
+        const int run = s >> 4, sz = s & 15;
+        if (sz == 0) {
+            zz = run == 15 ? zz + 16 : 64;                   // ZRL, EOB
+        } else {
+            zz += run;
+            if (zz > 63) { err = JP_ST_CODE; break; }
+            const int v = br.receive(sz);
+            if (write) blk[jp_zigzag[zz & 63]] = (short)v;
+            ++zz;
+        }
+        if (zz >= 64) {
+            zz = 0;
+            u = u + 1 == bpm ? 0 : u + 1;
+            ++blocks; ++bidx;
+            if (write && bidx < g.nblocks) blk = jpeg_scan_block(coef, g, bidx);
+        }
+    }
+    br.refill();
+    const int hp = br.head_byte(), hb = br.head_bit();
+    if (write && !err && (hp > f.bytes || (hp == f.bytes && hb > 0))) err = JP_ST_DATA;       // bits were taken from behind the segment's end
+    out->exit = err == JP_ST_CODE ? JP_SYNC_INVALID : jpeg_sync_pack(hp, hb, u, zz);
+    out->blocks = blocks; out->dc0 = dc0; out->dc1 = dc1; out->dc2 = dc2;
+    return write ? err : 0;
+}
+
+// LDS: the four Huffman tables of the frame (13,312 bytes), three round flags, and per subsequence two exit states (this round's and the
+// last one's) and the four counts: 32 bytes each, dynamic, sized for max_subs <= JP_SYNC_MAX_SUBS (1536: 48 KiB, 62,480 bytes in all,
+// inside the 64 KiB a launch gets without asking for more)
+__global__ __launch_bounds__(JP_SYNC_THREADS) void jpeg_entropy_sync_kernel(const JpegArgs a, int S, int max_subs) {
+    extern __shared__ unsigned long jp_sync_lds[];
+    __shared__ int huff[4 * JP_HT_WORDS];
+    __shared__ int any[4];
+    const int tid = (int)threadIdx.x, r = (int)blockIdx.x;
+    // the same words are read by every lane, so the workgroup leaves as a whole, in front of its first barrier
+    if (r >= a.rows || S < 16 || max_subs < 1 || max_subs > JP_SYNC_MAX_SUBS) return;
+    const JpegRow f = jpeg_row(a, r);
+    JpegGrid g = {};
+    if (f.ok) g = jpeg_grid(a, f.clip);
+    const int n = jpeg_sync_subs(f, g, S, max_subs);
+    if (n == 0) return;
+    unsigned long* ex0 = jp_sync_lds;
+    unsigned long* ex1 = jp_sync_lds + max_subs;
+    int* rec = reinterpret_cast<int*>(jp_sync_lds + 2L * max_subs);
+    if (tid == 0) a.owner[f.lane0] = -1;                     // jpeg_entropy_kernel passes over this frame
+    const int* set = a.tables + (long)JP_SET_WORDS * f.set + JP_SET_HUFF;
+    for (int i = tid; i < 4 * JP_HT_WORDS; i += JP_SYNC_THREADS) huff[i] = set[i];
+    if (tid < 3) any[tid] = 0;
+    __syncthreads();
+    // round 0: every subsequence from its speculative start, subsequence 0 from the true state
+    for (int j = tid; j < n; j += JP_SYNC_THREADS) {
+        JpegSub s;
+        jpeg_sub_decode(a, f, g, r, huff, jpeg_sync_start(a, f, j, S), min((j + 1) * S, f.bytes), false, 0, 0, 0, 0, &s);
+        ex0[j] = s.exit | JP_SYNC_CHG;
+        rec[4 * j] = s.blocks; rec[4 * j + 1] = s.dc0; rec[4 * j + 2] = s.dc1; rec[4 * j + 3] = s.dc2;
+    }
+    __syncthreads();
+    // round k: from the predecessor's exit of round k - 1, where that is not the entry used last.  The trip count (n) and the decision to
+    // stop (a flag in LDS, read behind the barrier; three flags in rotation, so that the reset never meets a reader) are uniform.
+    int k = 1;
+    for (; k < n; ++k) {
+        const unsigned long* was = (k & 1) ? ex0 : ex1;
+        unsigned long* now = (k & 1) ? ex1 : ex0;
+        bool moved = false;
+        for (int j = tid; j < n; j += JP_SYNC_THREADS) {
+            const unsigned long own = was[j] & ~JP_SYNC_CHG;
+            if (j == 0) { now[0] = own; continue; }
+            const unsigned long pe = was[j - 1], spec = jpeg_sync_start(a, f, j, S);
+            const unsigned long entry = (pe & ~JP_SYNC_CHG) == JP_SYNC_INVALID ? spec : (pe & ~JP_SYNC_CHG);
+            if (!(pe & JP_SYNC_CHG) || (k == 1 && entry == spec)) { now[j] = own; continue; }
+            JpegSub s;
+            jpeg_sub_decode(a, f, g, r, huff, entry, min((j + 1) * S, f.bytes), false, 0, 0, 0, 0, &s);
+            const bool c = s.exit != own;
+            now[j] = s.exit | (c ? JP_SYNC_CHG : 0ul);
+            rec[4 * j] = s.blocks; rec[4 * j + 1] = s.dc0; rec[4 * j + 2] = s.dc1; rec[4 * j + 3] = s.dc2;
+            moved = moved || c;
+        }
+        if (moved) any[k % 3] = 1;
+        if (tid == 0) any[(k + 1) % 3] = 0;
+        __syncthreads();
+        if (!any[k % 3]) break;
+    }
+    const unsigned long* fin = ((k < n ? k : n - 1) & 1) ? ex1 : ex0;
+    // exclusive scan of the four counts over the subsequences, by the first wave: first block and entry predictors of every subsequence
+    if (tid < 64) {
+        int carry[4] = {0, 0, 0, 0};
+        for (int base = 0; base < n; base += 64) {
+            const int j = base + tid;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int v = j < n ? rec[4 * j + q] : 0;
+                int incl = v;
+#pragma unroll
+                for (int o = 1; o < 64; o <<= 1) {
+                    const int t = __shfl_up(incl, o, 64);
+                    if (tid >= o) incl += t;
+                }
+                if (j < n) rec[4 * j + q] = carry[q] + incl - v;
+                carry[q] += __shfl(incl, 63, 64);
+            }
+        }
+    }
+    __syncthreads();
+    // the write pass, from the true entries
+    int err = 0;
+    for (int j = tid; j < n; j += JP_SYNC_THREADS) {
+        const unsigned long entry = j == 0 ? 0ul : (fin[j - 1] & ~JP_SYNC_CHG);
+        const int first = rec[4 * j];
+        if (entry == JP_SYNC_INVALID || first < 0 || first >= g.nblocks) continue;
+        JpegSub s;
+        err |= jpeg_sub_decode(a, f, g, r, huff, entry, min((j + 1) * S, f.bytes), true, first, rec[4 * j + 1], rec[4 * j + 2], rec[4 * j + 3], &s);
+        if (j == n - 1 && !err && first + s.blocks < g.nblocks) err = JP_ST_DATA;              // the segment ended in front of the last block
+    }
+    if (err) atomicOr(a.status + r, err);
+}
+
 // ---- host ------------------------------------------------------------------------------------------------------------------------------
 static long jp_align(long v) { return (v + 255) & ~255L; }
 
@@ -408,7 +681,9 @@ void jpeg_workspace_layout(int rows, long slots, int lanes, int blocks_max, Jpeg
     l->total = jp_align(l->samp + blocks * 64);
 }
 
-int jpeg_decode_launch(JpegArgs a, void* ws, void* stream) {
+// sub_bytes = 0: the lane-per-interval decode alone (cfn_jpeg_decode_u8).  Otherwise the sync kernel runs between the scan and the
+// lane-per-interval kernel, which then finds the frames it took struck from the owner list.
+static int jpeg_decode_launch_mode(JpegArgs a, void* ws, void* stream, int sub_bytes, int max_subs, const char* who) {
     hipStream_t st = (hipStream_t)stream;
     JpegLayout l;
     jpeg_workspace_layout(a.rows, (long)a.N * a.T, a.lanes, a.blocks_max, &l);
@@ -417,17 +692,26 @@ int jpeg_decode_launch(JpegArgs a, void* ws, void* stream) {
     a.samp = (unsigned char*)(w + l.samp);
     const long pixels = (long)a.N * a.T * a.H * a.W, blocks = (long)a.rows * a.blocks_max;
     const long cgrid = (pixels + 1023) / 1024, igrid = (blocks + 255) / 256;
-    CFN_REQUIRE(cgrid < (1L << 31) && igrid < (1L << 31), "cfn_jpeg_decode_u8: too many pixels or blocks for one grid");
+    CFN_REQUIRE(cgrid < (1L << 31) && igrid < (1L << 31), "%s: too many pixels or blocks for one grid", who);
     CfnProfScope prof(CFN_K_ELEMWISE, st, (double)pixels * 3.0 + (double)a.data_bytes + (double)blocks * 384.0);
     if (hipMemsetAsync(w + l.coef, 0, (size_t)(l.owner - l.coef), st) != hipSuccess ||
         hipMemsetAsync(w + l.owner, 0xFF, (size_t)(l.samp - l.owner), st) != hipSuccess ||
         hipMemsetAsync(a.status, 0, 4 * (size_t)a.rows, st) != hipSuccess)
-        return cfn_fail(CFN_ERR_LAUNCH, "cfn_jpeg_decode_u8: hipMemsetAsync failed: %s", hipGetErrorString(hipGetLastError()));
+        return cfn_fail(CFN_ERR_LAUNCH, "%s: hipMemsetAsync failed: %s", who, hipGetErrorString(hipGetLastError()));
     hipLaunchKernelGGL(jpeg_scan_kernel, dim3((unsigned)((a.rows + 3) / 4)), dim3(256), 0, st, a);
+    if (sub_bytes > 0)
+        hipLaunchKernelGGL(jpeg_entropy_sync_kernel, dim3((unsigned)a.rows), dim3(JP_SYNC_THREADS), (size_t)max_subs * JP_SYNC_SUB_LDS, st, a, sub_bytes,
+                           max_subs);
     // one lane per restart interval: a wave is only filled once there are lanes for ~4 waves on each of the 1024 SIMDs
     const int per_wave = min(64, max(1, a.lanes / 4096));
     hipLaunchKernelGGL(jpeg_entropy_kernel, dim3((unsigned)((a.lanes + per_wave - 1) / per_wave)), dim3(64), 0, st, a, per_wave);
     hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)igrid), dim3(256), 0, st, a);
     hipLaunchKernelGGL(jpeg_colour_kernel, dim3((unsigned)cgrid), dim3(256), 0, st, a);
-    return cfn_check_launch("cfn_jpeg_decode_u8");
+    return cfn_check_launch(who);
+}
+
+int jpeg_decode_launch(JpegArgs a, void* ws, void* stream) { return jpeg_decode_launch_mode(a, ws, stream, 0, 0, "cfn_jpeg_decode_u8"); }
+
+int jpeg_decode_sync_launch(JpegArgs a, void* ws, void* stream, int sub_bytes, int max_subs) {
+    return jpeg_decode_launch_mode(a, ws, stream, sub_bytes, max_subs, "cfn_jpeg_decode_u8_sync");
 }

@@ -15,7 +15,7 @@
 // metrics: ap_append (mutates its stores), ap_sort, average_precision (csrc/apmeter.hip) -- no gradients.
 // loss: detection_loss + detection_loss_backward (csrc/detloss.hip), the opt-in fused detection loss of the three training scripts.
 // packed 16-bit fine features: feat_unpack, feat_pack (csrc/featpack.hip) -- no gradients.
-// baseline JPEG frames -> uint8 frames: jpeg_decode_u8 (csrc/jpegdec.hip) -- no gradient.
+// baseline JPEG frames -> uint8 frames: jpeg_decode_u8, jpeg_decode_sync_u8 (csrc/jpegdec.hip) -- no gradient.
 // annotation segments -> dense frame labels, mask and lengths: seg_labels (csrc/seglabels.hip) -- no gradient.
 #include <ATen/ATen.h>
 // (a ROCm build of torch presents its HIP devices as "cuda": the masquerading guard / stream classes are the ones that accept them)
@@ -1066,9 +1066,9 @@ Tensor feat_pack(at::TensorList feat, at::ScalarType dtype) {
 
 // ---- baseline JPEG frames decoded on the GPU (csrc/jpegdec.hip; cfn_hip/jpegdec.py) -- no gradient ---------------------------------------------
 // the members of a JpegClips batch; dims = (Tmax, Hmax, Wmax, decoder lanes, most blocks of a frame) -> (frames (N, Tmax, Hmax, Wmax, 3) uint8, status (R) int32)
-std::tuple<Tensor, Tensor> jpeg_decode_u8(const Tensor& data, const Tensor& frames, const Tensor& tables, const Tensor& geom, const Tensor& lengths,
-                                          at::IntArrayRef dims) {
-    const char* op = "cfn::jpeg_decode_u8";
+// sub_bytes = 0: one lane per restart interval; otherwise the sync entropy mode with that subsequence size
+static std::tuple<Tensor, Tensor> jpeg_decode_impl(const char* op, const Tensor& data, const Tensor& frames, const Tensor& tables, const Tensor& geom,
+                                                   const Tensor& lengths, at::IntArrayRef dims, int64_t sub_bytes, int64_t max_subs) {
     TORCH_CHECK(data.is_cuda(), op, ": device tensors only (there is no CPU path)");
     TORCH_CHECK(data.scalar_type() == at::kByte && data.dim() == 1 && data.numel() >= 1, op, ": data: a flat uint8 buffer expected, got ", data.scalar_type(), " ", data.sizes());
     TORCH_CHECK(frames.scalar_type() == at::kInt && frames.dim() == 2 && frames.size(0) >= 1 && frames.size(1) == 8, op, ": frames (R, 8) int32 expected, got ",
@@ -1089,12 +1089,33 @@ std::tuple<Tensor, Tensor> jpeg_decode_u8(const Tensor& data, const Tensor& fram
     Tensor ws = at::empty({(int64_t)need}, data.options());
     Tensor out = at::empty({N, dims[0], dims[1], dims[2], 3}, data.options());
     Tensor status = at::empty({R}, data.options().dtype(at::kInt));
-    ok(cfn_jpeg_decode_u8(d.data_ptr<uint8_t>(), f.data_ptr<int>(), tb.data_ptr<int>(), g.data_ptr<int>(), len.data_ptr<int>(), out.data_ptr<uint8_t>(),
-                          status.data_ptr<int>(), ws.data_ptr(), need, (long)d.numel(), (int)R, (int)tb.size(0), (int)N, (int)dims[0], (int)dims[1], (int)dims[2],
-                          (int)dims[3], (int)dims[4], stream_of(out)),
-       "cfn_jpeg_decode_u8");
+    if (sub_bytes > 0)
+        ok(cfn_jpeg_decode_u8_sync(d.data_ptr<uint8_t>(), f.data_ptr<int>(), tb.data_ptr<int>(), g.data_ptr<int>(), len.data_ptr<int>(), out.data_ptr<uint8_t>(),
+                                   status.data_ptr<int>(), ws.data_ptr(), need, (long)d.numel(), (int)R, (int)tb.size(0), (int)N, (int)dims[0], (int)dims[1],
+                                   (int)dims[2], (int)dims[3], (int)dims[4], (int)sub_bytes, (int)max_subs, stream_of(out)),
+           "cfn_jpeg_decode_u8_sync");
+    else
+        ok(cfn_jpeg_decode_u8(d.data_ptr<uint8_t>(), f.data_ptr<int>(), tb.data_ptr<int>(), g.data_ptr<int>(), len.data_ptr<int>(), out.data_ptr<uint8_t>(),
+                              status.data_ptr<int>(), ws.data_ptr(), need, (long)d.numel(), (int)R, (int)tb.size(0), (int)N, (int)dims[0], (int)dims[1], (int)dims[2],
+                              (int)dims[3], (int)dims[4], stream_of(out)),
+           "cfn_jpeg_decode_u8");
     return std::make_tuple(out, status);
 }
+
+std::tuple<Tensor, Tensor> jpeg_decode_u8(const Tensor& data, const Tensor& frames, const Tensor& tables, const Tensor& geom, const Tensor& lengths,
+                                          at::IntArrayRef dims) {
+    return jpeg_decode_impl("cfn::jpeg_decode_u8", data, frames, tables, geom, lengths, dims, 0, 0);
+}
+
+// the same with the sync entropy mode for frames without restart markers (csrc/jpegdec.hip jpeg_entropy_sync_kernel)
+std::tuple<Tensor, Tensor> jpeg_decode_sync_u8(const Tensor& data, const Tensor& frames, const Tensor& tables, const Tensor& geom, const Tensor& lengths,
+                                               at::IntArrayRef dims, int64_t sub_bytes, int64_t max_subs) {
+    const char* op = "cfn::jpeg_decode_sync_u8";
+    TORCH_CHECK(sub_bytes >= 16 && sub_bytes <= 1024 && sub_bytes % 4 == 0, op, ": sub_bytes: a multiple of 4 in [16, 1024] expected, got ", sub_bytes);
+    TORCH_CHECK(max_subs >= 1 && max_subs <= 1536, op, ": max_subs: 1 .. 1536 expected, got ", max_subs);
+    return jpeg_decode_impl(op, data, frames, tables, geom, lengths, dims, sub_bytes, max_subs);
+}
+
 
 // ---- frame labels from annotation segments (csrc/seglabels.hip; cfn_hip/seglabels.py) -- no gradient: labels are targets ------------------------
 // seg (S, 3) fp64 [class, start_s, end_s]; offsets (B + 1) int32; fps (B) fp64; window (B, 2) int32 = first frame, length
@@ -1172,6 +1193,7 @@ TORCH_LIBRARY_FRAGMENT(cfn, m) {
     m.def("feat_unpack(Tensor data, Tensor offsets, Tensor lengths, SymInt[] channels, SymInt t_max) -> Tensor[]");
     m.def("feat_pack(Tensor[] feat, ScalarType dtype) -> Tensor");
     m.def("jpeg_decode_u8(Tensor data, Tensor frames, Tensor tables, Tensor geom, Tensor lengths, SymInt[] dims) -> (Tensor, Tensor)");
+    m.def("jpeg_decode_sync_u8(Tensor data, Tensor frames, Tensor tables, Tensor geom, Tensor lengths, SymInt[] dims, int sub_bytes, int max_subs) -> (Tensor, Tensor)");
     m.def("seg_labels(Tensor seg, Tensor offsets, Tensor fps, Tensor window, SymInt n_classes, SymInt t_max) -> (Tensor, Tensor, Tensor)");
 }
 
@@ -1220,5 +1242,6 @@ TORCH_LIBRARY_IMPL(cfn, CUDA, m) {      // (the HIP backend of a ROCm build of t
     m.impl("feat_unpack", feat_unpack);
     m.impl("feat_pack", feat_pack);
     m.impl("jpeg_decode_u8", jpeg_decode_u8);
+    m.impl("jpeg_decode_sync_u8", jpeg_decode_sync_u8);
     m.impl("seg_labels", seg_labels);
 }

@@ -42,8 +42,9 @@ def build_tower(device, ckpt=None, n_classes=157, input_norm=None):
 
 
 @torch.no_grad()
-def extract(net, videos, save_dir, device='cuda', crop=224, feat_dtype=None):
-    """feat_dtype None: the reference's five fp32 files per video; 'fp16' / 'bf16': one packed record per video"""
+def extract(net, videos, save_dir, device='cuda', crop=224, feat_dtype=None, jpeg_entropy=None):
+    """feat_dtype None: the reference's five fp32 files per video; 'fp16' / 'bf16': one packed record per video.  jpeg_entropy: how JpegClips
+    videos are entropy-decoded, 'interval' or 'sync' (cfn_hip.jpegdec.decode_checked); None leaves the choice to CFN_JPEG_ENTROPY"""
     dt = None if feat_dtype is None else featpack.feat_dtype(feat_dtype)
     if dt is None:
         for k in FEAT_KEYS:
@@ -53,7 +54,7 @@ def extract(net, videos, save_dir, device='cuda', crop=224, feat_dtype=None):
     n = 0
     for vid, clip in videos:
         if isinstance(clip, JpegClips):            # frames still JPEG: decoded on the device into the RawU8Clips batch (one status read-back)
-            clip = decode_checked(clip, device, [vid]).flatten_crops()
+            clip = decode_checked(clip, device, [vid], entropy=jpeg_entropy).flatten_crops()
         clip = clip.to(device)
         if isinstance(clip, RawU8Clips):
             clip = clip.transform(crop)
@@ -78,8 +79,10 @@ if __name__ == '__main__':
     ap.add_argument('--synthetic', type=int, default=2, help='number of synthetic videos to run')
     ap.add_argument('--feat-dtype', default=None, choices=['fp16', 'bf16'],
                     help='write one packed 16-bit record per video (<save-dir>/packed/<vid>.cff) instead of five fp32 files')
+    ap.add_argument('--jpeg-entropy', choices=('interval', 'sync'), default=None,
+                    help='entropy mode of the GPU JPEG decode: sync = parallel inside a frame without restart markers')
     a = ap.parse_args()
     os.environ.setdefault('CUDA_VISIBLE_DEVICES', a.gpu)
     g = torch.Generator().manual_seed(0)
     vids = (('synthetic_%03d' % i, torch.randn(1, 3, 64, 224, 224, generator=g)) for i in range(a.synthetic))
-    print('wrote', extract(build_tower('cuda', a.ckpt), vids, a.save_dir, feat_dtype=a.feat_dtype), 'videos to', a.save_dir)
+    print('wrote', extract(build_tower('cuda', a.ckpt), vids, a.save_dir, feat_dtype=a.feat_dtype, jpeg_entropy=a.jpeg_entropy), 'videos to', a.save_dir)

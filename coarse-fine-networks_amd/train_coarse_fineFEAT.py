@@ -178,13 +178,15 @@ def run(init_lr=INIT_LR, warmup_steps=0, max_epochs=200, mode='rgb', root=None, 
         batch_size=BS * BS_UPSCALE, frames=80 * 4, dataloaders=None, max_steps=None,
         save_model='models/coarse_fineFEAT_charades_', pretrained='models/x3d_multigrid_kinetics_fb_pretrained.pt',
         csv_path='localize_corr_v1.csv', log=print, phase_hook=None, input_norm=None, device_ap=False,
-        fused_loss=False):
+        fused_loss=False, jpeg_entropy=None):
     """input_norm: see build_model -- needed when the loaders collate uint8 frames (collate.coarse_collate_u8, or coarse_collate_raw_u8:
     untransformed frames + crop boxes, transformed on the GPU -- per training batch, and per chunk of a validation video).
     device_ap: the training phases keep their AP rows and loss totals on the GPU (cfn_hip.metrics.StepMetrics): no read-back per step.
     The loaders may collate packed 16-bit fine features (collate.coarse_collate_packed*: member 3 is a PackedFeats); nothing changes for dicts.
     fused_loss: the loss runs as one forward and one backward kernel (train_fine.detection_loss(fused=True)); False leaves the choice to
-    CFN_FUSED_LOSS."""
+    CFN_FUSED_LOSS.
+    jpeg_entropy: how JpegClips batches are entropy-decoded, 'interval' or 'sync' (cfn_hip.jpegdec.decode_checked); None leaves the choice to
+    CFN_JPEG_ENTROPY."""
     fused = True if fused_loss else None
     rank, world, dev = cdist.init_from_env()
     gamma_tau = 5
@@ -227,7 +229,7 @@ def run(init_lr=INIT_LR, warmup_steps=0, max_epochs=200, mode='rgb', root=None, 
                     if not (cdist.all_agree(ok, dev) if world > 1 else ok):
                         continue
                 b, n = inputs.shape[:2]            # n crops per video at validation time (:198-201)
-                inputs = flatten_clips(inputs, dev, CROP if train else None, names=name)      # validation: forward_video transforms chunk by chunk
+                inputs = flatten_clips(inputs, dev, CROP if train else None, names=name, jpeg_entropy=jpeg_entropy)      # validation: forward_video transforms chunk by chunk
                 labels, masks = materialize(labels, masks, dev)      # dense tensors: .to(dev); a SegLabels batch (segment labels): one kernel
                 feat_masks, meta = feat_masks.to(dev), meta.to(dev)
                 feat = unpack_feat(feat, dev)      # a PackedFeats batch (coarse_collate_packed): unpacked once per batch / validation video
@@ -292,6 +294,8 @@ if __name__ == '__main__':
     parser.add_argument('--batch-size', type=int, default=BS * BS_UPSCALE)
     parser.add_argument('--device-ap', action='store_true', help='training AP rows and loss totals stay on the GPU')
     parser.add_argument('--fused-loss', action='store_true', help='the detection loss as one forward and one backward HIP kernel')
+    parser.add_argument('--jpeg-entropy', choices=('interval', 'sync'), default=None,
+                        help='entropy mode of the GPU JPEG decode: sync = parallel inside a frame without restart markers')
     args = parser.parse_args()
     if 'RANK' not in os.environ and len(args.gpu.split(',')) > 1:
         from train_fine import _spawn
@@ -302,7 +306,7 @@ if __name__ == '__main__':
                                   '--master-addr', '127.0.0.1', '--master-port', os.environ.get('MASTER_PORT', '29512'),
                                   os.path.abspath(__file__), '--batch-size', str(args.batch_size)] +
                                  (['--max-steps', str(args.max_steps)] if args.max_steps else []) + (['--device-ap'] if args.device_ap else []) +
-                                 (['--fused-loss'] if args.fused_loss else []), env=env))
+                                 (['--fused-loss'] if args.fused_loss else []) + (['--jpeg-entropy', args.jpeg_entropy] if args.jpeg_entropy else []), env=env))
     if 'RANK' not in os.environ:
         os.environ['CUDA_VISIBLE_DEVICES'] = args.gpu
-    run(batch_size=args.batch_size, max_steps=args.max_steps, device_ap=args.device_ap, fused_loss=args.fused_loss)
+    run(batch_size=args.batch_size, max_steps=args.max_steps, device_ap=args.device_ap, fused_loss=args.fused_loss, jpeg_entropy=args.jpeg_entropy)

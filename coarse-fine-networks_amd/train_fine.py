@@ -144,14 +144,15 @@ def build_model(device, n_classes=NUM_CLASSES, pretrained=None, dropout=0.5, act
     return net.to(device)
 
 
-def flatten_clips(inputs, dev, crop=None, names=None):
+def flatten_clips(inputs, dev, crop=None, names=None, jpeg_entropy=None):
     """(b, n crops, ...) -> (b * n, ...) on `dev`: an fp32 clip tensor (b, n, 3, T, H, W), a U8Clips batch, or a RawU8Clips batch
     (frames as decoded + crop boxes, collate.fine_collate_raw_u8), which is cropped, resized to `crop` x `crop` and flipped on `dev`, on
     the current stream, into the U8Clips batch the net takes (crop=None: handed on as it is).  A JpegClips batch (frames still JPEG,
     collate.fine_collate_jpeg) is first decoded on `dev`, on the current stream, into that RawU8Clips batch; its status words are read
-    back once, and a frame that did not decode raises, naming the video (names: one per video of the batch)."""
+    back once, and a frame that did not decode raises, naming the video (names: one per video of the batch).  jpeg_entropy: the entropy
+    mode of that decode, 'interval' or 'sync' (cfn_hip.jpegdec.decode_checked; None leaves the choice to CFN_JPEG_ENTROPY)."""
     if isinstance(inputs, JpegClips):
-        inputs = decode_checked(inputs, dev, names)
+        inputs = decode_checked(inputs, dev, names, entropy=jpeg_entropy)
     if isinstance(inputs, RawU8Clips):
         raw = inputs.flatten_crops().to(dev, non_blocking=True)
         return raw if crop is None else raw.transform(crop)
@@ -274,13 +275,14 @@ _ap_rows = metrics.ap_rows      # per video: (scores (v,157), targets (v,157)) n
 def run(init_lr=INIT_LR, warmup_steps=0, max_epochs=200, mode='rgb', root=None, train_split=None,
         batch_size=BS * BS_UPSCALE, frames=80 * 4, dataloaders=None, max_steps=None, save_model='models/fine_charades_',
         pretrained='models/x3d_multigrid_kinetics_fb_pretrained.pt', log=print, phase_hook=None, input_norm=None,
-        device_ap=False, fused_loss=False):
+        device_ap=False, fused_loss=False, jpeg_entropy=None):
     """input_norm: see build_model -- needed when the loaders collate uint8 frames (collate.fine_collate_u8, or fine_collate_raw_u8:
     untransformed frames + crop boxes, cropped / resized to the model's crop size / flipped on the GPU in front of the step).
     device_ap: the training phases keep their AP rows and loss totals on the GPU (cfn_hip.metrics.StepMetrics, apmeter.DeviceAPMeter):
     no read-back per step, the host waits for the device only where a line is logged.
     fused_loss: the loss of every step and of validation runs as one forward and one backward kernel (detection_loss(fused=True)); False leaves
-    the choice to CFN_FUSED_LOSS."""
+    the choice to CFN_FUSED_LOSS.
+    jpeg_entropy: how JpegClips batches are entropy-decoded, 'interval' or 'sync' (flatten_clips); None leaves the choice to CFN_JPEG_ENTROPY."""
     fused = True if fused_loss else None
     rank, world, dev = cdist.init_from_env()
     gamma_tau = {'S': 6, 'M': 5, 'XL': 5}[X3D_VERSION]
@@ -324,7 +326,7 @@ def run(init_lr=INIT_LR, warmup_steps=0, max_epochs=200, mode='rgb', root=None, 
                 if not ok:
                     continue
                 b, n = inputs.shape[:2]          # n crops per video (1 in training, train_fine.py:176-185)
-                inputs = flatten_clips(inputs, dev, crop, names=_name)
+                inputs = flatten_clips(inputs, dev, crop, names=_name, jpeg_entropy=jpeg_entropy)
                 labels, masks = materialize(labels, masks, dev)      # dense tensors: .to(dev); a SegLabels batch (segment labels): one kernel
                 valid_t = masks.sum(1).int()
                 n_it += 1
@@ -390,11 +392,13 @@ if __name__ == '__main__':
     parser.add_argument('--batch-size', type=int, default=BS * BS_UPSCALE)
     parser.add_argument('--device-ap', action='store_true', help='training AP rows and loss totals stay on the GPU')
     parser.add_argument('--fused-loss', action='store_true', help='the detection loss as one forward and one backward HIP kernel')
+    parser.add_argument('--jpeg-entropy', choices=('interval', 'sync'), default=None,
+                        help='entropy mode of the GPU JPEG decode: sync = parallel inside a frame without restart markers')
     args = parser.parse_args()
     if 'RANK' not in os.environ and len(args.gpu.split(',')) > 1:
         sys.exit(_spawn(args.gpu, ['--batch-size', str(args.batch_size)] +
                         (['--max-steps', str(args.max_steps)] if args.max_steps else []) + (['--device-ap'] if args.device_ap else []) +
-                        (['--fused-loss'] if args.fused_loss else [])))
+                        (['--fused-loss'] if args.fused_loss else []) + (['--jpeg-entropy', args.jpeg_entropy] if args.jpeg_entropy else [])))
     if 'RANK' not in os.environ:
         os.environ['CUDA_VISIBLE_DEVICES'] = args.gpu
-    run(batch_size=args.batch_size, max_steps=args.max_steps, device_ap=args.device_ap, fused_loss=args.fused_loss)
+    run(batch_size=args.batch_size, max_steps=args.max_steps, device_ap=args.device_ap, fused_loss=args.fused_loss, jpeg_entropy=args.jpeg_entropy)

@@ -126,14 +126,16 @@ def train_step(fine, coarse, reducer, optimizer, clip, labels, masks, pre_step=N
 
 def run(init_lr=INIT_LR, warmup_steps=0, max_steps=None, batch_size=BS, fine_frames=128, coarse_frames=64, dataloader=None,
         pretrained_fine=None, pretrained_coarse=None, save_model='models/joint_charades_', log=print, fine_act_dtype=None, coarse_act_dtype=None,
-        input_norm=None, crop=tc.CROP, device_ap=False, fused_loss=False):
+        input_norm=None, crop=tc.CROP, device_ap=False, fused_loss=False, jpeg_entropy=None):
     """input_norm: see build_models -- needed when the loader yields the clip as uint8 frames: U8Clips, or RawU8Clips (untransformed
     frames + crop boxes), which is cropped / resized to `crop` / flipped on the GPU in front of the step.
     device_ap: this loop reads its losses back only where it logs and keeps no AP meter; with device_ap the training rows of every step
     go to a device-resident meter as well (cfn_hip.metrics.StepMetrics, no read-back per step) and the logged lines carry the mAP of
     the steps since the last one.
     fused_loss: the loss runs as one forward and one backward kernel (train_fine.detection_loss(fused=True)); False leaves the choice to
-    CFN_FUSED_LOSS."""
+    CFN_FUSED_LOSS.
+    jpeg_entropy: how JpegClips batches are entropy-decoded, 'interval' or 'sync' (cfn_hip.jpegdec.decode_checked); None leaves the choice to
+    CFN_JPEG_ENTROPY."""
     fused = True if fused_loss else None
     rank, world, dev = cdist.init_from_env()
     local_bs = max(batch_size // world, 1)
@@ -157,7 +159,7 @@ def run(init_lr=INIT_LR, warmup_steps=0, max_steps=None, batch_size=BS, fine_fra
             continue
         warm = (lambda: lr_warmup(init_lr, steps, warmup_steps, optimizer))
         if isinstance(clip, JpegClips):            # frames still JPEG (collate_jpeg): decoded on the device, one status read-back per batch
-            clip = decode_checked(clip, dev).flatten_crops()
+            clip = decode_checked(clip, dev, entropy=jpeg_entropy).flatten_crops()
         clip = clip.to(dev)
         if isinstance(clip, tc.RawU8Clips):
             clip = clip.transform(crop)
@@ -189,6 +191,8 @@ if __name__ == '__main__':
     parser.add_argument('--batch-size', type=int, default=BS)
     parser.add_argument('--device-ap', action='store_true', help='training AP rows on the GPU, mAP in the logged lines')
     parser.add_argument('--fused-loss', action='store_true', help='the detection loss as one forward and one backward HIP kernel')
+    parser.add_argument('--jpeg-entropy', choices=('interval', 'sync'), default=None,
+                        help='entropy mode of the GPU JPEG decode: sync = parallel inside a frame without restart markers')
     args = parser.parse_args()
     if 'RANK' not in os.environ and len(args.gpu.split(',')) > 1:
         import subprocess
@@ -198,7 +202,7 @@ if __name__ == '__main__':
                                   '--master-addr', '127.0.0.1', '--master-port', os.environ.get('MASTER_PORT', '29513'),
                                   os.path.abspath(__file__), '--batch-size', str(args.batch_size)] +
                                  (['--max-steps', str(args.max_steps)] if args.max_steps else []) + (['--device-ap'] if args.device_ap else []) +
-                                 (['--fused-loss'] if args.fused_loss else []), env=env))
+                                 (['--fused-loss'] if args.fused_loss else []) + (['--jpeg-entropy', args.jpeg_entropy] if args.jpeg_entropy else []), env=env))
     if 'RANK' not in os.environ:
         os.environ['CUDA_VISIBLE_DEVICES'] = args.gpu
-    run(batch_size=args.batch_size, max_steps=args.max_steps, device_ap=args.device_ap, fused_loss=args.fused_loss)
+    run(batch_size=args.batch_size, max_steps=args.max_steps, device_ap=args.device_ap, fused_loss=args.fused_loss, jpeg_entropy=args.jpeg_entropy)

@@ -532,6 +532,25 @@ int cfn_jpeg_decode_u8(const unsigned char* data, const int* frames, const int* 
                        int Tmax, int Hmax, int Wmax, int lanes, int blocks_max, void* stream);
 
 /* =====================================================================================================================
+ * cfn_jpeg_decode_u8 with the SYNC entropy mode (csrc/jpegdec.hip jpeg_entropy_sync_kernel; stated on the CPU by
+ * cfn_hip/jpegdec.py decode_coefficients_sync): the same replacement of the reference's per-frame host decode,
+ * Image.open(f).convert('RGB') in pil_loader / video_loader of charades_fine.py and charades_coarse_fineFEAT.py, bit for bit, for
+ * data sets whose frames carry no restart markers (Charades_v1_rgb), where one lane per restart interval means one lane per frame.
+ * Huffman-coded data self-synchronises (Weissenberger & Schmidt, "Accelerating JPEG Decompression on GPUs"): a frame with restart
+ * interval 0, more than `sub_bytes` bytes and at most `max_subs` subsequences of `sub_bytes` raw bytes is decoded by one workgroup,
+ * one lane per subsequence: speculative decodes in rounds until no exit state changes (at most as many rounds as subsequences,
+ * which always reaches the true states), a scan of block counts and DC sums, one write pass.  Every other frame of the batch
+ * (restart markers, short, too many subsequences) is decoded one lane per restart interval by the same call.  Arguments, output,
+ * status bits, workspace (cfn_jpeg_workspace_bytes: it does not grow, the per-subsequence records live in 32 * max_subs bytes of
+ * LDS) and checks are those of cfn_jpeg_decode_u8; only the write pass sets status bits.  sub_bytes: a multiple of 4 in
+ * [16, 1024], so that a symbol and its value (<= 31 bits, stuffing included) end inside the next subsequence; max_subs in
+ * [1, 1536]; anything else returns 1 naming the argument.  3 memsets + 5 launches on `stream`.
+ * ===================================================================================================================== */
+int cfn_jpeg_decode_u8_sync(const unsigned char* data, const int* frames, const int* tables, const int* geom, const int* lengths,
+                            unsigned char* out, int* status, void* ws, long ws_bytes, long data_bytes, int rows, int sets, int N,
+                            int Tmax, int Hmax, int Wmax, int lanes, int blocks_max, int sub_bytes, int max_subs, void* stream);
+
+/* =====================================================================================================================
  * Frame labels from annotation segments (csrc/seglabels.hip; the sample record and the batch type: cfn_hip/seglabels.py).
  * Replaces, on the GPU, the dense label array the reference builds per video in make_dataset (charades_fine.py:110-117,
  * the same loop in charades_coarse_fineFEAT.py:115-122), slices per sample in Charades.__getitem__ (charades_fine.py:149-165,

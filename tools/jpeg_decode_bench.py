@@ -11,10 +11,16 @@ then walk their bit streams in step, which real frames would not -- the JSON say
                    RawU8Clips batch (crop/resize/flip + step), alternating in one process; 180 x 320 only
   4. host          (--host-only, needs PIL) PIL's Image.open().convert('RGB') per frame on one core of the machine it runs on
 
+  5. entropy modes (--entropy sync --sub-bytes 64,128,256) legs 1 and 3 with the sync entropy mode (one workgroup per frame, one lane per
+                   subsequence) beside the lane-per-interval mode, alternating in the same run: decode and per-kernel times per
+                   subsequence size, the rounds decode_coefficients_sync needs for the stored frame, and the train step fed the
+                   resident JpegClips batch in both modes (the sync leg at jpegdec.SYNC_SUB_BYTES) against the RawU8Clips batch
+
 No pass bar; the JSON is the record.  One JSON document on stdout and in --out.
 
     python tools/jpeg_decode_bench.py --host-only --out profiles/jpeg_decode_host.json        # any machine with PIL
     python tools/jpeg_decode_bench.py --host-leg profiles/jpeg_decode_host.json --out profiles/jpeg_decode.json
+    python tools/jpeg_decode_bench.py --entropy sync --sub-bytes 64,128,256 --out profiles/jpeg_decode_sync.json
 """
 import argparse
 import io
@@ -122,6 +128,43 @@ def decode_leg(jc, dev, iters):
             'kernel_ms': per_kernel_ms(run, 3)}
 
 
+def modes_leg(jc, jpg, dev, iters, subs, max_subs=None):
+    """leg 1 for the lane-per-interval mode and the sync mode at every size of `subs`, alternating; the outputs are compared byte for byte"""
+    from cfn_hip import ops
+    d = jc.to(dev)
+    N, T, H, W = d.lengths.numel(), d.dims[0], d.dims[1], d.dims[2]
+    out = torch.empty(N, T, H, W, 3, dtype=torch.uint8, device=dev)
+    status = torch.empty(d.frames.shape[0], dtype=torch.int32, device=dev)
+    ws = torch.empty(ops.jpeg_workspace_bytes(d.frames.shape[0], N * T, d.dims[3], d.dims[4]), dtype=torch.uint8, device=dev)
+    runs = {'interval': lambda: ops.jpeg_decode_u8(d, out=out, status=status, workspace=ws)}
+    for sb in subs:
+        runs['sync_%d' % sb] = (lambda sb=sb: ops.jpeg_decode_u8(d, out=out, status=status, workspace=ws, entropy='sync', sub_bytes=sb, max_subs=max_subs))
+    want = None
+    for name, run in runs.items():
+        out.fill_(0xA5)
+        run()
+        assert not status.cpu().any(), 'the bench frames did not decode (%s)' % name
+        want = out.clone() if want is None else want
+        assert torch.equal(out, want), 'the %s mode decodes other bytes than the interval mode' % name
+    del want
+    raw = {k: [] for k in runs}
+    for _ in range(3):                                 # alternating: every repeat visits every mode
+        for name, run in runs.items():
+            raw[name].append(event_ms(run, iters))
+    res = {'frames': d.frames.shape[0], 'encoded_bytes_per_frame_segment': int(d.frames[0, jpegdec.F_BYTES]),
+           'max_subs': max_subs or jpegdec.SYNC_DEFAULT_MAX_SUBS, 'modes': {}}
+    for name, run in runs.items():
+        ms = statistics.median(raw[name])
+        m = {'decode_ms': round(ms, 4), 'decode_ms_min_max': [round(min(raw[name]), 4), round(max(raw[name]), 4)], 'kernel_ms': per_kernel_ms(run, 3)}
+        if name != 'interval':
+            st = {}
+            jpegdec.decode_coefficients_sync(jpg, int(name.split('_')[1]), stats=st)
+            m['subsequences'], m['rounds'] = st['subsequences'], st['rounds']
+            m['taken_by_sync'] = st['subsequences'] <= (max_subs or jpegdec.SYNC_DEFAULT_MAX_SUBS)          # otherwise: one lane per frame, as 'interval'
+        res['modes'][name] = m
+    return res
+
+
 def train_leg(jc, dev, a):
     import torch.optim as optim
     import train_fine
@@ -137,22 +180,26 @@ def train_leg(jc, dev, a):
     masks = torch.ones(B, T * 10, device=dev)
     dj = jc.to(dev)
     legs = {'resident_jpeg': dj, 'resident_raw_u8': dj.decode()}
+    modes = {'resident_jpeg': 'interval', 'resident_raw_u8': None}
+    if a.entropy == 'sync':
+        legs = {'resident_jpeg': dj, 'resident_jpeg_sync': dj, 'resident_raw_u8': legs['resident_raw_u8']}
+        modes['resident_jpeg_sync'] = 'sync'
     torch.cuda.synchronize()
 
-    def timed(batch):
+    def timed(batch, mode):
         t0 = None
         for i in range(a.warmup + a.steps):
             if i == a.warmup:
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
-            x = train_fine.flatten_clips(batch, dev, 224)          # a JpegClips batch: decode (+ one status read-back), then as RawU8Clips
+            x = train_fine.flatten_clips(batch, dev, 224, jpeg_entropy=mode)          # a JpegClips batch: decode (+ one status read-back), then as RawU8Clips
             train_fine.train_step(net, reducer, optimizer, x, labels, masks)
         torch.cuda.synchronize()
         return (time.perf_counter() - t0) / a.steps * 1e3
     raw = {k: [] for k in legs}
     for _ in range(a.repeats):                         # alternating: every repeat visits both legs
         for name, batch in legs.items():
-            raw[name].append(timed(batch))
+            raw[name].append(timed(batch, modes[name]))
             print('%s: %.3f ms/step' % (name, raw[name][-1]), file=sys.stderr, flush=True)
     return {k: {'ms_per_step': round(statistics.median(v), 3), 'min': round(min(v), 3), 'max': round(max(v), 3)} for k, v in raw.items()}
 
@@ -184,6 +231,9 @@ def main():
     ap.add_argument('--no-step', action='store_true')
     ap.add_argument('--host-only', action='store_true', help="PIL's decode time alone (needs PIL, no GPU)")
     ap.add_argument('--host-leg', default=None, help='a JSON written with --host-only, embedded as measured on that machine')
+    ap.add_argument('--entropy', default='interval', choices=('interval', 'sync'), help='sync: leg 5, both entropy modes side by side')
+    ap.add_argument('--sub-bytes', default='64,128,256', help='the subsequence sizes of the sync legs')
+    ap.add_argument('--max-subs', type=int, default=None, help='most subsequences of a frame in the sync legs (default: the library\'s)')
     ap.add_argument('--out', default=None)
     a = ap.parse_args()
     frames = frames_npz()
@@ -199,6 +249,16 @@ def main():
                'device': cfn_hip.device_info(), 'sizes': {}}
         for k in SIZES:
             jc = replicated(frames[k], a.clips, a.frames)
+            if a.entropy == 'sync':
+                res = {'encoded_bytes_per_frame': len(frames[k]), 'decode': modes_leg(jc, frames[k], dev, a.iters, [int(v) for v in a.sub_bytes.split(',')], a.max_subs)}
+                if k == SIZES[0] and not a.no_step:
+                    res['train_step'] = train_leg(jc, dev, a)
+                    res['train_step_sync_sub_bytes'] = jpegdec.SYNC_SUB_BYTES
+                out['sizes'][k] = res
+                print('%s done' % k, file=sys.stderr, flush=True)
+                del jc
+                torch.cuda.empty_cache()
+                continue
             res = {'encoded_bytes_per_frame': len(frames[k]), 'decode': decode_leg(jc, dev, a.iters)}
             raw_bytes = a.clips * a.frames * jc.dims[1] * jc.dims[2] * 3 + a.clips * 4 + a.clips * 16
             res['host_bytes_per_step'] = {'jpeg_clips': nbytes(jc), 'raw_u8_clips': raw_bytes, 'ratio': round(raw_bytes / nbytes(jc), 1)}

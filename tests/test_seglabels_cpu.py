@@ -231,6 +231,5 @@ def test_ops_and_operator_have_no_cpu_path():
     lab, mask, valid = torch.ops.cfn.seg_labels(m(9, 3, dt=torch.float64), m(4, dt=torch.int32), m(3, dt=torch.float64), m(3, 2, dt=torch.int32), 33, 17)
     assert (tuple(lab.shape), lab.dtype, tuple(mask.shape), mask.dtype, tuple(valid.shape), valid.dtype) == (
         (3, 33, 17), torch.float32, (3, 17), torch.float32, (3,), torch.int32)
-    if tl.NATIVE:
-        with pytest.raises(RuntimeError):
-            torch.ops.cfn.seg_labels(sl.seg, sl.offsets, sl.fps, sl.window, 157, sl.t_max)
+    with pytest.raises(RuntimeError):
+        torch.ops.cfn.seg_labels(sl.seg, sl.offsets, sl.fps, sl.window, 157, sl.t_max)

@@ -246,34 +246,90 @@ def test_bottleneck_on_torch_ops_compiles_without_graph_breaks(train, monkeypatc
 
 
 # ---- native registration: TORCH_LIBRARY inside a shared library (csrc/torch/cfn_torch.cpp -> cfn_hip/libcfn_torch.so) -------------
-NATIVE_OPS = ('dwconv3d', 'dwconv3d_backward', 'pwconv', 'pwconv_backward', 'time_sample', 'time_sample_backward')
+def _native_names(tl):
+    """(forward names of the eight tuples, the `_backward` twins of OPERATORS)"""
+    fwd = (tl.OPERATORS + tl.INPUT_OPERATORS + tl.AUGMENT_OPERATORS + tl.METRIC_OPERATORS + tl.FEATURE_OPERATORS + tl.DECODE_OPERATORS
+           + tl.DECODE_SYNC_OPERATORS + tl.LABEL_OPERATORS)
+    return fwd, tuple(n + '_backward' for n in tl.OPERATORS)
 
 
 def test_native_library_defines_the_hot_path_operators():
-    """the library exists, loads next to libcfn_hip.so, and the six operators carry a native kernel under the CUDA (= HIP) dispatch key whose
-    schema is the one the Python definitions declare; everything else of the operator set is still registered (from Python)"""
+    """the library exists, loads next to libcfn_hip.so, and every operator of the set (the eight tuples and the backward twins of OPERATORS)
+    carries a native kernel under the CUDA (= HIP) dispatch key -- clip_lut, which takes no tensor, under CompositeImplicitAutograd -- and a
+    _NativeOp handle in cfn_hip.torchlib; the schema is the one the library declares"""
     import os
     from cfn_hip import torchlib
     assert os.path.exists(torchlib.NATIVE_LIB), 'run python __graft_entry__.py (build_torch_library)'
-    if os.environ.get('CFN_NATIVE_OPS', '1') == '0':
-        pytest.skip('native operators switched off')
-    assert torchlib.NATIVE
-    for name in NATIVE_OPS:
-        assert torch._C._dispatch_has_kernel_for_dispatch_key('cfn::' + name, 'CUDA'), name
-        assert isinstance(getattr(torchlib, name), torchlib._NativeOp), name          # not a Python custom_op
+    fwd, bwd = _native_names(torchlib)
+    assert len(fwd + bwd) == len(set(fwd + bwd)) == 47
+    for name in fwd + bwd:
+        key = 'CompositeImplicitAutograd' if name == 'clip_lut' else 'CUDA'
+        assert torch._C._dispatch_has_kernel_for_dispatch_key('cfn::' + name, key), name
+        assert isinstance(getattr(torchlib, name), torchlib._NativeOp), name          # a handle of the native operator
+    assert not torch._C._dispatch_has_kernel_for_dispatch_key('cfn::clip_lut', 'CUDA')
     assert str(torch.ops.cfn.pwconv_backward.default._schema) == (
         'cfn::pwconv_backward(Tensor gy, Tensor gs, Tensor gq, Tensor x, Tensor w, Tensor y, Tensor? A=None, Tensor? B=None, SymInt act=0, '
         'SymInt stride=1) -> (Tensor, Tensor, Tensor, Tensor)')
     assert hasattr(torch.ops.cfn, 'bn_add_relu') and hasattr(torch.ops.cfn, 'fusion_gather')
 
 
+def test_registration_is_complete():
+    """the dispatcher holds exactly the operator set, each with what cfn_hip.torchlib has to attach: a fake (Meta) implementation for every
+    operator that takes a tensor, an autograd formula for exactly OPERATORS"""
+    from cfn_hip import torchlib
+    fwd, bwd = _native_names(torchlib)
+    names = {n for n in torch._C._dispatch_get_all_op_names() if n.startswith('cfn::')}
+    assert names == {'cfn::' + n for n in fwd + bwd}
+    assert len(names) == 47
+    has = torch._C._dispatch_has_kernel_for_dispatch_key
+    for n in sorted(names - {'cfn::clip_lut'}):
+        assert has(n, 'Meta'), n
+    assert {n for n in names if has(n, 'Autograd')} == {'cfn::' + n for n in torchlib.OPERATORS}
+
+
+def _import_torchlib(env_lib=None):
+    import os
+    import subprocess
+    import sys
+    from cfn_hip import torchlib
+    env = {k: v for k, v in os.environ.items() if k != 'CFN_HIP_LIB'}
+    if env_lib is not None:
+        env['CFN_HIP_LIB'] = env_lib
+    pkg = os.path.dirname(os.path.dirname(os.path.abspath(torchlib.__file__)))
+    code = 'import sys; sys.path.insert(0, %r); import cfn_hip.torchlib, torch; assert hasattr(torch.ops.cfn, "pwconv")' % pkg
+    return subprocess.run([sys.executable] + (['-s'] if sys.flags.no_user_site else []) + ['-c', code], env=env, capture_output=True, text=True)
+
+
+def test_import_refuses_a_variant_kernel_library(tmp_path):
+    """libcfn_torch.so is linked against the in-tree libcfn_hip.so: with CFN_HIP_LIB naming another file the two routes would run two
+    libraries in one process, so the import raises (in a fresh process: CFN_HIP_LIB is read at import); the in-tree path itself is fine"""
+    import os
+    import shutil
+    from cfn_hip import torchlib
+    default = os.path.join(os.path.dirname(torchlib.NATIVE_LIB), 'libcfn_hip.so')
+    variant = str(tmp_path / 'libcfn_hip_variant.so')
+    shutil.copy(default, variant)
+    r = _import_torchlib(variant)
+    assert r.returncode != 0 and 'RuntimeError' in r.stderr and 'CFN_HIP_LIB' in r.stderr, r.stderr
+    assert 'linked against the default' in r.stderr
+    r = _import_torchlib(default)
+    assert r.returncode == 0, r.stderr
+
+
+def test_missing_operator_library_is_an_error(tmp_path):
+    """no Python fallback: a missing libcfn_torch.so raises with the build instruction, as cfn_hip.load() does for libcfn_hip.so"""
+    from cfn_hip import torchlib
+    torchlib._require_library(torchlib.NATIVE_LIB)
+    with pytest.raises(RuntimeError, match=r'__graft_entry__\.py.*no Python fallback'):
+        torchlib._require_library(str(tmp_path / 'libcfn_torch.so'))
+
+
 @pytest.mark.gpu
 def test_native_operators_equal_the_ctypes_route_bit_for_bit():
     """the native operators and cfn_hip.ops (ctypes) call the same C-ABI entry points on the same stream: identical bits, forward and backward,
     fp32 and bf16 / fp16 depthwise; errors of the C ABI surface as RuntimeError"""
-    from cfn_hip import ops, torchlib
-    if not torchlib.NATIVE:
-        pytest.skip('native operators switched off')
+    from cfn_hip import ops
+    import cfn_hip.torchlib  # noqa: F401
     for dt in (torch.float32, torch.bfloat16, torch.float16):
         x = rnd(1, 2, 6, 5, 14, 14).to(DEV).to(dt).requires_grad_(True)
         w = (0.3 * rnd(2, 6, 1, 3, 3, 3)).to(DEV).requires_grad_(True)

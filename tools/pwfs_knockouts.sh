@@ -9,5 +9,5 @@ if [ "$1" = build ]; then exec bash $R/tools/variant_lib.sh knockouts pwfuseds.h
 [ -f $KO ] || { echo "$KO is missing: run  tools/pwfs_knockouts.sh build  first" >&2; exit 1; }
 for d in 0 1 2 3 4 8 7 15; do
   echo "## CFN_PWFS_DBG=$d"
-  CFN_HIP_LIB=$KO CFN_NATIVE_OPS=0 CFN_PWF_SPLIT=2 CFN_PWFS_DBG=$d python $R/tools/pwfs_bench.py 2>&1 | grep "fused" | sed 's/separate [0-9.]* ms *//'
+  CFN_HIP_LIB=$KO CFN_PWF_SPLIT=2 CFN_PWFS_DBG=$d python $R/tools/pwfs_bench.py 2>&1 | grep "fused" | sed 's/separate [0-9.]* ms *//'
 done

@@ -41,7 +41,7 @@ python $R/tools/salb_bench.py 2>&1 | grep -v "$FILT" > $O/salb_bench.txt
 # the one-pass split-bf16 pointwise backward of layer 2 (csrc/pwfuseds.hip): same-process A/B against the separate kernels, knock-out table, bit-repeat stress
 # (the knock-outs need the -DCFN_PWFS_KNOCKOUTS variant of the library: build it with  tools/pwfs_knockouts.sh build  before this script runs)
 KO=$R/coarse-fine-networks_amd/cfn_hip/variants/libcfn_hip_knockouts.so
-{ CFN_PWF_SPLIT=2 python $R/tools/pwfs_bench.py; L3=1 python $R/tools/pwfs_bench.py; echo '## layer-3 variant, knock-outs (CFN_PWFS_DBG: 1 weight gradient, 2 data gradient, 8 stores)'; for d in 1 2 3 11; do echo -n "dbg=$d  "; L3=1 CFN_HIP_LIB=$KO CFN_NATIVE_OPS=0 CFN_PWFS_DBG=$d python $R/tools/pwfs_bench.py | grep fused; done; } 2>&1 | grep -v "$FILT" > $O/pwfs_bench.txt
+{ CFN_PWF_SPLIT=2 python $R/tools/pwfs_bench.py; L3=1 python $R/tools/pwfs_bench.py; echo '## layer-3 variant, knock-outs (CFN_PWFS_DBG: 1 weight gradient, 2 data gradient, 8 stores)'; for d in 1 2 3 11; do echo -n "dbg=$d  "; L3=1 CFN_HIP_LIB=$KO CFN_PWFS_DBG=$d python $R/tools/pwfs_bench.py | grep fused; done; } 2>&1 | grep -v "$FILT" > $O/pwfs_bench.txt
 bash $R/tools/pwfs_knockouts.sh 2>&1 | grep -v "$FILT" > $O/pwfs_knockouts.txt
 RUNS=200 python $R/tools/pwfs_stress.py 2>&1 | grep -v "$FILT" > $O/pwfs_stress.txt
 { for i in 1 2; do for v in 0 1 2; do echo -n "CFN_PWF_SPLIT=$v  "; CFN_PWF_SPLIT=$v python $R/bench.py --full --no-cpu-baseline --no-coarse-roofline 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['ms_per_step'], 'ms/step', d['value'], 'clips/s  figure A', d['roofline']['frac'])"; done; done; } > $O/pwfs_step_ab.txt

@@ -2,7 +2,7 @@
 # Where the split-bf16 saliency forward (csrc/salconvb.hip) spends its time: the same launch with parts switched off (wrong results, timing only).
 #   for v in 1 2 6 8 15; do tools/variant_lib.sh salko$v salconvb.hip "-DSALB_KO=$v"; done; tools/salb_knockouts.sh
 cd "$(dirname "$0")/.."
-run() { CFN_NATIVE_OPS=0 CFN_HIP_LIB=$2 python - <<PY
+run() { CFN_HIP_LIB=$2 python - <<PY
 import sys, torch
 sys.path.insert(0, 'coarse-fine-networks_amd')
 import cfn_hip

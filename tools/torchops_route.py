@@ -52,7 +52,7 @@ if __name__ == '__main__':
     ap.add_argument('--steps', type=int, default=5)
     a = ap.parse_args()
     import cfn_hip.torchlib as tl
-    print('# x3d_fine X3D-M train step, %d x 3 x %d x 224 x 224, fp32; native operator library: %s' % (a.batch, a.frames, tl.NATIVE))
+    print('# x3d_fine X3D-M train step, %d x 3 x %d x 224 x 224, fp32; operator library: %s' % (a.batch, a.frames, os.path.relpath(tl.NATIVE_LIB, ROOT)))
     for route in ('ctypes', 'dispatcher', 'ctypes', 'dispatcher'):
         ms, gb, l0, l1 = run(route, a.batch, a.frames, a.steps)
         print('%-10s %8.2f ms/step   peak %6.1f GiB   first loss (cls, loc) %s   last %s' % (route, ms, gb, ['%.5f' % v for v in l0], ['%.5f' % v for v in l1]), flush=True)

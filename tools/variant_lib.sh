@@ -1,7 +1,7 @@
 #!/bin/bash
 # Build a variant of libcfn_hip.so with ONE source recompiled under extra flags (same-box A/B of kernel experiments):
 #   tools/variant_lib.sh NAME SOURCE.hip "-DFOO=1 ..."   ->  coarse-fine-networks_amd/cfn_hip/variants/libcfn_hip_NAME.so
-# (git-ignored; select it with CFN_HIP_LIB=... (beside CFN_NATIVE_OPS=0 where the torch operator library is in play))
+# (git-ignored; select it with CFN_HIP_LIB=...: the cfn_hip.ops route only -- `import cfn_hip.torchlib` refuses a variant)
 set -e
 R=$(cd "$(dirname "$0")/.." && pwd)
 P=$R/coarse-fine-networks_amd

@@ -15,7 +15,7 @@ from torch.autograd.function import once_differentiable
 import ctypes
 import threading
 
-from . import call, call_try, check, query, ACT_NONE, ACT_RELU, ACT_SWISH, ACT_SIGMOID  # noqa: F401
+from . import call, call_try, check, query, last_error, ACT_NONE, ACT_RELU, ACT_SWISH, ACT_SIGMOID  # noqa: F401
 
 
 _scratch_epoch = [0]
@@ -439,6 +439,14 @@ def pwconv(x, w, A=None, B=None, act=ACT_NONE, stride=1, stats=True, token=None,
             s, q = (sc, qc) if s is None else (s + sc, q + qc)
         t0 = t1
     return y, s, q
+
+
+def pwconv_route(op, N, Cin, Cout, T, H, W, stride=1, act=ACT_NONE, flags=0):
+    """the kernel a pointwise conv of this shape runs on (cfn_pwconv_route, include/cfn_hip.h): host only, no GPU needed"""
+    out = ctypes.create_string_buffer(256)
+    if query('cfn_pwconv_route', op, N, Cin, Cout, T, H, W, stride, act, flags, out, 256):
+        raise RuntimeError(last_error())
+    return out.value.decode()
 
 
 def _sfx(t):

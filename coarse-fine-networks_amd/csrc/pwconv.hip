@@ -523,12 +523,7 @@ __global__ __launch_bounds__(256) void pw_wgrad_kernel(const WgArgs a) {
 // ---------------------------------------------------------------------------------------------
 template <int MODE, bool STATS, int ACT, bool STEM>
 static int pw_launch_mt(const PwArgs& a, int MT, unsigned blocks, size_t lds, hipStream_t st) {
-#define CFN_PW_GO(MTV)                                                                                         \
-    do {                                                                                                       \
-        auto k = pw_gemm_kernel<MTV, MODE, STATS, ACT, STEM>;                                                  \
-        if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        hipLaunchKernelGGL(k, dim3(blocks), dim3(256), lds, st, a);                                            \
-    } while (0)
+#define CFN_PW_GO(MTV) cfn_launch(pw_gemm_kernel<MTV, MODE, STATS, ACT, STEM>, blocks, 256, lds, st, a)
     switch (MT) {
         case 1: CFN_PW_GO(1); break;
         case 2: CFN_PW_GO(2); break;
@@ -540,15 +535,16 @@ static int pw_launch_mt(const PwArgs& a, int MT, unsigned blocks, size_t lds, hi
 }
 
 template <int MODE, bool STATS>
-static int pw_launch(const PwArgs& a, int MT, unsigned blocks, size_t lds, hipStream_t st) {
-    switch (a.act) {
+static int pw_launch(const PwArgs& a, int act, int MT, unsigned blocks, size_t lds, hipStream_t st) {
+    switch (act) {
         case CFN_ACT_RELU: return pw_launch_mt<MODE, STATS, CFN_ACT_RELU, false>(a, MT, blocks, lds, st);
         case CFN_ACT_SWISH: return pw_launch_mt<MODE, STATS, CFN_ACT_SWISH, false>(a, MT, blocks, lds, st);
         default: return pw_launch_mt<MODE, STATS, CFN_ACT_NONE, false>(a, MT, blocks, lds, st);
     }
 }
 
-static int pw_plan(PwArgs& a, int& MT, unsigned& blocks, size_t& lds) {
+// false: a sample's tensor is beyond the 2 GiB buffer-descriptor range (pw_too_large reports it)
+static bool pw_plan(PwArgs& a, int& MT, unsigned& blocks, size_t& lds) {
     a.Kpad = (a.K + PW_UNIT - 1) / PW_UNIT * PW_UNIT;
     a.kres = a.Kpad <= PW_KRES_MAX ? a.Kpad : PW_KRES_MAX;
     const int M32 = cfn_cdiv(a.M, 32);
@@ -574,11 +570,31 @@ static int pw_plan(PwArgs& a, int& MT, unsigned& blocks, size_t& lds) {
     a.nstrips = cfn_cdiv(tiles, tpb);
     blocks = (unsigned)((long)a.N * a.nstrips * a.mtiles);
     lds = ((size_t)a.kres * BM + 4 * (a.Kpad + PW_UNIT) + 2 * BM + 2 * BM + 4 * 32 * PW_RED_PITCH + (a.stem ? 2 * (a.Kpad + PW_UNIT) : 0)) * sizeof(float);
+    return !((!a.stem && ((long)a.K * a.Pin * 4 >= (1L << 31) || (long)a.K * a.Q * 4 >= (1L << 31))) ||
+             (long)a.M * a.Pin * 4 >= (1L << 31) || (long)a.M * a.Q * 4 >= (1L << 31));
+}
+
+static int pw_too_large(const PwArgs& a) {
     const long span = (long)a.K * (a.stem ? 1 : (a.src2 || a.gs || a.gq || a.ex ? a.Q : a.Pin)) * 4;
-    if ((!a.stem && ((long)a.K * a.Pin * 4 >= (1L << 31) || (long)a.K * a.Q * 4 >= (1L << 31))) ||
-        (long)a.M * a.Pin * 4 >= (1L << 31) || (long)a.M * a.Q * 4 >= (1L << 31))
-        return cfn_fail(CFN_ERR_UNSUPPORTED, "pwconv: one sample's K x positions x 4 B = %ld exceeds the 2 GiB buffer-descriptor range", span);
-    return CFN_OK;
+    return cfn_fail(CFN_ERR_UNSUPPORTED, "pwconv: one sample's K x positions x 4 B = %ld exceeds the 2 GiB buffer-descriptor range", span);
+}
+
+bool pw_gemm_plan(const PwArgs& a, int mode, bool stats, const PwSwitches&, PwPlan& p) {
+    p.a = a;
+    size_t lds;
+    if (!pw_plan(p.a, p.MT, p.blocks, lds)) return false;
+    if (mode == PW_DGRAD && !stats) p.a.act = CFN_ACT_NONE;
+    p.family = PW_FAM_GEMM; p.mode = mode; p.stats = stats; p.two = a.src2 != nullptr;
+    p.act = p.a.act == CFN_ACT_RELU || p.a.act == CFN_ACT_SWISH ? p.a.act : CFN_ACT_NONE;
+    p.threads = 256; p.lds = lds;
+    return true;
+}
+
+int pw_gemm_launch(const PwPlan& p, hipStream_t st) {
+    if (p.mode == PW_FWD)
+        return p.stats ? pw_launch<PW_FWD, true>(p.a, p.act, p.MT, p.blocks, p.lds, st) : pw_launch<PW_FWD, false>(p.a, p.act, p.MT, p.blocks, p.lds, st);
+    if (!p.stats) return pw_launch<PW_DGRAD, false>(p.a, p.act, p.MT, p.blocks, p.lds, st);
+    return pw_launch<PW_DGRAD, true>(p.a, p.act, p.MT, p.blocks, p.lds, st);
 }
 
 static void pw_geom(PwArgs& a, int T, int Hi, int Wi, int stride) {
@@ -605,6 +621,32 @@ __global__ __launch_bounds__(256) void pw_lattice_add_kernel(float* __restrict__
     *p += acc[e];
 }
 
+// Route (pwroute.hip), then launch: the first family whose plan accepts and whose launcher gets its workspace.  Where the plan says lattice_add, the
+// contraction ran without the compact shortcut gradient a.acc and pw_lattice_add_kernel adds it behind it.
+static int pw_run(const PwArgs& a, int mode, bool stats, hipStream_t st) {
+    const PwSwitches sw = pw_switches_now(false);
+    PwPlan p = {};
+    p.align_io = (unsigned)(((uintptr_t)a.src | (uintptr_t)a.dst | (uintptr_t)a.src2) & 15);
+    p.align_ex = (unsigned)((uintptr_t)a.ex & 15);
+    for (int from = 0; mode == PW_FWD ? pw_route_fwd(a, stats, sw, p, from) : pw_route_dgrad(a, stats, sw, p, from); from = p.slot + 1) {
+        int rc;
+        switch (p.family) {
+            case PW_FAM_PWK: rc = pwk_launch(p, st); break;
+            case PW_FAM_PWT: rc = pwt_launch(p, st); break;
+            case PW_FAM_PWS: rc = pws_launch(p, st); break;
+            case PW_FAM_PWD: rc = pwd_launch(p, st); break;
+            default: rc = pw_gemm_launch(p, st); break;
+        }
+        if (rc < 0) continue;
+        if (rc > 0 || !p.lattice_add) return rc;
+        const long total = (long)a.N * a.M * (a.Pin / (a.Hi * a.Wi)) * a.acc_Ho * a.acc_Wo;
+        hipLaunchKernelGGL(pw_lattice_add_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, a.dst, a.acc, total, a.acc_Ho, a.acc_Wo, a.Hi, a.Wi,
+                           a.acc_s);
+        return cfn_check_launch("pwconv_bwd_data(lattice add)");
+    }
+    return pw_too_large(a);
+}
+
 extern "C" int cfn_pwconv_fwd(const float* x, const double* A, const double* B, int act, const float* w, float* y,
                               double* sum, double* sumsq, int N, int Cin, int Cout, int T, int Hi, int Wi, int stride,
                               void* stream) {
@@ -620,13 +662,7 @@ extern "C" int cfn_pwconv_fwd(const float* x, const double* A, const double* B, 
     CFN_REQUIRE((long)T * Hi * Wi < (1L << 31), "cfn_pwconv_fwd: per-sample volume too large");
     hipStream_t st = (hipStream_t)stream;
     CfnProfScope prof(CFN_K_PWCONV_FWD, st, 4.0 * N * ((double)Cin * a.Q + (double)Cout * a.Q) + 4.0 * Cin * Cout);
-    { const int rc = pwk_try_launch(a, PW_FWD, sum != nullptr, st); if (rc >= 0) return rc; }
-    { const int rc = pwt_try_launch(a, PW_FWD, sum != nullptr, st); if (rc >= 0) return rc; }
-    { const int rc = pws_try_launch(a, PW_FWD, sum != nullptr, st); if (rc >= 0) return rc; }
-    { const int rc = pwd_try_launch(a, PW_FWD, sum != nullptr, st); if (rc >= 0) return rc; }
-    int MT; unsigned blocks; size_t lds;
-    { int rc = pw_plan(a, MT, blocks, lds); if (rc) return rc; }
-    return sum ? pw_launch<PW_FWD, true>(a, MT, blocks, lds, st) : pw_launch<PW_FWD, false>(a, MT, blocks, lds, st);
+    return pw_run(a, PW_FWD, sum != nullptr, st);
 }
 
 // gx must be zero-filled by the caller when stride == 2 (only the strided positions are written)
@@ -650,29 +686,7 @@ extern "C" int cfn_pwconv_bwd_data_acc(const float* gy, const float* y, const do
     if (acc) { a.acc = acc; a.acc_s = acc_stride; a.acc_Ho = (Hi - 1) / acc_stride + 1; a.acc_Wo = (Wi - 1) / acc_stride + 1; }
     hipStream_t st = (hipStream_t)stream;
     CfnProfScope prof(CFN_K_PWCONV_BWD, st, 4.0 * N * ((double)Cout * a.Q * (a.src2 ? 2 : 1) + (double)Cin * a.Q * (A ? 2 : 1)));
-    if (acc && !A) {
-        // no act' epilogue: contraction on a split-bf16 kernel (those decline the compact shortcut gradient), lattice add behind it
-        // (stage-first conv1 of layers 3 / 4, 8 clips x 256 frames: 0.77 ms on pw_deep_kernel with the in-kernel lattice loads)
-        PwArgs a2 = a;
-        a2.acc = nullptr;
-        int rc = pwk_try_launch(a2, PW_DGRAD, false, st);
-        if (rc < 0) rc = pwt_try_launch(a2, PW_DGRAD, false, st);
-        if (rc > 0) return rc;
-        if (rc == 0) {
-            const long total = (long)N * Cin * T * a.acc_Ho * a.acc_Wo;
-            hipLaunchKernelGGL(pw_lattice_add_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, gx, acc, total, a.acc_Ho, a.acc_Wo, Hi, Wi,
-                               acc_stride);
-            return cfn_check_launch("pwconv_bwd_data(lattice add)");
-        }
-    }
-    { const int rc = pwk_try_launch(a, PW_DGRAD, A != nullptr, st); if (rc >= 0) return rc; }
-    { const int rc = pwt_try_launch(a, PW_DGRAD, A != nullptr, st); if (rc >= 0) return rc; }
-    { const int rc = pws_try_launch(a, PW_DGRAD, A != nullptr, st); if (rc >= 0) return rc; }
-    { const int rc = pwd_try_launch(a, PW_DGRAD, A != nullptr, st); if (rc >= 0) return rc; }
-    int MT; unsigned blocks; size_t lds;
-    { int rc = pw_plan(a, MT, blocks, lds); if (rc) return rc; }
-    if (!A) { a.act = CFN_ACT_NONE; return pw_launch<PW_DGRAD, false>(a, MT, blocks, lds, st); }
-    return pw_launch<PW_DGRAD, true>(a, MT, blocks, lds, st);
+    return pw_run(a, PW_DGRAD, A != nullptr, st);
 }
 
 extern "C" int cfn_pwconv_bwd_data(const float* gy, const float* y, const double* gsum, const double* gsumsq,
@@ -699,17 +713,17 @@ static void wg_plan(WgArgs& a, int& MTW, int& NTW) {
     a.nstrips = cfn_cdiv(nst, stages);
 }
 
-static int wg_launch(const WgArgs& a, int MTW, int NTW, hipStream_t st) {
-    const unsigned blocks = (unsigned)((long)a.N * a.nstrips * a.mtiles * a.ktiles);
+static unsigned wg_blocks(const WgArgs& a) { return (unsigned)((long)a.N * a.nstrips * a.mtiles * a.ktiles); }
+static size_t wg_lds(int MTW, int NTW) {
     size_t lds = ((size_t)2 * (32 * MTW + 32 * NTW) * WG_PITCH + 2 * (32 * MTW + 32 * NTW) + 32 * MTW) * sizeof(float);
     const size_t lds_cw = (size_t)4 * 32 * MTW * (32 * NTW + 1) * sizeof(float);
-    if (lds_cw > lds) lds = lds_cw;
-#define CFN_WG_GO(MW, NW)                                                                                       \
-    do {                                                                                                        \
-        auto k = pw_wgrad_kernel<MW, NW>;                                                                       \
-        if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        hipLaunchKernelGGL(k, dim3(blocks), dim3(256), lds, st, a);                                             \
-    } while (0)
+    return lds_cw > lds ? lds_cw : lds;
+}
+
+static int wg_launch(const WgArgs& a, int MTW, int NTW, hipStream_t st) {
+    const unsigned blocks = wg_blocks(a);
+    const size_t lds = wg_lds(MTW, NTW);
+#define CFN_WG_GO(MW, NW) cfn_launch(pw_wgrad_kernel<MW, NW>, blocks, 256, lds, st, a)
     if (MTW == 1 && NTW == 1) CFN_WG_GO(1, 1);
     else if (MTW == 1) CFN_WG_GO(1, 2);
     else if (NTW == 1) CFN_WG_GO(2, 1);
@@ -735,20 +749,28 @@ extern "C" int cfn_pwconv_bwd_weight(const float* gy, const float* y, const doub
     a.gy = gy; a.y = gsumsq ? y : nullptr; a.gs = gsum; a.gq = gsumsq; a.gsc = gscale; a.x = x; a.pa = A; a.pb = B; a.act = act;
     a.gw = gw;
     wg_geom(a, N, Cin, Cout, T, Hi, Wi, stride);
-    int MTW, NTW;
-    wg_plan(a, MTW, NTW);
+    PwBwdShape s = {N, Cin, Cout, T, Hi, Wi, stride, act};
+    s.pro = A != nullptr; s.two = a.y != nullptr;
+    s.align_g = (unsigned)(((uintptr_t)gy | (uintptr_t)(a.y ? a.y : gy)) & 15); s.align_x = (unsigned)((uintptr_t)x & 15);
+    PwBwdPlan p = {};
+    if (!pw_route_wgrad(s, pw_switches_now(true), p, 0)) return cfn_fail(CFN_ERR_UNSUPPORTED, "cfn_pwconv_bwd_weight: no kernel for this shape");
     hipStream_t st = (hipStream_t)stream;
     CfnProfScope prof(CFN_K_PWCONV_WGRAD, st, 4.0 * N * ((double)Cout * a.Q * (a.y ? 2 : 1) + (double)Cin * a.Q));
-    if (stride == 1) {
-        const int rc = pws_wgrad_try_launch(gy, a.y, gsum, gsumsq, gscale, x, A, B, act, gw, N, Cout, Cin, a.Q, st);
-        if (rc >= 0) return rc;
-    }
-    {
-        const int rc = stride == 1 ? pwd_wgrad_try_launch(gy, a.y, gsum, gsumsq, gscale, x, A, B, act, gw, N, Cout, Cin, a.Q, st)
-                                   : pwd_wgrad_try_strided(gy, a.y, gsum, gsumsq, gscale, x, A, B, act, gw, N, Cout, Cin, T, Hi, Wi, stride, st);
-        if (rc >= 0) return rc;
-    }
+    if (p.family == PW_FAM_PSS) return pws_wgrad_launch(p, gy, a.y, gsum, gsumsq, gscale, x, A, B, act, gw, N, Cout, Cin, a.Q, st);
+    if (p.family == PW_FAM_WD) return pwd_wgrad_launch(p, gy, a.y, gsum, gsumsq, gscale, x, A, B, act, gw, N, Cout, Cin, T, Hi, Wi, stride, st);
+    int MTW, NTW;
+    wg_plan(a, MTW, NTW);
     return wg_launch(a, MTW, NTW, st);
+}
+
+// the LDS-staged fp32 weight gradient takes every shape.  t[] = row / column tiles
+bool pw_wg_plan(const PwBwdShape& s, const PwSwitches&, PwBwdPlan& p) {
+    WgArgs a = {};
+    wg_geom(a, s.N, s.Cin, s.Cout, s.T, s.Hi, s.Wi, s.stride);
+    wg_plan(a, p.t[0], p.t[1]);
+    p.family = PW_FAM_WG; p.stages = a.stages; p.nstrips = a.nstrips; p.threads = 256;
+    p.blocks = wg_blocks(a); p.lds = wg_lds(p.t[0], p.t[1]);
+    return true;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -795,8 +817,7 @@ extern "C" int cfn_conv3d_dense_fwd(const float* x, const double* A, const doubl
         if (rs >= 0) return rs;
     }
     int MT; unsigned blocks; size_t lds;
-    rc = pw_plan(a, MT, blocks, lds);
-    if (rc) return rc;
+    if (!pw_plan(a, MT, blocks, lds)) return pw_too_large(a);
     if (sum) {
         if (act == CFN_ACT_RELU) return pw_launch_mt<PW_FWD, true, CFN_ACT_RELU, true>(a, MT, blocks, lds, st);
         return pw_launch_mt<PW_FWD, true, CFN_ACT_NONE, true>(a, MT, blocks, lds, st);

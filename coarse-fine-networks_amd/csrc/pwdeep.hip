@@ -308,16 +308,9 @@ __global__ __launch_bounds__(64 * PWD_WAVES) void pw_deep_kernel(const PwArgs a)
 // host side
 // ---------------------------------------------------------------------------------------------
 template <int MODE, bool STATS, int ACT>
-static int pwd_go(const PwArgs& a, int MT, int NW, unsigned blocks, size_t lds, hipStream_t st) {
-#define CFN_PWD_GO(MTV)                                                                                        \
-    do {                                                                                                       \
-        {                                                                                                      \
-            auto k = pw_deep_kernel<MTV, MODE, STATS, ACT, 8>;                                                 \
-            if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-            hipLaunchKernelGGL(k, dim3(blocks), dim3(64 * 8), lds, st, a);                                     \
-        }                                                                                                      \
-    } while (0)
-    switch (MT) {
+static int pwd_go(const PwPlan& p, hipStream_t st) {
+#define CFN_PWD_GO(MTV) cfn_launch(pw_deep_kernel<MTV, MODE, STATS, ACT, 8>, p.blocks, p.threads, p.lds, st, p.a)
+    switch (p.MT) {
         case 2: CFN_PWD_GO(2); break;
         case 3: CFN_PWD_GO(3); break;
         case 4: CFN_PWD_GO(4); break;
@@ -330,49 +323,58 @@ static int pwd_go(const PwArgs& a, int MT, int NW, unsigned blocks, size_t lds, 
 }
 
 template <int MODE, bool STATS>
-static int pwd_act(const PwArgs& a, int MT, int NW, unsigned blocks, size_t lds, hipStream_t st) {
-    switch (a.act) {
-        case CFN_ACT_RELU: return pwd_go<MODE, STATS, CFN_ACT_RELU>(a, MT, NW, blocks, lds, st);
-        case CFN_ACT_SWISH: return pwd_go<MODE, STATS, CFN_ACT_SWISH>(a, MT, NW, blocks, lds, st);
-        default: return pwd_go<MODE, STATS, CFN_ACT_NONE>(a, MT, NW, blocks, lds, st);
+static int pwd_act(const PwPlan& p, hipStream_t st) {
+    switch (p.act) {
+        case CFN_ACT_RELU: return pwd_go<MODE, STATS, CFN_ACT_RELU>(p, st);
+        case CFN_ACT_SWISH: return pwd_go<MODE, STATS, CFN_ACT_SWISH>(p, st);
+        default: return pwd_go<MODE, STATS, CFN_ACT_NONE>(p, st);
     }
 }
 
-int pwd_try_launch(PwArgs& a, int mode, bool stats, hipStream_t st) {
-    if (a.stem || a.stride != 1 || a.K < 48 || a.M <= 32) return -1;
-    if (a.act != CFN_ACT_NONE && a.act != CFN_ACT_RELU && a.act != CFN_ACT_SWISH) return -1;
+// false when the shape is not handled (pw_gemm_kernel takes it).  mode: PW_FWD / PW_DGRAD; stats: epilogue statistics / act' epilogue present.
+bool pwd_plan(const PwArgs& a, int mode, bool stats, const PwSwitches&, PwPlan& p) {
+    if (a.stem || a.stride != 1 || a.K < 48 || a.M <= 32) return false;
+    if (a.act != CFN_ACT_NONE && a.act != CFN_ACT_RELU && a.act != CFN_ACT_SWISH) return false;
     const int Kpad = (a.K + PW_UNIT - 1) / PW_UNIT * PW_UNIT;
     int mt_max = (120 * 1024 / 4 / Kpad) / 32;            // resident weight image <= 120 KiB
     if (mt_max > 7) mt_max = 7;
-    if (mt_max < 2) return -1;
+    if (mt_max < 2) return false;
     if ((long)a.K * a.Pin * 4 >= (1L << 31) || (long)a.K * a.Q * 4 >= (1L << 31) || (long)a.M * a.Pin * 4 >= (1L << 31) ||
         (long)a.M * a.Q * 4 >= (1L << 31))
-        return -1;
+        return false;
     const int M32 = cfn_cdiv(a.M, 32);
     const int ntile = cfn_cdiv(M32, mt_max);
     const int MT = cfn_cdiv(M32, ntile);
-    if (MT < 2) return -1;
-    a.Kpad = Kpad;
-    a.mtiles = cfn_cdiv(a.M, 32 * MT);
+    if (MT < 2) return false;
     const int BM = 32 * MT;
     // one workgroup (8 waves, one resident weight image) per CU: the ~256 workgroups are split evenly over the
     // (sample, row tile) groups; inside a group the 32-position wave tiles are dealt round robin
     const int NW = 8;
+    const size_t lds = ((size_t)Kpad * BM + 4 * (Kpad + PW_UNIT) + 2 * BM + NW * 32 * PW_RED_PITCH) * sizeof(float);
+    if (lds > 160 * 1024) return false;
+    PwArgs& b = p.a;
+    b = a;
+    b.Kpad = Kpad;
+    b.mtiles = cfn_cdiv(a.M, 32 * MT);
     const long wtiles = cfn_cdiv(a.Q, 32);
-    const long groups = (long)a.N * a.mtiles;
+    const long groups = (long)a.N * b.mtiles;
     // two workgroups per CU where both fit (LDS <= 80 KiB, <= 128 VGPRs: 4 row tiles, or 2 with the act' epilogue): the
     // HBM-bound layer-2 shapes gain (48->108 @28 dgrad 0.50 -> 0.42 ms); the big-image layers stay at one per CU
-    const size_t lds_probe = ((size_t)Kpad * BM + 4 * (Kpad + PW_UNIT) + 2 * BM + NW * 32 * PW_RED_PITCH) * sizeof(float);
-    const bool two = lds_probe <= 80 * 1024 && MT <= ((mode == PW_DGRAD && stats) ? 2 : 4);
+    const bool two = lds <= 80 * 1024 && MT <= ((mode == PW_DGRAD && stats) ? 2 : 4);
     long bpg = (two ? 512L : 256L) / groups;
     if (bpg < 1) bpg = 1;
     if (bpg > cfn_cdiv(wtiles, NW)) bpg = cfn_cdiv(wtiles, NW);
-    a.nstrips = (int)bpg;
-    a.tpb = 0;
-    const unsigned blocks = (unsigned)(groups * bpg);
-    const size_t lds = ((size_t)Kpad * BM + 4 * (Kpad + PW_UNIT) + 2 * BM + NW * 32 * PW_RED_PITCH) * sizeof(float);
-    if (lds > 160 * 1024) return -1;
-    if (mode == PW_FWD) return stats ? pwd_act<PW_FWD, true>(a, MT, NW, blocks, lds, st) : pwd_act<PW_FWD, false>(a, MT, NW, blocks, lds, st);
-    if (!stats) { a.act = CFN_ACT_NONE; return pwd_go<PW_DGRAD, false, CFN_ACT_NONE>(a, MT, NW, blocks, lds, st); }
-    return pwd_act<PW_DGRAD, true>(a, MT, NW, blocks, lds, st);
+    b.nstrips = (int)bpg;
+    b.tpb = 0;
+    if (mode == PW_DGRAD && !stats) b.act = CFN_ACT_NONE;
+    p.family = PW_FAM_PWD; p.mode = mode; p.stats = stats; p.two = a.src2 != nullptr; p.act = b.act;
+    p.MT = MT;
+    p.blocks = (unsigned)(groups * bpg); p.threads = 64 * NW; p.lds = lds;
+    return true;
+}
+
+int pwd_launch(const PwPlan& p, hipStream_t st) {
+    if (p.mode == PW_FWD) return p.stats ? pwd_act<PW_FWD, true>(p, st) : pwd_act<PW_FWD, false>(p, st);
+    if (!p.stats) return pwd_go<PW_DGRAD, false, CFN_ACT_NONE>(p, st);
+    return pwd_act<PW_DGRAD, true>(p, st);
 }

@@ -285,23 +285,41 @@ __global__ __launch_bounds__(256, ACT < 0 ? 3 : 2) void pw_bwd_fused_kernel(cons
 }
 
 template <int MTW, int NTW>
-static int pf_launch(const PfArgs& a, int act, bool epi, unsigned blocks, hipStream_t st) {
-    constexpr int BM = 32 * MTW, BN = 32 * NTW;
-    size_t lds = ((size_t)2 * (BM + BN) * PF_PITCH + 3 * BM + 10 * BN) * sizeof(float);
-    const size_t lds_cw = (size_t)4 * BM * (BN + 1) * sizeof(float);
-    if (lds_cw > lds) lds = lds_cw;
-#define CFN_PF_GO(ACTV)                                                                                         \
-    do {                                                                                                        \
-        auto k = pw_bwd_fused_kernel<MTW, NTW, ACTV>;                                                           \
-        if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        hipLaunchKernelGGL(k, dim3(blocks), dim3(256), lds, st, a);                                             \
-    } while (0)
+static int pf_launch(const PfArgs& a, int act, bool epi, unsigned blocks, size_t lds, hipStream_t st) {
+#define CFN_PF_GO(ACTV) cfn_launch(pw_bwd_fused_kernel<MTW, NTW, ACTV>, blocks, 256, lds, st, a)
     if (!epi) CFN_PF_GO(-1);
     else if (act == CFN_ACT_RELU) CFN_PF_GO(CFN_ACT_RELU);
     else if (act == CFN_ACT_SWISH) CFN_PF_GO(CFN_ACT_SWISH);
     else CFN_PF_GO(CFN_ACT_NONE);
 #undef CFN_PF_GO
     return cfn_check_launch("pwconv_bwd_fused");
+}
+
+// the fp32 one-pass backward: few channels (layer 1: HBM bound); false = declined.  t[] = row / column tiles
+bool pf_plan(const PwBwdShape& s, const PwSwitches&, PwBwdPlan& p) {
+    const int Cin = s.Cin, Cout = s.Cout;
+    const long Ql = (long)s.T * s.Hi * s.Wi;
+    if (Cin > 64 || Cout > 64 || (Cin > 32 && Cout > 32) || Ql % 4 != 0 || Ql >= (1L << 30)) return false;
+    if ((long)Cout * Ql * 4 >= 0x7ffffff0L || (long)Cin * Ql * 4 >= 0x7ffffff0L) return false;   // 32-bit buffer offsets per sample
+    if (s.pro && s.act != CFN_ACT_NONE && s.act != CFN_ACT_RELU && s.act != CFN_ACT_SWISH) return false;
+    if ((s.align_g | s.align_x) & 15) return false;
+    // >= 4 stages per workgroup
+    const long nst = cfn_cdiv(Ql, PF_PT);
+    // whole rounds of the chip: 2 workgroups per CU are resident with a prologue (3 without), so 1024 (1536) workgroups
+    // are 2 full rounds; 640 (= 1.25 rounds) cost 4.56 instead of 3.83 ms on 24->54 @112
+    long want = (s.pro ? 1024 : 1536) / s.N;
+    if (want < 1) want = 1;
+    long stages = cfn_cdiv(nst, want);
+    if (stages < 4) stages = 4;
+    p.stages = (int)stages;
+    p.nstrips = (int)cfn_cdiv(nst, stages);
+    p.blocks = (unsigned)((long)s.N * p.nstrips); p.threads = 256;
+    const int MTW = Cout > 32 ? 2 : 1, NTW = Cout <= 32 && Cin > 32 ? 2 : 1, BM = 32 * MTW, BN = 32 * NTW;
+    p.family = PW_FAM_PF; p.t[0] = MTW; p.t[1] = NTW; p.act = s.pro ? s.act : -1;
+    p.lds = ((size_t)2 * (BM + BN) * PF_PITCH + 3 * BM + 10 * BN) * sizeof(float);
+    const size_t lds_cw = (size_t)4 * BM * (BN + 1) * sizeof(float);
+    if (lds_cw > p.lds) p.lds = lds_cw;
+    return true;
 }
 
 extern "C" int cfn_pwconv_bwd_fused(const float* gy, const float* y, const double* gsum, const double* gsumsq, const float* w,
@@ -313,36 +331,31 @@ extern "C" int cfn_pwconv_bwd_fused(const float* gy, const float* y, const doubl
     CFN_REQUIRE(A == nullptr || (gA && gB), "cfn_pwconv_bwd_fused: prologue needs gA, gB");
     CFN_REQUIRE(gsumsq == nullptr || y != nullptr, "cfn_pwconv_bwd_fused: gsumsq needs y");
     CFN_REQUIRE(acc == nullptr || acc_stride >= 1, "cfn_pwconv_bwd_fused: bad acc_stride");
-    {   // layer-2 widths: the split-bf16 kernel of pwfuseds.hip (CFN_PWF_SPLIT: 0 off, 1 = default: the shapes without a prologue, 2 = all)
-        const int rs = pwfs_try_launch(gy, y, gsum, gsumsq, w, x, A, B, act, gx, gA, gB, gw, N, Cin, Cout, T, Hi, Wi, acc, acc_stride, gscale, (hipStream_t)stream);
-        if (rs != -1) return rs;
-    }
-    const long Ql = (long)T * Hi * Wi;
-    if (Cin > 64 || Cout > 64 || (Cin > 32 && Cout > 32) || Ql % 4 != 0 || Ql >= (1L << 30)) return -1;
-    if ((long)Cout * Ql * 4 >= 0x7ffffff0L || (long)Cin * Ql * 4 >= 0x7ffffff0L) return -1;   // 32-bit buffer offsets per sample
-    if (A && act != CFN_ACT_NONE && act != CFN_ACT_RELU && act != CFN_ACT_SWISH) return -1;
-    if ((((uintptr_t)gy | (uintptr_t)x | (uintptr_t)(y ? y : gy)) & 15) != 0) return -1;
-    PfArgs a = {};
-    a.gy = gy; a.y = gsumsq ? y : nullptr; a.gs = gsum; a.gq = gsumsq; a.gsc = gscale; a.w = w; a.x = x; a.pa = A; a.pb = B;
-    a.gx = gx; a.gA = gA; a.gB = gB; a.gw = gw;
-    a.acc = acc; a.acc_s = acc ? acc_stride : 1; a.Hi = Hi; a.Wi = Wi; a.T = T;
-    a.acc_Ho = (Hi - 1) / a.acc_s + 1; a.acc_Wo = (Wi - 1) / a.acc_s + 1;
-    a.N = N; a.M = Cout; a.K = Cin; a.Q = (int)Ql;
-    // >= 4 stages per workgroup
-    const long nst = cfn_cdiv(Ql, PF_PT);
-    // whole rounds of the chip: 2 workgroups per CU are resident with a prologue (3 without), so 1024 (1536) workgroups
-    // are 2 full rounds; 640 (= 1.25 rounds) cost 4.56 instead of 3.83 ms on 24->54 @112
-    const bool epi = A != nullptr;
-    long want = (epi ? 1024 : 1536) / N;
-    if (want < 1) want = 1;
-    long stages = cfn_cdiv(nst, want);
-    if (stages < 4) stages = 4;
-    a.stages = (int)stages;
-    a.nstrips = (int)cfn_cdiv(nst, stages);
-    const unsigned blocks = (unsigned)((long)N * a.nstrips);
+    PwBwdShape s = {N, Cin, Cout, T, Hi, Wi, 1, act};
+    s.pro = A != nullptr; s.acc = acc != nullptr; s.acc_stride = acc_stride;
+    s.align_g = (unsigned)(((uintptr_t)gy | (uintptr_t)(y ? y : gy)) & 15); s.align_x = (unsigned)((uintptr_t)x & 15);
+    const PwSwitches sw = pw_switches_now(true);
     hipStream_t st = (hipStream_t)stream;
-    CfnProfScope prof(CFN_K_PWCONV_BWD, st, 4.0 * N * ((double)Cout * Ql * (a.y ? 2 : 1) + (double)Cin * Ql * 2));
-    if (Cout > 32) return pf_launch<2, 1>(a, act, epi, blocks, st);
-    if (Cin > 32) return pf_launch<1, 2>(a, act, epi, blocks, st);
-    return pf_launch<1, 1>(a, act, epi, blocks, st);
+    PwBwdPlan p = {};
+    for (int from = 0; pw_route_fused(s, sw, p, from); from = p.slot + 1) {
+        if (p.family != PW_FAM_PF) {      // the split-bf16 kernels of pwfuseds.hip; -1 = no workspace: on to the next family
+            const int rs = pwfs_launch(p, gy, y, gsum, gsumsq, w, x, A, B, act, gx, gA, gB, gw, N, Cin, Cout, T, Hi, Wi, acc, acc_stride, gscale, st);
+            if (rs != -1) return rs;
+            continue;
+        }
+        const long Ql = (long)T * Hi * Wi;
+        PfArgs a = {};
+        a.gy = gy; a.y = gsumsq ? y : nullptr; a.gs = gsum; a.gq = gsumsq; a.gsc = gscale; a.w = w; a.x = x; a.pa = A; a.pb = B;
+        a.gx = gx; a.gA = gA; a.gB = gB; a.gw = gw;
+        a.acc = acc; a.acc_s = acc ? acc_stride : 1; a.Hi = Hi; a.Wi = Wi; a.T = T;
+        a.acc_Ho = (Hi - 1) / a.acc_s + 1; a.acc_Wo = (Wi - 1) / a.acc_s + 1;
+        a.N = N; a.M = Cout; a.K = Cin; a.Q = (int)Ql;
+        a.stages = p.stages; a.nstrips = p.nstrips;
+        CfnProfScope prof(CFN_K_PWCONV_BWD, st, 4.0 * N * ((double)Cout * Ql * (a.y ? 2 : 1) + (double)Cin * Ql * 2));
+        const bool epi = A != nullptr;
+        if (p.t[0] == 2) return pf_launch<2, 1>(a, act, epi, p.blocks, p.lds, st);
+        if (p.t[1] == 2) return pf_launch<1, 2>(a, act, epi, p.blocks, p.lds, st);
+        return pf_launch<1, 1>(a, act, epi, p.blocks, p.lds, st);
+    }
+    return -1;
 }

@@ -388,11 +388,7 @@ __global__ __launch_bounds__(512, 1) void pw_bwd_fused_split_kernel(const PfsArg
 }
 
 template <int MTW, int NTW>
-static int pfs_launch(const PfsArgs& a, int act, bool epi, unsigned blocks, hipStream_t st) {
-    constexpr int BM = 32 * MTW, BN = 32 * NTW, BMP = BM + 8;
-    size_t lds = ((size_t)2 * (BM + BN) * PFS_PITCH + 3 * BM + 10 * BN) * sizeof(float) + (size_t)3 * BN * BMP * 2;
-    const size_t lds_cw = (size_t)4 * (MTW * NTW / 2) * 32 * 33 * sizeof(float);   // the four weight-gradient waves' tiles, after the last stage
-    if (lds_cw > lds) lds = lds_cw;
+static int pfs_launch(const PfsArgs& a, int act, bool epi, unsigned blocks, size_t lds, hipStream_t st) {
 #define CFN_PFS_GO(ACTV)                                                                                        \
     do {                                                                                                        \
         auto k = pw_bwd_fused_split_kernel<MTW, NTW, ACTV>;                                                     \
@@ -1012,11 +1008,10 @@ static unsigned* pf3_workspace(size_t bytes, hipStream_t st) {
 
 template <int NT>
 static int pf3_launch(const float* gy, const float* y, const double* gsum, const double* gsumsq, const float* w, const float* x, float* gx, double* gw,
-                      int N, int Cin, int Cout, int T, int Hi, int Wi, const float* acc, int acc_stride, const double* gscale, hipStream_t st) {
+                      int N, int Cin, int Cout, int T, int Hi, int Wi, const float* acc, int acc_stride, const double* gscale, const PwBwdPlan& p, hipStream_t st) {
     constexpr int MT = 7, BM = 32 * MT, BN = 32 * NT, BMP = BM + 8;
     const long Ql = (long)T * Hi * Wi;
-    const size_t wbytes = (size_t)3 * BN * (BMP / 2) * 4;
-    unsigned* ws = pf3_workspace(wbytes, st);
+    unsigned* ws = pf3_workspace(p.ws_bytes, st);
     if (!ws) return -1;
     hipLaunchKernelGGL((pf3_presplit_kernel<MT, NT>), dim3((BN * (BMP / 2) + 255) / 256), dim3(256), 0, st, w, Cout, Cin, ws);
     Pf3Args a = {};
@@ -1027,19 +1022,10 @@ static int pf3_launch(const float* gy, const float* y, const double* gsum, const
 #ifdef CFN_PWFS_KNOCKOUTS      // tools/pwfs_knockouts.sh builds a library of its own with this; a.dbg stays 0 otherwise
     { const char* e = getenv("CFN_PWFS_DBG"); a.dbg = e ? atoi(e) : 0; }
 #endif
-    const long nst = cfn_cdiv(Ql, PF3_PT);
-    // whole rounds of the chip (one workgroup per CU is resident) and few of them: every workgroup pays the W^T load and M x K fp64 atomics once; measured at 96 -> 216,
-    // 8 clips x 256 frames x 14 x 14: 256 / 512 / 1024 workgroups = 0.301 / 0.333 / 0.395 ms, 320 / 384 (partial rounds) 0.416 / 0.376.  One round; two where a workgroup
-    // would otherwise walk more than ~100 stages (the first block of layer 3 at 28 x 28)
-    const long wgs = (long)N * nst > 256L * 100 ? 512 : 256;
-    long want = wgs / N;
-    if (want < 1) want = 1;
-    long stages = cfn_cdiv(nst, want);
-    if (stages < 4) stages = 4;
-    a.stages = (int)stages;
-    a.nstrips = (int)cfn_cdiv(nst, stages);
-    const unsigned blocks = (unsigned)((long)N * a.nstrips);
-    const size_t lds = ((size_t)2 * (BM + BN) * PF3_PITCH + 3 * 32 * PF3_TP) * sizeof(float);      // two images + the data-gradient waves' output tiles
+    a.stages = p.stages;
+    a.nstrips = p.nstrips;
+    const unsigned blocks = p.blocks;
+    const size_t lds = p.lds;
     CfnProfScope prof(CFN_K_PWCONV_BWD, st, 4.0 * N * ((double)Cout * Ql * (a.y ? 2 : 1) + (double)Cin * Ql * 2));
     auto k = pw_bwd_fused_split3_kernel<MT, NT>;
     (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -1047,26 +1033,20 @@ static int pf3_launch(const float* gy, const float* y, const double* gsum, const
     return cfn_check_launch("pwconv_bwd_fused (split bf16, layer 3)");
 }
 
-static int pf3e_try_launch(const float* gy, const float* y, const double* gsum, const double* gsumsq, const float* w, const float* x, const double* A, const double* B,
-                           int act, float* gx, double* gA, double* gB, double* gw, int N, int Cin, int Cout, long Ql, const double* gscale, hipStream_t st) {
+static int pf3e_launch(const float* gy, const float* y, const double* gsum, const double* gsumsq, const float* w, const float* x, const double* A, const double* B,
+                           int act, float* gx, double* gA, double* gB, double* gw, int N, int Cin, int Cout, long Ql, const double* gscale, const PwBwdPlan& p, hipStream_t st) {
     constexpr int MT = 3, NT = 7, BM = 32 * MT, BN = 32 * NT, BMP = BM + 8;
-    const size_t wbytes = (size_t)3 * BN * (BMP / 2) * 4;
-    unsigned* ws = pf3_workspace(wbytes, st);
+    unsigned* ws = pf3_workspace(p.ws_bytes, st);
     if (!ws) return -1;
     hipLaunchKernelGGL((pf3_presplit_kernel<MT, NT>), dim3((BN * (BMP / 2) + 255) / 256), dim3(256), 0, st, w, Cout, Cin, ws);
     Pf3eArgs a = {};
     a.gy = gy; a.y = gsumsq ? y : nullptr; a.gs = gsum; a.gq = gsumsq; a.gsc = gscale; a.x = x; a.pa = A; a.pb = B; a.wsplit = ws;
     a.gx = gx; a.gA = gA; a.gB = gB; a.gw = gw;
     a.N = N; a.M = Cout; a.K = Cin; a.Q = (int)Ql;
-    const long nst = cfn_cdiv(Ql, PF3_PT);
-    long want = 256 / N;                      // one round of the chip
-    if (want < 1) want = 1;
-    long stages = cfn_cdiv(nst, want);
-    if (stages < 4) stages = 4;
-    a.stages = (int)stages;
-    a.nstrips = (int)cfn_cdiv(nst, stages);
-    const unsigned blocks = (unsigned)((long)N * a.nstrips);
-    const size_t lds = ((size_t)2 * (BM + BN) * PF3_PITCH + 2 * BN) * sizeof(float);
+    a.stages = p.stages;
+    a.nstrips = p.nstrips;
+    const unsigned blocks = p.blocks;
+    const size_t lds = p.lds;
     CfnProfScope prof(CFN_K_PWCONV_BWD, st, 4.0 * N * ((double)Cout * Ql * (a.y ? 2 : 1) + (double)Cin * Ql * 2));
 #define CFN_PF3E_GO(ACTV)                                                                                       \
     do {                                                                                                        \
@@ -1081,44 +1061,82 @@ static int pf3e_try_launch(const float* gy, const float* y, const double* gsum, 
     return cfn_check_launch("pwconv_bwd_fused (split bf16, layer 3 conv3)");
 }
 
-// -1 = not handled (cfn_pwconv_bwd_fused goes on to its fp32 kernel / declines)
-int pwfs_try_launch(const float* gy, const float* y, const double* gsum, const double* gsumsq, const float* w, const float* x, const double* A,
-                    const double* B, int act, float* gx, double* gA, double* gB, double* gw, int N, int Cin, int Cout, int T, int Hi, int Wi,
-                    const float* acc, int acc_stride, const double* gscale, hipStream_t st) {
-    const char* env_on = getenv("CFN_PWF_SPLIT");      // read per call: tests and A/B harnesses switch it inside one process
-    const int on = env_on ? atoi(env_on) : 1;          // default 1: the no-prologue shapes (measured in the step: -1.3 .. -1.9 ms; level 2 loses 0.5 ms of it)
-    if (!on || pws_terms_now() != 6) return -1;
-    // CFN_PWF_SPLIT: 1 = the shapes WITHOUT a prologue (conv1 of the layer-2 blocks, whose input is a materialised block output), 2 (or more) = also
-    // the shapes with one (conv3: BN2 + swish in front)
+static void pfx_strips(const PwBwdShape& s, long nst, long want, PwBwdPlan& p) {
+    if (want < 1) want = 1;
+    long stages = cfn_cdiv(nst, want);
+    if (stages < 4) stages = 4;
+    p.stages = (int)stages;
+    p.nstrips = (int)cfn_cdiv(nst, stages);
+    p.blocks = (unsigned)((long)s.N * p.nstrips); p.threads = 512;
+}
+
+// The one-pass backward on the split-bf16 pipe: pf3 (layer 3's conv1), pf3e (layer 3's conv3, CFN_PWF_L3E), pfs (the layer-2 widths).  which: the family asked
+// (the router asks them in this order); false = not this family's shape.  t[] = the kernel's row / column tiles.
+bool pwfs_plan(const PwBwdShape& s, const PwSwitches& sw, int which, PwBwdPlan& p) {
+    const int on = sw.pwf_split, Cin = s.Cin, Cout = s.Cout;      // 1 = the shapes WITHOUT a prologue (conv1 of the layer-2 blocks, whose input is a materialised block output),
+    if (!on || sw.split_terms != 6) return false;                 // 2 (or more) = also the shapes with one (conv3: BN2 + swish in front)
+    const long Ql = (long)s.T * s.Hi * s.Wi;
+    const bool aligned = ((s.align_g | s.align_x) & 15) == 0;
+    const bool act_ok = s.act == CFN_ACT_NONE || s.act == CFN_ACT_RELU || s.act == CFN_ACT_SWISH;
+    p.act = s.pro ? s.act : -1;
+    if (which == PW_FAM_PF3) {
+        // layer 3's conv1 (96 -> 216, no prologue): the variant with W^T resident in the data-gradient waves' registers; 48 -> 216 @28: its first block
+        if (!(on >= 1 && !s.pro && Cout > 192 && Cout <= 224 && Cin > 32 && Cin <= 96)) return false;
+        if (!(Ql % 4 == 0 && Ql < (1L << 30) && (long)Cout * Ql * 4 < 0x7ffffff0L && aligned && (!s.acc || s.acc_stride >= 1))) return false;
+        const int MT = 7, NT = Cin > 64 ? 3 : 2, BM = 32 * MT, BN = 32 * NT, BMP = BM + 8;
+        const long nst = cfn_cdiv(Ql, PF3_PT);
+        // whole rounds of the chip (one workgroup per CU is resident) and few of them: every workgroup pays the W^T load and M x K fp64 atomics once; measured at 96 -> 216,
+        // 8 clips x 256 frames x 14 x 14: 256 / 512 / 1024 workgroups = 0.301 / 0.333 / 0.395 ms, 320 / 384 (partial rounds) 0.416 / 0.376.  One round; two where a workgroup
+        // would otherwise walk more than ~100 stages (the first block of layer 3 at 28 x 28)
+        const long wgs = (long)s.N * nst > 256L * 100 ? 512 : 256;
+        pfx_strips(s, nst, wgs / s.N, p);
+        p.family = PW_FAM_PF3; p.t[0] = MT; p.t[1] = NT;
+        p.lds = ((size_t)2 * (BM + BN) * PF3_PITCH + 3 * 32 * PF3_TP) * sizeof(float);      // two images + the data-gradient waves' output tiles
+        p.ws_bytes = (size_t)3 * BN * (BMP / 2) * 4;
+        return true;
+    }
+    if (which == PW_FAM_PF3E) {
+        // layer 3's conv3 (216 -> 96 behind BN2 + swish): the same structure with the sides exchanged (CFN_PWF_L3E: 0 off; while it is being measured: off unless set)
+        if (!(on >= 1 && sw.pwf_l3e && s.pro && !s.acc && Cout > 64 && Cout <= 96 && Cin > 192 && Cin <= 224)) return false;
+        if (!(Ql % 4 == 0 && Ql < (1L << 30) && (long)Cin * Ql * 4 < 0x7ffffff0L && aligned && act_ok)) return false;
+        const int MT = 3, NT = 7, BM = 32 * MT, BN = 32 * NT, BMP = BM + 8;
+        pfx_strips(s, cfn_cdiv(Ql, PF3_PT), 256 / s.N, p);                      // one round of the chip
+        p.family = PW_FAM_PF3E; p.t[0] = MT; p.t[1] = NT;
+        p.lds = ((size_t)2 * (BM + BN) * PF3_PITCH + 2 * BN) * sizeof(float);
+        p.ws_bytes = (size_t)3 * BN * (BMP / 2) * 4;
+        return true;
+    }
     const bool wide_m = Cout > 64 && Cout <= 128 && Cin > 32 && Cin <= 64;          // conv1 of layer 2: 48 -> 108
     const bool thin_k = Cout > 64 && Cout <= 128 && Cin >= 16 && Cin <= 32;         // conv1 of the first block of layer 2: 24 -> 108
     const bool wide_k = Cin > 64 && Cin <= 128 && Cout > 32 && Cout <= 64;          // conv3 of layer 2: 108 -> 48
     // (the layer-1 widths, 24 <-> 54, stay on the fp32 kernel of pwfused.hip)
-    // layer 3's conv1 (96 -> 216, no prologue, no shortcut gradient): the variant with W^T resident in the data-gradient waves' registers
-    if (on >= 1 && A == nullptr && Cout > 192 && Cout <= 224 && Cin > 32 && Cin <= 96) {
-        const long Ql3 = (long)T * Hi * Wi;
-        if (Ql3 % 4 == 0 && Ql3 < (1L << 30) && (long)Cout * Ql3 * 4 < 0x7ffffff0L && ((((uintptr_t)gy | (uintptr_t)x | (uintptr_t)(y ? y : gy)) & 15) == 0) &&
-            (acc == nullptr || acc_stride >= 1)) {
-            if (Cin > 64) return pf3_launch<3>(gy, y, gsum, gsumsq, w, x, gx, gw, N, Cin, Cout, T, Hi, Wi, acc, acc_stride, gscale, st);       // 96 -> 216: the blocks of layer 3
-            return pf3_launch<2>(gy, y, gsum, gsumsq, w, x, gx, gw, N, Cin, Cout, T, Hi, Wi, acc, acc_stride, gscale, st);                      // 48 -> 216 @28: its first block
-        }
-    }
-    // layer 3's conv3 (216 -> 96 behind BN2 + swish): the same structure with the sides exchanged (CFN_PWF_L3E: 0 off; while it is being measured: off unless set)
-    const char* env_l3e = getenv("CFN_PWF_L3E");          // read per call (tests / A-B harnesses switch it inside one process)
-    const int l3e_on = env_l3e ? atoi(env_l3e) : 0;
-    if (on >= 1 && l3e_on && A != nullptr && acc == nullptr && Cout > 64 && Cout <= 96 && Cin > 192 && Cin <= 224) {
-        const long Ql3 = (long)T * Hi * Wi;
-        if (Ql3 % 4 == 0 && Ql3 < (1L << 30) && (long)Cin * Ql3 * 4 < 0x7ffffff0L && ((((uintptr_t)gy | (uintptr_t)x | (uintptr_t)(y ? y : gy)) & 15) == 0) &&
-            (act == CFN_ACT_NONE || act == CFN_ACT_RELU || act == CFN_ACT_SWISH))
-            return pf3e_try_launch(gy, y, gsum, gsumsq, w, x, A, B, act, gx, gA, gB, gw, N, Cin, Cout, Ql3, gscale, st);
-    }
-    if (!wide_m && !wide_k && !thin_k) return -1;
-    if (A != nullptr && on < 2) return -1;
+    if (!wide_m && !wide_k && !thin_k) return false;
+    if (s.pro && on < 2) return false;
+    if (Ql % 4 != 0 || Ql >= (1L << 30)) return false;
+    if ((long)Cout * Ql * 4 >= 0x7ffffff0L || (long)Cin * Ql * 4 >= 0x7ffffff0L) return false;   // 32-bit buffer offsets per sample
+    if (s.pro && !act_ok) return false;
+    if (!aligned) return false;
+    // one workgroup per CU is resident: whole rounds of the chip, and few of them (a workgroup splits W^T once and ends with M x K fp64 atomics): measured, 48 -> 108 at
+    // 8 clips x 256 frames: 256 / 512 / 768 / 1024 / 2048 workgroups = 0.495 / 0.471-0.481 / 0.491 / 0.504 / 0.553 ms; 320 (1.25 rounds) 0.619
+    pfx_strips(s, cfn_cdiv(Ql, PFS_PT), 512 / s.N, p);
+    const int MTW = wide_m || thin_k ? 4 : 2, NTW = wide_m ? 2 : (thin_k ? 1 : 4), BM = 32 * MTW, BN = 32 * NTW, BMP = BM + 8;
+    p.family = PW_FAM_PFS; p.t[0] = MTW; p.t[1] = NTW;
+    p.lds = ((size_t)2 * (BM + BN) * PFS_PITCH + 3 * BM + 10 * BN) * sizeof(float) + (size_t)3 * BN * BMP * 2;
+    const size_t lds_cw = (size_t)4 * (MTW * NTW / 2) * 32 * 33 * sizeof(float);   // the four weight-gradient waves' tiles, after the last stage
+    if (lds_cw > p.lds) p.lds = lds_cw;
+    return true;
+}
+
+// -1 = no workspace (pf3 / pf3e under stream capture): nothing launched
+int pwfs_launch(const PwBwdPlan& p, const float* gy, const float* y, const double* gsum, const double* gsumsq, const float* w, const float* x, const double* A,
+                const double* B, int act, float* gx, double* gA, double* gB, double* gw, int N, int Cin, int Cout, int T, int Hi, int Wi,
+                const float* acc, int acc_stride, const double* gscale, hipStream_t st) {
     const long Ql = (long)T * Hi * Wi;
-    if (Ql % 4 != 0 || Ql >= (1L << 30)) return -1;
-    if ((long)Cout * Ql * 4 >= 0x7ffffff0L || (long)Cin * Ql * 4 >= 0x7ffffff0L) return -1;   // 32-bit buffer offsets per sample
-    if (A && act != CFN_ACT_NONE && act != CFN_ACT_RELU && act != CFN_ACT_SWISH) return -1;
-    if ((((uintptr_t)gy | (uintptr_t)x | (uintptr_t)(y ? y : gy)) & 15) != 0) return -1;
+    if (p.family == PW_FAM_PF3) {
+        if (p.t[1] == 3) return pf3_launch<3>(gy, y, gsum, gsumsq, w, x, gx, gw, N, Cin, Cout, T, Hi, Wi, acc, acc_stride, gscale, p, st);       // 96 -> 216: the blocks of layer 3
+        return pf3_launch<2>(gy, y, gsum, gsumsq, w, x, gx, gw, N, Cin, Cout, T, Hi, Wi, acc, acc_stride, gscale, p, st);                        // 48 -> 216 @28: its first block
+    }
+    if (p.family == PW_FAM_PF3E) return pf3e_launch(gy, y, gsum, gsumsq, w, x, A, B, act, gx, gA, gB, gw, N, Cin, Cout, Ql, gscale, p, st);
     PfsArgs a = {};
     a.gy = gy; a.y = gsumsq ? y : nullptr; a.gs = gsum; a.gq = gsumsq; a.gsc = gscale; a.w = w; a.x = x; a.pa = A; a.pb = B;
     a.gx = gx; a.gA = gA; a.gB = gB; a.gw = gw;
@@ -1128,19 +1146,11 @@ int pwfs_try_launch(const float* gy, const float* y, const double* gsum, const d
 #ifdef CFN_PWFS_KNOCKOUTS      // tools/pwfs_knockouts.sh builds a library of its own with this; a.dbg stays 0 otherwise
     { const char* e = getenv("CFN_PWFS_DBG"); a.dbg = e ? atoi(e) : 0; }
 #endif
-    const long nst = cfn_cdiv(Ql, PFS_PT);
-    // one workgroup per CU is resident: whole rounds of the chip, and few of them (a workgroup splits W^T once and ends with M x K fp64 atomics): measured, 48 -> 108 at
-    // 8 clips x 256 frames: 256 / 512 / 768 / 1024 / 2048 workgroups = 0.495 / 0.471-0.481 / 0.491 / 0.504 / 0.553 ms; 320 (1.25 rounds) 0.619
-    long want = 512 / N;
-    if (want < 1) want = 1;
-    long stages = cfn_cdiv(nst, want);
-    if (stages < 4) stages = 4;
-    a.stages = (int)stages;
-    a.nstrips = (int)cfn_cdiv(nst, stages);
-    const unsigned blocks = (unsigned)((long)N * a.nstrips);
+    a.stages = p.stages;
+    a.nstrips = p.nstrips;
     CfnProfScope prof(CFN_K_PWCONV_BWD, st, 4.0 * N * ((double)Cout * Ql * (a.y ? 2 : 1) + (double)Cin * Ql * 2));
     const bool epi = A != nullptr;
-    if (wide_m) return pfs_launch<4, 2>(a, act, epi, blocks, st);
-    if (thin_k) return pfs_launch<4, 1>(a, act, epi, blocks, st);
-    return pfs_launch<2, 4>(a, act, epi, blocks, st);
+    if (p.t[0] == 4 && p.t[1] == 2) return pfs_launch<4, 2>(a, act, epi, p.blocks, p.lds, st);
+    if (p.t[0] == 4) return pfs_launch<4, 1>(a, act, epi, p.blocks, p.lds, st);
+    return pfs_launch<2, 4>(a, act, epi, p.blocks, p.lds, st);
 }

@@ -355,31 +355,27 @@ __global__ __launch_bounds__(64 * PWK_WAVES) void pwk_kernel(const PwArgs a) {
 }
 
 template <int NKB, int KS>
-static int pwk_go(const PwArgs& a, int mode, bool stats, unsigned blocks, size_t lds, hipStream_t st) {
-#define PWK_GO(...)                                                                                                         \
-    do {                                                                                                                    \
-        auto k = pwk_kernel<NKB, KS, __VA_ARGS__>;                                                                          \
-        if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        hipLaunchKernelGGL(k, dim3(blocks), dim3(64 * PWK_WAVES), lds, st, a);                                              \
-    } while (0)
-    if (mode == PW_DGRAD && stats) {
+static int pwk_go(const PwPlan& p, hipStream_t st) {
+    const PwArgs& a = p.a;
+#define PWK_GO(...) cfn_launch(pwk_kernel<NKB, KS, __VA_ARGS__>, p.blocks, p.threads, p.lds, st, a)
+    if (p.mode == PW_DGRAD && p.stats) {
         if constexpr (KS == 1 && NKB <= 7) {
-            switch (a.act) {
-                case CFN_ACT_RELU: if (a.src2) PWK_GO(PW_DGRAD, CFN_ACT_RELU, true, true); else PWK_GO(PW_DGRAD, CFN_ACT_RELU, true, false); break;
-                case CFN_ACT_SWISH: if (a.src2) PWK_GO(PW_DGRAD, CFN_ACT_SWISH, true, true); else PWK_GO(PW_DGRAD, CFN_ACT_SWISH, true, false); break;
-                default: if (a.src2) PWK_GO(PW_DGRAD, CFN_ACT_NONE, true, true); else PWK_GO(PW_DGRAD, CFN_ACT_NONE, true, false); break;
+            switch (p.act) {
+                case CFN_ACT_RELU: if (p.two) PWK_GO(PW_DGRAD, CFN_ACT_RELU, true, true); else PWK_GO(PW_DGRAD, CFN_ACT_RELU, true, false); break;
+                case CFN_ACT_SWISH: if (p.two) PWK_GO(PW_DGRAD, CFN_ACT_SWISH, true, true); else PWK_GO(PW_DGRAD, CFN_ACT_SWISH, true, false); break;
+                default: if (p.two) PWK_GO(PW_DGRAD, CFN_ACT_NONE, true, true); else PWK_GO(PW_DGRAD, CFN_ACT_NONE, true, false); break;
             }
         }
-    } else if (mode == PW_DGRAD) {
-        if (a.src2) PWK_GO(PW_DGRAD, CFN_ACT_NONE, false, true); else PWK_GO(PW_DGRAD, CFN_ACT_NONE, false, false);
-    } else if (stats) {
-        switch (a.act) {
+    } else if (p.mode == PW_DGRAD) {
+        if (p.two) PWK_GO(PW_DGRAD, CFN_ACT_NONE, false, true); else PWK_GO(PW_DGRAD, CFN_ACT_NONE, false, false);
+    } else if (p.stats) {
+        switch (p.act) {
             case CFN_ACT_RELU: PWK_GO(PW_FWD, CFN_ACT_RELU, true, false); break;
             case CFN_ACT_SWISH: PWK_GO(PW_FWD, CFN_ACT_SWISH, true, false); break;
             default: PWK_GO(PW_FWD, CFN_ACT_NONE, true, false); break;
         }
     } else {
-        switch (a.act) {
+        switch (p.act) {
             case CFN_ACT_RELU: PWK_GO(PW_FWD, CFN_ACT_RELU, false, false); break;
             case CFN_ACT_SWISH: PWK_GO(PW_FWD, CFN_ACT_SWISH, false, false); break;
             default: PWK_GO(PW_FWD, CFN_ACT_NONE, false, false); break;
@@ -389,51 +385,58 @@ static int pwk_go(const PwArgs& a, int mode, bool stats, unsigned blocks, size_t
     return cfn_check_launch("pwconv(split bf16, register-resident weights)");
 }
 
-// returns -1 when the shape is not handled.  DGRAD: only without the act' epilogue (stats == false) and without the compact shortcut gradient
-int pwk_try_launch(PwArgs& a, int mode, bool stats, hipStream_t st) {
-    if (pws_terms_now() != 6 || a.stem || a.stride != 1 || a.acc) return -1;
-    if (mode == PW_DGRAD && stats && !(a.ea && a.ex && a.s1)) return -1;
-    if (a.Q & 3) return -1;
+// false when the shape is not handled.  DGRAD: only without the compact shortcut gradient; with the act' epilogue (stats) only the one-slice shapes
+bool pwk_plan(const PwArgs& a, int mode, bool stats, const PwSwitches& sw, PwPlan& p) {
+    if (sw.split_terms != 6 || a.stem || a.stride != 1 || a.acc) return false;
+    if (mode == PW_DGRAD && stats && !(a.ea && a.ex && a.s1)) return false;
+    if (a.Q & 3) return false;
     const int nkb = cfn_cdiv(a.K, 16);
     int KS;
     if (a.K > 128 && a.K <= 224 && a.M > 32 && a.M <= 128 && !(nkb & 1)) KS = 2;        // two equal slices
     else if (a.K >= 48 && a.K <= (a.M > 256 ? 192 : 112) && a.M > 128 && a.M <= 512 && (mode == PW_FWD || stats)) KS = 1;   // deep + many rows: two slabs
-    else return -1;
-    if (mode == PW_DGRAD && stats && (KS != 1 || a.M > 256)) return -1;     // act' epilogue: one-slice shapes without slabs (192 -> 432 rows: 256 VGPRs + 63 spilled
+    else return false;
+    if (mode == PW_DGRAD && stats && (KS != 1 || a.M > 256)) return false;  // act' epilogue: one-slice shapes without slabs (192 -> 432 rows: 256 VGPRs + 63 spilled
                                                                             // dwords, 0.256 vs 0.260 ms for pw_deep_kernel: not instantiated)
-    if (mode == PW_DGRAD && stats && (((uintptr_t)a.ex) & 15)) return -1;
-    if (a.act != CFN_ACT_NONE && a.act != CFN_ACT_RELU && a.act != CFN_ACT_SWISH) return -1;
-    if ((long)a.K * a.Q * 4 >= 0x3ffffff0L || (long)a.M * a.Q * 4 >= 0x3ffffff0L) return -1;
-    if (((uintptr_t)a.src | (uintptr_t)a.dst | (uintptr_t)(a.src2 ? a.src2 : a.src)) & 15) return -1;
+    if (mode == PW_DGRAD && stats && (p.align_ex & 15)) return false;
+    if (a.act != CFN_ACT_NONE && a.act != CFN_ACT_RELU && a.act != CFN_ACT_SWISH) return false;
+    if ((long)a.K * a.Q * 4 >= 0x3ffffff0L || (long)a.M * a.Q * 4 >= 0x3ffffff0L) return false;
+    if (p.align_io & 15) return false;
     const int KP = 16 * nkb, nrt = cfn_cdiv(a.M, 32), NKS = (nkb + KS - 1) / KS;
     size_t lds = (size_t)2 * 3 * 32 * (KP * 2 + 16) + (size_t)KP * 16 + (size_t)KS * (nrt > 8 ? cfn_cdiv(nrt, cfn_cdiv(nrt, 8)) : nrt) * 2 * 32 * 36 * 4;
     const size_t wtmp = (size_t)PWK_WAVES * (mode == PW_FWD ? 32 * ((NKS > 6 ? 6 : NKS) * 16 + 4) : NKS * 16 * 36) * 4;
     if (wtmp > lds) lds = wtmp;
-    if (lds > 160 * 1024) return -1;
-    PwArgs b = a;
+    if (lds > 160 * 1024) return false;
+    // the instantiated (k-blocks, slices) pairs
+    if (KS == 2 ? (nkb != 10 && nkb != 12 && nkb != 14) : ((nkb < 3 || nkb > 7) && nkb != 12)) return false;
+    p.a = a;
     const int slabs = KS == 1 ? cfn_cdiv(nrt, 8) : 1, rts = cfn_cdiv(nrt, slabs);       // row tiles per slab (<= 8)
-    b.mtiles = slabs; b.kres = KS == 1 ? 32 * rts : a.M;
+    p.a.mtiles = slabs; p.a.kres = KS == 1 ? 32 * rts : a.M;
     const int ntiles = cfn_cdiv(a.Q, 32);
     long wgs = cfn_cdiv(256, (long)a.N * slabs);      // one workgroup per CU (128 / 192 / 256 / 384 / 512: 0.30 / 0.22 / 0.176 / 0.23 / 0.185 ms)
     if (wgs > ntiles) wgs = ntiles;
     if (wgs < 1) wgs = 1;
-    b.nstrips = (int)wgs;
-    const unsigned blocks = (unsigned)((long)a.N * wgs * slabs);
-    if (KS == 2) {
-        switch (nkb) {
-            case 10: return pwk_go<10, 2>(b, mode, stats, blocks, lds, st);
-            case 12: return pwk_go<12, 2>(b, mode, stats, blocks, lds, st);
-            case 14: return pwk_go<14, 2>(b, mode, stats, blocks, lds, st);
-            default: return -1;
+    p.a.nstrips = (int)wgs;
+    p.family = PW_FAM_PWK; p.mode = mode; p.stats = stats; p.two = a.src2 != nullptr;
+    p.act = mode == PW_DGRAD && !stats ? CFN_ACT_NONE : a.act;
+    p.nkb = nkb; p.KS = KS;
+    p.blocks = (unsigned)((long)a.N * wgs * slabs); p.threads = 64 * PWK_WAVES; p.lds = lds;
+    return true;
+}
+
+int pwk_launch(const PwPlan& p, hipStream_t st) {
+    if (p.KS == 2) {
+        switch (p.nkb) {
+            case 10: return pwk_go<10, 2>(p, st);
+            case 12: return pwk_go<12, 2>(p, st);
+            default: return pwk_go<14, 2>(p, st);
         }
     }
-    switch (nkb) {
-        case 3: return pwk_go<3, 1>(b, mode, stats, blocks, lds, st);
-        case 4: return pwk_go<4, 1>(b, mode, stats, blocks, lds, st);
-        case 5: return pwk_go<5, 1>(b, mode, stats, blocks, lds, st);
-        case 6: return pwk_go<6, 1>(b, mode, stats, blocks, lds, st);
-        case 7: return pwk_go<7, 1>(b, mode, stats, blocks, lds, st);
-        case 12: return pwk_go<12, 1>(b, mode, stats, blocks, lds, st);
-        default: return -1;
+    switch (p.nkb) {
+        case 3: return pwk_go<3, 1>(p, st);
+        case 4: return pwk_go<4, 1>(p, st);
+        case 5: return pwk_go<5, 1>(p, st);
+        case 6: return pwk_go<6, 1>(p, st);
+        case 7: return pwk_go<7, 1>(p, st);
+        default: return pwk_go<12, 1>(p, st);
     }
 }

@@ -269,35 +269,70 @@ __global__ __launch_bounds__(64 * WM * WP, OCC) void pw_short_bwd_kernel(const P
 }
 
 template <int MT, int NT, int KT16, int KS, int WM, int WP, int PSH_PT, int OCC>
-static int psh_launch(PshArgs& a, int act, int vec, hipStream_t st) {
-    constexpr int BM = 32 * MT, BN = 32 * NT, PSH_PITCH = PSH_PT + 1;
-    size_t lds = ((size_t)2 * (BM + BN) * PSH_PITCH + 3 * BM) * sizeof(float);
+static int psh_go(const PshArgs& a, const PwBwdPlan& p, hipStream_t st) {
+    const unsigned blocks = p.blocks;
+    const size_t lds = p.lds;
+#define CFN_PSH_GO(VECV, ACTV) cfn_launch(pw_short_bwd_kernel<MT, NT, KT16, KS, WM, WP, PSH_PT, VECV, ACTV, OCC>, blocks, 64 * WM * WP, lds, st, a)
+    const bool relu = p.act == CFN_ACT_RELU;
+    if (p.vec == 2) { if (relu) CFN_PSH_GO(2, CFN_ACT_RELU); else CFN_PSH_GO(2, CFN_ACT_NONE); }
+    else if (p.vec == 1) { if (relu) CFN_PSH_GO(1, CFN_ACT_RELU); else CFN_PSH_GO(1, CFN_ACT_NONE); }
+    else { if (relu) CFN_PSH_GO(0, CFN_ACT_RELU); else CFN_PSH_GO(0, CFN_ACT_NONE); }
+#undef CFN_PSH_GO
+    return cfn_check_launch("pwconv_short_bwd");
+}
+
+// false = declined (callers use the two separate entry points).  t[] = MT NT KT16 KS WM WP PT OCC of the variant
+bool psh_plan(const PwBwdShape& s, const PwSwitches& sw, PwBwdPlan& p) {
+    if (s.stride != 2) return false;
+    if (!sw.pw_short) return false;      // 0 = the two separate kernels
+    if (s.pro && s.act != CFN_ACT_NONE && s.act != CFN_ACT_RELU) return false;
+    if (s.Cout > 192 || s.Cin > 96) return false;
+    const int Ho = (s.Hi - 1) / 2 + 1, Wo = (s.Wi - 1) / 2 + 1;
+    const long Ql = (long)s.T * Ho * Wo, Pl = (long)s.T * s.Hi * s.Wi;
+    const int big = s.Cout > s.Cin ? s.Cout : s.Cin;
+    if ((long)big * Pl * 4 >= 0x7ffffff0L || s.N > 65535) return false;       // 32-bit buffer offsets per sample
+    if ((s.align_g | s.align_x | s.align_out) & 3) return false;
+    // 16-byte loads: rows of gy / y start on 16 bytes (Q % 4); for x also: a position pair never straddles a row (Wo even), even input
+    // rows start on 16 bytes (Wi even, Hi*Wi % 4) and every fourth column holds two lattice points
+    const bool gvec = Ql % 4 == 0 && (s.align_g & 15) == 0;
+    const bool xvec = Wo % 2 == 0 && s.Wi % 2 == 0 && ((long)s.Hi * s.Wi) % 4 == 0 && (s.align_x & 15) == 0;
+    //                                 MT NT KT16 KS WM WP PT OCC
+    static const int variants[4][8] = {{1, 1, 2, 6, 1, 4, 64, 3},        // layer 1: 24 -> 24
+                                       {2, 1, 2, 12, 1, 4, 64, 2},       // layer 2: 24 -> 48
+                                       {3, 2, 3, 24, 3, 2, 64, 1},       // layer 3: 48 -> 96
+                                       {6, 3, 6, 48, 6, 1, 32, 1}};      // layer 4: 96 -> 192
+    const int v = s.Cout <= 24 && s.Cin <= 32 ? 0 : (s.Cout <= 48 && s.Cin <= 32 ? 1 : (s.Cout <= 96 && s.Cin <= 48 ? 2 : 3));
+    const int* t = variants[v];
+    for (int i = 0; i < 8; ++i) p.t[i] = t[i];
+    const int BM = 32 * t[0], BN = 32 * t[1], WP = t[5], PT = t[6], OCC = t[7];
+    size_t lds = ((size_t)2 * (BM + BN) * (PT + 1) + 3 * BM) * sizeof(float);
     const size_t lds_cw = (size_t)WP * BM * (BN + 1) * sizeof(float);
     if (lds_cw > lds) lds = lds_cw;
     // whole rounds of the 256 CUs (OCC workgroups resident per CU): two rounds where a workgroup still gets >= 16 stages, else one;
     // a partly filled extra round costs a full one (pwfused.hip)
-    const long nst = cfn_cdiv(a.Q, PSH_PT);
+    const long nst = cfn_cdiv(Ql, PT);
     const long slots = 256L * OCC;
-    const long rounds = (nst * a.N >= slots * 2 * 16) ? 2 : 1;
-    long want = slots * rounds / a.N;
+    const long rounds = (nst * s.N >= slots * 2 * 16) ? 2 : 1;
+    long want = slots * rounds / s.N;
     if (want < 1) want = 1;
     long stages = cfn_cdiv(nst, want);
     if (stages < 4) stages = 4;
-    a.stages = (int)stages;
-    a.nstrips = cfn_cdiv(nst, stages);
-    const unsigned blocks = (unsigned)((long)a.N * a.nstrips);
-#define CFN_PSH_GO(VECV, ACTV)                                                                                  \
-    do {                                                                                                        \
-        auto k = pw_short_bwd_kernel<MT, NT, KT16, KS, WM, WP, PSH_PT, VECV, ACTV, OCC>;                                \
-        if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        hipLaunchKernelGGL(k, dim3(blocks), dim3(64 * WM * WP), lds, st, a);                                    \
-    } while (0)
-    const bool relu = act == CFN_ACT_RELU;
-    if (vec == 2) { if (relu) CFN_PSH_GO(2, CFN_ACT_RELU); else CFN_PSH_GO(2, CFN_ACT_NONE); }
-    else if (vec == 1) { if (relu) CFN_PSH_GO(1, CFN_ACT_RELU); else CFN_PSH_GO(1, CFN_ACT_NONE); }
-    else { if (relu) CFN_PSH_GO(0, CFN_ACT_RELU); else CFN_PSH_GO(0, CFN_ACT_NONE); }
-#undef CFN_PSH_GO
-    return cfn_check_launch("pwconv_short_bwd");
+    p.family = PW_FAM_PSH; p.variant = v;
+    p.stages = (int)stages;
+    p.nstrips = (int)cfn_cdiv(nst, stages);
+    p.blocks = (unsigned)((long)s.N * p.nstrips); p.threads = 64 * t[4] * t[5]; p.lds = lds;
+    p.vec = gvec ? (xvec ? 2 : 1) : 0;
+    p.act = s.pro && s.act == CFN_ACT_RELU ? CFN_ACT_RELU : CFN_ACT_NONE;
+    return true;
+}
+
+static int psh_launch(const PwBwdPlan& p, const PshArgs& a, hipStream_t st) {
+    switch (p.variant) {
+        case 0: return psh_go<1, 1, 2, 6, 1, 4, 64, 3>(a, p, st);
+        case 1: return psh_go<2, 1, 2, 12, 1, 4, 64, 2>(a, p, st);
+        case 2: return psh_go<3, 2, 3, 24, 3, 2, 64, 1>(a, p, st);
+        default: return psh_go<6, 3, 6, 48, 6, 1, 32, 1>(a, p, st);
+    }
 }
 
 extern "C" int cfn_pwconv_short_bwd(const float* gy, const float* y, const double* gsum, const double* gsumsq, const double* gscale,
@@ -307,31 +342,20 @@ extern "C" int cfn_pwconv_short_bwd(const float* gy, const float* y, const doubl
     CFN_REQUIRE((A == nullptr) == (B == nullptr), "cfn_pwconv_short_bwd: A/B mismatch");
     CFN_REQUIRE(gsumsq == nullptr || y != nullptr, "cfn_pwconv_short_bwd: gsumsq needs y");
     CFN_REQUIRE(N > 0 && Cin > 0 && Cout > 0 && T > 0 && Hi > 0 && Wi > 0 && stride >= 1, "cfn_pwconv_short_bwd: bad shape");
-    if (stride != 2) return -1;
-    { const char* e = getenv("CFN_PW_SHORT"); if (e && e[0] && atoi(e) == 0) return -1; }      // read per call: 0 = the two separate kernels
-    if (A && act != CFN_ACT_NONE && act != CFN_ACT_RELU) return -1;
-    if (Cout > 192 || Cin > 96) return -1;
+    PwBwdShape s = {N, Cin, Cout, T, Hi, Wi, stride, act};
+    s.pro = A != nullptr;
+    s.align_g = (unsigned)(((uintptr_t)gy | (uintptr_t)(y ? y : gy)) & 15); s.align_x = (unsigned)((uintptr_t)x & 15); s.align_out = (unsigned)((uintptr_t)da & 15);
+    PwBwdPlan p = {};
+    if (!pw_route_short(s, pw_switches_now(true), p)) return -1;
     const int Ho = (Hi - 1) / 2 + 1, Wo = (Wi - 1) / 2 + 1;
     const long Ql = (long)T * Ho * Wo, Pl = (long)T * Hi * Wi;
-    const int big = Cout > Cin ? Cout : Cin;
-    if ((long)big * Pl * 4 >= 0x7ffffff0L || N > 65535) return -1;       // 32-bit buffer offsets per sample
-    if ((((uintptr_t)gy | (uintptr_t)x | (uintptr_t)da | (uintptr_t)(y ? y : gy)) & 3) != 0) return -1;
-    // 16-byte loads: rows of gy / y start on 16 bytes (Q % 4); for x also: a position pair never straddles a row (Wo even), even input
-    // rows start on 16 bytes (Wi even, Hi*Wi % 4) and every fourth column holds two lattice points
-    const bool gvec = Ql % 4 == 0 && (((uintptr_t)gy | (uintptr_t)(y ? y : gy)) & 15) == 0;
-    const bool xvec = Wo % 2 == 0 && Wi % 2 == 0 && ((long)Hi * Wi) % 4 == 0 && ((uintptr_t)x & 15) == 0;
-    const int vec = gvec ? (xvec ? 2 : 1) : 0;
     PshArgs a = {};
     a.gy = gy; a.y = gsumsq ? y : nullptr; a.gs = gsum; a.gq = gsumsq; a.gsc = gscale; a.w = w; a.x = x; a.pa = A; a.pb = B;
     a.da = da; a.gw = gw;
     a.N = N; a.M = Cout; a.K = Cin; a.Q = (int)Ql; a.P = (int)Pl;
     a.HiWi = Hi * Wi; a.Wi = Wi; a.HoWo = Ho * Wo; a.Wo = Wo;
-    const int pact = A ? act : CFN_ACT_NONE;
+    a.stages = p.stages; a.nstrips = p.nstrips;
     hipStream_t st = (hipStream_t)stream;
     CfnProfScope prof(CFN_K_PWCONV_BWD, st, 4.0 * N * ((double)Cout * Ql * (a.y ? 2 : 1) + (double)Cin * Ql * 3));
-    //                          MT NT KT16 KS WM WP PT OCC
-    if (Cout <= 24 && Cin <= 32) return psh_launch<1, 1, 2, 6, 1, 4, 64, 3>(a, pact, vec, st);       // layer 1: 24 -> 24
-    if (Cout <= 48 && Cin <= 32) return psh_launch<2, 1, 2, 12, 1, 4, 64, 2>(a, pact, vec, st);      // layer 2: 24 -> 48
-    if (Cout <= 96 && Cin <= 48) return psh_launch<3, 2, 3, 24, 3, 2, 64, 1>(a, pact, vec, st);      // layer 3: 48 -> 96
-    return psh_launch<6, 3, 6, 48, 6, 1, 32, 1>(a, pact, vec, st);                                   // layer 4: 96 -> 192
+    return psh_launch(p, a, st);
 }

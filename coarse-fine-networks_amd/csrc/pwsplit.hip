@@ -5,39 +5,19 @@
 // ---------------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------------
-static int g_pws_terms = -1;      // 0 = off (fp32 MFMA kernels), 3 / 6 = MFMAs per k-block
-int pws_terms_now() {
-    if (g_pws_terms < 0) {
-        const char* e = getenv("CFN_PW_SPLIT");
-        g_pws_terms = e ? atoi(e) : 6;
-        if (g_pws_terms != 0 && g_pws_terms != 3 && g_pws_terms != 6) g_pws_terms = 6;
-    }
-    return g_pws_terms;
-}
-extern "C" int cfn_pw_split_terms(int terms) {
-    const int prev = pws_terms_now();
-    if (terms == 0 || terms == 3 || terms == 6) g_pws_terms = terms;
-    else if (terms != -1) return cfn_fail(CFN_ERR_ARG, "cfn_pw_split_terms: terms must be 0 (fp32 MFMA), 3 or 6 (or -1 to query)"), -2;
-    return prev;
-}
-
 static size_t pws_lds(int BM, int Kp, int rowb, int NS) {
     const size_t red = (size_t)PWS_WAVES * 4 * (BM * 2 > 32 * 20 ? BM * 2 : 32 * 20);
     return (size_t)NS * BM * rowb + (size_t)Kp * 16 + (size_t)BM * 8 + red;
 }
 
 template <int MODE, bool STATS, int ACT, bool TWO, int NS>
-static int pws_go_mt(const PwArgs& a, int MT, int NP, unsigned blocks, size_t lds, hipStream_t st) {
-#define PWS_GO(MTV, NPV)                                                                                                   \
-    do {                                                                                                                   \
-        auto k = pws_kernel<MTV, NPV, MODE, STATS, ACT, TWO, NS>;                                                          \
-        if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        hipLaunchKernelGGL(k, dim3(blocks), dim3(64 * PWS_WAVES), lds, st, a);                                             \
-    } while (0)
-    // pws_try_launch's plan reaches exactly these tiles.  64 positions (NP = 2): one slab of more than 32 rows, or two slabs of more than
+static int pws_go_mt(const PwPlan& p, hipStream_t st) {
+#define PWS_GO(MTV, NPV) cfn_launch(pws_kernel<MTV, NPV, MODE, STATS, ACT, TWO, NS>, p.blocks, p.threads, p.lds, st, p.a)
+    // pws_plan reaches exactly these tiles.  64 positions (NP = 2): one slab of more than 32 rows, or two slabs of more than
     // 32 * mt2 rows together, so MT >= 2.  32 positions (NP = 1) are chosen only where they save a slab over NP = 2: with one staged tensor
     // that takes more than 96 rows (MT >= 4), with two more than 64 (MT >= 3).
-    if (NP == 1) {      // 32-position tiles: the many-row slabs
+    const int MT = p.MT;
+    if (p.NP == 1) {      // 32-position tiles: the many-row slabs
         if constexpr (MODE == PW_DGRAD && TWO) {
             switch (MT) { case 3: PWS_GO(3, 1); break; case 4: PWS_GO(4, 1); break; case 5: PWS_GO(5, 1); break; default: PWS_GO(6, 1); break; }
         } else {
@@ -53,43 +33,39 @@ static int pws_go_mt(const PwArgs& a, int MT, int NP, unsigned blocks, size_t ld
 }
 
 template <int MODE, bool STATS, bool TWO, int NS>
-static int pws_go_act(const PwArgs& a, int MT, int NP, unsigned blocks, size_t lds, hipStream_t st) {
+static int pws_go_act(const PwPlan& p, hipStream_t st) {
     if constexpr (MODE == PW_DGRAD && !STATS) {
-        return pws_go_mt<MODE, STATS, CFN_ACT_NONE, TWO, NS>(a, MT, NP, blocks, lds, st);
+        return pws_go_mt<MODE, STATS, CFN_ACT_NONE, TWO, NS>(p, st);
     } else {
-        switch (a.act) {
-            case CFN_ACT_RELU: return pws_go_mt<MODE, STATS, CFN_ACT_RELU, TWO, NS>(a, MT, NP, blocks, lds, st);
-            case CFN_ACT_SWISH: return pws_go_mt<MODE, STATS, CFN_ACT_SWISH, TWO, NS>(a, MT, NP, blocks, lds, st);
-            default: return pws_go_mt<MODE, STATS, CFN_ACT_NONE, TWO, NS>(a, MT, NP, blocks, lds, st);
+        switch (p.act) {
+            case CFN_ACT_RELU: return pws_go_mt<MODE, STATS, CFN_ACT_RELU, TWO, NS>(p, st);
+            case CFN_ACT_SWISH: return pws_go_mt<MODE, STATS, CFN_ACT_SWISH, TWO, NS>(p, st);
+            default: return pws_go_mt<MODE, STATS, CFN_ACT_NONE, TWO, NS>(p, st);
         }
     }
 }
 
 template <int NS>
-static int pws_go(const PwArgs& a, int mode, bool stats, int MT, int NP, unsigned blocks, size_t lds, hipStream_t st) {
-    if (mode == PW_FWD) return stats ? pws_go_act<PW_FWD, true, false, NS>(a, MT, NP, blocks, lds, st) : pws_go_act<PW_FWD, false, false, NS>(a, MT, NP, blocks, lds, st);
-    if (a.src2) return stats ? pws_go_act<PW_DGRAD, true, true, NS>(a, MT, NP, blocks, lds, st) : pws_go_act<PW_DGRAD, false, true, NS>(a, MT, NP, blocks, lds, st);
-    return stats ? pws_go_act<PW_DGRAD, true, false, NS>(a, MT, NP, blocks, lds, st) : pws_go_act<PW_DGRAD, false, false, NS>(a, MT, NP, blocks, lds, st);
+static int pws_go(const PwPlan& p, hipStream_t st) {
+    if (p.mode == PW_FWD) return p.stats ? pws_go_act<PW_FWD, true, false, NS>(p, st) : pws_go_act<PW_FWD, false, false, NS>(p, st);
+    if (p.two) return p.stats ? pws_go_act<PW_DGRAD, true, true, NS>(p, st) : pws_go_act<PW_DGRAD, false, true, NS>(p, st);
+    return p.stats ? pws_go_act<PW_DGRAD, true, false, NS>(p, st) : pws_go_act<PW_DGRAD, false, false, NS>(p, st);
 }
 
-// returns -1 when the shape is not handled (caller falls through to the fp32-MFMA kernels), otherwise the launch status.
+// false when the shape is not handled (the fp32-MFMA kernels take it).
 // FWD prologue: pa == nullptr means A = 1, B = 0 (act still applies, as in the fp32-MFMA kernels); DGRAD: stats == (ea != nullptr)
-int pws_try_launch(PwArgs& a, int mode, bool stats, hipStream_t st) {
-    const int terms = pws_terms_now();
-    if (terms == 0) return -1;
-    // the compact shortcut gradient `acc` (first block of a stage: 3 calls per step) stays on the fp32-MFMA kernel: its lattice
-    // loads cost the many-row variants 90+ registers
-    if (a.stem || a.stride != 1 || a.K < 48 || a.M <= 32 || (a.Q & 3) || a.acc) return -1;      // Q % 4: whole 16-byte groups
-    if (a.act != CFN_ACT_NONE && a.act != CFN_ACT_RELU && a.act != CFN_ACT_SWISH) return -1;
-    // The split costs VALU work per CONTRACTION-side element (prologue + 9 instructions per pair for three terms) and saves matrix
-    // time per product: measured (8 clips, T = 256, profiles/r03_microbench_b8.txt) it wins up to K = 108 (layer 2 both convs,
-    // layer 3 conv1 forward 0.18 vs 0.21 ms, conv3 data gradient 0.24 vs 0.33 ms) and loses from K = 216 on (layer 3 conv3
-    // forward 0.22-0.26 vs 0.20 ms): those stay on the fp32-MFMA kernel
-    if (a.K > 128) return -1;
-    if ((long)a.K * a.Q * 4 >= 0x3ffffff0L || (long)a.M * a.Q * 4 >= 0x3ffffff0L) return -1;
-    if (((uintptr_t)a.src | (uintptr_t)a.dst | (uintptr_t)(a.src2 ? a.src2 : a.src) | (uintptr_t)(a.ex ? a.ex : a.src)) & 15) return -1;
+bool pws_plan(const PwArgs& a, int mode, bool stats, const PwSwitches& sw, PwPlan& p) {
+    const int terms = sw.split_terms;
+    if (terms == 0) return false;
+    // (why K <= 128, M > 32 and no `acc`: the table of pwroute.hip)
+    if (a.stem || a.stride != 1 || a.K < 48 || a.M <= 32 || (a.Q & 3) || a.acc) return false;      // Q % 4: whole 16-byte groups
+    if (a.act != CFN_ACT_NONE && a.act != CFN_ACT_RELU && a.act != CFN_ACT_SWISH) return false;
+    if (a.K > 128) return false;
+    if ((long)a.K * a.Q * 4 >= 0x3ffffff0L || (long)a.M * a.Q * 4 >= 0x3ffffff0L) return false;
+    if ((p.align_io | p.align_ex) & 15) return false;
     const int NS = terms == 3 ? 2 : 3;
-    PwArgs b = a;
+    PwArgs& b = p.a;
+    b = a;
     b.Kpad = (a.K + 47) / 48 * 48;
     b.kres = b.Kpad * 2 + 16;
     if (((b.kres / 16) & 1) == 0) b.kres += 16;                          // odd number of 16-byte slots per row
@@ -100,7 +76,7 @@ int pws_try_launch(PwArgs& a, int mode, bool stats, hipStream_t st) {
     // LDS.  Fewer slabs win (every extra slab re-reads the activations), then the wider tile.
     auto fit = [&](int mt) { while (mt > 0 && pws_lds(32 * mt, b.Kpad, b.kres, NS) > 160 * 1024) --mt; return mt; };
     const int mt2 = fit(mode == PW_FWD ? 3 : (a.src2 ? 2 : 3)), mt1 = fit(mode == PW_DGRAD && a.src2 ? 6 : 7);
-    if (mt2 < 1) return -1;
+    if (mt2 < 1) return false;
     int NP = 2, mt_max = mt2;
     if (mt1 >= 3 && cfn_cdiv(a.M, 32 * mt1) < cfn_cdiv(a.M, 32 * mt2)) { NP = 1; mt_max = mt1; }
     int slabs = cfn_cdiv(a.M, 32 * mt_max);
@@ -110,9 +86,8 @@ int pws_try_launch(PwArgs& a, int mode, bool stats, hipStream_t st) {
     slabs = cfn_cdiv(a.M, 32 * MT);
     // three or more slabs (X3D layer 4: the weight images of 432 x 192 do not fit LDS in fewer) re-read every activation that
     // often: measured slower than the fp32-MFMA kernel with its 4-byte weight image (0.19-0.31 vs 0.20-0.24 ms) -- declined
-    if (slabs > 2) return -1;
+    if (slabs > 2) return false;
     b.mtiles = slabs;
-    const size_t lds = pws_lds(32 * MT, b.Kpad, b.kres, NS);
     const int ntiles = cfn_cdiv(a.Q, 32 * NP);
     const long groups = (long)a.N * slabs;
     long wgs = cfn_cdiv(256, groups);              // one 8-wave workgroup per CU (up to 256 VGPRs)
@@ -120,6 +95,10 @@ int pws_try_launch(PwArgs& a, int mode, bool stats, hipStream_t st) {
     if (wgs > maxw) wgs = maxw;
     if (wgs < 1) wgs = 1;
     b.nstrips = (int)wgs;
-    const unsigned blocks = (unsigned)(groups * wgs);
-    return NS == 2 ? pws_go<2>(b, mode, stats, MT, NP, blocks, lds, st) : pws_go<3>(b, mode, stats, MT, NP, blocks, lds, st);
+    p.family = PW_FAM_PWS; p.mode = mode; p.stats = stats; p.two = a.src2 != nullptr; p.act = b.act;
+    p.MT = MT; p.NP = NP; p.NS = NS;
+    p.blocks = (unsigned)(groups * wgs); p.threads = 64 * PWS_WAVES; p.lds = pws_lds(32 * MT, b.Kpad, b.kres, NS);
+    return true;
 }
+
+int pws_launch(const PwPlan& p, hipStream_t st) { return p.NS == 2 ? pws_go<2>(p, st) : pws_go<3>(p, st); }

@@ -555,13 +555,8 @@ static size_t pwss_lds(int mtg, int ktg, int NS) {
 }
 
 template <int SM, int TPW, int NS, int ES = 4, int BR = 0, int BC = 0, bool PIPE = false>
-static int pwss_launch(const WssArgs& a, unsigned blocks, size_t lds, hipStream_t st) {
-#define PWSS_GO(AV, HY)                                                                                                    \
-    do {                                                                                                                   \
-        auto k = pws_wgrad_staged_kernel<SM, TPW, AV, HY, NS, ES, BR, BC, PIPE>;                                                           \
-        if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        hipLaunchKernelGGL(k, dim3(blocks), dim3(PWSS_THREADS), lds, st, a);                                               \
-    } while (0)
+static int pwss_go(const WssArgs& a, unsigned blocks, size_t lds, hipStream_t st) {
+#define PWSS_GO(AV, HY) cfn_launch(pws_wgrad_staged_kernel<SM, TPW, AV, HY, NS, ES, BR, BC, PIPE>, blocks, PWSS_THREADS, lds, st, a)
 #define PWSS_ACT(HY)                                                                                                       \
     do {                                                                                                                   \
         if (a.act == CFN_ACT_RELU) PWSS_GO(CFN_ACT_RELU, HY);                                                              \
@@ -574,78 +569,95 @@ static int pwss_launch(const WssArgs& a, unsigned blocks, size_t lds, hipStream_
     return cfn_check_launch("pwconv_bwd_weight(split bf16, staged)");
 }
 
-static int pwss_launch_any(const WssArgs& a, unsigned blocks, size_t lds, int tiles, int NS, hipStream_t st);
-
-// -1 = shape not handled
-// terms: 3 / 6 (fp32 tensors, split), 1 (bf16 tensors)
-static int pwss_try(const void* gy, const void* y, const double* gs, const double* gq, const double* gsc, const void* x,
-                    const double* pa, const double* pb, int act, double* gw, int N, int M, int K, int Q, int terms, hipStream_t st) {
+// The staged weight gradient's plan: tile groups, strips, kernel variant.  terms: 3 / 6 (fp32 tensors, split), 1 (bf16 tensors).  false = no tile
+// grouping fits a workgroup.  t[] = SM, TPW, NS, ES, BR, BC, PIPE of the variant; ws_bytes = 0: every workgroup adds with fp64 atomics
+static bool pwss_plan(int N, int M, int K, int Q, bool has_y, int terms, PwBwdPlan& p) {
     const int NS = terms == 1 ? 1 : (terms == 3 ? 2 : 3);
-    WssArgs a = {gy, gq ? y : nullptr, gs, gq, gsc, x, pa, pb, gw, N, M, K, Q, act};
-    a.mt32 = cfn_cdiv(M, 32); a.kt32 = cfn_cdiv(K, 32);
+    const int mt32 = cfn_cdiv(M, 32), kt32 = cfn_cdiv(K, 32);
     // tile groups: least operand traffic  kgroups * M rows (x2 with y) + mgroups * K rows  under the limits of one workgroup:
     // <= 8 tiles (256 rows) per side, <= 48 tiles, both double-buffered LDS images within 160 KiB
     long best = -1;
-    for (int mg = 1; mg <= a.mt32; ++mg)
-        for (int kg = 1; kg <= a.kt32; ++kg) {
-            const int mtg = cfn_cdiv(a.mt32, mg), ktg = cfn_cdiv(a.kt32, kg);
+    for (int mg = 1; mg <= mt32; ++mg)
+        for (int kg = 1; kg <= kt32; ++kg) {
+            const int mtg = cfn_cdiv(mt32, mg), ktg = cfn_cdiv(kt32, kg);
             if (mtg > 8 || ktg > 8 || mtg * ktg > 48 || pwss_lds(mtg, ktg, NS) > 160 * 1024) continue;
-            const long cost = ((long)kg * M * (a.y ? 2 : 1) + (long)mg * K) * 64 + mg * kg;
-            if (best < 0 || cost < best) { best = cost; a.mgroups = mg; a.kgroups = kg; a.mtg = mtg; a.ktg = ktg; }
+            const long cost = ((long)kg * M * (has_y ? 2 : 1) + (long)mg * K) * 64 + mg * kg;
+            if (best < 0 || cost < best) { best = cost; p.mgroups = mg; p.kgroups = kg; p.mtg = mtg; p.ktg = ktg; }
         }
-    if (best < 0) return -1;
-    const long groups = (long)N * a.mgroups * a.kgroups;
+    if (best < 0) return false;
+    const long groups = (long)N * p.mgroups * p.kgroups;
     long strips = 256 / groups;          // one 8-wave workgroup per CU
     if (strips < 1) strips = 1;
     const long maxs = cfn_cdiv(Q, 4 * PWSS_P);                    // >= 4 half-stages per strip
     if (strips > maxs) strips = maxs;
-    a.per = cfn_cdiv(cfn_cdiv(Q, strips), PWSS_P) * PWSS_P;
-    a.nstrips = cfn_cdiv(Q, a.per);
-    const unsigned blocks = (unsigned)(groups * a.nstrips);
-    const size_t lds = pwss_lds(a.mtg, a.ktg, NS);
-    const int tiles = a.mtg * a.ktg;
+    p.per = cfn_cdiv(cfn_cdiv(Q, strips), PWSS_P) * PWSS_P;
+    p.nstrips = cfn_cdiv(Q, p.per);
+    p.blocks = (unsigned)(groups * p.nstrips); p.threads = PWSS_THREADS;
+    p.lds = pwss_lds(p.mtg, p.ktg, NS);
+    const int tiles = p.mtg * p.ktg;
     // (without a workspace -- few workgroups, or a stream under capture -- every workgroup adds with fp64 atomics)
-    a.ws = N * a.nstrips >= 8 ? pwss_workspace((size_t)blocks * tiles * 4096, st) : nullptr;
-    const int rc1 = pwss_launch_any(a, blocks, lds, tiles, NS, st);
-    if (rc1 != 0 || !a.ws) return rc1;
-    hipLaunchKernelGGL(pws_wgrad_reduce_kernel, dim3((unsigned)(a.mgroups * a.kgroups * tiles * 4)), dim3(1024), 0, st, a);
-    return cfn_check_launch("pwconv_bwd_weight(split bf16, staged) reduce");
-}
-
-static int pwss_launch_any(const WssArgs& a, unsigned blocks, size_t lds, int tiles, int NS, hipStream_t st) {
-    if (NS == 1) {
-        if (a.mtg <= 4 && a.ktg <= 4) return pwss_launch<2, 2, 1, 2>(a, blocks, lds, st);
-        if (tiles <= 24) return pwss_launch<4, 3, 1, 2>(a, blocks, lds, st);
-        return pwss_launch<4, 6, 1, 2>(a, blocks, lds, st);
-    }
+    p.ws_bytes = N * p.nstrips >= 8 ? (size_t)p.blocks * tiles * 4096 : 0;
+    const bool small = p.mtg <= 4 && p.ktg <= 4;
+    int v;      // index into pwss_launch's list
+    if (NS == 1) v = small ? 0 : (tiles <= 24 ? 1 : 2);
     // <= 8 tiles (layer 2: 48 x 108): ONE tile per wave -- with two per wave only four of the eight waves multiply while the other four only stage
     // operands a phase ahead of them: idle matrix pipes, and the configuration of the round-3 race (a staging-only wave's packed FMA read
     // a just-returned LDS coefficient as zero in lanes 48-63; the coefficients are registers now and uneven groups keep every wave in one phase)
-    if (a.mtg <= 4 && a.ktg <= 4 && tiles <= 8) return NS == 2 ? pwss_launch<2, 1, 2>(a, blocks, lds, st) : pwss_launch<2, 1, 3>(a, blocks, lds, st);
-    if (a.mtg <= 4 && a.ktg <= 4) return NS == 2 ? pwss_launch<2, 2, 2>(a, blocks, lds, st) : pwss_launch<2, 2, 3>(a, blocks, lds, st);
-    if (tiles <= 24) {
-        // blocks of 1 x 3 / 3 x 1 tiles per wave where the group's grid fits the 8 waves (layer 3: 7 x 3 / 3 x 7 tiles, layer 4: 4 x 6 / 3 x 7)
-        // Every grid that gets here fits one of the two: a side of 5..8 tiles leaves the other at most 4 (<= 24 tiles), and of
-        // (5..8) x (1..3) the first holds, of (5, 6) x 4 the second (2 x 4 blocks), likewise with the sides swapped.
-        if (NS == 2) return pwss_launch<4, 3, 2>(a, blocks, lds, st);
-        if (a.mtg * cfn_cdiv(a.ktg, 3) <= 8) return pwss_launch<4, 3, 3, 4, 1, 3, true>(a, blocks, lds, st);
-        return pwss_launch<4, 3, 3, 4, 3, 1, true>(a, blocks, lds, st);
-    }
-    return NS == 2 ? pwss_launch<4, 6, 2>(a, blocks, lds, st) : pwss_launch<4, 6, 3>(a, blocks, lds, st);
+    else if (small && tiles <= 8) v = 3;
+    else if (small) v = 4;
+    // blocks of 1 x 3 / 3 x 1 tiles per wave where the group's grid fits the 8 waves (layer 3: 7 x 3 / 3 x 7 tiles, layer 4: 4 x 6 / 3 x 7)
+    // Every grid that gets here fits one of the two: a side of 5..8 tiles leaves the other at most 4 (<= 24 tiles), and of
+    // (5..8) x (1..3) the first holds, of (5, 6) x 4 the second (2 x 4 blocks), likewise with the sides swapped.
+    else if (tiles <= 24) v = NS == 2 ? 5 : (p.mtg * cfn_cdiv(p.ktg, 3) <= 8 ? 6 : 7);
+    else v = 8;
+    static const int targs[9][7] = {{2, 2, 1, 2, 0, 0, 0}, {4, 3, 1, 2, 0, 0, 0}, {4, 6, 1, 2, 0, 0, 0}, {2, 1, 0, 4, 0, 0, 0}, {2, 2, 0, 4, 0, 0, 0},
+                                    {4, 3, 2, 4, 0, 0, 0}, {4, 3, 3, 4, 1, 3, 1}, {4, 3, 3, 4, 3, 1, 1}, {4, 6, 0, 4, 0, 0, 0}};
+    for (int i = 0; i < 7; ++i) p.t[i] = targs[v][i];
+    p.t[2] = NS;
+    p.family = PW_FAM_PSS; p.variant = v; p.two = has_y;
+    return true;
 }
 
-extern "C" int cfn_pw_split_terms(int terms);
+// launches what the plan says; no workspace (stream under capture) = atomics, not a decline
+static int pwss_launch(const PwBwdPlan& p, WssArgs a, hipStream_t st) {
+    a.mt32 = cfn_cdiv(a.M, 32); a.kt32 = cfn_cdiv(a.K, 32);
+    a.mgroups = p.mgroups; a.kgroups = p.kgroups; a.mtg = p.mtg; a.ktg = p.ktg; a.per = p.per; a.nstrips = p.nstrips;
+    a.ws = p.ws_bytes ? pwss_workspace(p.ws_bytes, st) : nullptr;
+    const unsigned blocks = p.blocks;
+    const size_t lds = p.lds;
+    const int NS = p.t[2];
+    int rc1;
+    switch (p.variant) {
+        case 0: rc1 = pwss_go<2, 2, 1, 2>(a, blocks, lds, st); break;
+        case 1: rc1 = pwss_go<4, 3, 1, 2>(a, blocks, lds, st); break;
+        case 2: rc1 = pwss_go<4, 6, 1, 2>(a, blocks, lds, st); break;
+        case 3: rc1 = NS == 2 ? pwss_go<2, 1, 2>(a, blocks, lds, st) : pwss_go<2, 1, 3>(a, blocks, lds, st); break;
+        case 4: rc1 = NS == 2 ? pwss_go<2, 2, 2>(a, blocks, lds, st) : pwss_go<2, 2, 3>(a, blocks, lds, st); break;
+        case 5: rc1 = pwss_go<4, 3, 2>(a, blocks, lds, st); break;
+        case 6: rc1 = pwss_go<4, 3, 3, 4, 1, 3, true>(a, blocks, lds, st); break;
+        case 7: rc1 = pwss_go<4, 3, 3, 4, 3, 1, true>(a, blocks, lds, st); break;
+        default: rc1 = NS == 2 ? pwss_go<4, 6, 2>(a, blocks, lds, st) : pwss_go<4, 6, 3>(a, blocks, lds, st); break;
+    }
+    if (rc1 != 0 || !a.ws) return rc1;
+    hipLaunchKernelGGL(pws_wgrad_reduce_kernel, dim3((unsigned)(a.mgroups * a.kgroups * p.mtg * p.ktg * 4)), dim3(1024), 0, st, a);
+    return cfn_check_launch("pwconv_bwd_weight(split bf16, staged) reduce");
+}
 
-// contiguous pointwise conv (stride 1), M, K >= 48; -1 = not handled (caller falls through to the fp32-MFMA kernels)
-int pws_wgrad_try_launch(const float* gy, const float* y, const double* gs, const double* gq, const double* gsc, const float* x,
-                         const double* pa, const double* pb, int act, double* gw, int N, int M, int K, int Q, hipStream_t st) {
-    const int terms = cfn_pw_split_terms(-1);
-    if (terms == 0 || M < 48 || K < 48) return -1;
-    if (act != CFN_ACT_NONE && act != CFN_ACT_RELU && act != CFN_ACT_SWISH) return -1;
-    if (((uintptr_t)gy | (uintptr_t)(y ? y : gy) | (uintptr_t)x) & 15) return -1;
-    if ((long)M * Q * 4 >= (1L << 31) - 64 || (long)K * Q * 4 >= (1L << 31) - 64) return -1;
+// contiguous pointwise conv (stride 1), M, K >= 48; false = not handled (the fp32-MFMA kernels take it)
+bool pws_wgrad_plan(const PwBwdShape& s, const PwSwitches& sw, PwBwdPlan& p) {
+    const int M = s.Cout, K = s.Cin, Q = s.T * s.Hi * s.Wi;
+    if (s.stride != 1 || sw.split_terms == 0 || M < 48 || K < 48) return false;
+    if (s.act != CFN_ACT_NONE && s.act != CFN_ACT_RELU && s.act != CFN_ACT_SWISH) return false;
+    if ((s.align_g | s.align_x) & 15) return false;
+    if ((long)M * Q * 4 >= (1L << 31) - 64 || (long)K * Q * 4 >= (1L << 31) - 64) return false;
     // (Q % 4 != 0, rows on 4-byte boundaries, is handled: per-element strip masks)
-    return pwss_try(gy, y, gs, gq, gsc, x, pa, pb, act, gw, N, M, K, Q, terms, st);
+    p.act = s.act;
+    return pwss_plan(s.N, M, K, Q, s.two, sw.split_terms, p);
+}
+
+int pws_wgrad_launch(const PwBwdPlan& p, const float* gy, const float* y, const double* gs, const double* gq, const double* gsc, const float* x,
+                     const double* pa, const double* pb, int act, double* gw, int N, int M, int K, int Q, hipStream_t st) {
+    return pwss_launch(p, WssArgs{gy, gq ? y : nullptr, gs, gq, gsc, x, pa, pb, gw, N, M, K, Q, act}, st);
 }
 
 // bf16 tensors (cfn_pwconv_bwd_weight_bf16), M, K >= 48; -1 = not handled (the caller keeps its direct-operand kernel)
@@ -656,5 +668,7 @@ int pwss_wgrad_try_bf16(const uint16_t* gy, const uint16_t* y, const double* gs,
     if (act != CFN_ACT_NONE && act != CFN_ACT_RELU && act != CFN_ACT_SWISH) return -1;
     if (((uintptr_t)gy | (uintptr_t)(y ? y : gy) | (uintptr_t)x) & 7) return -1;
     if ((long)M * Q * 2 >= (1L << 31) - 64 || (long)K * Q * 2 >= (1L << 31) - 64) return -1;
-    return pwss_try(gy, y, gs, gq, gsc, x, pa, pb, act, gw, N, M, K, Q, 1, st);
+    PwBwdPlan p = {};
+    if (!pwss_plan(N, M, K, Q, gq && y, 1, p)) return -1;
+    return pwss_launch(p, WssArgs{gy, gq ? y : nullptr, gs, gq, gsc, x, pa, pb, gw, N, M, K, Q, act}, st);
 }

@@ -76,46 +76,38 @@ static size_t pwt_lds(int BM, int Kp) {
 }
 
 template <int MODE, bool STATS, int ACT, bool TWO>
-static int pwt_go_mt(const PwArgs& a, int MT, unsigned blocks, size_t lds, hipStream_t st) {
-#define PWT_GO(MTV)                                                                                                        \
-    do {                                                                                                                   \
-        auto k = pws_kernel<MTV, 1, MODE, STATS, ACT, TWO, 3, PWT_KCH>;                                                    \
-        if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        hipLaunchKernelGGL(k, dim3(blocks), dim3(64 * PWS_WAVES), lds, st, a);                                             \
-    } while (0)
-    switch (MT) { case 3: PWT_GO(3); break; case 4: PWT_GO(4); break; case 5: PWT_GO(5); break; default: PWT_GO(6); break; }
+static int pwt_go_mt(const PwPlan& p, const PwArgs& a, hipStream_t st) {
+#define PWT_GO(MTV) cfn_launch(pws_kernel<MTV, 1, MODE, STATS, ACT, TWO, 3, PWT_KCH>, p.blocks, p.threads, p.lds, st, a)
+    switch (p.MT) { case 3: PWT_GO(3); break; case 4: PWT_GO(4); break; case 5: PWT_GO(5); break; default: PWT_GO(6); break; }
 #undef PWT_GO
     return cfn_check_launch("pwconv(split bf16, streamed weights)");
 }
 
 template <int MODE, bool STATS, bool TWO>
-static int pwt_go_act(const PwArgs& a, int MT, unsigned blocks, size_t lds, hipStream_t st) {
+static int pwt_go_act(const PwPlan& p, const PwArgs& a, hipStream_t st) {
     if constexpr (MODE == PW_DGRAD && !STATS) {
-        return pwt_go_mt<MODE, STATS, CFN_ACT_NONE, TWO>(a, MT, blocks, lds, st);
+        return pwt_go_mt<MODE, STATS, CFN_ACT_NONE, TWO>(p, a, st);
     } else {
-        switch (a.act) {
-            case CFN_ACT_RELU: return pwt_go_mt<MODE, STATS, CFN_ACT_RELU, TWO>(a, MT, blocks, lds, st);
-            case CFN_ACT_SWISH: return pwt_go_mt<MODE, STATS, CFN_ACT_SWISH, TWO>(a, MT, blocks, lds, st);
-            default: return pwt_go_mt<MODE, STATS, CFN_ACT_NONE, TWO>(a, MT, blocks, lds, st);
+        switch (p.act) {
+            case CFN_ACT_RELU: return pwt_go_mt<MODE, STATS, CFN_ACT_RELU, TWO>(p, a, st);
+            case CFN_ACT_SWISH: return pwt_go_mt<MODE, STATS, CFN_ACT_SWISH, TWO>(p, a, st);
+            default: return pwt_go_mt<MODE, STATS, CFN_ACT_NONE, TWO>(p, a, st);
         }
     }
 }
 
-// returns -1 when the shape is not handled.  DGRAD: stats == (ea != nullptr), i.e. with the act' epilogue
-int pwt_try_launch(PwArgs& a, int mode, bool stats, hipStream_t st) {
-    if (pws_terms_now() != 6 || a.stem || a.stride != 1 || a.acc) return -1;
-    // K >= 400: every mode (measured, 8 clips x 256 frames @7x7, against pw_deep_kernel: forward 432 -> 192 0.223 -> 0.142 ms, data gradient with
-    // two staged operands 0.229 -> 0.161, 432 rows 0.50 -> 0.31, 96 rows @14x14 0.54 -> 0.37); the data gradient WITH the act' epilogue into more
-    // than 256 rows also from K = 160 (layer-4 conv3: contraction over 192, 432 rows in three slabs: 0.273 -> 0.223 ms; pwk_kernel takes the
-    // shapes of up to 256 rows first)
-    const bool deep = a.K >= 400, epi = mode == PW_DGRAD && stats && a.K >= 160 && a.M > 256;
+// false when the shape is not handled.  DGRAD: stats == (ea != nullptr), i.e. with the act' epilogue
+bool pwt_plan(const PwArgs& a, int mode, bool stats, const PwSwitches& sw, PwPlan& p) {
+    if (sw.split_terms != 6 || a.stem || a.stride != 1 || a.acc) return false;
+    const bool deep = a.K >= 400, epi = mode == PW_DGRAD && stats && a.K >= 160 && a.M > 256;      // (why: the table of pwroute.hip)
     // whole 16-byte groups per row (Q % 4 == 0) are only needed by the forward's transposed epilogue (16-byte stores); the data gradient moves 4-byte
     // elements both ways -- the coarse stream's layer 4 (65 x 7 x 7 = 3,185 positions per row) runs its data gradients here
-    if (!(deep || epi) || a.M <= 32 || (mode == PW_FWD && (a.Q & 3))) return -1;
-    if (a.act != CFN_ACT_NONE && a.act != CFN_ACT_RELU && a.act != CFN_ACT_SWISH) return -1;
-    if ((long)a.K * a.Q * 4 >= 0x3ffffff0L || (long)a.M * a.Q * 4 >= 0x3ffffff0L) return -1;
-    if (((uintptr_t)a.src | (uintptr_t)a.dst | (uintptr_t)(a.src2 ? a.src2 : a.src) | (uintptr_t)(a.ex ? a.ex : a.src)) & (mode == PW_FWD ? 15 : 3)) return -1;
-    PwArgs b = a;
+    if (!(deep || epi) || a.M <= 32 || (mode == PW_FWD && (a.Q & 3))) return false;
+    if (a.act != CFN_ACT_NONE && a.act != CFN_ACT_RELU && a.act != CFN_ACT_SWISH) return false;
+    if ((long)a.K * a.Q * 4 >= 0x3ffffff0L || (long)a.M * a.Q * 4 >= 0x3ffffff0L) return false;
+    if ((p.align_io | p.align_ex) & (mode == PW_FWD ? 15 : 3)) return false;
+    PwArgs& b = p.a;
+    b = a;
     b.Kpad = (a.K + 47) / 48 * 48;
     if (mode == PW_DGRAD && !stats) b.act = CFN_ACT_NONE;
     // rows per slab: 6 row tiles (two chunk buffers of 7 do not fit LDS); as few slabs as possible, then as even as possible
@@ -125,13 +117,7 @@ int pwt_try_launch(PwArgs& a, int mode, bool stats, hipStream_t st) {
     slabs = cfn_cdiv(a.M, 32 * MT);
     const int BM = 32 * MT, nchunks = b.Kpad / (16 * PWT_KCH);
     const size_t lds = pwt_lds(BM, b.Kpad);
-    if (lds > 160 * 1024) return -1;
-    unsigned char* ws = pwt_workspace((size_t)slabs * nchunks * 3 * BM * PWT_ROWB, st);
-    if (!ws) return -1;
-    if (mode == PW_FWD) hipLaunchKernelGGL(pws_presplit_kernel<PW_FWD>, dim3(nchunks, slabs, PWT_PRE_Z), dim3(256), 0, st, a.w, a.Cin, a.M, a.K, BM, ws);
-    else hipLaunchKernelGGL(pws_presplit_kernel<PW_DGRAD>, dim3(nchunks, slabs, PWT_PRE_Z), dim3(256), 0, st, a.w, a.Cin, a.M, a.K, BM, ws);
-    { const int rc = cfn_check_launch("pwconv(split bf16, streamed weights) pre-split"); if (rc) return rc; }
-    b.w = reinterpret_cast<const float*>(ws);
+    if (lds > 160 * 1024) return false;
     b.mtiles = slabs;
     b.kres = PWT_ROWB;
     const int ntiles = cfn_cdiv(a.Q, 32);
@@ -141,8 +127,24 @@ int pwt_try_launch(PwArgs& a, int mode, bool stats, hipStream_t st) {
     if (wgs > maxw) wgs = maxw;
     if (wgs < 1) wgs = 1;
     b.nstrips = (int)wgs;
-    const unsigned blocks = (unsigned)(groups * wgs);
-    if (mode == PW_FWD) return stats ? pwt_go_act<PW_FWD, true, false>(b, MT, blocks, lds, st) : pwt_go_act<PW_FWD, false, false>(b, MT, blocks, lds, st);
-    if (a.src2) return stats ? pwt_go_act<PW_DGRAD, true, true>(b, MT, blocks, lds, st) : pwt_go_act<PW_DGRAD, false, true>(b, MT, blocks, lds, st);
-    return stats ? pwt_go_act<PW_DGRAD, true, false>(b, MT, blocks, lds, st) : pwt_go_act<PW_DGRAD, false, false>(b, MT, blocks, lds, st);
+    p.family = PW_FAM_PWT; p.mode = mode; p.stats = stats; p.two = a.src2 != nullptr; p.act = b.act;
+    p.MT = MT; p.NP = 1; p.NS = 3;
+    p.blocks = (unsigned)(groups * wgs); p.threads = 64 * PWS_WAVES; p.lds = lds;
+    p.ws_bytes = (size_t)slabs * nchunks * 3 * BM * PWT_ROWB;
+    return true;
+}
+
+// -1: no workspace (nothing launched)
+int pwt_launch(const PwPlan& p, hipStream_t st) {
+    unsigned char* ws = pwt_workspace(p.ws_bytes, st);
+    if (!ws) return -1;
+    PwArgs b = p.a;
+    const int BM = 32 * p.MT, nchunks = b.Kpad / (16 * PWT_KCH);
+    if (p.mode == PW_FWD) hipLaunchKernelGGL(pws_presplit_kernel<PW_FWD>, dim3(nchunks, b.mtiles, PWT_PRE_Z), dim3(256), 0, st, b.w, b.Cin, b.M, b.K, BM, ws);
+    else hipLaunchKernelGGL(pws_presplit_kernel<PW_DGRAD>, dim3(nchunks, b.mtiles, PWT_PRE_Z), dim3(256), 0, st, b.w, b.Cin, b.M, b.K, BM, ws);
+    { const int rc = cfn_check_launch("pwconv(split bf16, streamed weights) pre-split"); if (rc) return rc; }
+    b.w = reinterpret_cast<const float*>(ws);
+    if (p.mode == PW_FWD) return p.stats ? pwt_go_act<PW_FWD, true, false>(p, b, st) : pwt_go_act<PW_FWD, false, false>(p, b, st);
+    if (p.two) return p.stats ? pwt_go_act<PW_DGRAD, true, true>(p, b, st) : pwt_go_act<PW_DGRAD, false, true>(p, b, st);
+    return p.stats ? pwt_go_act<PW_DGRAD, true, false>(p, b, st) : pwt_go_act<PW_DGRAD, false, false>(p, b, st);
 }

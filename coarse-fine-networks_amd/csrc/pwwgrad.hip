@@ -227,22 +227,28 @@ __global__ __launch_bounds__(64 * WD_WAVES) void pw_wgrad_direct_kernel(const Wd
         }
 }
 
-template <int XMODE, int WD_TM, int WD_TN>
-static int wd_launch(WdArgs& a, hipStream_t st) {
-    constexpr int WD_T = WD_TM * WD_TN;                 // 1 = the single-tile variant
-    a.mt32 = cfn_cdiv(a.M, 32); a.kt32 = cfn_cdiv(a.K, 32);
-    a.mgroups = cfn_cdiv(a.mt32, WD_TM); a.kgroups = cfn_cdiv(a.kt32, WD_TN);
-    const long groups = (long)a.N * a.mgroups * a.kgroups;
+// position strips and grid of a (WD_TM x WD_TN)-tile variant: the one formula of the launcher and of the plan
+static long wd_strips(int N, int M, int K, int Q, int WD_TM, int WD_TN, unsigned& blocks) {
+    const int WD_T = WD_TM * WD_TN;                     // 1 = the single-tile variant
+    const long groups = (long)N * cfn_cdiv(cfn_cdiv(M, 32), WD_TM) * cfn_cdiv(cfn_cdiv(K, 32), WD_TN);
     // ~one workgroup per CU (measured: more, shorter strips lose); the single-tile variant is load bound and small:
     // four workgroups per CU
     // (re-measured with the round-2 kernels, 8 clips: 2x2 / 2x3 tiles everywhere lose 3-12 % against the shapes chosen below;
     //  two workgroups per CU gain 5-6 % for the 2x4 / 4x2 groups of layer 2 and nothing elsewhere)
     long strips = (WD_T == 1 ? 1024 : (WD_T == 8 ? 512 : 256)) / groups;
     if (strips < 1) strips = 1;
-    const long g8 = cfn_cdiv(a.Q, 8);
+    const long g8 = cfn_cdiv(Q, 8);
     if (strips > cfn_cdiv(g8, WD_WAVES * 4)) strips = cfn_cdiv(g8, WD_WAVES * 4);   // >= 4 position groups per wave
-    a.nstrips = (int)strips;
-    const unsigned blocks = (unsigned)(groups * strips);
+    blocks = (unsigned)(groups * strips);
+    return strips;
+}
+
+template <int XMODE, int WD_TM, int WD_TN>
+static int wd_launch(WdArgs& a, hipStream_t st) {
+    a.mt32 = cfn_cdiv(a.M, 32); a.kt32 = cfn_cdiv(a.K, 32);
+    a.mgroups = cfn_cdiv(a.mt32, WD_TM); a.kgroups = cfn_cdiv(a.kt32, WD_TN);
+    unsigned blocks;
+    a.nstrips = (int)wd_strips(a.N, a.M, a.K, a.Q, WD_TM, WD_TN, blocks);
     switch (a.act) {
         case CFN_ACT_RELU: hipLaunchKernelGGL((pw_wgrad_direct_kernel<CFN_ACT_RELU, XMODE, WD_TM, WD_TN>), dim3(blocks), dim3(64 * WD_WAVES), 0, st, a); break;
         case CFN_ACT_SWISH: hipLaunchKernelGGL((pw_wgrad_direct_kernel<CFN_ACT_SWISH, XMODE, WD_TM, WD_TN>), dim3(blocks), dim3(64 * WD_WAVES), 0, st, a); break;
@@ -251,45 +257,54 @@ static int wd_launch(WdArgs& a, hipStream_t st) {
     return cfn_check_launch("pwconv_bwd_weight(direct)");
 }
 
-static bool wd_common_ok(const float* gy, const float* y, const float* x, int act, int M, int K, int Q) {
+static bool wd_common_ok(unsigned align_g, int act, int M, int K, int Q) {
     if (Q % 4 != 0) return false;
     if (act != CFN_ACT_NONE && act != CFN_ACT_RELU && act != CFN_ACT_SWISH) return false;
-    if (((uintptr_t)gy | (uintptr_t)(y ? y : gy)) & 15) return false;
+    if (align_g & 15) return false;
     return (long)M * Q * 4 < (1L << 31) - 64;
 }
 
-// contiguous pointwise conv (stride 1): M, K >= 48 (smaller layers are HBM bound and stay on the LDS-staged kernel)
-int pwd_wgrad_try_launch(const float* gy, const float* y, const double* gs, const double* gq, const double* gsc, const float* x,
-                         const double* pa, const double* pb, int act, double* gw, int N, int M, int K, int Q, hipStream_t st) {
-    if (M < 48 || K < 48 || !wd_common_ok(gy, y, x, act, M, K, Q)) return -1;
-    if (((uintptr_t)x & 15) || (long)K * Q * 4 >= (1L << 31) - 64) return -1;
-    WdArgs a = {gy, y, gs, gq, x, pa, pb, gw, N, M, K, Q, act, gsc};
-    a.Pin = Q;
-    {   // balanced groups never exceed 2 tiles either way (e.g. 108 x 48): the 2x2 variant needs half the registers
+// The direct-operand weight gradient of a pointwise conv.  Stride 1: M, K >= 48 (smaller layers are HBM bound and stay on the LDS-staged kernel);
+// stride 2 (shortcut convs): gathered x operand.  t[] = XMODE, row tiles, column tiles of a wave's block.  false = not handled
+bool pwd_wgrad_plan(const PwBwdShape& s, const PwSwitches&, PwBwdPlan& p) {
+    const int M = s.Cout, K = s.Cin, Ho = (s.Hi - 1) / s.stride + 1, Wo = (s.Wi - 1) / s.stride + 1, Q = s.T * Ho * Wo;
+    int TM = 3, TN = 3;
+    if (s.stride == 1) {
+        if (M < 48 || K < 48 || !wd_common_ok(s.align_g, s.act, M, K, Q)) return false;
+        if ((s.align_x & 15) || (long)K * Q * 4 >= (1L << 31) - 64) return false;
+        // balanced groups never exceed 2 tiles either way (e.g. 108 x 48): the 2x2 variant needs half the registers
         const int mt = cfn_cdiv(M, 32), kt = cfn_cdiv(K, 32);
         const int gm = cfn_cdiv(mt, cfn_cdiv(mt, 3)), gk = cfn_cdiv(kt, cfn_cdiv(kt, 3));
         // narrow x wide (e.g. 48 x 108): one 2x4 / 4x2 group instead of two 2x2 groups halves the re-reads of the operand
         // both groups share
-        if (mt <= 2 && kt == 4) return wd_launch<0, 2, 4>(a, st);
-        if (mt == 4 && kt <= 2) return wd_launch<0, 4, 2>(a, st);
-        if (gm <= 2 && gk <= 2) return wd_launch<0, 2, 2>(a, st);
+        if (mt <= 2 && kt == 4) { TM = 2; TN = 4; }
+        else if (mt == 4 && kt <= 2) { TM = 4; TN = 2; }
+        else if (gm <= 2 && gk <= 2) { TM = 2; TN = 2; }
         // 7 row tiles x 3 column tiles (216 x 96): row groups of 3 leave a 1-tile group (7/9 of the MFMA slots used), groups
         // of 2 use 7/8 (measured 0.363 -> 0.332 ms; the transposed 3 x 7 case shows no difference and stays on 3x3)
-        if (mt == 7 && kt == 3) return wd_launch<0, 2, 3>(a, st);
+        else if (mt == 7 && kt == 3) { TM = 2; TN = 3; }
+    } else {
+        if (Wo % 4 != 0 || !wd_common_ok(s.align_g, s.act, M, K, Q)) return false;
+        if ((long)K * s.T * s.Hi * s.Wi * 4 >= (1L << 31) - 64) return false;
     }
-    return wd_launch<0, 3, 3>(a, st);
+    p.family = PW_FAM_WD; p.t[0] = s.stride == 1 ? 0 : 1; p.t[1] = TM; p.t[2] = TN; p.act = s.act;
+    p.nstrips = (int)wd_strips(s.N, M, K, Q, TM, TN, p.blocks); p.threads = 64 * WD_WAVES;
+    return true;
 }
 
-// pointwise conv with spatial stride 2 (shortcut convs): gathered x operand
-int pwd_wgrad_try_strided(const float* gy, const float* y, const double* gs, const double* gq, const double* gsc, const float* x,
-                          const double* pa, const double* pb, int act, double* gw, int N, int M, int K, int T, int Hi, int Wi,
-                          int stride, hipStream_t st) {
+int pwd_wgrad_launch(const PwBwdPlan& p, const float* gy, const float* y, const double* gs, const double* gq, const double* gsc, const float* x,
+                     const double* pa, const double* pb, int act, double* gw, int N, int M, int K, int T, int Hi, int Wi, int stride, hipStream_t st) {
     const int Ho = (Hi - 1) / stride + 1, Wo = (Wi - 1) / stride + 1;
-    const int Q = T * Ho * Wo;
-    if (Wo % 4 != 0 || !wd_common_ok(gy, y, x, act, M, K, Q)) return -1;
-    if ((long)K * T * Hi * Wi * 4 >= (1L << 31) - 64) return -1;
-    WdArgs a = {gy, y, gs, gq, x, pa, pb, gw, N, M, K, Q, act, gsc};
-    a.Pin = T * Hi * Wi; a.Hi = Hi; a.Wi = Wi; a.Ho = Ho; a.Wo = Wo; a.stride = stride;
+    WdArgs a = {gy, y, gs, gq, x, pa, pb, gw, N, M, K, T * Ho * Wo, act, gsc};
+    a.Pin = T * Hi * Wi;
+    if (p.t[0] == 0) {
+        if (p.t[1] == 2 && p.t[2] == 4) return wd_launch<0, 2, 4>(a, st);
+        if (p.t[1] == 4) return wd_launch<0, 4, 2>(a, st);
+        if (p.t[1] == 2 && p.t[2] == 2) return wd_launch<0, 2, 2>(a, st);
+        if (p.t[1] == 2) return wd_launch<0, 2, 3>(a, st);
+        return wd_launch<0, 3, 3>(a, st);
+    }
+    a.Hi = Hi; a.Wi = Wi; a.Ho = Ho; a.Wo = Wo; a.stride = stride;
     return wd_launch<1, 3, 3>(a, st);
 }
 
@@ -302,7 +317,7 @@ int pwd_wgrad_try_dense(const float* gy, const float* y, const double* gs, const
     const long Ql = (long)To * Ho * Wo;
     if (To < 1 || Ho < 1 || Wo < 1 || Wo % 4 != 0 || Ql >= (1L << 30)) return -1;
     const int Q = (int)Ql;
-    if (!wd_common_ok(gy, y, x, act, M, K, Q)) return -1;
+    if (!wd_common_ok((unsigned)(((uintptr_t)gy | (uintptr_t)(y ? y : gy)) & 15), act, M, K, Q)) return -1;
     if ((long)Cimg * T * Hi * Wi * 4 >= (1L << 31) - 64) return -1;
     WdArgs a = {gy, y, gs, gq, x, pa, pb, gw, N, M, K, Q, act};
     a.Pin = T * Hi * Wi; a.Hi = Hi; a.Wi = Wi; a.Ho = Ho; a.Wo = Wo; a.stride = 1; a.Ti = T; a.Cimg = Cimg;

@@ -101,6 +101,14 @@ int cfn_pwconv_bwd_weight(const float* gy, const float* y, const double* gsum, c
  * Default 6 (env CFN_PW_SPLIT).  -1 only queries.  Returns the previous setting.  Host-side, no stream. */
 int cfn_pw_split_terms(int terms);
 
+/* Which kernel a pointwise conv call would launch: op 0 cfn_pwconv_fwd, 1 cfn_pwconv_bwd_data_acc, 2 cfn_pwconv_bwd_weight, 3 cfn_pwconv_bwd_fused,
+ * 4 cfn_pwconv_short_bwd -- the same routing function as the entry point, asked without a device or a stream.  flags: 1 = prologue A, B present,
+ * 2 = statistics (forward: sum, sumsq; backward: gsum, and gsumsq where y is present too), 4 = y present, 8 = compact shortcut gradient acc present
+ * (stride-2 lattice), 16 = tensors misaligned by 4 bytes.  Writes one line into out: family, kernel with the selected template arguments, grid,
+ * workgroup size, dynamic LDS bytes, workspace bytes, "+lattice_add" where the shortcut gradient is added behind the contraction; "declined" where
+ * the entry point would return -1 (ops 3, 4) or refuse the shape. */
+int cfn_pwconv_route(int op, int N, int Cin, int Cout, int T, int Hi, int Wi, int stride, int act, int flags, char* out, int cap);
+
 /* Deterministic mode ("Threading / streams": "deterministic reductions preferred for parity tests (atomics order) -- offer a
  * deterministic mode"; the reference's own reductions are PyTorch's, train_fine.py:199-226 runs them in whatever mode torch is in).
  * on = 1: every cross-workgroup fp64 accumulation of the library (BN statistics, coefficient / weight gradients: ~100 sites) is recorded as an

@@ -152,6 +152,9 @@ PW_CASES = [
     (1, 3, 5, 40, 13, 11, 1, 1, True),     # odd everything, many position tiles
     (2, 192, 432, 5, 7, 7, 1, 1, True),    # odd volume (245 positions: rows start on 4-byte boundaries), the coarse stream's layer 4
     (2, 432, 192, 13, 7, 7, 1, 2, True),
+    (1, 108, 48, 2, 4, 4, 1, 2, True),     # layer-2 conv3 on the split-bf16 kernels (32 positions: whole 16-byte groups), Swish prologue both ways
+    (1, 48, 108, 2, 4, 4, 1, 0, False),    # layer-2 conv1 forward without a prologue: four row tiles of 32 positions
+    (1, 2048, 157, 3, 1, 1, 1, 0, False),  # fc2 without a prologue: its data gradient into 2048 rows has no act' epilogue (six row tiles)
 ]
 
 

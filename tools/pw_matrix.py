@@ -26,4 +26,5 @@ for stats in (True, False):
         torch.cuda.synchronize()
         cfn_hip.prof_enable('pwconv_fwd', False)
         ms, n, _ = cfn_hip.prof_collect('pwconv_fwd')
-        print('split=%s stats=%d act=%d  %.3f ms  %.0f GB/s' % (os.environ.get('CFN_PW_SPLIT', '-'), stats, act, ms / n, gb / (ms / n) * 1e3))
+        print('split=%s stats=%d act=%d  %.3f ms  %.0f GB/s  %s' % (os.environ.get('CFN_PW_SPLIT', '-'), stats, act, ms / n, gb / (ms / n) * 1e3,
+                                                                  ops.pwconv_route(0, NB, ci, co, T, H, H, 1, act, 1 | (2 if stats else 0))))

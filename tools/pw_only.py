@@ -17,6 +17,8 @@ LAYERS = [('L2 conv3 108->48 @28', 108, 48, 28), ('L2 conv1 48->108 @28', 48, 10
 for name, ci, co, H in LAYERS:
     if ONLY and ONLY not in name:
         continue
+    if DT == torch.float32:      # the kernels this layer's forward and data gradient run on (host-side query of the router)
+        print('%s\n  fwd   %s\n  dgrad %s\n  wgrad %s' % ((name,) + tuple(ops.pwconv_route(op, NB, ci, co, T, H, H, 1, 2, 3 if op == 0 else 7) for op in (0, 1, 2))))
     x = torch.randn(NB, ci, T, H, H, device='cuda').to(DT).requires_grad_(True)
     w = (torch.randn(co, ci, 1, 1, 1, device='cuda') * 0.1).requires_grad_(True)
     A = (torch.rand(NB, ci, device='cuda') + 0.5).requires_grad_(True)

@@ -1543,6 +1543,84 @@ def seg_labels(seg, offsets, fps, window, n_classes, t_max, out=None):
     return out
 
 
+# ---- activity segments from per-frame scores (csrc/detections.hip; the batch type, the host reference and the writer: cfn_hip/detections.py) --
+DECODE_MAX_TL = 65536
+
+
+def decode_segments_cap(B, C, TL):
+    """the worst case of decode_segments: every second frame of every row a run of its own"""
+    return int(B) * int(C) * ((int(TL) + 1) // 2)
+
+
+def decode_segments_workspace_bytes(B, C, TL):
+    n = int(query('cfn_decode_segments_workspace_bytes', int(B), int(C), int(TL)))
+    if n < 0:
+        raise RuntimeError('decode_segments: probs: B <= 65535, C < 2^19, TL <= %d and B * C * TL < 2^31 expected, got (%d, %d, %d)'
+                           % (DECODE_MAX_TL, B, C, TL))
+    return n
+
+
+def decode_segments(probs, valid_t, fps, start, thr, max_gap=0, min_len=1, cap=None, out=None):
+    """probs (B, C, TL) fp32 on the GPU; valid_t (B,) int32; fps (B,) fp64; start (B,) int32 = first frame of each window
+    (SegLabels.window[:, 0]); thr: a float or a (C,) fp32 device tensor -> (seg (cap, 3) fp64 rows [class, start_s, end_s], frames (cap, 3)
+    int32 [t0, t1, n_active], score (cap, 2) fp32 [max, mean], offsets (B + 1,) int32, total (1,) int32): the runs of frames with
+    probs > thr[c] in front of valid_t, gaps of at most `max_gap` inactive frames closed, runs shorter than `min_len` dropped, ordered by
+    (b, c, t0) -- the definition is in cfn_hip/detections.py (decode_reference spells it on the host).  offsets and total are true counts;
+    rows >= cap are not written (cap=None: B * C * ((TL + 1) // 2), which cannot overflow).  Three launches, no atomics, nothing is read
+    back (no wait, capturable with out=); `max_gap`, `min_len` and `cap` are host ints.  out: the five preallocated tensors and a uint8
+    workspace of decode_segments_workspace_bytes(B, C, TL) bytes (then thr must be a tensor for nothing to be allocated).  No gradient, no CPU path."""
+    if not torch.is_tensor(probs) or probs.dtype != torch.float32 or probs.dim() != 3 or min(probs.shape) < 1 or not probs.is_contiguous():
+        raise RuntimeError('decode_segments: probs: a contiguous (B, C, TL) float32 tensor expected, got %s %s'
+                           % (getattr(probs, 'dtype', type(probs).__name__), tuple(getattr(probs, 'shape', ()))))
+    B, C, TL = (int(s) for s in probs.shape)
+    if TL > DECODE_MAX_TL or B > 65535 or C >= (1 << 19) or B * C * TL >= (1 << 31):
+        raise RuntimeError('decode_segments: probs: B <= 65535, C < 2^19, TL <= %d and B * C * TL < 2^31 expected, got (%d, %d, %d)'
+                           % (DECODE_MAX_TL, B, C, TL))
+    for name, t, dt in (('valid_t', valid_t, torch.int32), ('fps', fps, torch.float64), ('start', start, torch.int32)):
+        if not torch.is_tensor(t) or t.dtype != dt or tuple(t.shape) != (B,):
+            raise RuntimeError('decode_segments: %s (%d,) %s expected, got %s %s'
+                               % (name, B, dt, getattr(t, 'dtype', type(t).__name__), tuple(getattr(t, 'shape', ()))))
+    if torch.is_tensor(thr):
+        if thr.dtype != torch.float32 or tuple(thr.shape) != (C,):
+            raise RuntimeError('decode_segments: thr: a float or a (%d,) float32 tensor expected, got %s %s' % (C, thr.dtype, tuple(thr.shape)))
+    elif isinstance(thr, bool) or not isinstance(thr, (int, float)):
+        raise RuntimeError('decode_segments: thr: a float or a (%d,) float32 tensor expected, got %s' % (C, type(thr).__name__))
+    max_gap, min_len = int(max_gap), int(min_len)
+    if max_gap < 0:
+        raise RuntimeError('decode_segments: max_gap >= 0 expected, got %d' % max_gap)
+    if min_len < 1:
+        raise RuntimeError('decode_segments: min_len >= 1 expected, got %d' % min_len)
+    cap = decode_segments_cap(B, C, TL) if cap is None else int(cap)
+    if cap < 1 or cap >= (1 << 31):
+        raise RuntimeError('decode_segments: cap in [1, 2^31) expected, got %d' % cap)
+    dev = probs.device
+    for name, t in (('probs', probs), ('valid_t', valid_t), ('fps', fps), ('start', start), ('thr', thr)):
+        if torch.is_tensor(t) and (t.device.type != 'cuda' or t.device != dev):
+            raise RuntimeError('decode_segments: %s is on %s: device tensors on one GPU expected (there is no CPU path; '
+                               'cfn_hip.detections.decode_reference is the host spelling)' % (name, t.device))
+    if not torch.is_tensor(thr):
+        thr = torch.full((C,), float(thr), dtype=torch.float32, device=dev)
+    ws_bytes = decode_segments_workspace_bytes(B, C, TL)
+    if out is None:
+        out = (torch.empty(cap, 3, dtype=torch.float64, device=dev), torch.empty(cap, 3, dtype=torch.int32, device=dev),
+               torch.empty(cap, 2, dtype=torch.float32, device=dev), torch.empty(B + 1, dtype=torch.int32, device=dev),
+               torch.empty(1, dtype=torch.int32, device=dev), torch.empty(ws_bytes, dtype=torch.uint8, device=dev))
+    else:
+        out = tuple(out)
+        want = ((torch.float64, 3), (torch.int32, 3), (torch.float32, 2))
+        if len(out) != 6 or any(y.dtype != dt or y.dim() != 2 or y.shape[1] != w or y.shape[0] < cap or not y.is_contiguous()
+                                for y, (dt, w) in zip(out, want)) \
+                or out[3].dtype != torch.int32 or tuple(out[3].shape) != (B + 1,) or out[4].dtype != torch.int32 or tuple(out[4].shape) != (1,) \
+                or out[5].dtype != torch.uint8 or out[5].dim() != 1 or out[5].numel() < ws_bytes or out[5].data_ptr() % 8 \
+                or not (out[3].is_contiguous() and out[5].is_contiguous()):
+            raise RuntimeError('decode_segments: out: contiguous seg (>= %d, 3) fp64, frames (>= %d, 3) int32, score (>= %d, 2) fp32, offsets (%d,) '
+                               'int32, total (1,) int32 and an 8-byte aligned uint8 workspace of >= %d bytes expected, got %s'
+                               % (cap, cap, cap, B + 1, ws_bytes, [(y.dtype, tuple(y.shape)) for y in out]))
+    call('cfn_decode_segments', probs, valid_t.contiguous(), fps.contiguous(), start.contiguous(), thr.contiguous(), out[0], out[1], out[2], out[3],
+         out[4], out[5], B, C, TL, max_gap, min_len, cap)
+    return out[:5]
+
+
 # ---- baseline JPEG frames decoded on the GPU (csrc/jpegdec.hip; the host side and the batch type: cfn_hip/jpegdec.py) ------------------------
 def jpeg_workspace_bytes(rows, slots, lanes, blocks_max, entropy=None, sub_bytes=None, max_subs=None):
     """bytes of workspace cfn_jpeg_decode_u8 needs for `rows` frames into `slots` = clips x Tmax frame slots.  entropy, sub_bytes,

@@ -32,6 +32,7 @@ from cfn_hip.jpegdec import JpegClips, decode_checked        # noqa: E402
 from apmeter import APMeter                       # noqa: E402
 from cfn_hip import metrics                       # noqa: E402
 from cfn_hip.seglabels import materialize         # noqa: E402
+from cfn_hip.detections import DetectionWriter, epoch_path   # noqa: E402
 
 BS = 8
 BS_UPSCALE = 1
@@ -275,8 +276,11 @@ _ap_rows = metrics.ap_rows      # per video: (scores (v,157), targets (v,157)) n
 def run(init_lr=INIT_LR, warmup_steps=0, max_epochs=200, mode='rgb', root=None, train_split=None,
         batch_size=BS * BS_UPSCALE, frames=80 * 4, dataloaders=None, max_steps=None, save_model='models/fine_charades_',
         pretrained='models/x3d_multigrid_kinetics_fb_pretrained.pt', log=print, phase_hook=None, input_norm=None,
-        device_ap=False, fused_loss=False, jpeg_entropy=None):
-    """input_norm: see build_model -- needed when the loaders collate uint8 frames (collate.fine_collate_u8, or fine_collate_raw_u8:
+        device_ap=False, fused_loss=False, jpeg_entropy=None, detections=None):
+    """detections: a cfn_hip.detections.DetectionWriter -- every validation phase decodes its probs into activity segments on the GPU
+    (cfn_hip.ops.decode_segments) and rank 0 writes them, all ranks' videos, as JSON lines to the writer's path with the epoch inserted
+    (cfn_hip.detections.epoch_path); seconds when the loaders collate SegLabel samples, frames otherwise.  None: nothing changes.
+    input_norm: see build_model -- needed when the loaders collate uint8 frames (collate.fine_collate_u8, or fine_collate_raw_u8:
     untransformed frames + crop boxes, cropped / resized to the model's crop size / flipped on the GPU in front of the step).
     device_ap: the training phases keep their AP rows and loss totals on the GPU (cfn_hip.metrics.StepMetrics, apmeter.DeviceAPMeter):
     no read-back per step, the host waits for the device only where a line is logged.
@@ -327,6 +331,7 @@ def run(init_lr=INIT_LR, warmup_steps=0, max_epochs=200, mode='rgb', root=None, 
                     continue
                 b, n = inputs.shape[:2]          # n crops per video (1 in training, train_fine.py:176-185)
                 inputs = flatten_clips(inputs, dev, crop, names=_name, jpeg_entropy=jpeg_entropy)
+                seg_batch = labels if detections is not None else None      # (its fps / window, before materialize drops the SegLabels)
                 labels, masks = materialize(labels, masks, dev)      # dense tensors: .to(dev); a SegLabels batch (segment labels): one kernel
                 valid_t = masks.sum(1).int()
                 n_it += 1
@@ -340,6 +345,8 @@ def run(init_lr=INIT_LR, warmup_steps=0, max_epochs=200, mode='rgb', root=None, 
                         logits = net([inputs, masks[:, ::gamma_tau * 2]])
                         cls_loss, loc_loss, probs = detection_loss(logits, labels, masks, True, crops=n, local_norm=True, fused=fused)
                     val_rows.extend(_ap_rows(probs, labels, valid_t))
+                    if detections is not None:      # decoded on the device; the segments stay there until the end of the phase
+                        detections.add(probs, valid_t, seg_batch, _name)
                     tot_cls += float(cls_loss)
                     tot_loc += float(loc_loss)
                 if train and steps % max(iters // 2, 1) == 0:
@@ -367,11 +374,35 @@ def run(init_lr=INIT_LR, warmup_steps=0, max_epochs=200, mode='rgb', root=None, 
                         g_loc, g_cls, g_it = g_loc + r_loc, g_cls + r_cls, g_it + r_it
                     log(' Epoch:{} val Loc Loss: {:.4f} Cls Loss: {:.4f} mAP: {:.4f}'.format(
                         epochs, g_loc / max(g_it, 1), g_cls / max(g_it, 1), _mean_ap(val_apm)))
+                if detections is not None:      # every rank's videos, one file per validation phase
+                    det_rows = cdist.gather_objects(detections.take())
+                    if rank == 0:
+                        detections.flush(epoch_path(detections.path, epochs), [r for part in det_rows for r in part])
                 val_apm.reset()
                 lr_sched.step()            # once per val phase, as the reference (not per epoch, not per step)
             if phase_hook is not None:         # test / logging hook: end of a phase (not in the reference's signature)
                 phase_hook(phase, epochs, optimizer)
     return net
+
+
+def add_detect_args(parser):
+    """the --detect group: activity segments of every validation phase as JSON lines (cfn_hip.detections.DetectionWriter)"""
+    g = parser.add_argument_group('detections')
+    g.add_argument('--detect', metavar='PATH', default=None, help='write the decoded segments of every validation phase to PATH (epoch number inserted)')
+    g.add_argument('--detect-thr', type=float, default=0.5, help='a frame is active when its probability is above this')
+    g.add_argument('--detect-gap', type=int, default=0, help='close gaps of at most N inactive frames')
+    g.add_argument('--detect-min-len', type=int, default=1, help='drop segments shorter than N frames')
+
+
+def detect_argv(args):
+    """the --detect group of `args` as a worker's command line"""
+    if not args.detect:
+        return []
+    return ['--detect', args.detect, '--detect-thr', repr(args.detect_thr), '--detect-gap', str(args.detect_gap), '--detect-min-len', str(args.detect_min_len)]
+
+
+def detect_writer(args):
+    return DetectionWriter(args.detect, args.detect_thr, args.detect_gap, args.detect_min_len) if args.detect else None
 
 
 def _spawn(gpus, argv):
@@ -394,11 +425,14 @@ if __name__ == '__main__':
     parser.add_argument('--fused-loss', action='store_true', help='the detection loss as one forward and one backward HIP kernel')
     parser.add_argument('--jpeg-entropy', choices=('interval', 'sync'), default=None,
                         help='entropy mode of the GPU JPEG decode: sync = parallel inside a frame without restart markers')
+    add_detect_args(parser)
     args = parser.parse_args()
     if 'RANK' not in os.environ and len(args.gpu.split(',')) > 1:
         sys.exit(_spawn(args.gpu, ['--batch-size', str(args.batch_size)] +
                         (['--max-steps', str(args.max_steps)] if args.max_steps else []) + (['--device-ap'] if args.device_ap else []) +
-                        (['--fused-loss'] if args.fused_loss else []) + (['--jpeg-entropy', args.jpeg_entropy] if args.jpeg_entropy else [])))
+                        (['--fused-loss'] if args.fused_loss else []) + (['--jpeg-entropy', args.jpeg_entropy] if args.jpeg_entropy else []) +
+                        detect_argv(args)))
     if 'RANK' not in os.environ:
         os.environ['CUDA_VISIBLE_DEVICES'] = args.gpu
-    run(batch_size=args.batch_size, max_steps=args.max_steps, device_ap=args.device_ap, fused_loss=args.fused_loss, jpeg_entropy=args.jpeg_entropy)
+    run(batch_size=args.batch_size, max_steps=args.max_steps, device_ap=args.device_ap, fused_loss=args.fused_loss, jpeg_entropy=args.jpeg_entropy,
+        detections=detect_writer(args))

@@ -579,6 +579,35 @@ int cfn_jpeg_decode_u8_sync(const unsigned char* data, const int* frames, const 
 int cfn_seg_labels(const double* seg, const int* offsets, const double* fps, const int* window, float* labels, float* mask,
                    int* valid_t, int B, int C, int t_max, long n_seg, void* stream);
 
+/* =====================================================================================================================
+ * Activity segments from per-frame scores (csrc/detections.hip; the batch type, the host reference and the writer:
+ * cfn_hip/detections.py).  The reference stops at probs (B, C, TL) (train_fine.py:199-206, the same lines in
+ * train_coarse_fineFEAT.py); this replaces the per-video Python decode every caller writes after them (threshold, find the
+ * runs, frames -> seconds) by one device-side step, and is the inverse of cfn_seg_labels.
+ *   probs (B, C, TL) fp32; valid_t (B) int32; fps (B) fp64; start (B) int32 = first frame of each window; thr (C) fp32.
+ *     1. frame t of row (b, c) is active iff t < min(valid_t[b], TL) and probs[b, c, t] > thr[c] (strict: NaN is never active)
+ *     2. active frames t < u with only inactive frames between them and u - t - 1 <= max_gap are joined
+ *     3. a segment is a maximal run [t0, t1] after 2; runs with t1 - t0 + 1 < min_len are dropped
+ *     4. start_s = ((double)(start[b] + t0) - 0.5) / fps[b], end_s = ((double)(start[b] + t1) + 0.5) / fps[b]  (IEEE fp64)
+ *     5. max (fp32) and mean (fp64 sum in a fixed order / count, rounded to fp32) over the ACTIVE frames of the run only
+ *     6. rows are ordered by (b, c, t0), through counts and prefix sums: no atomics, the same bits in every run
+ *   seg (cap, 3) fp64 rows [class, start_s, end_s] (the layout of cfn_seg_labels' seg); frames (cap, 3) int32 [t0, t1, n_active];
+ *   score (cap, 2) fp32 [max, mean]; offsets (B + 1) int32: sample b owns rows offsets[b] .. offsets[b + 1] - 1; total (1) int32 =
+ *   offsets[B].  offsets and total are the TRUE counts, not clamped by cap; rows >= cap are not written, rows of the three
+ *   buffers behind min(total, cap) are not touched.  cap = B * C * ((TL + 1) / 2) can never overflow.
+ *   workspace: cfn_decode_segments_workspace_bytes(B, C, TL) bytes on an 8-byte boundary (the rows' bit masks, TL / 8 bytes per
+ *   row, and B * C + 1 counts); the library keeps no state, the caller owns the buffer until the stream has passed.
+ * Everything but B, C, TL, max_gap, min_len and cap is read on the device only.  3 launches on `stream` ordered by the stream
+ * alone, no allocation, no synchronisation (capturable); nothing accumulates across workgroups, so the deterministic mode
+ * changes nothing.  Returns 1 for null pointers, B, C or TL < 1, B > 65535, C >= 2^19, TL > 65536, B * C * TL >= 2^31,
+ * max_gap < 0, min_len < 1, cap outside [1, 2^31) or a misaligned workspace; cfn_decode_segments_workspace_bytes -1 for the
+ * same shapes.
+ * ===================================================================================================================== */
+long cfn_decode_segments_workspace_bytes(int B, int C, int TL);
+int cfn_decode_segments(const float* probs, const int* valid_t, const double* fps, const int* start, const float* thr, double* seg,
+                        int* frames, float* score, int* offsets, int* total, void* workspace, int B, int C, int TL, int max_gap,
+                        int min_len, long cap, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

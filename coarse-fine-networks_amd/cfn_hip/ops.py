@@ -1621,6 +1621,135 @@ def decode_segments(probs, valid_t, fps, start, thr, max_gap=0, min_len=1, cap=N
     return out[:5]
 
 
+# ---- segment-level AP at temporal-IoU thresholds (csrc/segap.hip; the rule, the host reference and the meter: cfn_hip/segap.py) -------------
+SEGAP_GT_TILE = 64               # ground-truth rows of a video per tile of lanes (cfn_segap_gt_tile(); more take the general path)
+SEGAP_DET_TILE = 1024            # detections of a (video, class) group ordered in LDS (cfn_segap_det_tile(); more take the general path)
+SEGAP_MAX_THR = 8
+SEGAP_FLAG_OVERFLOW = 2
+
+
+def segap_workspace_bytes(B, C, det_cap, n_seg):
+    n = int(query('cfn_segap_workspace_bytes', int(B), int(C), int(det_cap), int(n_seg)))
+    if n < 0:
+        raise RuntimeError('segap: B and C in [1, 65535], det_cap and n_seg in [1, 2^31) expected, got (%d, %d, %d, %d)' % (B, C, det_cap, n_seg))
+    return n
+
+
+def _segap_dev(what, **tensors):
+    dev = None
+    for name, t in tensors.items():
+        if not torch.is_tensor(t) or t.device.type != 'cuda' or (dev is not None and t.device != dev):
+            raise RuntimeError('%s: %s: device tensors on one GPU expected (there is no CPU path; cfn_hip.segap.match_reference / ap_reference '
+                               'are the host spelling), got %s' % (what, name, getattr(t, 'device', type(t).__name__)))
+        if not t.is_contiguous():
+            raise RuntimeError('%s: %s must be contiguous' % (what, name))
+        dev = t.device
+    return dev
+
+
+def segap_match(det_seg, det_score, det_offsets, seg, offsets, fps, window, tiou, n_classes, t_max, score_col=0, want_match=True, out=None):
+    """Match the detections of a batch (det_seg (cap, 3) fp64, det_score (cap, 2) fp32, det_offsets (B + 1,) int32: Detections) against its
+    ground truth (seg (S, 3) fp64, offsets (B + 1,) int32, fps (B,) fp64, window (B, 2) int32: SegLabels) at the thresholds tiou (n_thr,)
+    fp64 on the device -> (tp (cap,) uint8: bit k = true positive at tiou[k], match (n_thr, cap) int32 = ground-truth row or -1 (None with
+    want_match=False), workspace).  Rules 1-5 of cfn_hip/segap.py; one launch, nothing is read back (no wait; capturable with out=).  Only
+    the rows of the batch's detections are written.  `n_classes`, `t_max` and `score_col` (0 = max, 1 = mean) are host ints.  out:
+    (tp, match or None, a uint8 workspace of segap_workspace_bytes(B, C, cap, S) bytes); the workspace goes to segap_append.  No CPU path."""
+    what = 'segap_match'
+    dev = _segap_dev(what, det_seg=det_seg, det_score=det_score, det_offsets=det_offsets, seg=seg, offsets=offsets, fps=fps, window=window, tiou=tiou)
+    if det_seg.dtype != torch.float64 or det_seg.dim() != 2 or det_seg.shape[1] != 3 or det_seg.shape[0] < 1:
+        raise RuntimeError('%s: det_seg: a (cap, 3) float64 tensor with cap >= 1 expected, got %s %s' % (what, det_seg.dtype, tuple(det_seg.shape)))
+    cap = int(det_seg.shape[0])
+    if det_score.dtype != torch.float32 or tuple(det_score.shape) != (cap, 2):
+        raise RuntimeError('%s: det_score (%d, 2) float32 expected, got %s %s' % (what, cap, det_score.dtype, tuple(det_score.shape)))
+    if seg.dtype != torch.float64 or seg.dim() != 2 or seg.shape[1] != 3 or seg.shape[0] < 1:
+        raise RuntimeError('%s: seg: a (S, 3) float64 tensor with S >= 1 expected, got %s %s' % (what, seg.dtype, tuple(seg.shape)))
+    S = int(seg.shape[0])
+    if offsets.dtype != torch.int32 or offsets.dim() != 1 or offsets.numel() < 2:
+        raise RuntimeError('%s: offsets (B + 1,) int32 expected, got %s %s' % (what, offsets.dtype, tuple(offsets.shape)))
+    B = int(offsets.numel()) - 1
+    if det_offsets.dtype != torch.int32 or tuple(det_offsets.shape) != (B + 1,):
+        raise RuntimeError('%s: det_offsets (%d,) int32 expected (one batch size for detections and ground truth), got %s %s'
+                           % (what, B + 1, det_offsets.dtype, tuple(det_offsets.shape)))
+    if fps.dtype != torch.float64 or tuple(fps.shape) != (B,) or window.dtype != torch.int32 or tuple(window.shape) != (B, 2):
+        raise RuntimeError('%s: fps (%d,) float64 and window (%d, 2) int32 expected, got %s %s and %s %s'
+                           % (what, B, B, fps.dtype, tuple(fps.shape), window.dtype, tuple(window.shape)))
+    if tiou.dtype != torch.float64 or tiou.dim() != 1 or not 1 <= tiou.numel() <= SEGAP_MAX_THR:
+        raise RuntimeError('%s: tiou: 1 to %d float64 thresholds expected, got %s %s' % (what, SEGAP_MAX_THR, tiou.dtype, tuple(tiou.shape)))
+    n_thr, n_classes, t_max, score_col = int(tiou.numel()), int(n_classes), int(t_max), int(score_col)
+    if n_classes < 1 or t_max < 1 or score_col not in (0, 1):
+        raise RuntimeError('%s: n_classes >= 1, t_max >= 1 and score_col 0 (max) or 1 (mean) expected, got %d, %d, %d' % (what, n_classes, t_max, score_col))
+    ws_bytes = segap_workspace_bytes(B, n_classes, cap, S)
+    if out is None:
+        out = (torch.empty(cap, dtype=torch.uint8, device=dev), torch.empty(n_thr, cap, dtype=torch.int32, device=dev) if want_match else None,
+               torch.empty(ws_bytes, dtype=torch.uint8, device=dev))
+    else:
+        out = tuple(out)
+        if len(out) != 3 or out[0].dtype != torch.uint8 or tuple(out[0].shape) != (cap,) or not out[0].is_contiguous() \
+                or (out[1] is not None and (out[1].dtype != torch.int32 or tuple(out[1].shape) != (n_thr, cap) or not out[1].is_contiguous())) \
+                or out[2].dtype != torch.uint8 or out[2].dim() != 1 or out[2].numel() < ws_bytes or out[2].data_ptr() % 8 or not out[2].is_contiguous():
+            raise RuntimeError('%s: out: tp (%d,) uint8, match (%d, %d) int32 or None and an 8-byte aligned uint8 workspace of >= %d bytes expected'
+                               % (what, cap, n_thr, cap, ws_bytes))
+    call('cfn_segap_match', det_seg, det_score, det_offsets, seg, offsets, fps, window, tiou, out[0], out[1], out[2], B, n_classes, t_max, n_thr,
+         score_col, cap, S)
+    return out
+
+
+def _segap_stores(what, scores, tps, counts, n_gt):
+    _segap_dev(what, scores=scores, tps=tps, counts=counts, n_gt=n_gt)
+    if scores.dtype != torch.float32 or scores.dim() != 2 or min(scores.shape) < 1 or tps.dtype != torch.uint8 or tuple(tps.shape) != tuple(scores.shape):
+        raise RuntimeError('%s: class-major stores expected, scores (C, cap) fp32 and tps (C, cap) uint8; got %s %s, %s %s'
+                           % (what, scores.dtype, tuple(scores.shape), tps.dtype, tuple(tps.shape)))
+    C, cap = int(scores.shape[0]), int(scores.shape[1])
+    for name, t in (('counts', counts), ('n_gt', n_gt)):
+        if t.dtype != torch.int32 or tuple(t.shape) != (C,):
+            raise RuntimeError('%s: %s (%d,) int32 expected, got %s %s' % (what, name, C, t.dtype, tuple(t.shape)))
+    return C, cap
+
+
+def segap_append(det_score, tp, workspace, scores, tps, counts, n_gt, flags, batch, score_col=0):
+    """Rule 6 of cfn_hip/segap.py behind segap_match of the same batch (its tp and workspace): class c's rows of scores (C, cap) fp32 / tps
+    (C, cap) uint8 receive the batch's detections of class c in (video, row) order; counts (C,) and n_gt (C,) int32 advance.  A batch that
+    would push any class past cap writes nothing, changes no count and sets SEGAP_FLAG_OVERFLOW in flags (one int32).  In place, two
+    launches, nothing is read back (capturable).  `batch` = B of the match."""
+    what = 'segap_append'
+    C, cap = _segap_stores(what, scores, tps, counts, n_gt)
+    _segap_dev(what, det_score=det_score, tp=tp, workspace=workspace, flags=flags, scores=scores)
+    dcap = int(tp.numel())
+    if tp.dtype != torch.uint8 or tp.dim() != 1 or det_score.dtype != torch.float32 or tuple(det_score.shape) != (dcap, 2):
+        raise RuntimeError('%s: tp (cap,) uint8 and det_score (cap, 2) float32 expected, got %s %s and %s %s'
+                           % (what, tp.dtype, tuple(tp.shape), det_score.dtype, tuple(det_score.shape)))
+    if flags.dtype != torch.int32 or flags.numel() != 1:
+        raise RuntimeError('%s: flags must be one int32 on the device' % what)
+    need = segap_workspace_bytes(int(batch), C, dcap, 1)
+    if workspace.dtype != torch.uint8 or workspace.dim() != 1 or workspace.numel() < need or workspace.data_ptr() % 8:
+        raise RuntimeError('%s: workspace: the 8-byte aligned uint8 tensor segap_match filled (>= %d bytes) expected' % (what, need))
+    call('cfn_segap_append', det_score, tp, workspace, scores, tps, counts, n_gt, flags, int(batch), C, int(score_col), dcap, cap)
+
+
+def segap_value(scores, tps, counts, n_gt, n_thr, out=None):
+    """Rule 7 of cfn_hip/segap.py: class-major stores -> (ap (n_thr, C) fp32, map (n_thr,) fp32) on the device: the stable descending sort of
+    ap_sort with one count per class and the tp byte as the payload, then the reduction.  Nothing is read back.  out = (sorted_scores,
+    sorted_tps, tmp_keys int32, tmp_tps, ap, map): buffers to reuse."""
+    what = 'segap_value'
+    C, cap = _segap_stores(what, scores, tps, counts, n_gt)
+    n_thr = int(n_thr)
+    if not 1 <= n_thr <= SEGAP_MAX_THR:
+        raise RuntimeError('%s: n_thr in [1, %d] expected, got %d' % (what, SEGAP_MAX_THR, n_thr))
+    dev = scores.device
+    if out is None:
+        out = (torch.empty_like(scores), torch.empty_like(tps), torch.empty(C, cap, dtype=torch.int32, device=dev), torch.empty_like(tps),
+               torch.empty(n_thr, C, dtype=torch.float32, device=dev), torch.empty(n_thr, dtype=torch.float32, device=dev))
+    ss, st, tk, tt, ap, mp = out
+    for x, shp, dt in ((ss, (C, cap), torch.float32), (st, (C, cap), torch.uint8), (tk, (C, cap), torch.int32), (tt, (C, cap), torch.uint8),
+                       (ap, (n_thr, C), torch.float32), (mp, (n_thr,), torch.float32)):
+        if tuple(x.shape) != shp or x.dtype != dt or x.device != dev or not x.is_contiguous():
+            raise RuntimeError('%s: out: sorted scores, sorted tps, tmp keys (int32), tmp tps of shape %s, ap %s and map %s fp32 on %s expected'
+                               % (what, (C, cap), (n_thr, C), (n_thr,), dev))
+    call('cfn_ap_sort_counts', scores, tps, counts, ss, st, tk, tt, C, cap)
+    call('cfn_segap_reduce', st, counts, n_gt, ap, mp, C, n_thr, cap)
+    return ap, mp
+
+
 # ---- baseline JPEG frames decoded on the GPU (csrc/jpegdec.hip; the host side and the batch type: cfn_hip/jpegdec.py) ------------------------
 def jpeg_workspace_bytes(rows, slots, lanes, blocks_max, entropy=None, sub_bytes=None, max_subs=None):
     """bytes of workspace cfn_jpeg_decode_u8 needs for `rows` frames into `slots` = clips x Tmax frame slots.  entropy, sub_bytes,

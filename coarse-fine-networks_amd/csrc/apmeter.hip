@@ -183,16 +183,16 @@ __device__ __forceinline__ void ap_pass_sync() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
 }
 
-// grid (K): workgroup k sorts rows 0 .. n - 1 of class k.  The two buffers alternate: scores -> tmp -> out -> tmp -> out.
+// grid (K): workgroup k sorts rows 0 .. n - 1 of class k, n = count[k * count_stride].  The two buffers alternate: scores -> tmp -> out -> tmp -> out.
 __global__ __launch_bounds__(AP_THREADS) void ap_sort_kernel(const float* __restrict__ scores, const unsigned char* __restrict__ targets,
                                                              const int* __restrict__ count, float* __restrict__ out_scores,
                                                              unsigned char* __restrict__ out_targets, int* __restrict__ tmp_keys,
-                                                             unsigned char* __restrict__ tmp_targets, long cap) {
+                                                             unsigned char* __restrict__ tmp_targets, long cap, int count_stride) {
     __shared__ unsigned hist[4 * 256];
     __shared__ unsigned wh[AP_WAVES * 256];
     const int tid = threadIdx.x, lane = tid & 63;
     const long cls = (long)blockIdx.x * cap;
-    const int n = (int)min(max((long)*count, 0L), cap);
+    const int n = (int)min(max((long)count[(long)blockIdx.x * count_stride], 0L), cap);      // (stride 0: one count for every class)
     const unsigned* s0 = reinterpret_cast<const unsigned*>(scores) + cls;
     const unsigned char* t0 = targets + cls;
     unsigned* ka = reinterpret_cast<unsigned*>(tmp_keys) + cls;
@@ -240,8 +240,21 @@ extern "C" int cfn_ap_sort(const float* scores, const unsigned char* targets, co
     hipStream_t st = (hipStream_t)stream;
     CfnProfScope prof(CFN_K_ELEMWISE, st, 0.0);                            // (the row count is on the device: tools/ap_meter_bench.py states the bytes)
     hipLaunchKernelGGL(ap_sort_kernel, dim3((unsigned)K), dim3(AP_THREADS), 0, st, scores, targets, count, sorted_scores, sorted_targets, tmp_keys,
-                       tmp_targets, cap);
+                       tmp_targets, cap, 0);
     return ap_launch_ok("ap_sort");
+}
+
+// cfn_ap_sort with one count per class: counts (K) int32 (the stores of cfn_segap_append)
+extern "C" int cfn_ap_sort_counts(const float* scores, const unsigned char* targets, const int* counts, float* sorted_scores,
+                                  unsigned char* sorted_targets, int* tmp_keys, unsigned char* tmp_targets, int K, long cap, void* stream) {
+    CFN_REQUIRE(scores && targets && counts && sorted_scores && sorted_targets && tmp_keys && tmp_targets, "cfn_ap_sort_counts: null tensor");
+    CFN_REQUIRE(K > 0 && cap > 0, "cfn_ap_sort_counts: bad shape");
+    CFN_REQUIRE(cap <= 0x7fffffffL - AP_TILE, "cfn_ap_sort_counts: bad shape (cap < 2^31 - tile)");
+    hipStream_t st = (hipStream_t)stream;
+    CfnProfScope prof(CFN_K_ELEMWISE, st, 0.0);
+    hipLaunchKernelGGL(ap_sort_kernel, dim3((unsigned)K), dim3(AP_THREADS), 0, st, scores, targets, counts, sorted_scores, sorted_targets, tmp_keys,
+                       tmp_targets, cap, 1);
+    return ap_launch_ok("ap_sort_counts");
 }
 
 extern "C" int cfn_ap_sort_tile(void) { return AP_TILE; }

@@ -32,6 +32,8 @@ from cfn_hip.seglabels import materialize         # noqa: E402
 from cfn_hip.detections import epoch_path         # noqa: E402
 from train_fine import lr_warmup, flatten_clips   # noqa: E402
 from train_fine import add_detect_args, detect_argv, detect_writer   # noqa: E402
+from train_fine import (check_segment_ap, seg_ap_arguments, seg_ap_argv, seg_ap_from_args, segment_ap_add,   # noqa: E402
+                        segment_ap_line)
 from cfn_hip.u8clips import RawU8Clips, U8Clips, CHARADES_MEAN, CHARADES_STD   # noqa: E402,F401
 from cfn_hip.featpack import PackedFeats          # noqa: E402
 
@@ -180,7 +182,7 @@ def run(init_lr=INIT_LR, warmup_steps=0, max_epochs=200, mode='rgb', root=None, 
         batch_size=BS * BS_UPSCALE, frames=80 * 4, dataloaders=None, max_steps=None,
         save_model='models/coarse_fineFEAT_charades_', pretrained='models/x3d_multigrid_kinetics_fb_pretrained.pt',
         csv_path='localize_corr_v1.csv', log=print, phase_hook=None, input_norm=None, device_ap=False,
-        fused_loss=False, jpeg_entropy=None, detections=None):
+        fused_loss=False, jpeg_entropy=None, detections=None, segment_ap=None):
     """detections: a cfn_hip.detections.DetectionWriter -- every validation phase decodes its probs into activity segments on the GPU and
     rank 0 writes all ranks' videos as JSON lines (see train_fine.run).  None: nothing changes.
     input_norm: see build_model -- needed when the loaders collate uint8 frames (collate.coarse_collate_u8, or coarse_collate_raw_u8:
@@ -193,6 +195,7 @@ def run(init_lr=INIT_LR, warmup_steps=0, max_epochs=200, mode='rgb', root=None, 
     CFN_JPEG_ENTROPY."""
     fused = True if fused_loss else None
     rank, world, dev = cdist.init_from_env()
+    check_segment_ap(segment_ap, world)
     gamma_tau = 5
     clip_frames = frames * 2 // (gamma_tau * 2)
     local_bs = max(batch_size // world, 1)
@@ -234,7 +237,7 @@ def run(init_lr=INIT_LR, warmup_steps=0, max_epochs=200, mode='rgb', root=None, 
                         continue
                 b, n = inputs.shape[:2]            # n crops per video at validation time (:198-201)
                 inputs = flatten_clips(inputs, dev, CROP if train else None, names=name, jpeg_entropy=jpeg_entropy)      # validation: forward_video transforms chunk by chunk
-                seg_batch = labels if detections is not None else None      # (its fps / window, before materialize drops the SegLabels)
+                seg_batch = labels if detections is not None or segment_ap is not None else None      # (its fps / window, before materialize drops the SegLabels)
                 labels, masks = materialize(labels, masks, dev)      # dense tensors: .to(dev); a SegLabels batch (segment labels): one kernel
                 feat_masks, meta = feat_masks.to(dev), meta.to(dev)
                 feat = unpack_feat(feat, dev)      # a PackedFeats batch (coarse_collate_packed): unpacked once per batch / validation video
@@ -251,8 +254,11 @@ def run(init_lr=INIT_LR, warmup_steps=0, max_epochs=200, mode='rgb', root=None, 
                         logits = forward_video(net, inputs, feat, feat_masks, i, meta)
                         cls_loss, loc_loss, probs = detection_loss(logits, labels, masks, crops=n, local_norm=True, fused=fused)
                     val_rows.extend(localize_rows(probs, labels, valid_t, name, dur))
+                    det = None
                     if detections is not None:      # decoded on the device; the segments stay there until the end of the phase
-                        detections.add(probs, valid_t, seg_batch, name)
+                        det = detections.add(probs, valid_t, seg_batch, name)
+                    if segment_ap is not None:      # train_fine.run: the same segments, matched against the segment labels on the device
+                        segment_ap_add(segment_ap, det, probs, valid_t, seg_batch, labels)
                     tot_cls += float(cls_loss)
                     tot_loc += float(loc_loss)
                 if train and steps % max(iters // 2, 1) == 0:
@@ -288,6 +294,8 @@ def run(init_lr=INIT_LR, warmup_steps=0, max_epochs=200, mode='rgb', root=None, 
                     det_rows = cdist.gather_objects(detections.take())
                     if rank == 0:
                         detections.flush(epoch_path(detections.path, epochs), [r for part in det_rows for r in part])
+                if segment_ap is not None:
+                    log(segment_ap_line(segment_ap, epochs))
                 if write_file:          # the reference closes the CSV after the first val phase (:295)
                     write_file.close()
                     write_file = writer = None
@@ -308,6 +316,7 @@ if __name__ == '__main__':
     parser.add_argument('--jpeg-entropy', choices=('interval', 'sync'), default=None,
                         help='entropy mode of the GPU JPEG decode: sync = parallel inside a frame without restart markers')
     add_detect_args(parser)
+    seg_ap_arguments(parser)
     args = parser.parse_args()
     if 'RANK' not in os.environ and len(args.gpu.split(',')) > 1:
         from train_fine import _spawn
@@ -319,8 +328,8 @@ if __name__ == '__main__':
                                   os.path.abspath(__file__), '--batch-size', str(args.batch_size)] +
                                  (['--max-steps', str(args.max_steps)] if args.max_steps else []) + (['--device-ap'] if args.device_ap else []) +
                                  (['--fused-loss'] if args.fused_loss else []) + (['--jpeg-entropy', args.jpeg_entropy] if args.jpeg_entropy else []) +
-                                 detect_argv(args), env=env))
+                                 detect_argv(args) + seg_ap_argv(args), env=env))
     if 'RANK' not in os.environ:
         os.environ['CUDA_VISIBLE_DEVICES'] = args.gpu
     run(batch_size=args.batch_size, max_steps=args.max_steps, device_ap=args.device_ap, fused_loss=args.fused_loss, jpeg_entropy=args.jpeg_entropy,
-        detections=detect_writer(args))
+        detections=detect_writer(args), segment_ap=seg_ap_from_args(args))

@@ -33,6 +33,7 @@ from apmeter import APMeter                       # noqa: E402
 from cfn_hip import metrics                       # noqa: E402
 from cfn_hip.seglabels import materialize         # noqa: E402
 from cfn_hip.detections import DetectionWriter, epoch_path   # noqa: E402
+from cfn_hip.seglabels import SegLabels           # noqa: E402
 
 BS = 8
 BS_UPSCALE = 1
@@ -276,10 +277,14 @@ _ap_rows = metrics.ap_rows      # per video: (scores (v,157), targets (v,157)) n
 def run(init_lr=INIT_LR, warmup_steps=0, max_epochs=200, mode='rgb', root=None, train_split=None,
         batch_size=BS * BS_UPSCALE, frames=80 * 4, dataloaders=None, max_steps=None, save_model='models/fine_charades_',
         pretrained='models/x3d_multigrid_kinetics_fb_pretrained.pt', log=print, phase_hook=None, input_norm=None,
-        device_ap=False, fused_loss=False, jpeg_entropy=None, detections=None):
+        device_ap=False, fused_loss=False, jpeg_entropy=None, detections=None, segment_ap=None):
     """detections: a cfn_hip.detections.DetectionWriter -- every validation phase decodes its probs into activity segments on the GPU
     (cfn_hip.ops.decode_segments) and rank 0 writes them, all ranks' videos, as JSON lines to the writer's path with the epoch inserted
     (cfn_hip.detections.epoch_path); seconds when the loaders collate SegLabel samples, frames otherwise.  None: nothing changes.
+    segment_ap: a cfn_hip.segap.SegmentAPMeter -- every validation phase matches the same decoded segments (the writer's decode; the meter's
+    own thr / max_gap / min_len without a writer) against the batch's segment labels on the GPU and logs ' Epoch:E val seg-mAP@t: ...' behind the
+    existing line.  One process only: AP is not additive and merging the stores of several ranks is out of scope, so a world size above 1
+    raises.  None: nothing changes.
     input_norm: see build_model -- needed when the loaders collate uint8 frames (collate.fine_collate_u8, or fine_collate_raw_u8:
     untransformed frames + crop boxes, cropped / resized to the model's crop size / flipped on the GPU in front of the step).
     device_ap: the training phases keep their AP rows and loss totals on the GPU (cfn_hip.metrics.StepMetrics, apmeter.DeviceAPMeter):
@@ -289,6 +294,7 @@ def run(init_lr=INIT_LR, warmup_steps=0, max_epochs=200, mode='rgb', root=None, 
     jpeg_entropy: how JpegClips batches are entropy-decoded, 'interval' or 'sync' (flatten_clips); None leaves the choice to CFN_JPEG_ENTROPY."""
     fused = True if fused_loss else None
     rank, world, dev = cdist.init_from_env()
+    check_segment_ap(segment_ap, world)
     gamma_tau = {'S': 6, 'M': 5, 'XL': 5}[X3D_VERSION]
     crop = {'S': 160, 'M': 224, 'XL': 312}[X3D_VERSION]
     clip_frames = frames * 2 // (gamma_tau * 2)          # 640-frame window at stride 10 -> 64 frames
@@ -331,7 +337,7 @@ def run(init_lr=INIT_LR, warmup_steps=0, max_epochs=200, mode='rgb', root=None, 
                     continue
                 b, n = inputs.shape[:2]          # n crops per video (1 in training, train_fine.py:176-185)
                 inputs = flatten_clips(inputs, dev, crop, names=_name, jpeg_entropy=jpeg_entropy)
-                seg_batch = labels if detections is not None else None      # (its fps / window, before materialize drops the SegLabels)
+                seg_batch = labels if detections is not None or segment_ap is not None else None      # (its fps / window, before materialize drops the SegLabels)
                 labels, masks = materialize(labels, masks, dev)      # dense tensors: .to(dev); a SegLabels batch (segment labels): one kernel
                 valid_t = masks.sum(1).int()
                 n_it += 1
@@ -345,8 +351,11 @@ def run(init_lr=INIT_LR, warmup_steps=0, max_epochs=200, mode='rgb', root=None, 
                         logits = net([inputs, masks[:, ::gamma_tau * 2]])
                         cls_loss, loc_loss, probs = detection_loss(logits, labels, masks, True, crops=n, local_norm=True, fused=fused)
                     val_rows.extend(_ap_rows(probs, labels, valid_t))
+                    det = None
                     if detections is not None:      # decoded on the device; the segments stay there until the end of the phase
-                        detections.add(probs, valid_t, seg_batch, _name)
+                        det = detections.add(probs, valid_t, seg_batch, _name)
+                    if segment_ap is not None:      # matched and appended on the device; nothing is read back before the end of the phase
+                        segment_ap_add(segment_ap, det, probs, valid_t, seg_batch, labels)
                     tot_cls += float(cls_loss)
                     tot_loc += float(loc_loss)
                 if train and steps % max(iters // 2, 1) == 0:
@@ -378,11 +387,70 @@ def run(init_lr=INIT_LR, warmup_steps=0, max_epochs=200, mode='rgb', root=None, 
                     det_rows = cdist.gather_objects(detections.take())
                     if rank == 0:
                         detections.flush(epoch_path(detections.path, epochs), [r for part in det_rows for r in part])
+                if segment_ap is not None:
+                    log(segment_ap_line(segment_ap, epochs))
                 val_apm.reset()
                 lr_sched.step()            # once per val phase, as the reference (not per epoch, not per step)
             if phase_hook is not None:         # test / logging hook: end of a phase (not in the reference's signature)
                 phase_hook(phase, epochs, optimizer)
     return net
+
+
+def check_segment_ap(meter, world):
+    """a SegmentAPMeter works in ONE process: AP is not additive, and merging the stores of several ranks is out of scope"""
+    if meter is not None and world > 1:
+        raise RuntimeError('segment_ap: a SegmentAPMeter holds the detections of ONE process; AP is not additive over ranks and merging their '
+                           'stores is not implemented (world size %d): validate on one GPU, or leave segment_ap=None' % world)
+
+
+def segment_ap_add(meter, det, probs, valid_t, seg_batch, labels):
+    """one validation batch into the meter: `det` = what the DetectionWriter decoded (None: decode here with the meter's parameters);
+    ground truth = the batch's SegLabels (seconds), or the dense labels decoded into frame units"""
+    from cfn_hip.detections import decode
+    valid_t = valid_t.to(torch.int32)
+    if isinstance(seg_batch, SegLabels):
+        seg_batch = seg_batch.to(probs.device)
+        if det is None:
+            det = decode(probs.detach(), valid_t, seg_batch.fps, seg_batch.window[:, 0].contiguous(), meter.thr, meter.max_gap, meter.min_len)
+        meter.add(det, seg_batch)
+    else:
+        if det is None:
+            det = decode(probs.detach(), valid_t, None, None, meter.thr, meter.max_gap, meter.min_len)
+        meter.add(det, (labels, valid_t))
+
+
+def segment_ap_line(meter, epochs):
+    """the phase's line (ONE read-back), and the meter is empty again"""
+    _, mp = meter.value()
+    meter.reset()
+    return ' Epoch:{} val {}'.format(epochs, ' '.join('seg-mAP@{:g}: {:.4f}'.format(t, float(m)) for t, m in zip(meter.tiou, mp)))
+
+
+def seg_ap_arguments(parser):
+    """the --seg-ap group: segment-level AP at tIoU thresholds of every validation phase (cfn_hip.segap.SegmentAPMeter)"""
+    g = parser.add_argument_group('segment AP')
+    g.add_argument('--seg-ap', action='store_true', help='log seg-mAP@tIoU of every validation phase (one process only)')
+    g.add_argument('--seg-ap-tiou', default='0.1,0.3,0.5,0.7,0.9', help='1 to 8 tIoU thresholds in (0, 1], comma separated')
+    g.add_argument('--seg-ap-score', choices=('max', 'mean'), default='max', help='the score column detections are ranked by')
+    g.add_argument('--seg-ap-capacity', type=int, default=None, help='rows per class, fixed (default: the stores grow)')
+    return parser
+
+
+def seg_ap_argv(args):
+    """the --seg-ap group of `args` as a worker's command line"""
+    if not args.seg_ap:
+        return []
+    return ['--seg-ap', '--seg-ap-tiou', args.seg_ap_tiou, '--seg-ap-score', args.seg_ap_score] + \
+        (['--seg-ap-capacity', str(args.seg_ap_capacity)] if args.seg_ap_capacity is not None else [])
+
+
+def seg_ap_from_args(args, n_classes=157):
+    """the meter of the --seg-ap group on this process's GPU (decode parameters: the --detect group's), or None"""
+    if not args.seg_ap:
+        return None
+    from cfn_hip.segap import SegmentAPMeter
+    return SegmentAPMeter(torch.device('cuda', torch.cuda.current_device()), n_classes, [float(x) for x in args.seg_ap_tiou.split(',')], args.seg_ap_score,
+                          args.seg_ap_capacity, args.detect_thr, args.detect_gap, args.detect_min_len)
 
 
 def add_detect_args(parser):
@@ -426,13 +494,14 @@ if __name__ == '__main__':
     parser.add_argument('--jpeg-entropy', choices=('interval', 'sync'), default=None,
                         help='entropy mode of the GPU JPEG decode: sync = parallel inside a frame without restart markers')
     add_detect_args(parser)
+    seg_ap_arguments(parser)
     args = parser.parse_args()
     if 'RANK' not in os.environ and len(args.gpu.split(',')) > 1:
         sys.exit(_spawn(args.gpu, ['--batch-size', str(args.batch_size)] +
                         (['--max-steps', str(args.max_steps)] if args.max_steps else []) + (['--device-ap'] if args.device_ap else []) +
                         (['--fused-loss'] if args.fused_loss else []) + (['--jpeg-entropy', args.jpeg_entropy] if args.jpeg_entropy else []) +
-                        detect_argv(args)))
+                        detect_argv(args) + seg_ap_argv(args)))
     if 'RANK' not in os.environ:
         os.environ['CUDA_VISIBLE_DEVICES'] = args.gpu
     run(batch_size=args.batch_size, max_steps=args.max_steps, device_ap=args.device_ap, fused_loss=args.fused_loss, jpeg_entropy=args.jpeg_entropy,
-        detections=detect_writer(args))
+        detections=detect_writer(args), segment_ap=seg_ap_from_args(args))

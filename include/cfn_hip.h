@@ -608,6 +608,57 @@ int cfn_decode_segments(const float* probs, const int* valid_t, const double* fp
                         int* frames, float* score, int* offsets, int* total, void* workspace, int B, int C, int TL, int max_gap,
                         int min_len, long cap, void* stream);
 
+/* =====================================================================================================================
+ * Segment-level average precision at temporal-IoU thresholds (csrc/segap.hip; the host reference and the meter:
+ * cfn_hip/segap.py).  The first consumer of the pair cfn_seg_labels' seg / cfn_decode_segments' seg; the reference stops at probs
+ * (train_fine.py:199-222), so the rule is stated here once:
+ *   detections det_seg (det_cap, 3) fp64, det_score (det_cap, 2) fp32, det_offsets (B + 1) int32 (cfn_decode_segments' outputs);
+ *   ground truth seg (n_seg, 3) fp64, offsets (B + 1) int32, fps (B) fp64, window (B, 2) int32 (cfn_seg_labels' inputs);
+ *   tiou (n_thr) fp64, 1 <= n_thr <= 8, each in (0, 1]; score_col 0 = max, 1 = mean.
+ *     1. n = clamp(window[b,1], 0, t_max), w0 = ((double)window[b,0] - 0.5) / fps[b], w1 = ((double)(window[b,0] + n) - 0.5) / fps[b]
+ *        (the extent cfn_decode_segments gives a detection over the whole window); s' = max(s, w0), e' = min(e, w1) (a NaN bound
+ *        gives way to the window's).  A row PARTICIPATES iff n > 0, its class is an integer of [0, C) and e' > s'.  n_gt[c] counts
+ *        participating rows.
+ *     2. tIoU of (sd, ed) and (s', e'): inter = min(ed, e') - max(sd, s'); 0 unless inter > 0, otherwise
+ *        inter / ((ed - sd) + (e' - s') - inter): IEEE fp64, no product, one division.
+ *     3. within a (video, class) group the detections are taken by det_score[:, score_col] descending (fp32), ties by row ascending.
+ *     4. greedy, independently per threshold k: a detection takes the participating row of its video and class that is not used up
+ *        at k with the largest tIoU among those with tIoU >= tiou[k]; ties go to the lowest row.  It is then a true positive at k
+ *        and the row is used up at k; otherwise a false positive.
+ *     5. tp (det_cap) uint8: bit k = true positive at k; match (n_thr, det_cap) int32 or NULL: the row index or -1.  Only the rows
+ *        of the batch's detections are written.
+ *     6. class c's store receives the batch's detections of class c in (video, row) order behind the rows it holds: scores (C, cap)
+ *        fp32 and tps (C, cap) uint8, class major; counts (C) and n_gt (C) int32 advance.  A batch that would push ANY class past
+ *        cap writes nothing, changes no count and sets bit 1 of flags (cfn_ap_append's rule).
+ *     7. cfn_ap_sort_counts: cfn_ap_sort (stable, descending, its order of special values) with one count per class, the tp byte as
+ *        the payload.  ap (n_thr, C) fp32: ap[k, c] = (sum over the ranks r whose bit k is set of tp_cum_r / r) / n_gt[c], fp64 in a
+ *        fixed order, 0 where n_gt[c] == 0; map (n_thr) fp32 = the mean over the classes with n_gt > 0, fp64 in class order.
+ *   cfn_segap_match (1 launch, one wave per (video, class)): rules 1-5; leaves the groups' ranges and counts in `workspace`
+ *     (cfn_segap_workspace_bytes(B, C, det_cap, n_seg) bytes on an 8-byte boundary; the caller owns it until cfn_segap_append of
+ *     the same batch has passed on the stream).  Lanes hold ground-truth rows, cfn_segap_gt_tile() = 64 per tile; the score order
+ *     of a group lives in LDS up to cfn_segap_det_tile() = 1024 detections; larger videos / groups take a general path through
+ *     the workspace, so no size is undefined.  The order is rank by counting: O(nd^2 / 64) per group of nd detections.
+ *   cfn_segap_append (2 launches): rule 6 from the workspace cfn_segap_match left.
+ *   cfn_segap_reduce (2 launches): rule 7 behind cfn_ap_sort_counts.
+ * Everything but B, C, t_max, n_thr, score_col, det_cap, n_seg and cap is read on the device only and clamped: a bad batch gives
+ * wrong values, never a store outside the outputs.  Ordered by the stream alone; no allocation, no synchronisation (capturable);
+ * nothing accumulates in floating point across workgroups.  Return 1 for null pointers (match may be NULL), B or C outside
+ * [1, 65535], t_max < 1, n_thr outside [1, 8], score_col outside {0, 1}, det_cap, n_seg or cap outside [1, 2^31) (the sort:
+ * cap < 2^31 less one tile) or a misaligned workspace; cfn_segap_workspace_bytes -1 for the same shapes.
+ * ===================================================================================================================== */
+long cfn_segap_workspace_bytes(int B, int C, long det_cap, long n_seg);
+int cfn_segap_gt_tile(void);
+int cfn_segap_det_tile(void);
+int cfn_segap_match(const double* det_seg, const float* det_score, const int* det_offsets, const double* seg, const int* offsets,
+                    const double* fps, const int* window, const double* tiou, unsigned char* tp, int* match, void* workspace, int B,
+                    int C, int t_max, int n_thr, int score_col, long det_cap, long n_seg, void* stream);
+int cfn_segap_append(const float* det_score, const unsigned char* tp, void* workspace, float* scores, unsigned char* tps,
+                     int* counts, int* n_gt, int* flags, int B, int C, int score_col, long det_cap, long cap, void* stream);
+int cfn_ap_sort_counts(const float* scores, const unsigned char* targets, const int* counts, float* sorted_scores,
+                       unsigned char* sorted_targets, int* tmp_keys, unsigned char* tmp_targets, int K, long cap, void* stream);
+int cfn_segap_reduce(const unsigned char* sorted_tps, const int* counts, const int* n_gt, float* ap, float* map, int C, int n_thr,
+                     long cap, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -28,7 +28,47 @@ B * C * ((TL + 1) // 2) is the worst case.
 ``decode_reference`` spells the six rules in numpy on any device and is the tests' reference; ``decode`` is the one call that needs the GPU
 library.  Limits: B <= 65535, C < 2^19, TL <= 65536, B * C * TL < 2^31; the 'loc' task only; no CPU path for the operator.
 
-This module is host only (numpy + torch) apart from that call.
+PROPOSALS (``decode_levels`` -> ``nms``, or ``propose`` for both; cfn_hip.ops.decode_segments_levels / nms_segments, csrc/detections.hip and
+csrc/segnms.hip).  ``decode`` thresholds a class at ONE value, so a (video, class) group never overlaps itself and every activity gets one
+candidate whose boundaries that value fixes.  The usual way from per-frame scores to ranked segments groups the frames at several thresholds
+("levels": tight segments from high levels, long ones from low levels) and removes near-duplicates by non-maximum suppression over temporal IoU.
+The rules, stated once (the kernels, the numpy references and include/cfn_hip.h spell the same):
+
+  Level decode.  The inputs of ``decode``, but ``levels (C, K)`` fp32, 1 <= K <= 16, in place of ``thr``: row c holds class c's K thresholds in
+  the order the caller gives them, which need not be sorted.
+
+    L1. candidate row (b, c, k) is rules 1-5 above applied to probs[b, c, :] with the threshold levels[c, k]: the same valid_t, max_gap,
+        min_len, half-frame-outward fp64 times, scores over active frames only
+    L2. the class column of ``seg`` holds c; a separate ``level (cap,)`` uint8 holds k
+    L3. the output order is lexicographic in (b, c, k, t0), from counts and prefix sums; offsets and total are true counts, rows >= cap are
+        not written
+    L4. the worst-case cap is B * C * K * ((TL + 1) // 2); K = 1 gives ``decode``'s result bit for bit
+
+  So the candidates of a (video, class) group are contiguous and the class column does not decrease inside a video: all segap_match needs, and
+  a candidate list is a valid ``Detections`` for the meter.
+
+  NMS.  A ``Detections`` whose rows are grouped like that, a host float ``nms_thr`` of [0, 1] and ``score_col`` (0 = max, 1 = mean).
+
+    N1. groups are (video, class) row ranges, found as segap_match finds them
+    N2. the order inside a group: score[:, score_col] descending (fp32), ties by row index ascending (cfn_hip/segap.py rule 3; a NaN score,
+        which a decode never gives, ranks as -inf).  NESTED CANDIDATES SHARE THEIR MAXIMUM, so under score='max' the caller's LEVEL ORDER
+        decides those ties: levels listed high to low put the tight segment first, low to high the long one
+    N3. tIoU is cfn_hip/segap.py rule 2 (``tiou_reference``) on the seg columns: plain fp64, one division, no product, 0 unless inter > 0
+    N4. greedy: walk the group in the order of N2; a candidate is KEPT iff no candidate KEPT BEFORE IT has tIoU with it strictly above
+        nms_thr.  A suppressed candidate suppresses nothing
+    N5. the output is a stable compaction: kept rows in their input order, seg / frames / score copied bit for bit; offsets and total are
+        recomputed as true counts; rows >= cap_out are not written
+    N6. two further outputs: ``keep (cap_in,)`` uint8 (written for the rows of the batch's groups) and ``src (cap_out,)`` int32 = the input
+        row of each output row; ``level`` can be gathered through src
+    N7. nms_thr = 1 keeps everything; with nms_thr < 1 exact duplicates across levels have tIoU exactly 1.0 and collapse to the first copy; a
+        single-level decode passes through unchanged for any nms_thr, because its candidates do not overlap
+
+``decode_levels_reference`` and ``nms_reference`` spell these in numpy on any device and are the tests' reference.  Limits: K <= 16,
+B * C * K * TL < 2^31; NMS: B and C <= 65535, ranking is O(nd^2) and suppression O(kept * nd) per group of nd candidates.  No accuracy gain
+is claimed: which levels and which nms_thr help a trained model is for the user to find with the meter.  Out of scope: soft-NMS, NMS across
+classes.
+
+This module is host only (numpy + torch) apart from those calls.
 """
 import collections
 import json
@@ -171,6 +211,154 @@ def decode_reference(probs, valid_t, fps=None, start=None, thr=0.5, max_gap=0, m
                       torch.tensor(offsets, dtype=torch.int32, device=dev), torch.tensor([total], dtype=torch.int32, device=dev), int(C), keep)
 
 
+SCORE_COLUMNS = {'max': 0, 'mean': 1}
+
+
+def _score_col(score):
+    if score not in SCORE_COLUMNS:
+        raise ValueError("score: 'max' or 'mean' expected, got %r" % (score,))
+    return SCORE_COLUMNS[score]
+
+
+def levels_tensor(levels, n_classes, device=None):
+    """levels: a sequence of 1 to 16 floats (every class the same, in that order) or a (C, K) tensor -> a contiguous (C, K) fp32 tensor"""
+    C = int(n_classes)
+    if torch.is_tensor(levels):
+        t = levels.detach().to(torch.float32)
+        if t.dim() != 2 or int(t.shape[0]) != C or not 1 <= int(t.shape[1]) <= 16:
+            raise ValueError('levels: 1 to 16 floats or a (%d, K) tensor with K <= 16 expected, got %s' % (C, tuple(levels.shape)))
+    else:
+        vals = [float(x) for x in levels]
+        if not 1 <= len(vals) <= 16:
+            raise ValueError('levels: 1 to 16 floats or a (%d, K) tensor with K <= 16 expected, got %r' % (C, levels))
+        t = torch.tensor(vals, dtype=torch.float32).repeat(C, 1)
+    return (t if device is None else t.to(device)).contiguous()
+
+
+def decode_levels(probs, valid_t, fps=None, start=None, levels=(0.5,), max_gap=0, min_len=1, cap=None, out=None):
+    """probs (B, C, TL) fp32 and valid_t (B,) int32 on the GPU -> (Detections of the candidates at every level, level (cap,) uint8) there (rules
+    L1-L4; ops.decode_segments_levels: three launches, nothing is read back).  levels: floats (every class) or a (C, K) fp32 tensor; fps, start
+    as decode().  cap, out: see ops.decode_segments_levels (with out=, hand a (C, K) device tensor for nothing to be allocated)."""
+    from . import ops
+    fps, start = _defaults(probs, fps, start)
+    C = int(probs.shape[1]) if probs.dim() == 3 else 0
+    if not (torch.is_tensor(levels) and levels.dtype == torch.float32 and levels.dim() == 2 and levels.device == probs.device and levels.is_contiguous()):
+        levels = levels_tensor(levels, C, probs.device)
+    if cap is None and probs.dim() == 3:
+        cap = ops.decode_segments_levels_cap(probs.shape[0], C, levels.shape[1], probs.shape[2])
+    seg, frames, score, level, offsets, total = ops.decode_segments_levels(probs, valid_t, fps, start, levels, max_gap, min_len, cap, out)
+    return Detections(seg, frames, score, offsets, total, C, int(cap)), level
+
+
+def decode_levels_reference(probs, valid_t, fps=None, start=None, levels=(0.5,), max_gap=0, min_len=1, cap=None):
+    """decode_levels() from rules L1-L4 in numpy: K decode_reference calls (one per level column), merged in (b, c, k, t0) order; tensors on
+    any device, the result on probs' device.  cap as in decode_reference."""
+    dev = probs.device
+    B, C = int(probs.shape[0]), int(probs.shape[1])
+    lv = levels_tensor(levels, C).cpu()
+    K = int(lv.shape[1])
+    parts = [decode_reference(probs.detach().cpu(), valid_t.cpu(), None if fps is None else fps.cpu(), None if start is None else start.cpu(),
+                              lv[:, k].contiguous(), max_gap, min_len) for k in range(K)]
+    rows = []                                                                         # (b, c, k, t0) -> (k, row of part k)
+    for k, d in enumerate(parts):
+        offs = d.offsets.tolist()
+        for b in range(B):
+            for i in range(offs[b], offs[b + 1]):
+                rows.append((b, int(d.seg[i, 0]), k, int(d.frames[i, 0]), i))
+    rows.sort()
+    total = len(rows)
+    keep = max(total, 1) if cap is None else int(cap)
+    if keep < 1:
+        raise ValueError('cap >= 1 expected, got %d' % keep)
+    seg, frames, score = torch.zeros(keep, 3, dtype=torch.float64), torch.zeros(keep, 3, dtype=torch.int32), torch.zeros(keep, 2, dtype=torch.float32)
+    level = torch.zeros(keep, dtype=torch.uint8)
+    n = min(total, keep)
+    if n:
+        first = np.cumsum([0] + [int(d.seg.shape[0]) for d in parts])                 # the parts' rows behind one another
+        pick = torch.tensor([first[k] + i for _, _, k, _, i in rows[:n]], dtype=torch.int64)
+        seg[:n], frames[:n], score[:n] = (torch.cat([d[j] for d in parts])[pick] for j in range(3))
+        level[:n] = torch.tensor([k for _, _, k, _, _ in rows[:n]], dtype=torch.uint8)
+    offsets = np.concatenate([[0], np.cumsum(np.bincount(np.asarray([r[0] for r in rows], np.int64), minlength=B))]).astype(np.int64).tolist()
+    return (Detections(seg.to(dev), frames.to(dev), score.to(dev), torch.tensor(offsets, dtype=torch.int32, device=dev),
+                       torch.tensor([total], dtype=torch.int32, device=dev), C, keep), level.to(dev))
+
+
+def _rows(det):
+    """a Detections' three record buffers cut to its cap (out= buffers may be longer than the decode's cap)"""
+    if int(det.seg.shape[0]) == int(det.cap):
+        return det.seg, det.frames, det.score
+    return det.seg[:det.cap], det.frames[:det.cap], det.score[:det.cap]
+
+
+def nms(det, nms_thr, score='max', cap=None, out=None):
+    """Temporal NMS of a Detections on the GPU -> (the kept Detections, keep (cap_in,) uint8, src (cap,) int32) there (rules N1-N7;
+    ops.nms_segments: three launches, nothing is read back).  cap (default: det.cap, which cannot overflow) and out: see ops.nms_segments."""
+    from . import ops
+    if not isinstance(det, Detections):
+        raise TypeError('nms: a cfn_hip.detections.Detections expected, got %s' % type(det).__name__)
+    seg, frames, score_t = _rows(det)
+    cap = int(det.cap) if cap is None else int(cap)
+    seg_o, frames_o, score_o, offsets, total, keep, src = ops.nms_segments(seg, frames, score_t, det.offsets, det.n_classes, nms_thr, _score_col(score),
+                                                                            cap, out)
+    return Detections(seg_o, frames_o, score_o, offsets, total, det.n_classes, cap), keep, src
+
+
+def nms_reference(det, nms_thr, score='max', cap=None):
+    """nms() from rules N1-N7 in numpy; a Detections on any device, the results on its device.  cap=None: exactly the kept rows (at least
+    one); a cap keeps the first `cap` kept rows and the true offsets / total, as the kernel does.  keep covers the min(total, cap_in) input
+    rows; src the rows written."""
+    from .segap import tiou_reference
+    col = _score_col(score)
+    nms_thr = float(nms_thr)
+    if not 0.0 <= nms_thr <= 1.0:
+        raise ValueError('nms_thr in [0, 1] expected, got %r' % (nms_thr,))
+    dev = det.seg.device
+    seg, frames, sc = (t.detach().cpu().numpy() for t in det[:3])
+    offs = det.offsets.detach().cpu().numpy().astype(np.int64)
+    cap_in = min(int(det.cap), seg.shape[0])
+    B = len(offs) - 1
+    n = min(max(int(offs[-1]), 0), cap_in)
+    keep = np.zeros(n, np.uint8)
+    new_offs = [0]
+    for b in range(B):
+        lo, hi = min(max(int(offs[b]), 0), cap_in), min(max(int(offs[b + 1]), 0), cap_in)
+        for c in np.unique(seg[lo:hi, 0]):                                            # N1
+            rows = lo + np.flatnonzero(seg[lo:hi, 0] == c)
+            key = sc[rows, col].astype(np.float32)
+            key = np.where(np.isnan(key), np.float32(-np.inf), key)
+            order = rows[np.argsort(-key, kind='stable')]                             # N2
+            kept = []
+            for d in order:                                                           # N4
+                if not any(tiou_reference(seg[k, 1], seg[k, 2], seg[d, 1], seg[d, 2]) > nms_thr for k in kept):     # N3
+                    kept.append(d)
+                    keep[d] = 1
+        new_offs.append(int(keep[:hi].sum()))
+    src = np.flatnonzero(keep).astype(np.int32)                                       # N5: input order
+    total = int(src.size)
+    rows_out = max(total, 1) if cap is None else int(cap)
+    if rows_out < 1:
+        raise ValueError('cap >= 1 expected, got %d' % rows_out)
+    k = min(total, rows_out)
+    o_seg, o_frames, o_score = np.zeros((rows_out, 3), np.float64), np.zeros((rows_out, 3), np.int32), np.zeros((rows_out, 2), np.float32)
+    o_src = np.zeros(rows_out, np.int32)
+    o_seg[:k], o_frames[:k], o_score[:k], o_src[:k] = seg[src[:k]], frames[src[:k]], sc[src[:k]], src[:k]
+    out = Detections(torch.from_numpy(o_seg).to(dev), torch.from_numpy(o_frames).to(dev), torch.from_numpy(o_score).to(dev),
+                     torch.tensor(new_offs, dtype=torch.int32, device=dev), torch.tensor([total], dtype=torch.int32, device=dev), det.n_classes, rows_out)
+    return out, torch.from_numpy(keep).to(dev), torch.from_numpy(o_src).to(dev)
+
+
+def propose(probs, valid_t, fps=None, start=None, levels=(0.8, 0.65, 0.5, 0.35, 0.2), nms_thr=0.5, score='max', max_gap=0, min_len=1, out=None,
+            reference=False):
+    """probs -> candidates at K levels -> NMS -> the post-NMS Detections, all on the device (six launches, nothing is read back).  Levels
+    listed high to low prefer the tight segment among nested candidates under score='max' (rule N2).  out: (the out of decode_levels, the out
+    of nms), both for the worst-case cap, for a call that allocates nothing (capturable).  reference=True: the numpy references instead."""
+    if reference:
+        cand, _ = decode_levels_reference(probs, valid_t, fps, start, levels, max_gap, min_len)
+        return nms_reference(cand, nms_thr, score)[0]
+    cand, _ = decode_levels(probs, valid_t, fps, start, levels, max_gap, min_len, out=None if out is None else out[0])
+    return nms(cand, nms_thr, score, out=None if out is None else out[1])[0]
+
+
 def epoch_path(path, epoch):
     """'val/det.jsonl', 4 -> 'val/det.ep004.jsonl': the file of one validation phase"""
     root, ext = os.path.splitext(path)
@@ -185,10 +373,19 @@ class DetectionWriter(object):
     add() decodes on the device and keeps the device tensors (nothing is read back, the host does not wait); take() / flush() read every
     kept batch back once.  ``unit`` is "s" when the batch's labels were a SegLabels (its fps and window give seconds) and "frame"
     otherwise (fps = 1, start = 0).  Every add() decodes with the worst-case cap, which cannot overflow, so a batch keeps
-    B * C * ((TL + 1) // 2) * 44 bytes on the device: the kept tensors are read back early once they exceed `max_pending_bytes`."""
+    B * C * ((TL + 1) // 2) * 44 bytes on the device: the kept tensors are read back early once they exceed `max_pending_bytes`.
 
-    def __init__(self, path, thr=0.5, max_gap=0, min_len=1, max_pending_bytes=1 << 30):
+    levels (floats or a (C, K) tensor), nms (a float of [0, 1], default 0.5), nms_score: with `levels` set add() runs propose() in place of
+    decode() -- candidates at the K levels, then temporal NMS -- and keeps only the post-NMS batch (K times the rows); `thr` is then not
+    used.  The JSON format is the same."""
+
+    def __init__(self, path, thr=0.5, max_gap=0, min_len=1, max_pending_bytes=1 << 30, levels=None, nms=None, nms_score='max'):
         self.path, self.thr, self.max_gap, self.min_len = path, thr, int(max_gap), int(min_len)
+        self.levels, self.nms, self.nms_score = levels, (0.5 if nms is None else float(nms)), nms_score
+        if levels is None and nms is not None:
+            raise ValueError('DetectionWriter: nms without levels: a single-level decode does not overlap itself (rule N7)')
+        _score_col(nms_score)
+        self._levels_dev = {}
         self.max_pending_bytes = int(max_pending_bytes)
         self._pending, self._pending_bytes, self._rows = [], 0, []
         self._thr_dev = {}
@@ -203,6 +400,20 @@ class DetectionWriter(object):
             thr = self._thr_dev[key]
         return thr
 
+    @property
+    def n_levels(self):
+        """K, the candidates' levels per class (1 without `levels`): what SegmentAPMeter.add(levels=) takes"""
+        if self.levels is None:
+            return 1
+        return int(self.levels.shape[1]) if torch.is_tensor(self.levels) else len(self.levels)
+
+    def _levels(self, probs):
+        """the levels as a (C, K) device tensor, made once per device and class count"""
+        key = (probs.device, int(probs.shape[1]))
+        if key not in self._levels_dev:
+            self._levels_dev[key] = levels_tensor(self.levels, key[1], probs.device)
+        return self._levels_dev[key]
+
     def add(self, probs, valid_t, labels, names, decoder=None):
         """probs (B, C, TL) fp32 and valid_t (B,) of one batch, its label member BEFORE it was made dense (a SegLabels batch gives fps and
         window; anything else, or None, gives frame units) and the B video names.  decoder: decode (the device, default) or
@@ -215,7 +426,11 @@ class DetectionWriter(object):
         if isinstance(labels, SegLabels):
             labels = labels.to(probs.device)
             fps, start, unit = labels.fps, labels.window[:, 0].contiguous(), 's'
-        det = (decoder or decode)(probs.detach(), valid_t.to(torch.int32), fps, start, self._thr(probs), self.max_gap, self.min_len)
+        if self.levels is not None:             # decoder: propose's `reference` switch (decode_reference: the numpy references)
+            det = propose(probs.detach(), valid_t.to(torch.int32), fps, start, self._levels(probs), self.nms, self.nms_score, self.max_gap, self.min_len,
+                          reference=decoder is decode_reference)
+        else:
+            det = (decoder or decode)(probs.detach(), valid_t.to(torch.int32), fps, start, self._thr(probs), self.max_gap, self.min_len)
         self._pending.append((det, names, unit))
         self._pending_bytes += sum(t.numel() * t.element_size() for t in det[:5])
         if self._pending_bytes > self.max_pending_bytes:

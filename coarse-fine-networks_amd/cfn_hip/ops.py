@@ -1621,6 +1621,150 @@ def decode_segments(probs, valid_t, fps, start, thr, max_gap=0, min_len=1, cap=N
     return out[:5]
 
 
+# ---- activity proposals: candidates at K levels, then temporal NMS (csrc/detections.hip, csrc/segnms.hip; the rules: cfn_hip/detections.py) ---
+DECODE_MAX_LEVELS = 16
+NMS_DET_TILE = 1024              # candidates of a (video, class) group suppressed in LDS (cfn_nms_det_tile(); more take the general path)
+
+
+def decode_segments_levels_cap(B, C, K, TL):
+    """the worst case of decode_segments_levels: every second frame of every row a run of its own, at every level"""
+    return int(B) * int(C) * int(K) * ((int(TL) + 1) // 2)
+
+
+def decode_segments_levels_workspace_bytes(B, C, K, TL):
+    n = int(query('cfn_decode_segments_levels_workspace_bytes', int(B), int(C), int(K), int(TL)))
+    if n < 0:
+        raise RuntimeError('decode_segments_levels: probs: B <= 65535, C < 2^19, TL <= %d, K in [1, %d] and B * C * K * TL < 2^31 expected, got '
+                           '(%d, %d, %d) and K = %d' % (DECODE_MAX_TL, DECODE_MAX_LEVELS, B, C, TL, K))
+    return n
+
+
+def decode_segments_levels(probs, valid_t, fps, start, levels, max_gap=0, min_len=1, cap=None, out=None):
+    """decode_segments at K threshold levels in one call: levels (C, K) fp32 on the device, 1 <= K <= 16, row c = class c's thresholds in the
+    caller's order -> (seg, frames, score, level (cap,) uint8, offsets, total): candidate row (b, c, k) is decode_segments' rules applied to
+    probs[b, c, :] with levels[c, k]; seg's class column holds c, `level` holds k; the order is (b, c, k, t0) (rules L1-L4 of
+    cfn_hip/detections.py; decode_levels_reference spells them on the host).  cap=None: B * C * K * ((TL + 1) // 2), which cannot overflow.
+    Three launches, nothing is read back (capturable with out=).  out: the six tensors and a uint8 workspace of
+    decode_segments_levels_workspace_bytes(B, C, K, TL) bytes.  No gradient, no CPU path."""
+    what = 'decode_segments_levels'
+    if not torch.is_tensor(probs) or probs.dtype != torch.float32 or probs.dim() != 3 or min(probs.shape) < 1 or not probs.is_contiguous():
+        raise RuntimeError('%s: probs: a contiguous (B, C, TL) float32 tensor expected, got %s %s'
+                           % (what, getattr(probs, 'dtype', type(probs).__name__), tuple(getattr(probs, 'shape', ()))))
+    B, C, TL = (int(s) for s in probs.shape)
+    if not torch.is_tensor(levels) or levels.dtype != torch.float32 or levels.dim() != 2 or int(levels.shape[0]) != C \
+            or not 1 <= int(levels.shape[1]) <= DECODE_MAX_LEVELS or not levels.is_contiguous():
+        raise RuntimeError('%s: levels: a contiguous (%d, K) float32 tensor with 1 <= K <= %d expected, got %s %s'
+                           % (what, C, DECODE_MAX_LEVELS, getattr(levels, 'dtype', type(levels).__name__), tuple(getattr(levels, 'shape', ()))))
+    K = int(levels.shape[1])
+    if TL > DECODE_MAX_TL or B > 65535 or C >= (1 << 19) or B * C * K * TL >= (1 << 31):
+        raise RuntimeError('%s: probs: B <= 65535, C < 2^19, TL <= %d and B * C * K * TL < 2^31 expected, got (%d, %d, %d) and K = %d'
+                           % (what, DECODE_MAX_TL, B, C, TL, K))
+    for name, t, dt in (('valid_t', valid_t, torch.int32), ('fps', fps, torch.float64), ('start', start, torch.int32)):
+        if not torch.is_tensor(t) or t.dtype != dt or tuple(t.shape) != (B,):
+            raise RuntimeError('%s: %s (%d,) %s expected, got %s %s' % (what, name, B, dt, getattr(t, 'dtype', type(t).__name__), tuple(getattr(t, 'shape', ()))))
+    max_gap, min_len = int(max_gap), int(min_len)
+    if max_gap < 0:
+        raise RuntimeError('%s: max_gap >= 0 expected, got %d' % (what, max_gap))
+    if min_len < 1:
+        raise RuntimeError('%s: min_len >= 1 expected, got %d' % (what, min_len))
+    cap = decode_segments_levels_cap(B, C, K, TL) if cap is None else int(cap)
+    if cap < 1 or cap >= (1 << 31):
+        raise RuntimeError('%s: cap in [1, 2^31) expected, got %d' % (what, cap))
+    dev = probs.device
+    for name, t in (('probs', probs), ('valid_t', valid_t), ('fps', fps), ('start', start), ('levels', levels)):
+        if t.device.type != 'cuda' or t.device != dev:
+            raise RuntimeError('%s: %s is on %s: device tensors on one GPU expected (there is no CPU path; '
+                               'cfn_hip.detections.decode_levels_reference is the host spelling)' % (what, name, t.device))
+    ws_bytes = decode_segments_levels_workspace_bytes(B, C, K, TL)
+    if out is None:
+        out = (torch.empty(cap, 3, dtype=torch.float64, device=dev), torch.empty(cap, 3, dtype=torch.int32, device=dev),
+               torch.empty(cap, 2, dtype=torch.float32, device=dev), torch.empty(cap, dtype=torch.uint8, device=dev),
+               torch.empty(B + 1, dtype=torch.int32, device=dev), torch.empty(1, dtype=torch.int32, device=dev),
+               torch.empty(ws_bytes, dtype=torch.uint8, device=dev))
+    else:
+        out = tuple(out)
+        want = ((torch.float64, 3), (torch.int32, 3), (torch.float32, 2))
+        if len(out) != 7 or any(y.dtype != dt or y.dim() != 2 or y.shape[1] != w or y.shape[0] < cap or not y.is_contiguous()
+                                for y, (dt, w) in zip(out, want)) \
+                or out[3].dtype != torch.uint8 or out[3].dim() != 1 or out[3].numel() < cap or not out[3].is_contiguous() \
+                or out[4].dtype != torch.int32 or tuple(out[4].shape) != (B + 1,) or out[5].dtype != torch.int32 or tuple(out[5].shape) != (1,) \
+                or out[6].dtype != torch.uint8 or out[6].dim() != 1 or out[6].numel() < ws_bytes or out[6].data_ptr() % 8 \
+                or not (out[4].is_contiguous() and out[6].is_contiguous()):
+            raise RuntimeError('%s: out: contiguous seg (>= %d, 3) fp64, frames (>= %d, 3) int32, score (>= %d, 2) fp32, level (>= %d,) uint8, offsets '
+                               '(%d,) int32, total (1,) int32 and an 8-byte aligned uint8 workspace of >= %d bytes expected, got %s'
+                               % (what, cap, cap, cap, cap, B + 1, ws_bytes, [(y.dtype, tuple(y.shape)) for y in out]))
+    call('cfn_decode_segments_levels', probs, valid_t.contiguous(), fps.contiguous(), start.contiguous(), levels, out[0], out[1], out[2], out[3],
+         out[4], out[5], out[6], B, C, K, TL, max_gap, min_len, cap)
+    return out[:6]
+
+
+def nms_segments_workspace_bytes(B, C, cap_in):
+    n = int(query('cfn_nms_segments_workspace_bytes', int(B), int(C), int(cap_in)))
+    if n < 0:
+        raise RuntimeError('nms_segments: B and C in [1, 65535] and cap_in in [1, 2^31) expected, got (%d, %d, %d)' % (B, C, cap_in))
+    return n
+
+
+def nms_segments(seg, frames, score, offsets, n_classes, nms_thr, score_col=0, cap_out=None, out=None):
+    """Temporal non-maximum suppression of a batch's detections (seg (cap_in, 3) fp64, frames (cap_in, 3) int32, score (cap_in, 2) fp32,
+    offsets (B + 1,) int32: a Detections whose (video, class) groups are contiguous) -> (seg, frames, score, offsets, total, keep (cap_in,)
+    uint8, src (cap_out,) int32): inside every group, in the order of score[:, score_col] descending (ties: the lower row), a candidate is
+    kept iff no candidate kept before it has a temporal IoU with it above `nms_thr`; the kept rows in their input order, copied bit for bit
+    (rules N1-N7 of cfn_hip/detections.py; nms_reference spells them on the host).  offsets and total are true counts; rows >= cap_out
+    (default: cap_in, which cannot overflow) are not written; keep is written for the rows of the batch's groups only; src holds the input
+    row of each output row.  `n_classes`, `nms_thr` (a float of [0, 1]), `score_col` (0 = max, 1 = mean) and `cap_out` are host values.
+    Three launches, nothing is read back (capturable with out=).  out: the seven tensors and a uint8 workspace of
+    nms_segments_workspace_bytes(B, C, cap_in) bytes.  No gradient, no CPU path."""
+    what = 'nms_segments'
+    for name, t in (('seg', seg), ('frames', frames), ('score', score), ('offsets', offsets)):
+        if not torch.is_tensor(t) or t.device.type != 'cuda' or t.device != getattr(seg, 'device', None):
+            raise RuntimeError('%s: %s: device tensors on one GPU expected (there is no CPU path; cfn_hip.detections.nms_reference is the host '
+                               'spelling), got %s' % (what, name, getattr(t, 'device', type(t).__name__)))
+        if not t.is_contiguous():
+            raise RuntimeError('%s: %s must be contiguous' % (what, name))
+    if seg.dtype != torch.float64 or seg.dim() != 2 or seg.shape[1] != 3 or seg.shape[0] < 1:
+        raise RuntimeError('%s: seg: a (cap_in, 3) float64 tensor with cap_in >= 1 expected, got %s %s' % (what, seg.dtype, tuple(seg.shape)))
+    cap_in = int(seg.shape[0])
+    if frames.dtype != torch.int32 or tuple(frames.shape) != (cap_in, 3) or score.dtype != torch.float32 or tuple(score.shape) != (cap_in, 2):
+        raise RuntimeError('%s: frames (%d, 3) int32 and score (%d, 2) float32 expected, got %s %s and %s %s'
+                           % (what, cap_in, cap_in, frames.dtype, tuple(frames.shape), score.dtype, tuple(score.shape)))
+    if offsets.dtype != torch.int32 or offsets.dim() != 1 or offsets.numel() < 2:
+        raise RuntimeError('%s: offsets (B + 1,) int32 expected, got %s %s' % (what, offsets.dtype, tuple(offsets.shape)))
+    B, n_classes, score_col = int(offsets.numel()) - 1, int(n_classes), int(score_col)
+    if n_classes < 1 or score_col not in (0, 1):
+        raise RuntimeError('%s: n_classes >= 1 and score_col 0 (max) or 1 (mean) expected, got %d, %d' % (what, n_classes, score_col))
+    if isinstance(nms_thr, bool) or not isinstance(nms_thr, (int, float)) or not 0.0 <= float(nms_thr) <= 1.0:
+        raise RuntimeError('%s: nms_thr: a host float of [0, 1] expected, got %r' % (what, nms_thr))
+    cap_out = cap_in if cap_out is None else int(cap_out)
+    if cap_out < 1 or cap_out >= (1 << 31):
+        raise RuntimeError('%s: cap_out in [1, 2^31) expected, got %d' % (what, cap_out))
+    dev = seg.device
+    ws_bytes = nms_segments_workspace_bytes(B, n_classes, cap_in)
+    if out is None:
+        out = (torch.empty(cap_out, 3, dtype=torch.float64, device=dev), torch.empty(cap_out, 3, dtype=torch.int32, device=dev),
+               torch.empty(cap_out, 2, dtype=torch.float32, device=dev), torch.empty(B + 1, dtype=torch.int32, device=dev),
+               torch.empty(1, dtype=torch.int32, device=dev), torch.empty(cap_in, dtype=torch.uint8, device=dev),
+               torch.empty(cap_out, dtype=torch.int32, device=dev), torch.empty(ws_bytes, dtype=torch.uint8, device=dev))
+    else:
+        out = tuple(out)
+        want = ((torch.float64, 3), (torch.int32, 3), (torch.float32, 2))
+        if len(out) != 8 or any(y.dtype != dt or y.dim() != 2 or y.shape[1] != w or y.shape[0] < cap_out or not y.is_contiguous()
+                                for y, (dt, w) in zip(out, want)) \
+                or out[3].dtype != torch.int32 or tuple(out[3].shape) != (B + 1,) or out[4].dtype != torch.int32 or tuple(out[4].shape) != (1,) \
+                or out[5].dtype != torch.uint8 or out[5].dim() != 1 or out[5].numel() < cap_in or not out[5].is_contiguous() \
+                or out[6].dtype != torch.int32 or out[6].dim() != 1 or out[6].numel() < cap_out or not out[6].is_contiguous() \
+                or out[7].dtype != torch.uint8 or out[7].dim() != 1 or out[7].numel() < ws_bytes or out[7].data_ptr() % 8 \
+                or not (out[3].is_contiguous() and out[7].is_contiguous()) \
+                or any(y.data_ptr() == x.data_ptr() for y, x in zip(out[:3], (seg, frames, score))):
+            raise RuntimeError('%s: out: contiguous seg (>= %d, 3) fp64, frames (>= %d, 3) int32, score (>= %d, 2) fp32 (none of them an input), offsets '
+                               '(%d,) int32, total (1,) int32, keep (>= %d,) uint8, src (>= %d,) int32 and an 8-byte aligned uint8 workspace of >= %d '
+                               'bytes expected, got %s' % (what, cap_out, cap_out, cap_out, B + 1, cap_in, cap_out, ws_bytes,
+                                                           [(y.dtype, tuple(y.shape)) for y in out]))
+    call('cfn_nms_segments', seg, frames, score, offsets, out[0], out[1], out[2], out[3], out[4], out[5], out[6], out[7], B, n_classes, score_col,
+         float(nms_thr), cap_in, cap_out)
+    return out[:7]
+
+
 # ---- segment-level AP at temporal-IoU thresholds (csrc/segap.hip; the rule, the host reference and the meter: cfn_hip/segap.py) -------------
 SEGAP_GT_TILE = 64               # ground-truth rows of a video per tile of lanes (cfn_segap_gt_tile(); more take the general path)
 SEGAP_DET_TILE = 1024            # detections of a (video, class) group ordered in LDS (cfn_segap_det_tile(); more take the general path)

@@ -41,11 +41,10 @@ This module is host only (numpy + torch) apart from the calls into cfn_hip.ops.
 import numpy as np
 import torch
 
-from .detections import Detections, decode
+from .detections import SCORE_COLUMNS, Detections, decode
 from .seglabels import SegLabels
 
 DEFAULT_TIOU = (0.1, 0.3, 0.5, 0.7, 0.9)
-SCORE_COLUMNS = {'max': 0, 'mean': 1}
 
 
 def _np(t, dtype):
@@ -194,11 +193,15 @@ class SegmentAPMeter(object):
     graph capture, and a batch that does not fit is dropped, flagged on the device and reported by ``value()``.
 
     thr, max_gap, min_len: the decode parameters the training entry points use when they are given the meter without a DetectionWriter.
+    levels, nms (default 0.5), nms_score: with `levels` set those entry points run cfn_hip.detections.propose (candidates at K levels, then
+    temporal NMS) in place of decode; the meter only keeps the three for them.  A batch of proposals can hold K times the rows of a decode:
+    ``add(levels=K)`` multiplies growing mode's bound (post-NMS groups can still exceed (TL + 1) // 2 rows).
     One process only: merging the stores of data-parallel ranks is out of scope."""
 
     MIN_CAPACITY = 1024
 
-    def __init__(self, device, n_classes, tiou=DEFAULT_TIOU, score='max', capacity=None, thr=0.5, max_gap=0, min_len=1):
+    def __init__(self, device, n_classes, tiou=DEFAULT_TIOU, score='max', capacity=None, thr=0.5, max_gap=0, min_len=1, levels=None, nms=None,
+                 nms_score='max'):
         self.device = torch.device(device)
         if self.device.type != 'cuda':
             raise RuntimeError('SegmentAPMeter keeps its rows on a GPU (got device %s); cfn_hip.segap.ap_reference is the host spelling' % self.device)
@@ -212,6 +215,11 @@ class SegmentAPMeter(object):
         self.n_classes, self.score, self.score_col = int(n_classes), score, SCORE_COLUMNS[score]
         self.capacity = None if capacity is None else int(capacity)
         self.thr, self.max_gap, self.min_len = thr, int(max_gap), int(min_len)
+        if levels is None and nms is not None:
+            raise ValueError('SegmentAPMeter: nms without levels: a single-level decode does not overlap itself')
+        if nms_score not in SCORE_COLUMNS:
+            raise ValueError("nms_score: 'max' or 'mean' expected, got %r" % (nms_score,))
+        self.levels, self.nms, self.nms_score = levels, (0.5 if nms is None else float(nms)), nms_score
         self._tiou = torch.tensor(self.tiou, dtype=torch.float64, device=self.device)
         self._state = torch.zeros(2 * self.n_classes + 1, dtype=torch.int32, device=self.device)      # counts, n_gt, flags
         cap = self.capacity if self.capacity is not None else self.MIN_CAPACITY
@@ -269,10 +277,18 @@ class SegmentAPMeter(object):
         window = torch.stack([torch.zeros_like(valid_t), valid_t], 1).contiguous()
         return gt.seg, gt.offsets, torch.ones(B, dtype=torch.float64, device=self.device), window, TL
 
-    def add(self, det, labels, want_match=False, out=None, tl=None):
+    @property
+    def n_levels(self):
+        """K of `levels` (1 without)"""
+        if self.levels is None:
+            return 1
+        return int(self.levels.shape[1]) if torch.is_tensor(self.levels) else len(self.levels)
+
+    def add(self, det, labels, want_match=False, out=None, tl=None, levels=1):
         """det: the Detections of a batch on the meter's device; labels: see ground_truth().  Returns (tp, match or None) of the batch on
         the device.  out: (tp (cap,) uint8, match (n_thr, cap) int32 or None, workspace) as ops.segap_match takes them.  tl: the frames
-        the detections were decoded over (growing mode's bound; default: the labels' t_max)."""
+        the detections were decoded over (growing mode's bound; default: the labels' t_max).  levels: K when det are proposals decoded at K
+        levels (growing mode's bound times K)."""
         from . import ops
         if not isinstance(det, Detections):
             raise TypeError('SegmentAPMeter.add: a cfn_hip.detections.Detections expected, got %s' % type(det).__name__)
@@ -285,8 +301,10 @@ class SegmentAPMeter(object):
         dseg, dscore = det.seg, det.score
         if int(dseg.shape[0]) != int(det.cap):                                        # (out= buffers may be longer than the decode's cap)
             dseg, dscore = dseg[:det.cap], dscore[:det.cap]
+        if int(levels) < 1:
+            raise ValueError('SegmentAPMeter.add: levels >= 1 expected, got %r' % (levels,))
         if self.capacity is None:
-            self._reserve(min(B * ((max(int(t_max if tl is None else tl), 1) + 1) // 2), int(det.cap)))
+            self._reserve(min(B * int(levels) * ((max(int(t_max if tl is None else tl), 1) + 1) // 2), int(det.cap)))
         tp, match, ws = ops.segap_match(dseg, dscore, det.offsets, seg, offsets, fps, window, self._tiou, self.n_classes, t_max, self.score_col,
                                         want_match, out)
         ops.segap_append(dscore, tp, ws, self._scores, self._tps, self.counts, self.n_gt, self.flags, B, self.score_col)

@@ -24,6 +24,11 @@
 //           lane 0 stores the record at base + rank if that is < cap.
 // valid_t, fps, start and thr are DATA read on the device; every index is derived from B, C, TL and the mask, so a bad batch gives wrong
 // values, never an access outside the tensors.  LDS: 40 bytes per 64 frames (dynamic), 40 KB at TL = 65536.
+//
+// Levels (cfn_decode_segments_levels; the rules L1-L4 are in cfn_hip/detections.py): the same three kernels with a level count K.  A row is
+// (b, c, k): it reads probs row / K against levels[row % (C * K)] (levels (C, K), row c = class c's thresholds in the caller's order), the
+// scan's offsets boundary sits at C * K, and the write stores c in seg and k in level (cap) uint8.  Output order (b, c, k, t0);
+// cfn_decode_segments is K = 1 without the level column: its results and its workspace are what they were.
 #include "cfn_common.h"
 
 #define DS_THREADS 256
@@ -174,16 +179,17 @@ __device__ __forceinline__ int ds_plan(const DsRow& r, int nwords, int max_gap, 
 template <bool VEC>
 __global__ __launch_bounds__(DS_THREADS) void det_count_kernel(const float* __restrict__ probs, const int* __restrict__ valid_t,
                                                                const float* __restrict__ thr, ds_u64* __restrict__ masks, int* __restrict__ counts,
-                                                               int C, int TL, int nwords, int max_gap, int min_len) {
+                                                               int C, int K, int TL, int nwords, int max_gap, int min_len) {
     extern __shared__ __attribute__((aligned(16))) unsigned char ds_smem[];
     __shared__ int s_wave[DS_THREADS / 64];
     const DsRow r = ds_carve(ds_smem, nwords);
     const int tid = threadIdx.x, lane = tid & 63, wave = cfn_uni(tid >> 6);
-    const long row = blockIdx.x;                                           // b * C + c
-    const int b = (int)(row / C), c = (int)(row - (long)b * C);
+    const long row = blockIdx.x;                                           // (b * C + c) * K + k
+    const long srow = row / K;                                             // b * C + c: the row of probs
+    const int b = (int)(srow / C);
     const int vlen = min(max(valid_t[b], 0), TL);
-    const float th = thr[c];
-    const float* src = probs + row * TL;
+    const float th = thr[row - (long)b * C * K];                           // thr (C, K): c * K + k
+    const float* src = probs + srow * TL;
     ds_u64* mrow = masks + row * nwords;
     bool any = false;
     for (int f0 = wave * 256; f0 < TL; f0 += DS_PASS) {                    // (wave uniform: every lane reaches the ballots)
@@ -257,8 +263,8 @@ __global__ __launch_bounds__(1024) void det_scan_kernel(int* __restrict__ counts
 
 __global__ __launch_bounds__(DS_THREADS) void det_write_kernel(const float* __restrict__ probs, const double* __restrict__ fps, const int* __restrict__ start,
                                                                const ds_u64* __restrict__ masks, const int* __restrict__ bases, double* __restrict__ seg,
-                                                               int* __restrict__ frames, float* __restrict__ score, int C, int TL, int nwords,
-                                                               int max_gap, int min_len, long cap) {
+                                                               int* __restrict__ frames, float* __restrict__ score, unsigned char* __restrict__ level,
+                                                               int C, int K, int TL, int nwords, int max_gap, int min_len, long cap) {
     extern __shared__ __attribute__((aligned(16))) unsigned char ds_smem[];
     __shared__ int s_wave[DS_THREADS / 64];
     const long row = blockIdx.x;
@@ -266,7 +272,8 @@ __global__ __launch_bounds__(DS_THREADS) void det_write_kernel(const float* __re
     if (bases[row + 1] - base <= 0 || base >= cap) return;                 // (workgroup uniform) nothing kept, or all of it behind cap
     const DsRow r = ds_carve(ds_smem, nwords);
     const int tid = threadIdx.x, lane = tid & 63, wave = cfn_uni(tid >> 6);
-    const int b = (int)(row / C), c = (int)(row - (long)b * C);
+    const long srow = row / K;
+    const int b = (int)(srow / C), c = (int)(srow - (long)b * C), lev = (int)(row - srow * K);
     const ds_u64* mrow = masks + row * nwords;
     for (int w = tid; w < nwords; w += DS_THREADS) r.M[w] = mrow[w];
     __syncthreads();
@@ -280,7 +287,7 @@ __global__ __launch_bounds__(DS_THREADS) void det_write_kernel(const float* __re
         run += __builtin_popcountll(r.K[w]);
     }
     __syncthreads();
-    const float* src = probs + row * TL;
+    const float* src = probs + srow * TL;
     const double f = fps[b];
     const long first = start[b];
     for (int w = wave; w < nwords; w += DS_THREADS / 64) {                 // (wave uniform from here on)
@@ -319,6 +326,7 @@ __global__ __launch_bounds__(DS_THREADS) void det_write_kernel(const float* __re
                 frames[3 * idx + 0] = t0; frames[3 * idx + 1] = t1; frames[3 * idx + 2] = n;
                 score[2 * idx + 0] = mx;
                 score[2 * idx + 1] = (float)(sum / (double)n);
+                if (level) level[idx] = (unsigned char)lev;
             }
         }
     }
@@ -326,37 +334,62 @@ __global__ __launch_bounds__(DS_THREADS) void det_write_kernel(const float* __re
 
 static inline long ds_mask_words(long B, long C, long TL) { return B * C * ((TL + 63) / 64); }
 
-// workspace: the rows' 64-bit mask words, then B * C + 1 int32 (counts, then bases)
-extern "C" long cfn_decode_segments_workspace_bytes(int B, int C, int TL) {
-    if (B < 1 || C < 1 || TL < 1 || B > 65535 || C >= (1 << 19) || TL > DS_MAX_TL || (long)B * C * TL >= (1L << 31)) return -1;
-    return ds_mask_words(B, C, TL) * 8 + ((long)B * C + 1) * 4;
+#define DS_MAX_LEVELS 16
+
+static inline bool ds_shape_ok(int B, int C, int K, int TL) {
+    return B >= 1 && C >= 1 && TL >= 1 && B <= 65535 && C < (1 << 19) && TL <= DS_MAX_TL && K >= 1 && K <= DS_MAX_LEVELS && (long)B * C * K * TL < (1L << 31);
 }
 
-extern "C" int cfn_decode_segments(const float* probs, const int* valid_t, const double* fps, const int* start, const float* thr, double* seg,
-                                   int* frames, float* score, int* offsets, int* total, void* workspace, int B, int C, int TL, int max_gap,
-                                   int min_len, long cap, void* stream) {
-    const char* what = "cfn_decode_segments";
+// workspace: the rows' 64-bit mask words, then B * C * K + 1 int32 (counts, then bases)
+static inline long ds_workspace_bytes(int B, int C, int K, int TL) { return ds_mask_words(B, (long)C * K, TL) * 8 + ((long)B * C * K + 1) * 4; }
+
+extern "C" long cfn_decode_segments_workspace_bytes(int B, int C, int TL) { return ds_shape_ok(B, C, 1, TL) ? ds_workspace_bytes(B, C, 1, TL) : -1; }
+
+extern "C" long cfn_decode_segments_levels_workspace_bytes(int B, int C, int K, int TL) {
+    return ds_shape_ok(B, C, K, TL) ? ds_workspace_bytes(B, C, K, TL) : -1;
+}
+
+// rows are (b, c, k); thr (C, K); level may be null (K = 1: cfn_decode_segments)
+static int ds_decode(const char* what, const float* probs, const int* valid_t, const double* fps, const int* start, const float* thr, double* seg,
+                     int* frames, float* score, unsigned char* level, int* offsets, int* total, void* workspace, int B, int C, int K, int TL,
+                     int max_gap, int min_len, long cap, void* stream) {
     CFN_REQUIRE(probs && valid_t && fps && start && thr && seg && frames && score && offsets && total && workspace, "%s: null tensor", what);
     CFN_REQUIRE(B >= 1 && C >= 1 && TL >= 1, "%s: bad shape (B %d, C %d, TL %d)", what, B, C, TL);
-    CFN_REQUIRE(B <= 65535 && C < (1 << 19) && TL <= DS_MAX_TL && (long)B * C * TL < (1L << 31), "%s: too large (B %d, C %d, TL %d; B * C * TL < 2^31)",
-                what, B, C, TL);
+    CFN_REQUIRE(K >= 1 && K <= DS_MAX_LEVELS, "%s: levels: K in [1, %d] expected, got %d", what, DS_MAX_LEVELS, K);
+    CFN_REQUIRE(ds_shape_ok(B, C, K, TL), "%s: too large (B %d, C %d, K %d, TL %d; B * C * K * TL < 2^31)", what, B, C, K, TL);
     CFN_REQUIRE(max_gap >= 0, "%s: max_gap >= 0 expected, got %d", what, max_gap);
     CFN_REQUIRE(min_len >= 1, "%s: min_len >= 1 expected, got %d", what, min_len);
     CFN_REQUIRE(cap >= 1 && cap < (1L << 31), "%s: cap in [1, 2^31) expected, got %ld", what, cap);
     CFN_REQUIRE(((uintptr_t)workspace & 7) == 0, "%s: workspace on an 8-byte boundary expected", what);
     hipStream_t st = (hipStream_t)stream;
-    const long rows = (long)B * C;
+    const long rows = (long)B * C * K;
     const int nwords = (TL + 63) / 64;
     ds_u64* masks = (ds_u64*)workspace;
-    int* counts = (int*)(masks + ds_mask_words(B, C, TL));
+    int* counts = (int*)(masks + ds_mask_words(B, (long)C * K, TL));
     const size_t lds = ds_lds_bytes(nwords);
     const bool vec = TL % 4 == 0 && ((uintptr_t)probs & 15) == 0;
     if (max_gap > DS_MAX_TL) max_gap = DS_MAX_TL;                                   // (a gap is shorter than the row: the same result, no overflow)
     CfnProfScope prof(CFN_K_ELEMWISE, st, (double)rows * TL * 4.0);
-    if (vec) hipLaunchKernelGGL(det_count_kernel<true>, dim3((unsigned)rows), dim3(DS_THREADS), lds, st, probs, valid_t, thr, masks, counts, C, TL, nwords, max_gap, min_len);
-    else hipLaunchKernelGGL(det_count_kernel<false>, dim3((unsigned)rows), dim3(DS_THREADS), lds, st, probs, valid_t, thr, masks, counts, C, TL, nwords, max_gap, min_len);
-    hipLaunchKernelGGL(det_scan_kernel, dim3(1), dim3(1024), 0, st, counts, offsets, total, rows, B, C);
-    hipLaunchKernelGGL(det_write_kernel, dim3((unsigned)rows), dim3(DS_THREADS), lds, st, probs, fps, start, (const ds_u64*)masks, (const int*)counts, seg, frames, score, C, TL,
-                       nwords, max_gap, min_len, cap);
+    if (vec) hipLaunchKernelGGL(det_count_kernel<true>, dim3((unsigned)rows), dim3(DS_THREADS), lds, st, probs, valid_t, thr, masks, counts, C, K, TL, nwords, max_gap, min_len);
+    else hipLaunchKernelGGL(det_count_kernel<false>, dim3((unsigned)rows), dim3(DS_THREADS), lds, st, probs, valid_t, thr, masks, counts, C, K, TL, nwords, max_gap, min_len);
+    hipLaunchKernelGGL(det_scan_kernel, dim3(1), dim3(1024), 0, st, counts, offsets, total, rows, B, C * K);
+    hipLaunchKernelGGL(det_write_kernel, dim3((unsigned)rows), dim3(DS_THREADS), lds, st, probs, fps, start, (const ds_u64*)masks, (const int*)counts, seg, frames, score, level,
+                       C, K, TL, nwords, max_gap, min_len, cap);
     return cfn_check_launch(what);
+}
+
+extern "C" int cfn_decode_segments(const float* probs, const int* valid_t, const double* fps, const int* start, const float* thr, double* seg,
+                                   int* frames, float* score, int* offsets, int* total, void* workspace, int B, int C, int TL, int max_gap,
+                                   int min_len, long cap, void* stream) {
+    return ds_decode("cfn_decode_segments", probs, valid_t, fps, start, thr, seg, frames, score, nullptr, offsets, total, workspace, B, C, 1, TL, max_gap,
+                     min_len, cap, stream);
+}
+
+extern "C" int cfn_decode_segments_levels(const float* probs, const int* valid_t, const double* fps, const int* start, const float* levels, double* seg,
+                                          int* frames, float* score, unsigned char* level, int* offsets, int* total, void* workspace, int B, int C, int K,
+                                          int TL, int max_gap, int min_len, long cap, void* stream) {
+    const char* what = "cfn_decode_segments_levels";
+    CFN_REQUIRE(level, "%s: null tensor", what);
+    return ds_decode(what, probs, valid_t, fps, start, levels, seg, frames, score, level, offsets, total, workspace, B, C, K, TL, max_gap, min_len, cap,
+                     stream);
 }

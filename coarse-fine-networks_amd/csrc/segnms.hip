@@ -1,0 +1,265 @@
+// Temporal non-maximum suppression of a batch's Detections (cfn_hip/detections.py nms / nms_reference): the stage between the level decode
+// (csrc/detections.hip, cfn_decode_segments_levels) and the writer / the segment-AP meter.  The rules (cfn_hip/detections.py spells the same):
+//
+//   N1. groups are (video, class) row ranges: the rows offsets[b] .. offsets[b + 1] (clamped to [0, cap_in]) whose class column is c, found by
+//       two binary searches on the class column as segap_match_kernel finds them (the class column does not decrease inside a video).
+//   N2. order inside a group: score[:, score_col] descending (fp32), ties by row index ascending (segap.py rule 3).  A NaN score ranks as
+//       -inf, so the ranks are a permutation of the group whatever the data.
+//   N3. tIoU of (s0, e0) and (s1, e1): inter = min(e0, e1) - max(s0, s1); 0 unless inter > 0, otherwise inter / ((e0 - s0) + (e1 - s1) - inter):
+//       plain IEEE fp64, no product, ONE division (segap.py rule 2).
+//   N4. greedy: walk the group in the order of N2; a candidate is KEPT iff no candidate kept before it has tIoU with it > nms_thr (strict).  A
+//       suppressed candidate suppresses nothing.
+//   N5. the output is a stable compaction: kept rows in their input order, seg / frames / score copied bit for bit; offsets and total are the
+//       true counts, rows >= cap_out are not written.
+//   N6. keep (cap_in) uint8 (written for the rows of the batch's groups only) and src (cap_out) int32 = the input row of each output row.
+//
+// Three launches, ordered by the stream alone; no atomics, no allocation, nothing is read back:
+//   select   one wave per group.  Rank by counting (O(nd^2 / 64), as segap_match_kernel).  The walk: the candidate at rank r is skipped if its
+//            suppressed flag is set; otherwise it is kept and the lanes take the ranks above r, 64 at a time in tiles aligned to 64, and set
+//            the flag where the tIoU is above nms_thr: O(kept * nd / 64).  The flag of rank j belongs to lane j & 63 and to no other: a lane
+//            reads back only what it wrote itself, the flag of rank r reaches the wave through a ballot.  Up to NMS_DET_TILE = 1024 candidates
+//            the start / end (in rank order), the scores and the order live in LDS and the flags in one register per lane (16 bits); a larger
+//            group (the general path) keeps its order and its flag bytes in the workspace: the ORDER is written by one lane and read by
+//            others, so it passes the release / acquire fence of segap_match_kernel; the flags stay lane-owned.
+//   scan     one workgroup: the groups' kept counts -> bases in place, offsets[b], total (the scheme of det_scan_kernel).
+//   write    one wave per group: 64 rows at a time, a kept row goes to base + the number of kept rows in front of it (ballot / popcount).
+// offsets, classes, ranks and counts are DATA: every index is clamped, so a bad batch gives wrong values, never a store outside the outputs.
+#include "cfn_common.h"
+
+#define NMS_DET_TILE 1024
+#define NMS_FLAG_WORDS (NMS_DET_TILE / 64)
+
+__device__ __forceinline__ long nms_clampl(long v, long lo, long hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+// first row i of [lo, hi) whose class is not below key (all lanes walk the same way; at most 32 steps whatever the data)
+__device__ __forceinline__ long nms_lower(const double* __restrict__ seg, long lo, long hi, double key) {
+    while (lo < hi) {
+        const long mid = (lo + hi) >> 1;
+        if (seg[3 * mid] < key) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+// rule N1: the rows [d0, d0 + nd) of group (b, c)
+__device__ __forceinline__ long nms_group(const double* __restrict__ seg, const int* __restrict__ offsets, int b, int c, long cap_in, int& nd) {
+    const long o0 = nms_clampl(offsets[b], 0, cap_in);
+    const long o1 = nms_clampl(offsets[b + 1], o0, cap_in);
+    const long d0 = nms_lower(seg, o0, o1, (double)c);
+    const long d1 = nms_lower(seg, d0, o1, (double)c + 1.0);
+    nd = (int)(d1 - d0);
+    return d0;
+}
+
+// rule N3
+__device__ __forceinline__ double nms_tiou(double s0, double e0, double s1, double e1) {
+    const double inter = (e0 < e1 ? e0 : e1) - (s0 > s1 ? s0 : s1);
+    if (!(inter > 0.0)) return 0.0;
+    return inter / ((e0 - s0) + (e1 - s1) - inter);
+}
+
+// rule N2's key: a NaN ranks as -inf
+__device__ __forceinline__ float nms_key(float s) { return s != s ? -INFINITY : s; }
+
+// exclusive scan of one int per thread over a workgroup of 1024 (wave scans + the wave totals in LDS); total = the sum
+__device__ __forceinline__ int nms_block_scan(int v, int* s_wave, int& total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    int inc = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const int o = __shfl_up(inc, d, 64);
+        if (lane >= d) inc += o;
+    }
+    __syncthreads();                                                       // (s_wave may still be read from the scan before)
+    if (lane == 63) s_wave[wave] = inc;
+    __syncthreads();
+    int before = 0, sum = 0;
+    for (int i = 0; i < nw; ++i) {
+        const int x = s_wave[i];
+        if (i < wave) before += x;
+        sum += x;
+    }
+    total = sum;
+    return before + inc - v;
+}
+
+// grid (B * C), one wave each
+__global__ __launch_bounds__(64) void nms_select_kernel(const double* __restrict__ seg, const float* __restrict__ score, const int* __restrict__ offsets,
+                                                        unsigned char* __restrict__ keep, int* __restrict__ counts, int* __restrict__ ws_order,
+                                                        unsigned char* __restrict__ ws_flag, int C, int score_col, double nms_thr, long cap_in) {
+    __shared__ double s_start[NMS_DET_TILE];                               // in rank order
+    __shared__ double s_end[NMS_DET_TILE];
+    __shared__ float s_key[NMS_DET_TILE];                                  // in row order
+    __shared__ int s_order[NMS_DET_TILE];                                  // rank -> row of the group
+    const int lane = threadIdx.x;
+    const long grp = blockIdx.x;
+    const int b = (int)(grp / C), c = (int)(grp - (long)b * C);
+    int nd;
+    const long d0 = nms_group(seg, offsets, b, c, cap_in, nd);
+    if (nd <= 0) {
+        if (lane == 0) counts[grp] = 0;
+        return;
+    }
+
+    if (nd <= NMS_DET_TILE) {
+        for (int i = lane; i < nd; i += 64) s_key[i] = nms_key(score[2 * (d0 + i) + score_col]);
+        __syncthreads();
+        for (int i = lane; i < nd; i += 64) {                              // rule N2: rank by counting, a permutation
+            const float si = s_key[i];
+            int r = 0;
+            for (int j = 0; j < nd; ++j) {
+                const float sj = s_key[j];
+                r += (sj > si || (sj == si && j < i)) ? 1 : 0;
+            }
+            r = min(r, nd - 1);                                            // (r < nd already: at most nd - 1 rows are in front of one)
+            s_order[r] = i;
+            s_start[r] = seg[3 * (d0 + i) + 1];
+            s_end[r] = seg[3 * (d0 + i) + 2];
+        }
+        __syncthreads();
+        unsigned sup = 0u;                                                 // bit t: rank 64 * t + lane is suppressed
+        for (int r = 0; r < nd; ++r) {                                     // rule N4 (r and everything derived from it are wave uniform)
+            const unsigned owner = (unsigned)__shfl((int)sup, r & 63, 64);
+            if ((owner >> (r >> 6)) & 1u) continue;
+            const double s0 = s_start[r], e0 = s_end[r];
+            for (int t = (r + 1) >> 6; 64 * t < nd; ++t) {
+                const int j = 64 * t + lane;
+                if (j > r && j < nd && nms_tiou(s0, e0, s_start[j], s_end[j]) > nms_thr) sup |= 1u << t;
+            }
+        }
+        int kept = 0;
+        for (int t = 0; 64 * t < nd; ++t) {
+            const int j = 64 * t + lane;
+            const bool k = j < nd && !((sup >> t) & 1u);
+            if (j < nd) keep[d0 + min(max(s_order[j], 0), nd - 1)] = k ? 1 : 0;
+            kept += __popcll(__ballot(k));
+        }
+        if (lane == 0) counts[grp] = kept;
+        return;
+    }
+
+    // the general path: order and flags in the workspace (the group's own range [d0, d0 + nd) of both)
+    int* order = ws_order + d0;
+    unsigned char* flag = ws_flag + d0;
+    for (int i = lane; i < nd; i += 64) {
+        const float si = nms_key(score[2 * (d0 + i) + score_col]);
+        int r = 0;
+        for (int j = 0; j < nd; ++j) {
+            const float sj = nms_key(score[2 * (d0 + j) + score_col]);
+            r += (sj > si || (sj == si && j < i)) ? 1 : 0;
+        }
+        order[min(r, nd - 1)] = i;
+        flag[i] = 0;                                                       // (rank i's flag: lane i & 63 = this lane owns it)
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");                     // the other lanes' ranks are read back through memory
+    __syncthreads();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    for (int r = 0; r < nd; ++r) {
+        const bool mine = lane == (r & 63) && flag[r] != 0;
+        if (__ballot(mine)) continue;
+        const long ri = d0 + min(max(order[r], 0), nd - 1);
+        const double s0 = seg[3 * ri + 1], e0 = seg[3 * ri + 2];
+        for (int j = ((r + 1) >> 6) * 64 + lane; j < nd; j += 64) {
+            if (j <= r || flag[j]) continue;
+            const long rj = d0 + min(max(order[j], 0), nd - 1);
+            if (nms_tiou(s0, e0, seg[3 * rj + 1], seg[3 * rj + 2]) > nms_thr) flag[j] = 1;
+        }
+    }
+    int kept = 0;
+    for (int j0 = 0; j0 < nd; j0 += 64) {
+        const int j = j0 + lane;
+        const bool k = j < nd && flag[j] == 0;
+        if (j < nd) keep[d0 + min(max(order[j], 0), nd - 1)] = k ? 1 : 0;
+        kept += __popcll(__ballot(k));
+    }
+    if (lane == 0) counts[grp] = kept;
+}
+
+// counts[0 .. n) -> exclusive sums in place, counts[n] = total; offsets[b] = sum of the groups of videos < b; one workgroup
+__global__ __launch_bounds__(1024) void nms_scan_kernel(int* __restrict__ counts, int* __restrict__ offsets, int* __restrict__ total_out, long n, int B,
+                                                        int C, long cap_in) {
+    __shared__ int s_wave[16];
+    const int tid = threadIdx.x;
+    int carry = 0;
+    for (long i0 = 0; i0 < n; i0 += 1024) {
+        const long i = i0 + tid;
+        const int v = i < n ? (int)nms_clampl(counts[i], 0, cap_in) : 0;
+        int total;
+        const int ex = carry + nms_block_scan(v, s_wave, total);
+        if (i < n) {
+            counts[i] = ex;
+            if (i % C == 0) offsets[i / C] = ex;
+        }
+        carry += total;
+    }
+    if (tid == 0) {
+        counts[n] = carry;
+        offsets[B] = carry;
+        total_out[0] = carry;
+    }
+}
+
+// grid (B * C), one wave each
+__global__ __launch_bounds__(64) void nms_write_kernel(const double* __restrict__ seg, const int* __restrict__ frames, const float* __restrict__ score,
+                                                       const int* __restrict__ offsets, const unsigned char* __restrict__ keep,
+                                                       const int* __restrict__ bases, double* __restrict__ out_seg, int* __restrict__ out_frames,
+                                                       float* __restrict__ out_score, int* __restrict__ src, int C, long cap_in, long cap_out) {
+    const int lane = threadIdx.x;
+    const long grp = blockIdx.x;
+    long base = bases[grp];
+    if (bases[grp + 1] - base <= 0 || base < 0 || base >= cap_out) return; // (wave uniform) nothing kept, or all of it behind cap_out
+    const int b = (int)(grp / C), c = (int)(grp - (long)b * C);
+    int nd;
+    const long d0 = nms_group(seg, offsets, b, c, cap_in, nd);
+    for (int i0 = 0; i0 < nd && base < cap_out; i0 += 64) {
+        const long i = d0 + i0 + lane;
+        const bool k = i0 + lane < nd && keep[i] != 0;
+        const unsigned long long m = __ballot(k);
+        const long dst = base + __popcll(m & ((1ull << lane) - 1));
+        if (k && dst < cap_out) {
+            out_seg[3 * dst + 0] = seg[3 * i + 0]; out_seg[3 * dst + 1] = seg[3 * i + 1]; out_seg[3 * dst + 2] = seg[3 * i + 2];
+            out_frames[3 * dst + 0] = frames[3 * i + 0]; out_frames[3 * dst + 1] = frames[3 * i + 1]; out_frames[3 * dst + 2] = frames[3 * i + 2];
+            out_score[2 * dst + 0] = score[2 * i + 0]; out_score[2 * dst + 1] = score[2 * i + 1];
+            src[dst] = (int)i;
+        }
+        base += __popcll(m);
+    }
+}
+
+static inline bool nms_shape_ok(int B, int C, long cap_in) {
+    return B >= 1 && C >= 1 && B <= 65535 && C <= 65535 && (long)B * C < (1L << 31) && cap_in >= 1 && cap_in < (1L << 31);
+}
+
+// workspace: int32 counts / bases [B * C + 1], order [cap_in]; then cap_in flag bytes
+static inline long nms_ws_ints(long groups, long cap_in) { return groups + 1 + cap_in; }
+
+extern "C" long cfn_nms_segments_workspace_bytes(int B, int C, long cap_in) {
+    if (!nms_shape_ok(B, C, cap_in)) return -1;
+    return nms_ws_ints((long)B * C, cap_in) * 4 + ((cap_in + 7) & ~7L);
+}
+
+extern "C" int cfn_nms_det_tile(void) { return NMS_DET_TILE; }
+
+extern "C" int cfn_nms_segments(const double* seg, const int* frames, const float* score, const int* offsets, double* out_seg, int* out_frames,
+                                float* out_score, int* out_offsets, int* out_total, unsigned char* keep, int* src, void* workspace, int B, int C,
+                                int score_col, double nms_thr, long cap_in, long cap_out, void* stream) {
+    const char* what = "cfn_nms_segments";
+    CFN_REQUIRE(seg && frames && score && offsets && out_seg && out_frames && out_score && out_offsets && out_total && keep && src && workspace,
+                "%s: null tensor", what);
+    CFN_REQUIRE(nms_shape_ok(B, C, cap_in), "%s: bad shape (B %d, C %d in [1, 65535]; cap_in %ld in [1, 2^31))", what, B, C, cap_in);
+    CFN_REQUIRE(cap_out >= 1 && cap_out < (1L << 31), "%s: cap_out in [1, 2^31) expected, got %ld", what, cap_out);
+    CFN_REQUIRE(score_col == 0 || score_col == 1, "%s: score_col 0 (max) or 1 (mean) expected, got %d", what, score_col);
+    CFN_REQUIRE(nms_thr >= 0.0 && nms_thr <= 1.0, "%s: nms_thr in [0, 1] expected, got %g", what, nms_thr);
+    CFN_REQUIRE(((uintptr_t)workspace & 7) == 0, "%s: workspace on an 8-byte boundary expected", what);
+    CFN_REQUIRE(seg != out_seg && frames != out_frames && score != out_score, "%s: the outputs must not be the inputs", what);
+    hipStream_t st = (hipStream_t)stream;
+    const long groups = (long)B * C;
+    int* counts = (int*)workspace;
+    int* order = counts + groups + 1;
+    unsigned char* flag = (unsigned char*)(order + cap_in);
+    CfnProfScope prof(CFN_K_ELEMWISE, st, 0.0);
+    hipLaunchKernelGGL(nms_select_kernel, dim3((unsigned)groups), dim3(64), 0, st, seg, score, offsets, keep, counts, order, flag, C, score_col, nms_thr, cap_in);
+    hipLaunchKernelGGL(nms_scan_kernel, dim3(1), dim3(1024), 0, st, counts, out_offsets, out_total, groups, B, C, cap_in);
+    hipLaunchKernelGGL(nms_write_kernel, dim3((unsigned)groups), dim3(64), 0, st, seg, frames, score, offsets, (const unsigned char*)keep, (const int*)counts,
+                       out_seg, out_frames, out_score, src, C, cap_in, cap_out);
+    return cfn_check_launch(what);
+}

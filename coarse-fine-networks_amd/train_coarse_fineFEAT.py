@@ -258,7 +258,7 @@ def run(init_lr=INIT_LR, warmup_steps=0, max_epochs=200, mode='rgb', root=None, 
                     if detections is not None:      # decoded on the device; the segments stay there until the end of the phase
                         det = detections.add(probs, valid_t, seg_batch, name)
                     if segment_ap is not None:      # train_fine.run: the same segments, matched against the segment labels on the device
-                        segment_ap_add(segment_ap, det, probs, valid_t, seg_batch, labels)
+                        segment_ap_add(segment_ap, det, probs, valid_t, seg_batch, labels, writer=detections)
                     tot_cls += float(cls_loss)
                     tot_loc += float(loc_loss)
                 if train and steps % max(iters // 2, 1) == 0:

@@ -284,7 +284,8 @@ def run(init_lr=INIT_LR, warmup_steps=0, max_epochs=200, mode='rgb', root=None, 
     segment_ap: a cfn_hip.segap.SegmentAPMeter -- every validation phase matches the same decoded segments (the writer's decode; the meter's
     own thr / max_gap / min_len without a writer) against the batch's segment labels on the GPU and logs ' Epoch:E val seg-mAP@t: ...' behind the
     existing line.  One process only: AP is not additive and merging the stores of several ranks is out of scope, so a world size above 1
-    raises.  None: nothing changes.
+    raises.  None: nothing changes.  A writer or a meter made with levels= decodes with cfn_hip.detections.propose instead (candidates at K
+    levels, then temporal NMS); the meter is still fed the writer's batch when both are given.
     input_norm: see build_model -- needed when the loaders collate uint8 frames (collate.fine_collate_u8, or fine_collate_raw_u8:
     untransformed frames + crop boxes, cropped / resized to the model's crop size / flipped on the GPU in front of the step).
     device_ap: the training phases keep their AP rows and loss totals on the GPU (cfn_hip.metrics.StepMetrics, apmeter.DeviceAPMeter):
@@ -355,7 +356,7 @@ def run(init_lr=INIT_LR, warmup_steps=0, max_epochs=200, mode='rgb', root=None, 
                     if detections is not None:      # decoded on the device; the segments stay there until the end of the phase
                         det = detections.add(probs, valid_t, seg_batch, _name)
                     if segment_ap is not None:      # matched and appended on the device; nothing is read back before the end of the phase
-                        segment_ap_add(segment_ap, det, probs, valid_t, seg_batch, labels)
+                        segment_ap_add(segment_ap, det, probs, valid_t, seg_batch, labels, writer=detections)
                     tot_cls += float(cls_loss)
                     tot_loc += float(loc_loss)
                 if train and steps % max(iters // 2, 1) == 0:
@@ -403,20 +404,21 @@ def check_segment_ap(meter, world):
                            'stores is not implemented (world size %d): validate on one GPU, or leave segment_ap=None' % world)
 
 
-def segment_ap_add(meter, det, probs, valid_t, seg_batch, labels):
-    """one validation batch into the meter: `det` = what the DetectionWriter decoded (None: decode here with the meter's parameters);
-    ground truth = the batch's SegLabels (seconds), or the dense labels decoded into frame units"""
-    from cfn_hip.detections import decode
+def segment_ap_add(meter, det, probs, valid_t, seg_batch, labels, writer=None):
+    """one validation batch into the meter: `det` = what the DetectionWriter `writer` decoded (None: decode here with the meter's
+    parameters -- propose() when it has levels); ground truth = the batch's SegLabels (seconds), or the dense labels decoded into frame units"""
+    from cfn_hip.detections import decode, propose
     valid_t = valid_t.to(torch.int32)
+    fps = start = None
     if isinstance(seg_batch, SegLabels):
         seg_batch = seg_batch.to(probs.device)
-        if det is None:
-            det = decode(probs.detach(), valid_t, seg_batch.fps, seg_batch.window[:, 0].contiguous(), meter.thr, meter.max_gap, meter.min_len)
-        meter.add(det, seg_batch)
-    else:
-        if det is None:
-            det = decode(probs.detach(), valid_t, None, None, meter.thr, meter.max_gap, meter.min_len)
-        meter.add(det, (labels, valid_t))
+        fps, start = seg_batch.fps, seg_batch.window[:, 0].contiguous()
+    levels = writer.n_levels if det is not None and writer is not None else meter.n_levels
+    if det is None and meter.levels is not None:
+        det = propose(probs.detach(), valid_t, fps, start, meter.levels, meter.nms, meter.nms_score, meter.max_gap, meter.min_len)
+    elif det is None:
+        det = decode(probs.detach(), valid_t, fps, start, meter.thr, meter.max_gap, meter.min_len)
+    meter.add(det, seg_batch if fps is not None else (labels, valid_t), levels=levels)
 
 
 def segment_ap_line(meter, epochs):
@@ -450,7 +452,7 @@ def seg_ap_from_args(args, n_classes=157):
         return None
     from cfn_hip.segap import SegmentAPMeter
     return SegmentAPMeter(torch.device('cuda', torch.cuda.current_device()), n_classes, [float(x) for x in args.seg_ap_tiou.split(',')], args.seg_ap_score,
-                          args.seg_ap_capacity, args.detect_thr, args.detect_gap, args.detect_min_len)
+                          args.seg_ap_capacity, args.detect_thr, args.detect_gap, args.detect_min_len, **detect_levels(args))
 
 
 def add_detect_args(parser):
@@ -460,17 +462,33 @@ def add_detect_args(parser):
     g.add_argument('--detect-thr', type=float, default=0.5, help='a frame is active when its probability is above this')
     g.add_argument('--detect-gap', type=int, default=0, help='close gaps of at most N inactive frames')
     g.add_argument('--detect-min-len', type=int, default=1, help='drop segments shorter than N frames')
+    g.add_argument('--detect-levels', metavar='T1,T2,...', default=None,
+                   help='proposals: candidates at these 1 to 16 thresholds in place of --detect-thr, e.g. 0.8,0.65,0.5,0.35,0.2 (high to low: '
+                        'the tight segment wins a tie of nested candidates), then temporal NMS')
+    g.add_argument('--detect-nms', type=float, default=None, help='with --detect-levels: suppress a candidate whose temporal IoU with a kept one is above this (default 0.5)')
+    g.add_argument('--detect-nms-score', choices=('max', 'mean'), default='max', help='with --detect-levels: the score column NMS ranks by')
+
+
+def detect_levels(args):
+    """the proposal options of the --detect group as the keywords of DetectionWriter / SegmentAPMeter ({} without --detect-levels)"""
+    if getattr(args, 'detect_levels', None) is None:
+        if getattr(args, 'detect_nms', None) is not None:
+            raise ValueError('--detect-nms needs --detect-levels: a single-level decode does not overlap itself')
+        return {}
+    return {'levels': [float(x) for x in args.detect_levels.split(',')], 'nms': args.detect_nms, 'nms_score': args.detect_nms_score}
 
 
 def detect_argv(args):
     """the --detect group of `args` as a worker's command line"""
     if not args.detect:
         return []
-    return ['--detect', args.detect, '--detect-thr', repr(args.detect_thr), '--detect-gap', str(args.detect_gap), '--detect-min-len', str(args.detect_min_len)]
+    more = (['--detect-levels', args.detect_levels, '--detect-nms-score', args.detect_nms_score] if args.detect_levels is not None else []) + \
+        (['--detect-nms', repr(args.detect_nms)] if args.detect_nms is not None else [])
+    return ['--detect', args.detect, '--detect-thr', repr(args.detect_thr), '--detect-gap', str(args.detect_gap), '--detect-min-len', str(args.detect_min_len)] + more
 
 
 def detect_writer(args):
-    return DetectionWriter(args.detect, args.detect_thr, args.detect_gap, args.detect_min_len) if args.detect else None
+    return DetectionWriter(args.detect, args.detect_thr, args.detect_gap, args.detect_min_len, **detect_levels(args)) if args.detect else None
 
 
 def _spawn(gpus, argv):

@@ -609,6 +609,51 @@ int cfn_decode_segments(const float* probs, const int* valid_t, const double* fp
                         int min_len, long cap, void* stream);
 
 /* =====================================================================================================================
+ * Activity proposals: candidates at K threshold levels, then temporal non-maximum suppression (csrc/detections.hip,
+ * csrc/segnms.hip; the rules, the host references and propose(): cfn_hip/detections.py).
+ * cfn_decode_segments_levels: cfn_decode_segments with levels (C, K) fp32, 1 <= K <= 16, in place of thr; row c holds class c's K
+ * thresholds in the caller's order (they need not be sorted).
+ *     L1. candidate row (b, c, k) is rules 1-5 above applied to probs[b, c, :] with the threshold levels[c, k]
+ *     L2. the class column of seg holds c; level (cap) uint8 holds k
+ *     L3. rows are ordered by (b, c, k, t0), through counts and prefix sums; offsets and total are TRUE counts, rows >= cap are
+ *         not written
+ *     L4. cap = B * C * K * ((TL + 1) / 2) can never overflow; K = 1 gives cfn_decode_segments' result bit for bit
+ *   The candidates of a (video, class) group are contiguous and the class column does not decrease inside a video: all
+ *   cfn_segap_match and cfn_nms_segments need.  workspace: cfn_decode_segments_levels_workspace_bytes(B, C, K, TL) bytes on an
+ *   8-byte boundary.  3 launches.  Returns 1 as cfn_decode_segments does, and for K outside [1, 16], B * C * K * TL >= 2^31 or a null
+ *   level; the workspace query -1 for the same shapes.
+ * cfn_nms_segments: seg (cap_in, 3) fp64, frames (cap_in, 3) int32, score (cap_in, 2) fp32, offsets (B + 1) int32 grouped like that;
+ * nms_thr a double of [0, 1]; score_col 0 = max, 1 = mean.
+ *     N1. groups are (video, class) row ranges, found as cfn_segap_match finds them (offsets clamped to [0, cap_in])
+ *     N2. order inside a group: score[:, score_col] descending (fp32), ties by row ascending; a NaN score ranks as -inf.  Nested
+ *         candidates share their maximum, so with score_col = 0 the caller's LEVEL ORDER decides those ties
+ *     N3. tIoU of (s0, e0) and (s1, e1): inter = min(e0, e1) - max(s0, s1); 0 unless inter > 0, otherwise
+ *         inter / ((e0 - s0) + (e1 - s1) - inter): IEEE fp64, no product, one division
+ *     N4. greedy in that order: a candidate is KEPT iff no candidate kept before it has tIoU with it > nms_thr (strict); a
+ *         suppressed candidate suppresses nothing
+ *     N5. stable compaction: kept rows in input order, out_seg / out_frames / out_score copied bit for bit; out_offsets (B + 1) and
+ *         out_total (1) are TRUE counts; rows >= cap_out are not written
+ *     N6. keep (cap_in) uint8, written for the rows of the batch's groups only; src (cap_out) int32 = the input row of each output row
+ *     N7. nms_thr = 1 keeps everything; below 1 exact duplicates (tIoU exactly 1.0) collapse to the first in the order
+ *   3 launches (select: one wave per group, O(nd^2 / 64) ranking and O(kept * nd / 64) suppression; groups of up to
+ *   cfn_nms_det_tile() = 1024 candidates in LDS, larger ones through the workspace; scan; write).  workspace:
+ *   cfn_nms_segments_workspace_bytes(B, C, cap_in) bytes on an 8-byte boundary.  The outputs must not be the inputs.
+ * Both: everything but the shapes, score_col, nms_thr and the caps is read on the device only and clamped: a bad batch gives wrong
+ * values, never a store outside the outputs.  Ordered by the stream alone, no atomics, no allocation, no synchronisation
+ * (capturable).  cfn_nms_segments returns 1 for null pointers, B or C outside [1, 65535], cap_in or cap_out outside [1, 2^31),
+ * score_col outside {0, 1}, nms_thr outside [0, 1] (a NaN included), a misaligned workspace or an output that is an input.
+ * ===================================================================================================================== */
+long cfn_decode_segments_levels_workspace_bytes(int B, int C, int K, int TL);
+int cfn_decode_segments_levels(const float* probs, const int* valid_t, const double* fps, const int* start, const float* levels,
+                               double* seg, int* frames, float* score, unsigned char* level, int* offsets, int* total,
+                               void* workspace, int B, int C, int K, int TL, int max_gap, int min_len, long cap, void* stream);
+long cfn_nms_segments_workspace_bytes(int B, int C, long cap_in);
+int cfn_nms_det_tile(void);
+int cfn_nms_segments(const double* seg, const int* frames, const float* score, const int* offsets, double* out_seg, int* out_frames,
+                     float* out_score, int* out_offsets, int* out_total, unsigned char* keep, int* src, void* workspace, int B,
+                     int C, int score_col, double nms_thr, long cap_in, long cap_out, void* stream);
+
+/* =====================================================================================================================
  * Segment-level average precision at temporal-IoU thresholds (csrc/segap.hip; the host reference and the meter:
  * cfn_hip/segap.py).  The first consumer of the pair cfn_seg_labels' seg / cfn_decode_segments' seg; the reference stops at probs
  * (train_fine.py:199-222), so the rule is stated here once:

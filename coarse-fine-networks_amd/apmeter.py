@@ -69,7 +69,8 @@ class DeviceAPMeter(object):
     batch; the kernels take the exact count from the device).  capacity=None: the stores grow geometrically when that bound passes the
     capacity (a new allocation and a stream-ordered copy).  An explicit capacity (rows) fixes the buffers for good: ``add_batch`` is then
     safe inside a graph capture, and a batch that does not fit is dropped, flagged on the device and reported by ``value()``.
-    Unweighted AP only."""
+    Unweighted AP only.  ``calibrate`` / ``value_and_thresholds`` turn the same sorted rows into per-class decode thresholds
+    (cfn_hip.calibrate.Calibration), in place and without a read-back."""
 
     MIN_CAPACITY = 16384
 
@@ -159,8 +160,35 @@ class DeviceAPMeter(object):
             raise RuntimeError('DeviceAPMeter.value_device: nothing was added yet')
         return ops.average_precision(self._scores, self._targets, self.count)
 
-    def value(self):
-        """(K,) float32 CPU tensor of per-class AP; 0 when nothing was added (as the reference)"""
+    def _sorted(self, what, out):
+        from cfn_hip import ops
+        if self._scores is None:
+            raise RuntimeError('DeviceAPMeter.%s: nothing was added yet' % what)
+        return ops.ap_sort(self._scores, self._targets, self.count, out=out)
+
+    def calibrate(self, calibration, out=None):
+        """per-class thresholds of the rows held into a cfn_hip.calibrate.Calibration, in place: ONE ap_sort and ap_calibrate on the sorted
+        stores; reads nothing back (flags are not looked at).  out: ap_sort's buffers to reuse (with a fixed capacity nothing is allocated
+        then: capturable).  Returns the calibration."""
+        from cfn_hip import ops
+        ss, st = self._sorted('calibrate', out)
+        ops.ap_calibrate(ss, st, self.count, calibration.kinds, calibration.values, out=calibration.outputs)
+        calibration.updates += 1
+        return calibration
+
+    def value_and_thresholds(self, calibration, out=None):
+        """(K,) fp32 AP on the device AND the calibration's thresholds from the same rows: ONE ap_sort, then ap_reduce and ap_calibrate on
+        the same sorted stores; reads nothing back.  The AP is value_device()'s, the thresholds are calibrate()'s, bit for bit."""
+        from cfn_hip import ops
+        ss, st = self._sorted('value_and_thresholds', out)
+        ap = ops.ap_reduce(st, self.count)
+        ops.ap_calibrate(ss, st, self.count, calibration.kinds, calibration.values, out=calibration.outputs)
+        calibration.updates += 1
+        return ap
+
+    def value(self, calibration=None):
+        """(K,) float32 CPU tensor of per-class AP; 0 when nothing was added (as the reference).  calibration: a
+        cfn_hip.calibrate.Calibration to update from the same sorted rows (value_and_thresholds); untouched when nothing was added"""
         if not self._added:
             return 0
         from cfn_hip import ops
@@ -168,4 +196,4 @@ class DeviceAPMeter(object):
         assert not flags & ops.AP_FLAG_NONBINARY, 'targets should be binary (0 or 1)'
         if flags & ops.AP_FLAG_OVERFLOW:
             raise RuntimeError('DeviceAPMeter: more rows were added than the fixed capacity of %d holds' % self._scores.shape[1])
-        return self.value_device().cpu()
+        return (self.value_device() if calibration is None else self.value_and_thresholds(calibration)).cpu()

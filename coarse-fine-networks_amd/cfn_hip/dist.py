@@ -18,6 +18,17 @@ import torch
 import torch.distributed as dist
 
 
+def local_device():
+    """the device init_from_env gives this process (LOCAL_RANK; CFN_SHARE_GPU: modulo the device count), without making it current: for
+    what is built from the command line in front of run(), such as train_fine.calibration_from_args"""
+    if not torch.cuda.is_available():
+        return torch.device('cpu')
+    local = int(os.environ.get('LOCAL_RANK', '0'))
+    if os.environ.get('CFN_SHARE_GPU'):
+        local = local % torch.cuda.device_count()
+    return torch.device('cuda', local)
+
+
 def init_from_env(backend=None):
     """torchrun-style rendezvous (RANK / WORLD_SIZE / LOCAL_RANK / MASTER_*); returns (rank, world, device)."""
     world = int(os.environ.get('WORLD_SIZE', '1'))

@@ -60,15 +60,32 @@ class StepMetrics(object):
             return loc, cls
         return self.tot_loc, self.tot_cls
 
-    def mean_ap(self):
-        v = self.apm.value()
+    def _need_device(self, calibration):
+        if calibration is not None and not self.device_ap:
+            raise RuntimeError('StepMetrics: a calibration takes its rows from the device meter: calibration needs device_ap=True (the host APMeter '
+                               'keeps its rows in numpy)')
+
+    def mean_ap(self, calibration=None):
+        """calibration: a cfn_hip.calibrate.Calibration updated from the same sorted rows (DeviceAPMeter.value_and_thresholds; device_ap only)"""
+        self._need_device(calibration)
+        v = self.apm.value() if calibration is None else self.apm.value(calibration)
         return float(v.mean()) if torch.is_tensor(v) else float(v)
 
-    def report(self):
-        """-> (mean loc loss, mean cls loss, mAP) over the steps since start_phase() / the AP rows since reset_ap()"""
+    def calibrate(self, calibration):
+        """thresholds from the AP rows held since reset_ap(), without the AP (DeviceAPMeter.calibrate; nothing is read back) -> True, or
+        False when no row was added since"""
+        self._need_device(calibration)
+        if not self.apm._added:
+            return False
+        self.apm.calibrate(calibration)
+        return True
+
+    def report(self, calibration=None):
+        """-> (mean loc loss, mean cls loss, mAP) over the steps since start_phase() / the AP rows since reset_ap(); calibration: see mean_ap"""
+        self._need_device(calibration)
         loc, cls = self.totals()
         n = max(self.steps, 1)
-        return loc / n, cls / n, self.mean_ap()
+        return loc / n, cls / n, self.mean_ap(calibration)
 
     def reset_ap(self):
         self.apm.reset()

@@ -799,6 +799,50 @@ def average_precision(scores, targets, count, out=None):
     return ap_reduce(st, count)
 
 
+# ---- per-class decode thresholds from the sorted AP rows (csrc/apcal.hip; the rule and the Calibration: cfn_hip/calibrate.py) -------------
+AP_CALIBRATE_TILE = 8192         # rows per tile of cfn_ap_calibrate's second walk (cfn_ap_calibrate_tile(); tests place sizes on its edges)
+AP_CALIBRATE_MAX_K = 16
+AP_KIND_F1, AP_KIND_PRECISION, AP_KIND_RECALL = 0, 1, 2
+
+
+def ap_calibrate(sorted_scores, sorted_targets, count, kinds, values, out=None):
+    """Per-class operating points of K criteria over the first count rows of SORTED class-major stores (ap_sort's outputs): sorted_scores
+    (C, cap) fp32, sorted_targets (C, cap) uint8, count one int32, kinds (K,) int32 (AP_KIND_*) and values (K,) fp64, 1 <= K <= 16, all on
+    the device -> (thr (C, K) fp32, cut (C, K) int32, tp (C, K) int32, ok (C, K) uint8, stat (C, 2) int32 [P, m]); the rule is in
+    cfn_hip/calibrate.py (thresholds_reference spells it on the host).  One launch, nothing is read back (no wait, capturable with out=):
+    kinds and values are NOT looked at here -- calibrate.criteria_tensors refuses what the rule does not know; on the device an unknown
+    kind or a value outside (0, 1] gives cut 0 and ok 0.  out: the five tensors to reuse, contiguous and exactly of these shapes
+    (the kernel writes dense (C, K) blocks).  No gradient, no CPU path."""
+    C, cap = _ap_stores(sorted_scores, sorted_targets, count, 'ap_calibrate')
+    for name, x, dt in (('kinds', kinds, torch.int32), ('values', values, torch.float64)):
+        if not torch.is_tensor(x) or not x.is_cuda:
+            raise RuntimeError('ap_calibrate: %s must be a device tensor; there is no CPU path' % name)
+        if x.dtype != dt or x.dim() != 1 or not x.is_contiguous():
+            raise RuntimeError('ap_calibrate: %s: a contiguous (K,) %s tensor expected, got %s %s' % (name, dt, x.dtype, tuple(x.shape)))
+    K = int(kinds.shape[0])
+    if not 1 <= K <= AP_CALIBRATE_MAX_K or int(values.shape[0]) != K:
+        raise RuntimeError('ap_calibrate: kinds and values of one length K in [1, %d] expected, got %d and %d' % (AP_CALIBRATE_MAX_K, K, int(values.shape[0])))
+    if C > 65535 or cap >= (1 << 31):
+        raise RuntimeError('ap_calibrate: C <= 65535 and cap < 2^31 expected, got stores %s' % ((C, cap),))
+    if not (sorted_scores.is_contiguous() and sorted_targets.is_contiguous()):
+        raise RuntimeError('ap_calibrate: contiguous class-major stores expected')
+    dev = sorted_scores.device
+    want = ((K, torch.float32), (K, torch.int32), (K, torch.int32), (K, torch.uint8), (2, torch.int32))
+    if out is None:
+        out = tuple(torch.empty(C, w, dtype=dt, device=dev) for w, dt in want)
+    else:
+        out = tuple(out)
+        if len(out) != 5 or any(not torch.is_tensor(y) or tuple(y.shape) != (C, w) or y.dtype != dt or y.device != dev or not y.is_contiguous()
+                                for y, (w, dt) in zip(out, want)):
+            raise RuntimeError('ap_calibrate: out: contiguous thr (%d, %d) fp32, cut and tp (%d, %d) int32, ok (%d, %d) uint8 and stat (%d, 2) int32 on %s '
+                               'expected' % (C, K, C, K, C, K, C, dev))
+    for name, x in (('count', count), ('kinds', kinds), ('values', values)):
+        if x.device != dev:
+            raise RuntimeError('ap_calibrate: %s is on %s, the stores on %s' % (name, x.device, dev))
+    call('cfn_ap_calibrate', sorted_scores, sorted_targets, count, kinds, values, out[0], out[1], out[2], out[3], out[4], C, K, cap)
+    return out
+
+
 class _BnFold(Function):
     """(sum, sumsq) of a conv output -> per-(n,c) prologue (A, B); optional fused SE gate.  cfn_bn_fold_*."""
 

@@ -31,7 +31,7 @@ from cfn_hip import metrics                       # noqa: E402
 from cfn_hip.seglabels import materialize         # noqa: E402
 from cfn_hip.detections import epoch_path         # noqa: E402
 from train_fine import lr_warmup, flatten_clips   # noqa: E402
-from train_fine import add_detect_args, detect_argv, detect_writer   # noqa: E402
+from train_fine import add_detect_args, detect_argv, detect_writer, calibration_from_args, calibration_line, check_calibration   # noqa: E402
 from train_fine import (check_segment_ap, seg_ap_arguments, seg_ap_argv, seg_ap_from_args, segment_ap_add,   # noqa: E402
                         segment_ap_line)
 from cfn_hip.u8clips import RawU8Clips, U8Clips, CHARADES_MEAN, CHARADES_STD   # noqa: E402,F401
@@ -182,9 +182,11 @@ def run(init_lr=INIT_LR, warmup_steps=0, max_epochs=200, mode='rgb', root=None, 
         batch_size=BS * BS_UPSCALE, frames=80 * 4, dataloaders=None, max_steps=None,
         save_model='models/coarse_fineFEAT_charades_', pretrained='models/x3d_multigrid_kinetics_fb_pretrained.pt',
         csv_path='localize_corr_v1.csv', log=print, phase_hook=None, input_norm=None, device_ap=False,
-        fused_loss=False, jpeg_entropy=None, detections=None, segment_ap=None):
+        fused_loss=False, jpeg_entropy=None, detections=None, segment_ap=None, calibration=None):
     """detections: a cfn_hip.detections.DetectionWriter -- every validation phase decodes its probs into activity segments on the GPU and
     rank 0 writes all ranks' videos as JSON lines (see train_fine.run).  None: nothing changes.
+    calibration: a cfn_hip.calibrate.Calibration -- per-class thresholds from the training AP rows wherever a training mAP is taken and in
+    front of a validation phase that no mAP line has calibrated for, read by the writer's / the meter's decode (see train_fine.run).  Needs device_ap=True.  None: nothing changes.
     input_norm: see build_model -- needed when the loaders collate uint8 frames (collate.coarse_collate_u8, or coarse_collate_raw_u8:
     untransformed frames + crop boxes, transformed on the GPU -- per training batch, and per chunk of a validation video).
     device_ap: the training phases keep their AP rows and loss totals on the GPU (cfn_hip.metrics.StepMetrics): no read-back per step.
@@ -193,9 +195,11 @@ def run(init_lr=INIT_LR, warmup_steps=0, max_epochs=200, mode='rgb', root=None, 
     CFN_FUSED_LOSS.
     jpeg_entropy: how JpegClips batches are entropy-decoded, 'interval' or 'sync' (cfn_hip.jpegdec.decode_checked); None leaves the choice to
     CFN_JPEG_ENTROPY."""
+    check_calibration(calibration, device_ap)
     fused = True if fused_loss else None
     rank, world, dev = cdist.init_from_env()
     check_segment_ap(segment_ap, world)
+    check_calibration(calibration, device_ap, dev)
     gamma_tau = 5
     clip_frames = frames * 2 // (gamma_tau * 2)
     local_bs = max(batch_size // world, 1)
@@ -217,6 +221,7 @@ def run(init_lr=INIT_LR, warmup_steps=0, max_epochs=200, mode='rgb', root=None, 
     # step (the reference: a synchronous `.cuda()` per tensor, train_coarse_fineFEAT.py:205-224); the `.to(dev)` calls below are then no-ops
     stager = staging.HostStager(dev) if dev.type == 'cuda' else None
     steps, epochs = 0, 0
+    cal_seen = 0          # calibration.updates at the end of the last validation phase
     while epochs < max_epochs:
         for phase in 2 * ['train'] + ['val']:
             train = phase == 'train'
@@ -229,6 +234,9 @@ def run(init_lr=INIT_LR, warmup_steps=0, max_epochs=200, mode='rgb', root=None, 
             tot_loc = tot_cls = 0.0
             n_it = 0
             val_rows = []
+            # no mAP line calibrated since the last validation phase: take the rows the meter holds (a leftover never replaces a whole interval)
+            if not train and calibration is not None and calibration.updates == cal_seen and tr.calibrate(calibration) and rank == 0:
+                log(calibration_line(calibration, epochs))
             tr.start_phase()
             for i, (inputs, labels, masks, feat, feat_masks, meta, name, dur) in enumerate(stager.stage(dataloaders[phase]) if stager else dataloaders[phase]):
                 if train:     # collective skip of a short last batch (:193-194)
@@ -264,9 +272,13 @@ def run(init_lr=INIT_LR, warmup_steps=0, max_epochs=200, mode='rgb', root=None, 
                 if train and steps % max(iters // 2, 1) == 0:
                     t_loc, t_cls = tr.totals()
                     m_loc, m_cls = cdist.mean_over_ranks([t_loc / n_it, t_cls / n_it], dev)
+                    if rank == 0 or calibration is not None:      # (a rank's thresholds come from the sort behind its own mAP)
+                        m_ap = tr.mean_ap(calibration)
                     if rank == 0:
                         log(' Epoch:{} {} steps: {} Loc Loss: {:.4f} Cls Loss: {:.4f} mAP: {:.4f}'.format(
-                            epochs, phase, steps, m_loc, m_cls, tr.mean_ap()))
+                            epochs, phase, steps, m_loc, m_cls, m_ap))
+                        if calibration is not None:
+                            log(calibration_line(calibration, epochs))
                     tr.reset_ap()
                 if train and steps % 1000 == 0 and rank == 0:
                     os.makedirs(os.path.dirname(save_model) or '.', exist_ok=True)
@@ -300,6 +312,7 @@ def run(init_lr=INIT_LR, warmup_steps=0, max_epochs=200, mode='rgb', root=None, 
                     write_file.close()
                     write_file = writer = None
                 val_apm.reset()
+                cal_seen = calibration.updates if calibration is not None else 0
                 lr_sched.step()            # once per val phase, as the reference (not per epoch, not per step)
             if phase_hook is not None:         # test / logging hook: end of a phase (not in the reference's signature)
                 phase_hook(phase, epochs, optimizer)
@@ -332,4 +345,4 @@ if __name__ == '__main__':
     if 'RANK' not in os.environ:
         os.environ['CUDA_VISIBLE_DEVICES'] = args.gpu
     run(batch_size=args.batch_size, max_steps=args.max_steps, device_ap=args.device_ap, fused_loss=args.fused_loss, jpeg_entropy=args.jpeg_entropy,
-        detections=detect_writer(args), segment_ap=seg_ap_from_args(args))
+        detections=detect_writer(args), segment_ap=seg_ap_from_args(args), calibration=calibration_from_args(args))

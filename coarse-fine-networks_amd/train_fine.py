@@ -277,7 +277,7 @@ _ap_rows = metrics.ap_rows      # per video: (scores (v,157), targets (v,157)) n
 def run(init_lr=INIT_LR, warmup_steps=0, max_epochs=200, mode='rgb', root=None, train_split=None,
         batch_size=BS * BS_UPSCALE, frames=80 * 4, dataloaders=None, max_steps=None, save_model='models/fine_charades_',
         pretrained='models/x3d_multigrid_kinetics_fb_pretrained.pt', log=print, phase_hook=None, input_norm=None,
-        device_ap=False, fused_loss=False, jpeg_entropy=None, detections=None, segment_ap=None):
+        device_ap=False, fused_loss=False, jpeg_entropy=None, detections=None, segment_ap=None, calibration=None):
     """detections: a cfn_hip.detections.DetectionWriter -- every validation phase decodes its probs into activity segments on the GPU
     (cfn_hip.ops.decode_segments) and rank 0 writes them, all ranks' videos, as JSON lines to the writer's path with the epoch inserted
     (cfn_hip.detections.epoch_path); seconds when the loaders collate SegLabel samples, frames otherwise.  None: nothing changes.
@@ -286,6 +286,13 @@ def run(init_lr=INIT_LR, warmup_steps=0, max_epochs=200, mode='rgb', root=None, 
     existing line.  One process only: AP is not additive and merging the stores of several ranks is out of scope, so a world size above 1
     raises.  None: nothing changes.  A writer or a meter made with levels= decodes with cfn_hip.detections.propose instead (candidates at K
     levels, then temporal NMS); the meter is still fed the writer's batch when both are given.
+    calibration: a cfn_hip.calibrate.Calibration whose thr_vector / levels the writer and the meter were made with -- wherever a
+    training mAP is taken the same sorted rows give the per-class thresholds (StepMetrics.mean_ap(calibration): no read-back of its own), and
+    a validation phase that starts with rows the meter still holds calibrates from those first (StepMetrics.calibrate); each is followed by one
+    ' Epoch:E calibrated ...' line (Calibration.summary_line, one read-back of a few integers).  The validation decode then reads the updated
+    tensor.  The calibration in front of a validation phase is skipped when an mAP line has updated the thresholds since the last validation
+    phase: the leftover of an interval (possibly a step or two) never replaces the thresholds of a whole one.  Every rank calibrates from
+    its own rows, so the calibration lives on the rank's device.  Needs device_ap=True.  None: nothing changes.
     input_norm: see build_model -- needed when the loaders collate uint8 frames (collate.fine_collate_u8, or fine_collate_raw_u8:
     untransformed frames + crop boxes, cropped / resized to the model's crop size / flipped on the GPU in front of the step).
     device_ap: the training phases keep their AP rows and loss totals on the GPU (cfn_hip.metrics.StepMetrics, apmeter.DeviceAPMeter):
@@ -293,9 +300,11 @@ def run(init_lr=INIT_LR, warmup_steps=0, max_epochs=200, mode='rgb', root=None, 
     fused_loss: the loss of every step and of validation runs as one forward and one backward kernel (detection_loss(fused=True)); False leaves
     the choice to CFN_FUSED_LOSS.
     jpeg_entropy: how JpegClips batches are entropy-decoded, 'interval' or 'sync' (flatten_clips); None leaves the choice to CFN_JPEG_ENTROPY."""
+    check_calibration(calibration, device_ap)
     fused = True if fused_loss else None
     rank, world, dev = cdist.init_from_env()
     check_segment_ap(segment_ap, world)
+    check_calibration(calibration, device_ap, dev)
     gamma_tau = {'S': 6, 'M': 5, 'XL': 5}[X3D_VERSION]
     crop = {'S': 160, 'M': 224, 'XL': 312}[X3D_VERSION]
     clip_frames = frames * 2 // (gamma_tau * 2)          # 640-frame window at stride 10 -> 64 frames
@@ -316,6 +325,7 @@ def run(init_lr=INIT_LR, warmup_steps=0, max_epochs=200, mode='rgb', root=None, 
     # in front of every step, train_fine.py:184-197); the `.to(dev)` calls below are no-ops on staged batches
     stager = staging.HostStager(dev) if dev.type == 'cuda' else None
     steps, epochs = 0, 0
+    cal_seen = 0          # calibration.updates at the end of the last validation phase
     while epochs < max_epochs:
         for phase in 4 * ['train'] + ['val']:
             train = phase == 'train'
@@ -328,6 +338,9 @@ def run(init_lr=INIT_LR, warmup_steps=0, max_epochs=200, mode='rgb', root=None, 
             tot_loc = tot_cls = 0.0
             n_it = 0
             val_rows = []
+            # no mAP line calibrated since the last validation phase: take the rows the meter holds (a leftover never replaces a whole interval)
+            if not train and calibration is not None and calibration.updates == cal_seen and tr.calibrate(calibration) and rank == 0:
+                log(calibration_line(calibration, epochs))
             tr.start_phase()
             for inputs, labels, masks, _name in (stager.stage(dataloaders[phase]) if stager else dataloaders[phase]):
                 want = local_bs if train else val_bs
@@ -362,9 +375,13 @@ def run(init_lr=INIT_LR, warmup_steps=0, max_epochs=200, mode='rgb', root=None, 
                 if train and steps % max(iters // 2, 1) == 0:
                     t_loc, t_cls = tr.totals()
                     m_loc, m_cls = cdist.mean_over_ranks([t_loc / n_it, t_cls / n_it], dev)
+                    if rank == 0 or calibration is not None:      # (a rank's thresholds come from the sort behind its own mAP)
+                        m_ap = tr.mean_ap(calibration)
                     if rank == 0:
                         log(' Epoch:{} {} steps: {} Loc Loss: {:.4f} Cls Loss: {:.4f} mAP: {:.4f}'.format(
-                            epochs, phase, steps, m_loc, m_cls, tr.mean_ap()))
+                            epochs, phase, steps, m_loc, m_cls, m_ap))
+                        if calibration is not None:
+                            log(calibration_line(calibration, epochs))
                     tr.reset_ap()
                 if train and steps % 1000 == 0 and rank == 0:
                     os.makedirs(os.path.dirname(save_model) or '.', exist_ok=True)
@@ -391,6 +408,7 @@ def run(init_lr=INIT_LR, warmup_steps=0, max_epochs=200, mode='rgb', root=None, 
                 if segment_ap is not None:
                     log(segment_ap_line(segment_ap, epochs))
                 val_apm.reset()
+                cal_seen = calibration.updates if calibration is not None else 0
                 lr_sched.step()            # once per val phase, as the reference (not per epoch, not per step)
             if phase_hook is not None:         # test / logging hook: end of a phase (not in the reference's signature)
                 phase_hook(phase, epochs, optimizer)
@@ -402,6 +420,21 @@ def check_segment_ap(meter, world):
     if meter is not None and world > 1:
         raise RuntimeError('segment_ap: a SegmentAPMeter holds the detections of ONE process; AP is not additive over ranks and merging their '
                            'stores is not implemented (world size %d): validate on one GPU, or leave segment_ap=None' % world)
+
+
+def check_calibration(calibration, device_ap, dev=None):
+    """a Calibration takes its rows from the device meter of the training phases, so it lives on this rank's device `dev`"""
+    if calibration is not None and not device_ap:
+        raise RuntimeError('calibration: the thresholds are calibrated from the AP rows the training phases keep on the GPU: '
+                           '--detect-calibrate needs --device-ap (run(device_ap=True))')
+    if calibration is not None and dev is not None and calibration.thr.device != dev:
+        raise RuntimeError('calibration: its tensors are on %s but this rank trains on %s: make the Calibration on the rank\'s own device '
+                           '(cfn_hip.dist.local_device())' % (calibration.thr.device, dev))
+
+
+def calibration_line(calibration, epochs):
+    """the line behind a training mAP line (ONE read-back of the calibration's integers)"""
+    return ' Epoch:{} {}'.format(epochs, calibration.summary_line())
 
 
 def segment_ap_add(meter, det, probs, valid_t, seg_batch, labels, writer=None):
@@ -446,13 +479,14 @@ def seg_ap_argv(args):
         (['--seg-ap-capacity', str(args.seg_ap_capacity)] if args.seg_ap_capacity is not None else [])
 
 
-def seg_ap_from_args(args, n_classes=157):
-    """the meter of the --seg-ap group on this process's GPU (decode parameters: the --detect group's), or None"""
+def seg_ap_from_args(args, n_classes=157, calibration=None):
+    """the meter of the --seg-ap group on this process's GPU (decode parameters: the --detect group's; calibration: see detect_writer), or None"""
     if not args.seg_ap:
         return None
     from cfn_hip.segap import SegmentAPMeter
+    thr, more = _calibrated(args.detect_thr, detect_levels(args), calibration_from_args(args, n_classes) if calibration is None else calibration)
     return SegmentAPMeter(torch.device('cuda', torch.cuda.current_device()), n_classes, [float(x) for x in args.seg_ap_tiou.split(',')], args.seg_ap_score,
-                          args.seg_ap_capacity, args.detect_thr, args.detect_gap, args.detect_min_len, **detect_levels(args))
+                          args.seg_ap_capacity, thr, args.detect_gap, args.detect_min_len, **more)
 
 
 def add_detect_args(parser):
@@ -467,6 +501,10 @@ def add_detect_args(parser):
                         'the tight segment wins a tie of nested candidates), then temporal NMS')
     g.add_argument('--detect-nms', type=float, default=None, help='with --detect-levels: suppress a candidate whose temporal IoU with a kept one is above this (default 0.5)')
     g.add_argument('--detect-nms-score', choices=('max', 'mean'), default='max', help='with --detect-levels: the score column NMS ranks by')
+    g.add_argument('--detect-calibrate', metavar='SPEC', default=None,
+                   help="per-class thresholds calibrated on the GPU from the training AP rows (needs --device-ap): f1 | precision:P | recall:Q replaces "
+                        "--detect-thr once the first training mAP is taken; recall:Q1,Q2,... (ascending: thresholds high to low) replaces the same "
+                        "number of --detect-levels")
 
 
 def detect_levels(args):
@@ -483,12 +521,61 @@ def detect_argv(args):
     if not args.detect:
         return []
     more = (['--detect-levels', args.detect_levels, '--detect-nms-score', args.detect_nms_score] if args.detect_levels is not None else []) + \
-        (['--detect-nms', repr(args.detect_nms)] if args.detect_nms is not None else [])
+        (['--detect-nms', repr(args.detect_nms)] if args.detect_nms is not None else []) + \
+        (['--detect-calibrate', args.detect_calibrate] if getattr(args, 'detect_calibrate', None) is not None else [])
     return ['--detect', args.detect, '--detect-thr', repr(args.detect_thr), '--detect-gap', str(args.detect_gap), '--detect-min-len', str(args.detect_min_len)] + more
 
 
-def detect_writer(args):
-    return DetectionWriter(args.detect, args.detect_thr, args.detect_gap, args.detect_min_len, **detect_levels(args)) if args.detect else None
+def calibration_from_args(args, n_classes=157, device=None):
+    """the Calibration of --detect-calibrate on this RANK's GPU (cfn_hip.dist.local_device: the device run() will make current, where the
+    rank's meter lives -- not the current device, which is cuda:0 on every worker in front of run()), or None.  One criterion calibrates the (C,) thr and starts from
+    --detect-thr; K > 1 criteria (recall:Q1,Q2,...) calibrate the (C, K) levels, which go through propose like typed levels (so --detect-nms
+    applies as it does without), and start from the K values of --detect-levels.  It is made once per `args` and kept there: the writer, the
+    meter and run() must share ONE tensor"""
+    spec = getattr(args, 'detect_calibrate', None)
+    if spec is None:
+        return None
+    if getattr(args, 'calibration', None) is not None:
+        return args.calibration
+    from cfn_hip.calibrate import Calibration, parse_criteria
+    criteria = parse_criteria(spec)
+    if not getattr(args, 'device_ap', False):
+        raise ValueError('--detect-calibrate needs --device-ap: the thresholds are calibrated from the AP rows the training phases keep on the GPU')
+    levels = detect_levels(args).get('levels')
+    if len(criteria) == 1:
+        if levels is not None:
+            raise ValueError('--detect-calibrate %s gives ONE threshold per class and replaces --detect-thr; --detect-levels asks for proposals at '
+                             'several: calibrate them with recall:Q1,Q2,... or drop one of the two' % spec)
+        initial = args.detect_thr
+    else:
+        if levels is None or len(levels) != len(criteria):
+            raise ValueError('--detect-calibrate %s gives %d levels per class, which go through the proposals (candidates at every level, then NMS): '
+                             'type the %d --detect-levels they start from' % (spec, len(criteria), len(criteria)))
+        initial = levels
+    args.calibration = Calibration(criteria, n_classes, cdist.local_device() if device is None else device, initial)
+    return args.calibration
+
+
+def _calibrated(thr, more, calibration):
+    """(thr, the proposal keywords) of a writer / meter: the typed ones, or the calibration's device tensors in their place"""
+    if calibration is None:
+        return thr, more
+    if calibration.n_criteria == 1:
+        if more.get('levels') is not None:
+            raise ValueError('a calibration of ONE criterion replaces --detect-thr, but --detect-levels asks for proposals at several levels: '
+                             'calibrate those with recall:Q1,Q2,... or drop one of the two')
+        return calibration.thr_vector, more
+    return thr, dict(more, levels=calibration.levels)
+
+
+def detect_writer(args, calibration=None):
+    """the writer of the --detect group, or None.  calibration (default: calibration_from_args(args), None without --detect-calibrate): its
+    thr_vector (one criterion) or levels take the place of the typed thresholds -- device tensors the writer passes through untouched, so an
+    update in place reaches every later decode"""
+    if not args.detect:
+        return None
+    thr, more = _calibrated(args.detect_thr, detect_levels(args), calibration_from_args(args) if calibration is None else calibration)
+    return DetectionWriter(args.detect, thr, args.detect_gap, args.detect_min_len, **more)
 
 
 def _spawn(gpus, argv):
@@ -522,4 +609,4 @@ if __name__ == '__main__':
     if 'RANK' not in os.environ:
         os.environ['CUDA_VISIBLE_DEVICES'] = args.gpu
     run(batch_size=args.batch_size, max_steps=args.max_steps, device_ap=args.device_ap, fused_loss=args.fused_loss, jpeg_entropy=args.jpeg_entropy,
-        detections=detect_writer(args), segment_ap=seg_ap_from_args(args))
+        detections=detect_writer(args), segment_ap=seg_ap_from_args(args), calibration=calibration_from_args(args))

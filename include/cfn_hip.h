@@ -704,6 +704,41 @@ int cfn_ap_sort_counts(const float* scores, const unsigned char* targets, const 
 int cfn_segap_reduce(const unsigned char* sorted_tps, const int* counts, const int* n_gt, float* ap, float* map, int C, int n_thr,
                      long cap, void* stream);
 
+/* =====================================================================================================================
+ * Per-class decode thresholds calibrated from the sorted AP rows (csrc/apcal.hip; the rule, the numpy reference and the
+ * Calibration that owns the tensors: cfn_hip/calibrate.py).  The thresholds cfn_decode_segments (thr (C)) and
+ * cfn_decode_segments_levels (levels (C, K)) take are typed constants otherwise; here they come from the rows cfn_ap_sort left:
+ *   sorted_scores (C, cap) fp32 descending and canonical (NaN last, -inf just in front), sorted_targets (C, cap) uint8 (positive
+ *   iff != 0), count ONE int on the device; per class the first n = clamp(count, 0, cap) rows.  kinds (K) int32 and values (K)
+ *   fp64 on the DEVICE, 1 <= K <= 16: kind 0 = f1 (value unused), 1 = precision p, 2 = recall q, p and q in (0, 1].
+ *     1. P = positives among the n rows; m = rows with score > -inf (fp32 compare, a NaN fails): a prefix.  Rows behind m can never
+ *        be active under the decode's strict probs > thr; their positives still count in P.
+ *     2. tp(r) = positives among rows 0 .. r - 1, tp(0) = 0.
+ *     3. a cut r of 1 .. m is ADMISSIBLE iff r == m or score[r - 1] > score[r] (strict): a threshold cannot separate equal scores.
+ *     4. f1: over r = 0 and the admissible cuts, maximise 2 tp(r) / (r + P), compared EXACTLY in unsigned 64-bit integers: a beats b
+ *        iff tp(a) * (b + P) > tp(b) * (a + P); start from r = 0, replace on strict improvement only (ties: the smallest r).
+ *        precision p: the LARGEST admissible r with (double)tp(r) >= p * (double)r (one fp64 multiply, one compare); none: r = 0.
+ *        recall q: P == 0 gives r = 0; otherwise the SMALLEST admissible r with (double)tp(r) >= q * (double)P; none (positives
+ *        behind m): r = m.
+ *        ok[c, k] = 1 iff the criterion was met: f1: tp > 0; precision, recall: the inequality holds at the returned r > 0.
+ *     5. the threshold of a cut: r == 0: +inf; 0 < r < m: score[r], the largest score NOT taken, so the decode's strict rule
+ *        activates exactly rows 0 .. r - 1 of the calibration data; r == m > 0: -inf.
+ *     6. thr (C, K) fp32 (the layout of levels; K = 1: a contiguous (C) thr), cut (C, K) int32, tp (C, K) int32, ok (C, K) uint8,
+ *        stat (C, 2) int32 = [P, m].
+ *   Recall criteria listed with ascending q give non-increasing thresholds: the high-to-low level order of rule N2.
+ * cfn_ap_calibrate: 1 launch, one workgroup per class; two walks (P and m; then the rows in front of m in tiles of
+ *   cfn_ap_calibrate_tile() rows with the running tp of cfn_ap_reduce's scan, every criterion against the tile's admissible cuts);
+ *   one fixed-shape reduction per criterion (argmax with ties to the smaller r, max, min: independent of the order).  count, kinds
+ *   and values are read on the device only and clamped: an unknown kind or a value outside (0, 1] gives r = 0, ok = 0; every
+ *   output index is in range by construction.  No atomics, no floating-point accumulation, no allocation, no synchronisation
+ *   (capturable); bit-identical from run to run.  16-byte loads where a class row is aligned, scalar loads otherwise (odd cap).
+ * Returns 1 for null pointers, C outside [1, 65535], K outside [1, 16], cap outside [1, 2^31).
+ * ===================================================================================================================== */
+int cfn_ap_calibrate(const float* sorted_scores, const unsigned char* sorted_targets, const int* count, const int* kinds,
+                     const double* values, float* thr, int* cut, int* tp, unsigned char* ok, int* stat, int C, int K, long cap,
+                     void* stream);
+int cfn_ap_calibrate_tile(void);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,6 +13,7 @@ from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
 import ctypes
+import os
 import threading
 
 from . import call, call_try, check, query, last_error, ACT_NONE, ACT_RELU, ACT_SWISH, ACT_SIGMOID  # noqa: F401
@@ -600,6 +601,84 @@ class _StemConv(Function):
 
 def stem_conv(x, w):
     return _StemConv.apply(x, w)
+
+
+def _stem_pair_switch():
+    """CFN_STEM_PAIR, read per call: bit 0 = fused forward, bit 1 = fused backward (default 3; 0 = the four separate kernels)"""
+    try:
+        return int(os.environ.get('CFN_STEM_PAIR', '3'))
+    except ValueError:
+        raise RuntimeError('CFN_STEM_PAIR must be an integer (bit 0: forward, bit 1: backward), got %r' % os.environ['CFN_STEM_PAIR'])
+
+
+class _StemPair(Function):
+    """conv1_s -> conv1_t of an fp32 clip with fp32 activations, one kernel each way (csrc/stempair.hip): the forward writes conv1_s's output xs
+    and does not read it back, the backward never writes its gradient.  Where an entry point declines (or CFN_STEM_PAIR switches it off)
+    the two separate ops' kernels run on the same tensors."""
+
+    @staticmethod
+    def forward(ctx, x, w_s, w_t, want_stats, run_frames):
+        x = check(x).contiguous()
+        if x.dtype != torch.float32:                   # (check() lets 16-bit activations through; the clip of the pair is fp32)
+            raise RuntimeError('stem_pair: fp32 clip expected, got %s' % x.dtype)
+        N, Ci, T, H, W = x.shape
+        Co = w_s.shape[0]
+        Ho, Wo = (H + 2 - 3) // 2 + 1, (W + 2 - 3) // 2 + 1
+        xs = torch.empty(N, Co, T, Ho, Wo, dtype=torch.float32, device=x.device)
+        y = torch.empty_like(xs)
+        s = q = None
+        if want_stats:
+            s, q = _f64(N, Co, x.device), _f64(N, Co, x.device)
+        ws2 = w_s.reshape(Co, Ci * 9).contiguous()
+        wt2 = w_t.reshape(Co, 5).contiguous()
+        if not (_stem_pair_switch() & 1 and call_try('cfn_stem_pair_fwd', x, ws2, wt2, xs, y, s, q, N, Ci, Co, T, H, W, run_frames)):
+            call('cfn_stem_conv_fwd', x, ws2, xs, N, Ci, Co, T, H, W)
+            call('cfn_dwconv_t5_fwd', xs, wt2, y, s, q, N, Co, T, Ho * Wo)
+        ctx.save_for_backward(x, xs, y, wt2)
+        ctx.params = (w_s, w_t)
+        ctx.run_frames = run_frames
+        if not want_stats:
+            return y, None, None
+        return y, s, q
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy, gs, gq):
+        x, xs, y, wt2 = ctx.saved_tensors
+        w_s, w_t = ctx.params
+        N, Ci, T, H, W = x.shape
+        _, Co, _, Ho, Wo = xs.shape
+        gy = torch.zeros_like(y) if gy is None else gy.contiguous()
+        gs, gq = _opt(gs), _opt(gq)
+        want_s, want_t = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        gws = gwt = None
+        if want_s and want_t:
+            gs64, fin_s = _gw_buffers(w_s, Co, Ci * 9, x.device)
+            gt64, fin_t = _gw_buffers(w_t, Co, 5, x.device)
+            if not (_stem_pair_switch() & 2 and
+                    call_try('cfn_stem_pair_bwd', gy, y, gs, gq, wt2, xs, x, gt64, gs64, N, Ci, Co, T, H, W, ctx.run_frames)):
+                gxs = torch.empty_like(xs)
+                if not call_try('cfn_dwconv_t5_bwd_fused', gy, y, gs, gq, wt2, xs, gxs, gt64, N, Co, T, Ho * Wo):
+                    call('cfn_dwconv_t5_bwd_data', gy, y, gs, gq, wt2, gxs, N, Co, T, Ho * Wo)
+                    call('cfn_dwconv_t5_bwd_weight', gy, y, gs, gq, xs, gt64, N, Co, T, Ho * Wo)
+                call('cfn_stem_conv_bwd_weight', gxs, x, gs64, N, Ci, Co, T, H, W)
+            gws, gwt = fin_s(), fin_t()
+        elif want_t:
+            gt64, fin_t = _gw_buffers(w_t, Co, 5, x.device)
+            call('cfn_dwconv_t5_bwd_weight', gy, y, gs, gq, xs, gt64, N, Co, T, Ho * Wo)
+            gwt = fin_t()
+        elif want_s:
+            gs64, fin_s = _gw_buffers(w_s, Co, Ci * 9, x.device)
+            gxs = torch.empty_like(xs)
+            call('cfn_dwconv_t5_bwd_data', gy, y, gs, gq, wt2, gxs, N, Co, T, Ho * Wo)
+            call('cfn_stem_conv_bwd_weight', gxs, x, gs64, N, Ci, Co, T, H, W)
+            gws = fin_s()
+        return None, gws, gwt, None, None
+
+
+def stem_pair(x, w_s, w_t, stats=True, run_frames=0):
+    """dwconv_t5(stem_conv(x, w_s), w_t, stats) for an fp32 clip and fp32 activations; run_frames: see cfn_stem_pair_fwd (0 = planned)"""
+    return _StemPair.apply(x, w_s, w_t, stats, run_frames)
 
 
 # ---- uint8 frames: normalised on the GPU (csrc/stem_u8.hip) -------------------------------------------------------------------

@@ -420,6 +420,12 @@ def GridUnpool(inp, return_aux=False):
 class ResNet(x3d_fine.ResNet):
     """Coarse stream (x3d_coarse.py:455-727); the X3D trunk, head and BN bookkeeping are x3d_fine's."""
 
+    # The stem keeps the two separate ops for every input: uint8 frames (U8Clips) always take them, and this stream's uint8 and fp32 inputs are held
+    # to the same gradients parameter by parameter, including the attention / re-weighting biases whose gradient is analytically zero (1e-10 of rounding
+    # noise: equal only while both inputs sum bn1's statistics in the same order).  That is a weakness of the comparison (tests/test_hip_u8_input.py
+    # _compare_nets divides by the norm of a zero gradient), not of this stream: once it floors that norm, drop this attribute (DESIGN.md 4.19).
+    FUSED_STEM_PAIR = False
+
     def __init__(self, block, layers, block_inplanes, n_input_channels=3, feat_depth={}, conv1_t_size=7,
                  conv1_t_stride=1, shortcut_type='B', widen_factor=1.0, dropout=0.5, n_classes=400, base_bn_splits=8,
                  task='class', extract_feat=False, t_pool=None, learnedMixing=False, isMixing=False, act_dtype=None):

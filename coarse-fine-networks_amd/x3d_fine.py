@@ -374,6 +374,10 @@ class ResNet(nn.Module):
         return self
 
     # -- pieces shared with x3d_coarse ---------------------------------------------------------------
+    # conv1_s -> conv1_t of an fp32 clip through ops.stem_pair (csrc/stempair.hip).  Its y is bit-identical to the two separate ops', its bn1 statistics
+    # are summed in another order (1e-7).  The coarse stream switches it off (x3d_coarse.ResNet).
+    FUSED_STEM_PAIR = True
+
     def _conv1_s(self, x):
         """fp32 clip (N, 3, T, H, W), or uint8 frames normalised at load time"""
         if not isinstance(x, U8Clips):
@@ -389,8 +393,12 @@ class ResNet(nn.Module):
 
     def _stem(self, x):
         """conv1_s -> conv1_t -> bn1 -> relu (x3d_fine.py:334-337); bn1+relu stay deferred."""
-        y = self._conv1_s(x)
-        y, s, q = ops.dwconv_t5(y, self.conv1_t.weight, stats=self.training, out_dtype=self.act_dtype)
+        if self.FUSED_STEM_PAIR and isinstance(x, torch.Tensor) and x.dtype == torch.float32 and self.act_dtype == torch.float32 and not USE_TORCH_OPS:
+            # nothing sits between the two convs: one kernel each way (conv1_s's output is not read back, its gradient never written)
+            y, s, q = ops.stem_pair(x, self.conv1_s.weight, self.conv1_t.weight, stats=self.training)
+        else:
+            y = self._conv1_s(x)
+            y, s, q = ops.dwconv_t5(y, self.conv1_t.weight, stats=self.training, out_dtype=self.act_dtype)
         A, B = self.bn1.fold(s, q, _count(y), y.shape[0])
         return Deferred(y, A, B, ACT_RELU)
 

@@ -153,6 +153,21 @@ int cfn_stem_conv_fwd(const float* x, const float* w, float* y, int N, int Cimg,
 int cfn_stem_conv_bwd_weight(const float* gy, const float* x, double* gw, int N, int Cimg, int Cout, int T, int Hi, int Wi,
                              void* stream);
 
+/* ---- the stem pair conv1_s -> conv1_t (nothing sits between them, x3d_fine.py:334-335) as one kernel each way (csrc/stempair.hip).
+ *   cfn_stem_pair_fwd: xs = cfn_stem_conv_fwd(x, w_s) and y, sum, sumsq = cfn_dwconv_t5_fwd(xs, w_t) with xs written once and not read back
+ *     (xs and y bit-identical to the two entry points; sum / sumsq (N, 24) fp64 zero-filled by the caller, both or neither).
+ *   cfn_stem_pair_bwd: gw_t (24, 5) and gw_s (24, 27), fp64, zero-filled by the caller = cfn_dwconv_t5_bwd_fused(gy, y, gsum, gsumsq, w_t, xs)
+ *     followed by cfn_stem_conv_bwd_weight(gxs, x), without the tensor gxs.  gsum, gsumsq may be NULL (y only with gsumsq).
+ * Workgroups walk runs of `run_frames` consecutive frames of one (sample, band of 2 output rows); 0 = the planner's choice (a run re-reads
+ * (backward) or recomputes (forward) two halo frames on either side).  Both return -1 WITHOUT launching for anything but a 3 -> 24 channel
+ * stem at 224 x 224 with 16-byte aligned tensors whose samples stay inside the 2 GiB buffer-descriptor range: callers then use the
+ * separate entry points. ---- */
+int cfn_stem_pair_fwd(const float* x, const float* w_s, const float* w_t, float* xs, float* y, double* sum, double* sumsq, int N,
+                      int Cimg, int Cout, int T, int Hi, int Wi, int run_frames, void* stream);
+int cfn_stem_pair_bwd(const float* gy, const float* y, const double* gsum, const double* gsumsq, const float* w_t, const float* xs,
+                      const float* x, double* gw_t, double* gw_s, int N, int Cimg, int Cout, int T, int Hi, int Wi, int run_frames,
+                      void* stream);
+
 /* ---- uint8 video frames, normalised on the GPU.  Replaces the host side ToTensor(255) + Normalize(mean, std) per frame
  * (spatial_transforms.py:46-85, :108-118) and the stack + permute per clip (charades_fine.py:170-173).
  * `unsigned char*` = uint8 tensor.  frames (N, T, H, W, 3) channels last, contiguous; lut (3, 256) fp32 = the normalised value of

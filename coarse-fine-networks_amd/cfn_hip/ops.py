@@ -1504,11 +1504,18 @@ class _GaussAlign(Function):
 
     @staticmethod
     def forward(ctx, meta, mask, gx, tx, ratio, crops, K):
+        # the C ABI takes pointers and sizes: refuse shapes that do not fit BEFORE any launch (the wording of cfn::gauss_align)
+        if mask.dim() != 2 or meta.dim() != 2 or tuple(meta.shape) != (mask.shape[0], 4) or meta.device != mask.device or crops < 1 or K < 1:
+            raise RuntimeError('gauss_align: meta (B, 4), mask (B, Tf) on one device, crops >= 1, K >= 1 (got meta %s mask %s crops %d K %d)'
+                               % (tuple(meta.shape), tuple(mask.shape), crops, K))
         meta, mask = meta.contiguous(), check(mask).contiguous()
         if meta.dtype != torch.int64:
             meta = meta.to(torch.int64)
         B, Tf = mask.shape
         if gx is not None:
+            if tuple(gx.shape) != (B * crops, K) or gx.device != mask.device:
+                raise RuntimeError('gauss_align: gx must be the (B * crops, K) CDF (got %s for B %d crops %d K %d)'
+                                   % (tuple(gx.shape), B, crops, K))
             gx = check(gx).contiguous()
         GX = torch.empty(B * crops, Tf, K, dtype=torch.float32, device=mask.device)
         call('cfn_gauss_align_fwd', meta, mask, gx, float(tx), float(ratio), GX, B, crops, Tf, K)

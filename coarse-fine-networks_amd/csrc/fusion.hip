@@ -336,6 +336,9 @@ __global__ __launch_bounds__(256) void fusion_gather_fwd_kernel(const float* __r
                                                                 const float* __restrict__ mask, float* __restrict__ z,
                                                                 float* __restrict__ den, int crops, int C, int Tf, int K, int P,
                                                                 long total) {
+    // no contraction here: the compiler would fold `d += w` into fma(a, GX * mask, d), one rounding fewer per frame than the tiled kernel
+    // below (which adds the rounded w), and z / den would differ from it in the last bit
+#pragma clang fp contract(off)
     const long e = (long)blockIdx.x * 256 + threadIdx.x;
     if (e >= total) return;
     const int p = (int)(e % P), k = (int)((e / P) % K), c = (int)((e / ((long)P * K)) % C);

@@ -1144,6 +1144,18 @@ def test_shape_mismatches_raise_instead_of_reading_out_of_bounds():
     y = rnd(7, 2, 8, 3, 12, 12).to(DEV)
     with pytest.raises(RuntimeError, match='residual'):
         o.bn_add_relu(y, torch.ones(2, 8, device=DEV), torch.zeros(2, 8, device=DEV), x)
+    # gauss_align: a CDF or a meta whose rows do not fit B * crops / B would be read past its end by the kernel
+    meta, fmask = torch.tensor([[0, 64, 6, 1], [3, 64, 6, 2]], device=DEV), torch.ones(2, 6, device=DEV)
+    cdf = torch.linspace(0, 1, 10, device=DEV).view(2, 5).contiguous()
+    with pytest.raises(RuntimeError, match=r'gx must be the \(B \* crops, K\) CDF'):
+        o.gauss_align(meta, fmask, cdf, 16, 2, 2, 5)                   # crops = 2 needs 4 CDF rows
+    with pytest.raises(RuntimeError, match=r'gx must be the \(B \* crops, K\) CDF'):
+        o.gauss_align(meta, fmask, cdf, 16, 2, 1, 9)                   # K = 9 against 5 knots
+    with pytest.raises(RuntimeError, match=r'meta \(B, 4\), mask \(B, Tf\)'):
+        o.gauss_align(meta[:1], fmask, cdf, 16, 2, 1, 5)               # one meta row for two videos
+    with pytest.raises(RuntimeError, match=r'meta \(B, 4\), mask \(B, Tf\)'):
+        o.gauss_align(meta[:, :3].contiguous(), fmask, None, None, 2, 1, 5)
+    assert o.gauss_align(meta, fmask, cdf, 16, 2, 1, 5).shape == (2, 6, 5)
 
 
 def test_double_backward_is_refused_loudly():

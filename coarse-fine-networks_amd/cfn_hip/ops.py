@@ -1007,7 +1007,9 @@ class _BnAddRelu(Function):
         sfx = _sfx(y)
         if link is not None:   # ReLU bit mask for the one-tensor backward (1/32 of a tensor instead of re-reading out)
             words = query('cfn_bn_add_relu_mask_words' + sfx, N * C, vol)
-            if words > 0:
+            # (the mask comes from the vector kernels only: a contiguous view that does not start on a 16-byte boundary takes the scalar route,
+            # whose entry point refuses a mask -- the backward then reads `out`)
+            if words > 0 and all(t.data_ptr() % 16 == 0 for t in (y, res, out)):
                 mask = torch.empty(words, dtype=torch.int32, device=y.device)
         call('cfn_bn_add_relu_fwd' + sfx, y, A, B, res, Ar, Br, out, mask, N * C, vol)
         ctx.link, ctx.has_mask = link, mask is not None

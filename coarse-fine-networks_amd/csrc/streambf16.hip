@@ -58,8 +58,9 @@ __global__ __launch_bounds__(256) void bn_add_relu_fwd_bf16_kernel(const uint16_
                 const float lo = fmaxf(fmaf(sb_lo(yv[e]), a, fmaf(sb_lo(rv[e]), ar, b)), 0.f);
                 const float hi = fmaxf(fmaf(sb_hi(yv[e]), a, fmaf(sb_hi(rv[e]), ar, b)), 0.f);
                 o[e] = sb_pack(lo, hi);
-                // the mask records the sign of the ROUNDED output (what the next layer sees); rounding keeps the sign
-                mw |= ((lo > 0.f ? 1u : 0u) | (hi > 0.f ? 2u : 0u)) << (8 * k + 2 * e);
+                // the mask records the sign of the output AS STORED (what the next layer and the mask-less backward see), so it is taken from
+                // the packed word: rounding does not always keep the sign -- fp16 stores an fp32 value in (0, 2^-25] as +0
+                mw |= ((sb_lo(o[e]) > 0.f ? 1u : 0u) | (sb_hi(o[e]) > 0.f ? 2u : 0u)) << (8 * k + 2 * e);
             }
             *reinterpret_cast<u4v*>(out + base + i) = o;
         }

@@ -63,10 +63,37 @@ The rules, stated once (the kernels, the numpy references and include/cfn_hip.h 
     N7. nms_thr = 1 keeps everything; with nms_thr < 1 exact duplicates across levels have tIoU exactly 1.0 and collapse to the first copy; a
         single-level decode passes through unchanged for any nms_thr, because its candidates do not overlap
 
-``decode_levels_reference`` and ``nms_reference`` spell these in numpy on any device and are the tests' reference.  Limits: K <= 16,
-B * C * K * TL < 2^31; NMS: B and C <= 65535, ranking is O(nd^2) and suppression O(kept * nd) per group of nd candidates.  No accuracy gain
-is claimed: which levels and which nms_thr help a trained model is for the user to find with the meter.  Out of scope: soft-NMS, NMS across
-classes.
+  SOFT-NMS (``soft_nms``, or ``propose(soft=SoftNMS(...))``; cfn_hip.ops.soft_nms_segments, csrc/segnms.hip).  Hard NMS deletes a candidate
+  whose tIoU with a kept one is above ``nms_thr``, so the ranked list is cut at a threshold the user has to guess.  Soft-NMS deletes nothing
+  by overlap: a candidate's score is decayed by its overlap with every candidate ranked in front of it, and the list is cut by a score floor
+  or a count.  The same ``Detections`` in and out, and the host parameters ``score_col``; ``method`` (0 = linear, 1 = gaussian); ``nms_thr``,
+  a double of [0, 1], linear only; ``sigma``, a double of [1/64, 2^20], gaussian only; ``min_score``, a double of [0, 1]; ``max_keep``, an
+  int >= 0 (0 = no limit):
+
+    S1. groups are rule N1's (video, class) row ranges
+    S2. row i gets the working score w_i = float64(score[i, score_col]); a row whose score is NaN or infinite is out of the group from the
+        start: never selected, never decayed, keep 0
+    S3. rounds: among the rows not yet selected take the largest w, on a tie the lowest row: m.  Stop when no row is left, when
+        not (w_m >= min_score), or when max_keep > 0 and max_keep rows are selected; otherwise m is selected and final_m = w_m.  Selected
+        finals never increase, so the selected set is exactly the rows whose final score is at least min_score, cut at max_keep
+    S4. decay of every row j not yet selected, iou = tIoU(m, j) by rule N3 unchanged.  linear: if iou > nms_thr (strict),
+        w_j = w_j * (1.0 - iou).  gaussian: if iou > 0, w_j = w_j * E((iou * iou) / sigma).  One fp64 subtraction or one E, then one fp64
+        product; the decays are applied in selection order
+    S5. E(t) = exp(-t) for t in [0, 64], written out so that both sides compute the same double (the device's exp and libm's differ in the
+        last bits): y = -(t * 2^-10); p = c8, then p = p * y + c_k for k = 7 .. 0 with c_k = 1.0 / k! as one IEEE fp64 division; then
+        p = p * p ten times.  Every product and sum is rounded separately, no fused multiply-add; fp64 subnormals follow IEEE
+        (``decay_exp_reference``: within 1.6e-13 relative of exp(-t), E(0) == 1.0 exactly)
+    S6. the output is a stable compaction of the selected rows in input order: seg, frames and the other score column copied bit for bit,
+        score[:, score_col] = float32(final), round to nearest; offsets and total are true counts; rows >= cap_out are not written; keep
+        and src as in N6
+    S7. linear with nms_thr = 1, min_score = 0, max_keep = 0 returns its input bit for bit; a single-level decode passes through either
+        method unchanged when min_score is not above its scores; max_keep = 1 leaves each group's first row in the order of N2; the first
+        selected row of every group is hard NMS's first kept row
+
+``decode_levels_reference``, ``nms_reference`` and ``soft_nms_reference`` spell these in numpy on any device and are the tests' reference.
+Limits: K <= 16, B * C * K * TL < 2^31; NMS: B and C <= 65535, ranking is O(nd^2) and suppression O(kept * nd) per group of nd candidates;
+soft-NMS is O(selected * nd) per group, which max_keep bounds.  No accuracy gain is claimed: which levels, which nms_thr, and whether hard or
+soft NMS help a trained model is for the user to find with the meter.  Out of scope: NMS across classes.
 
 This module is host only (numpy + torch) apart from those calls.
 """
@@ -347,15 +374,129 @@ def nms_reference(det, nms_thr, score='max', cap=None):
     return out, torch.from_numpy(keep).to(dev), torch.from_numpy(o_src).to(dev)
 
 
+SOFT_METHODS = {'linear': 0, 'gaussian': 1}
+SoftNMS = collections.namedtuple('SoftNMS', 'method sigma min_score max_keep', defaults=('gaussian', 0.5, 0.001, 0))
+SoftNMS.__doc__ = """The options of soft_nms (rules S1-S7): method 'linear' | 'gaussian', sigma in [1/64, 2^20] (gaussian), min_score in [0, 1] (the
+score floor that cuts the list), max_keep >= 0 rows per (video, class) group (0: no limit).  linear's threshold is the nms_thr of the call."""
+
+
+def _soft(soft, nms_thr, error=ValueError):
+    """a SoftNMS (or a plain tuple of its four fields) and nms_thr, checked -> (SoftNMS with host numbers, nms_thr)"""
+    if not isinstance(soft, tuple) or len(soft) != 4:
+        raise TypeError('soft: a cfn_hip.detections.SoftNMS expected, got %s' % type(soft).__name__)
+    method, sigma, min_score, max_keep = soft
+    if method not in SOFT_METHODS:
+        raise error("soft.method: 'linear' or 'gaussian' expected, got %r" % (method,))
+    for name, v, lo, hi, text in (('soft.sigma', sigma, 1.0 / 64.0, float(1 << 20), '[1/64, 2^20]'), ('soft.min_score', min_score, 0.0, 1.0, '[0, 1]'),
+                                  ('nms_thr', nms_thr, 0.0, 1.0, '[0, 1]')):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not lo <= float(v) <= hi:
+            raise error('%s in %s expected, got %r' % (name, text, v))
+    if isinstance(max_keep, bool) or not isinstance(max_keep, int) or not 0 <= max_keep < (1 << 31):
+        raise error('soft.max_keep: an int >= 0 expected (0: no limit), got %r' % (max_keep,))
+    return SoftNMS(method, float(sigma), float(min_score), max_keep), float(nms_thr)
+
+
+def decay_exp_reference(t):
+    """rule S5: E(t) = exp(-t) on [0, 64] in numpy float64 (a scalar or an array), every product and sum rounded separately -- the double the
+    kernel computes.  Neither numpy's nor the device's exp is used: they differ in their last bits."""
+    t = np.asarray(t, np.float64)
+    with np.errstate(all='ignore'):
+        y = -(t * np.float64(2.0 ** -10))
+        fact = [np.float64(1.0)]
+        for k in range(1, 9):
+            fact.append(fact[-1] * np.float64(k))                                     # k! is exact in fp64
+        p = np.float64(1.0) / fact[8] + np.zeros_like(y)
+        for k in range(7, -1, -1):
+            p = p * y + np.float64(1.0) / fact[k]
+        for _ in range(10):
+            p = p * p
+    return p
+
+
+def soft_nms(det, soft=SoftNMS(), nms_thr=0.5, score='max', cap=None, out=None):
+    """Soft-NMS of a Detections on the GPU -> (the selected Detections, keep (cap_in,) uint8, src (cap,) int32) there (rules S1-S7;
+    ops.soft_nms_segments: three launches, nothing is read back).  soft: a SoftNMS; nms_thr: linear's threshold (gaussian does not use it).
+    The score column `score` of the result holds the final, decayed scores.  cap (default: det.cap, which cannot overflow) and out: see
+    ops.soft_nms_segments."""
+    from . import ops
+    if not isinstance(det, Detections):
+        raise TypeError('soft_nms: a cfn_hip.detections.Detections expected, got %s' % type(det).__name__)
+    soft, nms_thr = _soft(soft, nms_thr)
+    seg, frames, score_t = _rows(det)
+    cap = int(det.cap) if cap is None else int(cap)
+    seg_o, frames_o, score_o, offsets, total, keep, src = ops.soft_nms_segments(seg, frames, score_t, det.offsets, det.n_classes, SOFT_METHODS[soft.method],
+                                                                                 soft.sigma, soft.min_score, soft.max_keep, nms_thr, _score_col(score),
+                                                                                 cap, out)
+    return Detections(seg_o, frames_o, score_o, offsets, total, det.n_classes, cap), keep, src
+
+
+def soft_nms_reference(det, soft=SoftNMS(), nms_thr=0.5, score='max', cap=None):
+    """soft_nms() from rules S1-S7 in numpy (a round is vectorised over the group: the elementwise fp64 operations give the same bits); a
+    Detections on any device, the results on its device.  cap, keep and src as nms_reference gives them."""
+    col = _score_col(score)
+    soft, nms_thr = _soft(soft, nms_thr)
+    gaussian, sigma, floor = soft.method == 'gaussian', np.float64(soft.sigma), np.float64(soft.min_score)
+    dev = det.seg.device
+    seg, frames, sc = (t.detach().cpu().numpy() for t in det[:3])
+    offs = det.offsets.detach().cpu().numpy().astype(np.int64)
+    cap_in = min(int(det.cap), seg.shape[0])
+    B = len(offs) - 1
+    n = min(max(int(offs[-1]), 0), cap_in)
+    keep = np.zeros(n, np.uint8)
+    final = sc[:n].copy()
+    new_offs = [0]
+    for b in range(B):
+        lo, hi = min(max(int(offs[b]), 0), cap_in), min(max(int(offs[b + 1]), 0), cap_in)
+        for c in np.unique(seg[lo:hi, 0]):                                            # S1
+            rows = lo + np.flatnonzero(seg[lo:hi, 0] == c)
+            s, e = seg[rows, 1], seg[rows, 2]
+            w = sc[rows, col].astype(np.float64)                                      # S2: -inf marks a row that is out, or selected
+            w = np.where(np.isfinite(w), w, -np.inf)
+            selected = 0
+            with np.errstate(all='ignore'):
+                while True:                                                           # S3
+                    m = int(np.argmax(w))                                             # (the first of equal maxima: the lowest row)
+                    wm = w[m]
+                    if wm == -np.inf or not wm >= floor or (soft.max_keep > 0 and selected >= soft.max_keep):
+                        break
+                    keep[rows[m]], final[rows[m], col] = 1, np.float32(wm)
+                    selected += 1
+                    w[m] = -np.inf
+                    inter = np.where(e[m] < e, e[m], e) - np.where(s[m] > s, s[m], s)  # S4: tiou_reference's expression, elementwise
+                    iou = np.where(inter > 0.0, inter / ((e[m] - s[m]) + (e - s) - inter), 0.0)
+                    if gaussian:
+                        hit = (iou > 0.0) & (w > -np.inf)
+                        w[hit] = w[hit] * decay_exp_reference((iou[hit] * iou[hit]) / sigma)
+                    else:
+                        hit = (iou > nms_thr) & (w > -np.inf)
+                        w[hit] = w[hit] * (1.0 - iou[hit])
+        new_offs.append(int(keep[:hi].sum()))
+    src = np.flatnonzero(keep).astype(np.int32)                                       # S6: input order
+    total = int(src.size)
+    rows_out = max(total, 1) if cap is None else int(cap)
+    if rows_out < 1:
+        raise ValueError('cap >= 1 expected, got %d' % rows_out)
+    k = min(total, rows_out)
+    o_seg, o_frames, o_score = np.zeros((rows_out, 3), np.float64), np.zeros((rows_out, 3), np.int32), np.zeros((rows_out, 2), np.float32)
+    o_src = np.zeros(rows_out, np.int32)
+    o_seg[:k], o_frames[:k], o_score[:k], o_src[:k] = seg[src[:k]], frames[src[:k]], final[src[:k]], src[:k]
+    out = Detections(torch.from_numpy(o_seg).to(dev), torch.from_numpy(o_frames).to(dev), torch.from_numpy(o_score).to(dev),
+                     torch.tensor(new_offs, dtype=torch.int32, device=dev), torch.tensor([total], dtype=torch.int32, device=dev), det.n_classes, rows_out)
+    return out, torch.from_numpy(keep).to(dev), torch.from_numpy(o_src).to(dev)
+
+
 def propose(probs, valid_t, fps=None, start=None, levels=(0.8, 0.65, 0.5, 0.35, 0.2), nms_thr=0.5, score='max', max_gap=0, min_len=1, out=None,
-            reference=False):
+            reference=False, soft=None):
     """probs -> candidates at K levels -> NMS -> the post-NMS Detections, all on the device (six launches, nothing is read back).  Levels
     listed high to low prefer the tight segment among nested candidates under score='max' (rule N2).  out: (the out of decode_levels, the out
-    of nms), both for the worst-case cap, for a call that allocates nothing (capturable).  reference=True: the numpy references instead."""
+    of nms), both for the worst-case cap, for a call that allocates nothing (capturable).  reference=True: the numpy references instead.
+    soft: a SoftNMS -- the second stage is soft_nms in place of nms (nms_thr is then linear's threshold; out[1] is the out of soft_nms)."""
     if reference:
         cand, _ = decode_levels_reference(probs, valid_t, fps, start, levels, max_gap, min_len)
-        return nms_reference(cand, nms_thr, score)[0]
+        return (nms_reference(cand, nms_thr, score) if soft is None else soft_nms_reference(cand, soft, nms_thr, score))[0]
     cand, _ = decode_levels(probs, valid_t, fps, start, levels, max_gap, min_len, out=None if out is None else out[0])
+    if soft is not None:
+        return soft_nms(cand, soft, nms_thr, score, out=None if out is None else out[1])[0]
     return nms(cand, nms_thr, score, out=None if out is None else out[1])[0]
 
 
@@ -377,14 +518,18 @@ class DetectionWriter(object):
 
     levels (floats or a (C, K) tensor), nms (a float of [0, 1], default 0.5), nms_score: with `levels` set add() runs propose() in place of
     decode() -- candidates at the K levels, then temporal NMS -- and keeps only the post-NMS batch (K times the rows); `thr` is then not
-    used.  The JSON format is the same."""
+    used.  The JSON format is the same.  soft (a SoftNMS, with `levels`): the second stage of propose() is soft_nms -- `nms` is then linear's
+    threshold and the score column `nms_score` of the file holds the final, decayed scores."""
 
-    def __init__(self, path, thr=0.5, max_gap=0, min_len=1, max_pending_bytes=1 << 30, levels=None, nms=None, nms_score='max'):
+    def __init__(self, path, thr=0.5, max_gap=0, min_len=1, max_pending_bytes=1 << 30, levels=None, nms=None, nms_score='max', soft=None):
         self.path, self.thr, self.max_gap, self.min_len = path, thr, int(max_gap), int(min_len)
         self.levels, self.nms, self.nms_score = levels, (0.5 if nms is None else float(nms)), nms_score
         if levels is None and nms is not None:
             raise ValueError('DetectionWriter: nms without levels: a single-level decode does not overlap itself (rule N7)')
+        if levels is None and soft is not None:
+            raise ValueError('DetectionWriter: soft without levels: a single-level decode does not overlap itself (rule S7)')
         _score_col(nms_score)
+        self.soft = None if soft is None else _soft(soft, self.nms)[0]
         self._levels_dev = {}
         self.max_pending_bytes = int(max_pending_bytes)
         self._pending, self._pending_bytes, self._rows = [], 0, []
@@ -428,7 +573,7 @@ class DetectionWriter(object):
             fps, start, unit = labels.fps, labels.window[:, 0].contiguous(), 's'
         if self.levels is not None:             # decoder: propose's `reference` switch (decode_reference: the numpy references)
             det = propose(probs.detach(), valid_t.to(torch.int32), fps, start, self._levels(probs), self.nms, self.nms_score, self.max_gap, self.min_len,
-                          reference=decoder is decode_reference)
+                          reference=decoder is decode_reference, soft=self.soft)
         else:
             det = (decoder or decode)(probs.detach(), valid_t.to(torch.int32), fps, start, self._thr(probs), self.max_gap, self.min_len)
         self._pending.append((det, names, unit))

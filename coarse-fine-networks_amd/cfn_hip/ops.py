@@ -1837,21 +1837,12 @@ def nms_segments_workspace_bytes(B, C, cap_in):
     return n
 
 
-def nms_segments(seg, frames, score, offsets, n_classes, nms_thr, score_col=0, cap_out=None, out=None):
-    """Temporal non-maximum suppression of a batch's detections (seg (cap_in, 3) fp64, frames (cap_in, 3) int32, score (cap_in, 2) fp32,
-    offsets (B + 1,) int32: a Detections whose (video, class) groups are contiguous) -> (seg, frames, score, offsets, total, keep (cap_in,)
-    uint8, src (cap_out,) int32): inside every group, in the order of score[:, score_col] descending (ties: the lower row), a candidate is
-    kept iff no candidate kept before it has a temporal IoU with it above `nms_thr`; the kept rows in their input order, copied bit for bit
-    (rules N1-N7 of cfn_hip/detections.py; nms_reference spells them on the host).  offsets and total are true counts; rows >= cap_out
-    (default: cap_in, which cannot overflow) are not written; keep is written for the rows of the batch's groups only; src holds the input
-    row of each output row.  `n_classes`, `nms_thr` (a float of [0, 1]), `score_col` (0 = max, 1 = mean) and `cap_out` are host values.
-    Three launches, nothing is read back (capturable with out=).  out: the seven tensors and a uint8 workspace of
-    nms_segments_workspace_bytes(B, C, cap_in) bytes.  No gradient, no CPU path."""
-    what = 'nms_segments'
+def _nms_arguments(what, seg, frames, score, offsets, n_classes, score_col, cap_out, out, workspace_bytes):
+    """the checks nms_segments and soft_nms_segments share -> (B, n_classes, score_col, cap_in, cap_out, out: the seven tensors and the workspace)"""
     for name, t in (('seg', seg), ('frames', frames), ('score', score), ('offsets', offsets)):
         if not torch.is_tensor(t) or t.device.type != 'cuda' or t.device != getattr(seg, 'device', None):
-            raise RuntimeError('%s: %s: device tensors on one GPU expected (there is no CPU path; cfn_hip.detections.nms_reference is the host '
-                               'spelling), got %s' % (what, name, getattr(t, 'device', type(t).__name__)))
+            raise RuntimeError('%s: %s: device tensors on one GPU expected (there is no CPU path; cfn_hip.detections.%s is the host '
+                               'spelling), got %s' % (what, name, what.replace('_segments', '_reference'), getattr(t, 'device', type(t).__name__)))
         if not t.is_contiguous():
             raise RuntimeError('%s: %s must be contiguous' % (what, name))
     if seg.dtype != torch.float64 or seg.dim() != 2 or seg.shape[1] != 3 or seg.shape[0] < 1:
@@ -1865,13 +1856,11 @@ def nms_segments(seg, frames, score, offsets, n_classes, nms_thr, score_col=0, c
     B, n_classes, score_col = int(offsets.numel()) - 1, int(n_classes), int(score_col)
     if n_classes < 1 or score_col not in (0, 1):
         raise RuntimeError('%s: n_classes >= 1 and score_col 0 (max) or 1 (mean) expected, got %d, %d' % (what, n_classes, score_col))
-    if isinstance(nms_thr, bool) or not isinstance(nms_thr, (int, float)) or not 0.0 <= float(nms_thr) <= 1.0:
-        raise RuntimeError('%s: nms_thr: a host float of [0, 1] expected, got %r' % (what, nms_thr))
     cap_out = cap_in if cap_out is None else int(cap_out)
     if cap_out < 1 or cap_out >= (1 << 31):
         raise RuntimeError('%s: cap_out in [1, 2^31) expected, got %d' % (what, cap_out))
     dev = seg.device
-    ws_bytes = nms_segments_workspace_bytes(B, n_classes, cap_in)
+    ws_bytes = workspace_bytes(B, n_classes, cap_in)
     if out is None:
         out = (torch.empty(cap_out, 3, dtype=torch.float64, device=dev), torch.empty(cap_out, 3, dtype=torch.int32, device=dev),
                torch.empty(cap_out, 2, dtype=torch.float32, device=dev), torch.empty(B + 1, dtype=torch.int32, device=dev),
@@ -1892,8 +1881,63 @@ def nms_segments(seg, frames, score, offsets, n_classes, nms_thr, score_col=0, c
                                '(%d,) int32, total (1,) int32, keep (>= %d,) uint8, src (>= %d,) int32 and an 8-byte aligned uint8 workspace of >= %d '
                                'bytes expected, got %s' % (what, cap_out, cap_out, cap_out, B + 1, cap_in, cap_out, ws_bytes,
                                                            [(y.dtype, tuple(y.shape)) for y in out]))
+    return B, n_classes, score_col, cap_in, cap_out, out
+
+
+def _host_float(what, name, v, lo, hi, text):
+    if isinstance(v, bool) or not isinstance(v, (int, float)) or not lo <= float(v) <= hi:
+        raise RuntimeError('%s: %s: a host float of %s expected, got %r' % (what, name, text, v))
+    return float(v)
+
+
+def nms_segments(seg, frames, score, offsets, n_classes, nms_thr, score_col=0, cap_out=None, out=None):
+    """Temporal non-maximum suppression of a batch's detections (seg (cap_in, 3) fp64, frames (cap_in, 3) int32, score (cap_in, 2) fp32,
+    offsets (B + 1,) int32: a Detections whose (video, class) groups are contiguous) -> (seg, frames, score, offsets, total, keep (cap_in,)
+    uint8, src (cap_out,) int32): inside every group, in the order of score[:, score_col] descending (ties: the lower row), a candidate is
+    kept iff no candidate kept before it has a temporal IoU with it above `nms_thr`; the kept rows in their input order, copied bit for bit
+    (rules N1-N7 of cfn_hip/detections.py; nms_reference spells them on the host).  offsets and total are true counts; rows >= cap_out
+    (default: cap_in, which cannot overflow) are not written; keep is written for the rows of the batch's groups only; src holds the input
+    row of each output row.  `n_classes`, `nms_thr` (a float of [0, 1]), `score_col` (0 = max, 1 = mean) and `cap_out` are host values.
+    Three launches, nothing is read back (capturable with out=).  out: the seven tensors and a uint8 workspace of
+    nms_segments_workspace_bytes(B, C, cap_in) bytes.  No gradient, no CPU path."""
+    what = 'nms_segments'
+    B, n_classes, score_col, cap_in, cap_out, out = _nms_arguments(what, seg, frames, score, offsets, n_classes, score_col, cap_out, out,
+                                                                   nms_segments_workspace_bytes)
+    nms_thr = _host_float(what, 'nms_thr', nms_thr, 0.0, 1.0, '[0, 1]')
     call('cfn_nms_segments', seg, frames, score, offsets, out[0], out[1], out[2], out[3], out[4], out[5], out[6], out[7], B, n_classes, score_col,
-         float(nms_thr), cap_in, cap_out)
+         nms_thr, cap_in, cap_out)
+    return out[:7]
+
+
+def soft_nms_segments_workspace_bytes(B, C, cap_in):
+    n = int(query('cfn_soft_nms_segments_workspace_bytes', int(B), int(C), int(cap_in)))
+    if n < 0:
+        raise RuntimeError('soft_nms_segments: B and C in [1, 65535] and cap_in in [1, 2^31) expected, got (%d, %d, %d)' % (B, C, cap_in))
+    return n
+
+
+def soft_nms_segments(seg, frames, score, offsets, n_classes, method=1, sigma=0.5, min_score=0.001, max_keep=0, nms_thr=0.5, score_col=0,
+                      cap_out=None, out=None):
+    """Soft-NMS of a batch's detections (the inputs and outputs of nms_segments): inside every (video, class) group the candidate with the
+    largest working score among those not yet selected is selected (ties: the lower row) and the working score of every other one is decayed
+    by its temporal IoU with it -- `method` 0 (linear): times 1 - iou where iou > nms_thr; 1 (gaussian): times E(iou^2 / sigma) where iou > 0
+    -- until the largest is below `min_score` or `max_keep` > 0 rows are selected.  The selected rows in their input order;
+    score[:, score_col] holds the final score, everything else is copied bit for bit; keep and src as nms_segments gives them (rules S1-S7 of
+    cfn_hip/detections.py; soft_nms_reference spells them on the host).  sigma in [1/64, 2^20], min_score and nms_thr in [0, 1], max_keep >= 0
+    (0: no limit) are host values.  Three launches, nothing is read back (capturable with out=).  out: the seven tensors and a uint8 workspace
+    of soft_nms_segments_workspace_bytes(B, C, cap_in) bytes.  No gradient, no CPU path."""
+    what = 'soft_nms_segments'
+    B, n_classes, score_col, cap_in, cap_out, out = _nms_arguments(what, seg, frames, score, offsets, n_classes, score_col, cap_out, out,
+                                                                   soft_nms_segments_workspace_bytes)
+    if isinstance(method, bool) or not isinstance(method, int) or method not in (0, 1):
+        raise RuntimeError('%s: method 0 (linear) or 1 (gaussian) expected, got %r' % (what, method))
+    nms_thr = _host_float(what, 'nms_thr', nms_thr, 0.0, 1.0, '[0, 1]')
+    sigma = _host_float(what, 'sigma', sigma, 1.0 / 64.0, float(1 << 20), '[1/64, 2^20]')
+    min_score = _host_float(what, 'min_score', min_score, 0.0, 1.0, '[0, 1]')
+    if isinstance(max_keep, bool) or not isinstance(max_keep, int) or not 0 <= max_keep < (1 << 31):
+        raise RuntimeError('%s: max_keep: a host int >= 0 expected (0: no limit), got %r' % (what, max_keep))
+    call('cfn_soft_nms_segments', seg, frames, score, offsets, out[0], out[1], out[2], out[3], out[4], out[5], out[6], out[7], B, n_classes, score_col,
+         nms_thr, method, sigma, min_score, max_keep, cap_in, cap_out)
     return out[:7]
 
 

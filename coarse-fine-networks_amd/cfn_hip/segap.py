@@ -41,7 +41,7 @@ This module is host only (numpy + torch) apart from the calls into cfn_hip.ops.
 import numpy as np
 import torch
 
-from .detections import SCORE_COLUMNS, Detections, decode
+from .detections import SCORE_COLUMNS, Detections, _soft, decode
 from .seglabels import SegLabels
 
 DEFAULT_TIOU = (0.1, 0.3, 0.5, 0.7, 0.9)
@@ -195,13 +195,14 @@ class SegmentAPMeter(object):
     thr, max_gap, min_len: the decode parameters the training entry points use when they are given the meter without a DetectionWriter.
     levels, nms (default 0.5), nms_score: with `levels` set those entry points run cfn_hip.detections.propose (candidates at K levels, then
     temporal NMS) in place of decode; the meter only keeps the three for them.  A batch of proposals can hold K times the rows of a decode:
-    ``add(levels=K)`` multiplies growing mode's bound (post-NMS groups can still exceed (TL + 1) // 2 rows).
+    ``add(levels=K)`` multiplies growing mode's bound (post-NMS groups can still exceed (TL + 1) // 2 rows).  soft (a
+    cfn_hip.detections.SoftNMS, with `levels`): propose's second stage is soft_nms; kept for the entry points like the three.
     One process only: merging the stores of data-parallel ranks is out of scope."""
 
     MIN_CAPACITY = 1024
 
     def __init__(self, device, n_classes, tiou=DEFAULT_TIOU, score='max', capacity=None, thr=0.5, max_gap=0, min_len=1, levels=None, nms=None,
-                 nms_score='max'):
+                 nms_score='max', soft=None):
         self.device = torch.device(device)
         if self.device.type != 'cuda':
             raise RuntimeError('SegmentAPMeter keeps its rows on a GPU (got device %s); cfn_hip.segap.ap_reference is the host spelling' % self.device)
@@ -220,6 +221,9 @@ class SegmentAPMeter(object):
         if nms_score not in SCORE_COLUMNS:
             raise ValueError("nms_score: 'max' or 'mean' expected, got %r" % (nms_score,))
         self.levels, self.nms, self.nms_score = levels, (0.5 if nms is None else float(nms)), nms_score
+        if levels is None and soft is not None:
+            raise ValueError('SegmentAPMeter: soft without levels: a single-level decode does not overlap itself')
+        self.soft = None if soft is None else _soft(soft, self.nms)[0]
         self._tiou = torch.tensor(self.tiou, dtype=torch.float64, device=self.device)
         self._state = torch.zeros(2 * self.n_classes + 1, dtype=torch.int32, device=self.device)      # counts, n_gt, flags
         cap = self.capacity if self.capacity is not None else self.MIN_CAPACITY

@@ -285,7 +285,7 @@ def run(init_lr=INIT_LR, warmup_steps=0, max_epochs=200, mode='rgb', root=None, 
     own thr / max_gap / min_len without a writer) against the batch's segment labels on the GPU and logs ' Epoch:E val seg-mAP@t: ...' behind the
     existing line.  One process only: AP is not additive and merging the stores of several ranks is out of scope, so a world size above 1
     raises.  None: nothing changes.  A writer or a meter made with levels= decodes with cfn_hip.detections.propose instead (candidates at K
-    levels, then temporal NMS); the meter is still fed the writer's batch when both are given.
+    levels, then temporal NMS -- soft-NMS when it was also made with soft=); the meter is still fed the writer's batch when both are given.
     calibration: a cfn_hip.calibrate.Calibration whose thr_vector / levels the writer and the meter were made with -- wherever a
     training mAP is taken the same sorted rows give the per-class thresholds (StepMetrics.mean_ap(calibration): no read-back of its own), and
     a validation phase that starts with rows the meter still holds calibrates from those first (StepMetrics.calibrate); each is followed by one
@@ -448,7 +448,7 @@ def segment_ap_add(meter, det, probs, valid_t, seg_batch, labels, writer=None):
         fps, start = seg_batch.fps, seg_batch.window[:, 0].contiguous()
     levels = writer.n_levels if det is not None and writer is not None else meter.n_levels
     if det is None and meter.levels is not None:
-        det = propose(probs.detach(), valid_t, fps, start, meter.levels, meter.nms, meter.nms_score, meter.max_gap, meter.min_len)
+        det = propose(probs.detach(), valid_t, fps, start, meter.levels, meter.nms, meter.nms_score, meter.max_gap, meter.min_len, soft=meter.soft)
     elif det is None:
         det = decode(probs.detach(), valid_t, fps, start, meter.thr, meter.max_gap, meter.min_len)
     meter.add(det, seg_batch if fps is not None else (labels, valid_t), levels=levels)
@@ -501,6 +501,13 @@ def add_detect_args(parser):
                         'the tight segment wins a tie of nested candidates), then temporal NMS')
     g.add_argument('--detect-nms', type=float, default=None, help='with --detect-levels: suppress a candidate whose temporal IoU with a kept one is above this (default 0.5)')
     g.add_argument('--detect-nms-score', choices=('max', 'mean'), default='max', help='with --detect-levels: the score column NMS ranks by')
+    g.add_argument('--detect-soft-nms', choices=('linear', 'gaussian'), default=None,
+                   help='with --detect-levels: soft-NMS in place of NMS -- nothing is deleted by overlap, a score is decayed by the overlap with every '
+                        'candidate ranked in front (linear: times 1 - tIoU where tIoU is above --detect-nms; gaussian: times exp(-tIoU^2 / sigma)), and '
+                        'the list is cut by --detect-min-score or --detect-max-keep')
+    g.add_argument('--detect-soft-sigma', type=float, default=None, help='with --detect-soft-nms gaussian: sigma, in [1/64, 2^20] (default 0.5)')
+    g.add_argument('--detect-min-score', type=float, default=None, help='with --detect-soft-nms: stop at the first decayed score below this (default 0.001)')
+    g.add_argument('--detect-max-keep', type=int, default=None, help='with --detect-soft-nms: at most N segments per video and class (default 0: no limit)')
     g.add_argument('--detect-calibrate', metavar='SPEC', default=None,
                    help="per-class thresholds calibrated on the GPU from the training AP rows (needs --device-ap): f1 | precision:P | recall:Q replaces "
                         "--detect-thr once the first training mAP is taken; recall:Q1,Q2,... (ascending: thresholds high to low) replaces the same "
@@ -509,11 +516,24 @@ def add_detect_args(parser):
 
 def detect_levels(args):
     """the proposal options of the --detect group as the keywords of DetectionWriter / SegmentAPMeter ({} without --detect-levels)"""
+    method = getattr(args, 'detect_soft_nms', None)
+    given = {k: getattr(args, 'detect_' + k, None) for k in ('soft_sigma', 'min_score', 'max_keep')}
+    if method is None and any(v is not None for v in given.values()):
+        raise ValueError('--detect-soft-sigma, --detect-min-score and --detect-max-keep need --detect-soft-nms linear|gaussian')
     if getattr(args, 'detect_levels', None) is None:
         if getattr(args, 'detect_nms', None) is not None:
             raise ValueError('--detect-nms needs --detect-levels: a single-level decode does not overlap itself')
+        if method is not None:
+            raise ValueError('--detect-soft-nms needs --detect-levels: a single-level decode does not overlap itself')
         return {}
-    return {'levels': [float(x) for x in args.detect_levels.split(',')], 'nms': args.detect_nms, 'nms_score': args.detect_nms_score}
+    more = {'levels': [float(x) for x in args.detect_levels.split(',')], 'nms': args.detect_nms, 'nms_score': args.detect_nms_score}
+    if method is not None:                                        # (the key only with the option: every caller without it sees the same dict)
+        from cfn_hip.detections import SoftNMS
+        if method == 'gaussian' and args.detect_nms is not None:
+            raise ValueError('--detect-nms is the threshold of NMS and of --detect-soft-nms linear; gaussian does not use it')
+        more['soft'] = SoftNMS(method)._replace(**{k: v for k, v in (('sigma', given['soft_sigma']), ('min_score', given['min_score']),
+                                                                      ('max_keep', given['max_keep'])) if v is not None})
+    return more
 
 
 def detect_argv(args):
@@ -522,6 +542,9 @@ def detect_argv(args):
         return []
     more = (['--detect-levels', args.detect_levels, '--detect-nms-score', args.detect_nms_score] if args.detect_levels is not None else []) + \
         (['--detect-nms', repr(args.detect_nms)] if args.detect_nms is not None else []) + \
+        [x for flag, k, f in (('--detect-soft-nms', 'detect_soft_nms', str), ('--detect-soft-sigma', 'detect_soft_sigma', repr),
+                              ('--detect-min-score', 'detect_min_score', repr), ('--detect-max-keep', 'detect_max_keep', str))
+         if getattr(args, k, None) is not None for x in (flag, f(getattr(args, k)))] + \
         (['--detect-calibrate', args.detect_calibrate] if getattr(args, 'detect_calibrate', None) is not None else [])
     return ['--detect', args.detect, '--detect-thr', repr(args.detect_thr), '--detect-gap', str(args.detect_gap), '--detect-min-len', str(args.detect_min_len)] + more
 

@@ -657,6 +657,36 @@ int cfn_decode_segments(const float* probs, const int* valid_t, const double* fp
  * values, never a store outside the outputs.  Ordered by the stream alone, no atomics, no allocation, no synchronisation
  * (capturable).  cfn_nms_segments returns 1 for null pointers, B or C outside [1, 65535], cap_in or cap_out outside [1, 2^31),
  * score_col outside {0, 1}, nms_thr outside [0, 1] (a NaN included), a misaligned workspace or an output that is an input.
+ * cfn_soft_nms_segments: soft-NMS over the same inputs and outputs.  Nothing is deleted by overlap: a candidate's score is decayed by
+ * its overlap with every candidate ranked in front of it, and the list is cut by a score floor or a count.  Host parameters beside
+ * cfn_nms_segments': method 0 = linear, 1 = gaussian; nms_thr in [0, 1] (linear only); sigma in [1/64, 2^20] (gaussian only);
+ * min_score in [0, 1]; max_keep >= 0 (0 = no limit).
+ *     S1. groups are rule N1's
+ *     S2. row i gets w_i = (double)score[i, score_col]; a row whose score is NaN or infinite is out of the group from the start: never
+ *         selected, never decayed, keep 0
+ *     S3. rounds: among the rows not yet selected m = the one with the largest w, ties to the lowest row.  Stop when no row is left,
+ *         when !(w_m >= min_score), or when max_keep > 0 and max_keep rows are selected; otherwise m is selected, final_m = w_m.
+ *         Selected finals never increase: the selected set is the rows whose final is at least min_score, cut at max_keep
+ *     S4. decay of every row j not yet selected, iou = tIoU(m, j) by rule N3 unchanged.  linear: if iou > nms_thr (strict)
+ *         w_j = w_j * (1.0 - iou).  gaussian: if iou > 0, w_j = w_j * E((iou * iou) / sigma).  One fp64 subtraction or one E, then
+ *         one fp64 product; the decays are applied in selection order
+ *     S5. E(t) = exp(-t) for t in [0, 64], spelled so that device and host compute the same double: y = -(t * 2^-10); p = c8, then
+ *         p = p * y + c_k for k = 7 .. 0 with c_k = 1.0 / k! (one IEEE fp64 division each); then p = p * p ten times.  Every product
+ *         and sum is rounded separately (no fused multiply-add); fp64 subnormals follow IEEE.  Within 1.6e-13 relative of exp(-t),
+ *         E(0) = 1.0 exactly
+ *     S6. stable compaction of the selected rows in input order: out_seg, out_frames and the other score column copied bit for
+ *         bit, out_score[:, score_col] = (float)final (round to nearest); out_offsets and out_total are TRUE counts; rows >= cap_out
+ *         are not written; keep (cap_in) uint8 and src (cap_out) int32 as in N6
+ *     S7. linear with nms_thr = 1, min_score = 0, max_keep = 0 returns its input bit for bit; a single-level decode passes through
+ *         either method unchanged when min_score is not above its scores; max_keep = 1 leaves each group's first row in the order
+ *         of N2; the first selected row of every group is cfn_nms_segments' first kept row
+ *   3 launches (soft_select: one wave per group, candidate j owned by lane j & 63, a round = per-lane maximum, wave reduction of the
+ *   (w, row) pair, decay of the own entries: O(selected * nd / 64), no barrier, fence or atomic inside the rounds; groups of up to
+ *   cfn_nms_det_tile() candidates in LDS, larger ones keep w in the workspace; cfn_nms_segments' scan; a write that takes column
+ *   score_col from the finals).  workspace: cfn_soft_nms_segments_workspace_bytes(B, C, cap_in) bytes on an 8-byte boundary (8 + 4
+ *   bytes per input row and B * C + 1 counts).  Clamped, ordered by the stream alone, no allocation, no synchronisation (capturable)
+ *   like cfn_nms_segments.  Returns 1 for everything cfn_nms_segments refuses, and for method outside {0, 1}, sigma outside
+ *   [1/64, 2^20], min_score outside [0, 1] (NaNs included) or max_keep < 0; the workspace query -1 for cfn_nms_segments' shapes.
  * ===================================================================================================================== */
 long cfn_decode_segments_levels_workspace_bytes(int B, int C, int K, int TL);
 int cfn_decode_segments_levels(const float* probs, const int* valid_t, const double* fps, const int* start, const float* levels,
@@ -667,6 +697,11 @@ int cfn_nms_det_tile(void);
 int cfn_nms_segments(const double* seg, const int* frames, const float* score, const int* offsets, double* out_seg, int* out_frames,
                      float* out_score, int* out_offsets, int* out_total, unsigned char* keep, int* src, void* workspace, int B,
                      int C, int score_col, double nms_thr, long cap_in, long cap_out, void* stream);
+long cfn_soft_nms_segments_workspace_bytes(int B, int C, long cap_in);
+int cfn_soft_nms_segments(const double* seg, const int* frames, const float* score, const int* offsets, double* out_seg, int* out_frames,
+                          float* out_score, int* out_offsets, int* out_total, unsigned char* keep, int* src, void* workspace, int B,
+                          int C, int score_col, double nms_thr, int method, double sigma, double min_score, int max_keep, long cap_in,
+                          long cap_out, void* stream);
 
 /* =====================================================================================================================
  * Segment-level average precision at temporal-IoU thresholds (csrc/segap.hip; the host reference and the meter:

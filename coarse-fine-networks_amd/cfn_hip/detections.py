@@ -330,37 +330,28 @@ def nms(det, nms_thr, score='max', cap=None, out=None):
     return Detections(seg_o, frames_o, score_o, offsets, total, det.n_classes, cap), keep, src
 
 
-def nms_reference(det, nms_thr, score='max', cap=None):
-    """nms() from rules N1-N7 in numpy; a Detections on any device, the results on its device.  cap=None: exactly the kept rows (at least
-    one); a cap keeps the first `cap` kept rows and the true offsets / total, as the kernel does.  keep covers the min(total, cap_in) input
-    rows; src the rows written."""
-    from .segap import tiou_reference
-    col = _score_col(score)
-    nms_thr = float(nms_thr)
-    if not 0.0 <= nms_thr <= 1.0:
-        raise ValueError('nms_thr in [0, 1] expected, got %r' % (nms_thr,))
-    dev = det.seg.device
-    seg, frames, sc = (t.detach().cpu().numpy() for t in det[:3])
+def _ranges(det):
+    """a Detections' offsets clamped to the rows it holds, as the kernels clamp them -> (rows covered by offsets[-1], [(lo, hi) per video])"""
     offs = det.offsets.detach().cpu().numpy().astype(np.int64)
-    cap_in = min(int(det.cap), seg.shape[0])
-    B = len(offs) - 1
-    n = min(max(int(offs[-1]), 0), cap_in)
-    keep = np.zeros(n, np.uint8)
-    new_offs = [0]
-    for b in range(B):
-        lo, hi = min(max(int(offs[b]), 0), cap_in), min(max(int(offs[b + 1]), 0), cap_in)
-        for c in np.unique(seg[lo:hi, 0]):                                            # N1
-            rows = lo + np.flatnonzero(seg[lo:hi, 0] == c)
-            key = sc[rows, col].astype(np.float32)
-            key = np.where(np.isnan(key), np.float32(-np.inf), key)
-            order = rows[np.argsort(-key, kind='stable')]                             # N2
-            kept = []
-            for d in order:                                                           # N4
-                if not any(tiou_reference(seg[k, 1], seg[k, 2], seg[d, 1], seg[d, 2]) > nms_thr for k in kept):     # N3
-                    kept.append(d)
-                    keep[d] = 1
-        new_offs.append(int(keep[:hi].sum()))
-    src = np.flatnonzero(keep).astype(np.int32)                                       # N5: input order
+    cap_in = min(int(det.cap), int(det.seg.shape[0]))
+    offs = [min(max(int(o), 0), cap_in) for o in offs]
+    return offs[-1], list(zip(offs[:-1], offs[1:]))
+
+
+def _groups(det, seg):
+    """rule N1 on the host: the row indices of every (video, class) group of `det` (seg: its seg as numpy), videos in order, classes ascending"""
+    for lo, hi in _ranges(det)[1]:
+        for c in np.unique(seg[lo:hi, 0]):
+            yield lo + np.flatnonzero(seg[lo:hi, 0] == c)
+
+
+def _compacted(det, keep, sc, cap):
+    """rules N5 / N6 (S6) on the host: keep over det's input rows and the score rows to copy -> (the stable compaction as a Detections,
+    keep, src) on det's device.  cap=None: exactly the kept rows (at least one)."""
+    dev = det.seg.device
+    seg, frames = (t.detach().cpu().numpy() for t in det[:2])
+    new_offs = [0] + [int(keep[:hi].sum()) for _, hi in _ranges(det)[1]]
+    src = np.flatnonzero(keep).astype(np.int32)                                       # input order
     total = int(src.size)
     rows_out = max(total, 1) if cap is None else int(cap)
     if rows_out < 1:
@@ -372,6 +363,29 @@ def nms_reference(det, nms_thr, score='max', cap=None):
     out = Detections(torch.from_numpy(o_seg).to(dev), torch.from_numpy(o_frames).to(dev), torch.from_numpy(o_score).to(dev),
                      torch.tensor(new_offs, dtype=torch.int32, device=dev), torch.tensor([total], dtype=torch.int32, device=dev), det.n_classes, rows_out)
     return out, torch.from_numpy(keep).to(dev), torch.from_numpy(o_src).to(dev)
+
+
+def nms_reference(det, nms_thr, score='max', cap=None):
+    """nms() from rules N1-N7 in numpy; a Detections on any device, the results on its device.  cap=None: exactly the kept rows (at least
+    one); a cap keeps the first `cap` kept rows and the true offsets / total, as the kernel does.  keep covers the min(total, cap_in) input
+    rows; src the rows written."""
+    from .segap import tiou_reference
+    col = _score_col(score)
+    nms_thr = float(nms_thr)
+    if not 0.0 <= nms_thr <= 1.0:
+        raise ValueError('nms_thr in [0, 1] expected, got %r' % (nms_thr,))
+    seg, sc = det.seg.detach().cpu().numpy(), det.score.detach().cpu().numpy()
+    keep = np.zeros(_ranges(det)[0], np.uint8)
+    for rows in _groups(det, seg):                                                    # N1
+        key = sc[rows, col].astype(np.float32)
+        key = np.where(np.isnan(key), np.float32(-np.inf), key)
+        order = rows[np.argsort(-key, kind='stable')]                                 # N2
+        kept = []
+        for d in order:                                                               # N4
+            if not any(tiou_reference(seg[k, 1], seg[k, 2], seg[d, 1], seg[d, 2]) > nms_thr for k in kept):         # N3
+                kept.append(d)
+                keep[d] = 1
+    return _compacted(det, keep, sc, cap)
 
 
 SOFT_METHODS = {'linear': 0, 'gaussian': 1}
@@ -436,53 +450,33 @@ def soft_nms_reference(det, soft=SoftNMS(), nms_thr=0.5, score='max', cap=None):
     col = _score_col(score)
     soft, nms_thr = _soft(soft, nms_thr)
     gaussian, sigma, floor = soft.method == 'gaussian', np.float64(soft.sigma), np.float64(soft.min_score)
-    dev = det.seg.device
-    seg, frames, sc = (t.detach().cpu().numpy() for t in det[:3])
-    offs = det.offsets.detach().cpu().numpy().astype(np.int64)
-    cap_in = min(int(det.cap), seg.shape[0])
-    B = len(offs) - 1
-    n = min(max(int(offs[-1]), 0), cap_in)
+    seg, sc = det.seg.detach().cpu().numpy(), det.score.detach().cpu().numpy()
+    n = _ranges(det)[0]
     keep = np.zeros(n, np.uint8)
     final = sc[:n].copy()
-    new_offs = [0]
-    for b in range(B):
-        lo, hi = min(max(int(offs[b]), 0), cap_in), min(max(int(offs[b + 1]), 0), cap_in)
-        for c in np.unique(seg[lo:hi, 0]):                                            # S1
-            rows = lo + np.flatnonzero(seg[lo:hi, 0] == c)
-            s, e = seg[rows, 1], seg[rows, 2]
-            w = sc[rows, col].astype(np.float64)                                      # S2: -inf marks a row that is out, or selected
-            w = np.where(np.isfinite(w), w, -np.inf)
-            selected = 0
-            with np.errstate(all='ignore'):
-                while True:                                                           # S3
-                    m = int(np.argmax(w))                                             # (the first of equal maxima: the lowest row)
-                    wm = w[m]
-                    if wm == -np.inf or not wm >= floor or (soft.max_keep > 0 and selected >= soft.max_keep):
-                        break
-                    keep[rows[m]], final[rows[m], col] = 1, np.float32(wm)
-                    selected += 1
-                    w[m] = -np.inf
-                    inter = np.where(e[m] < e, e[m], e) - np.where(s[m] > s, s[m], s)  # S4: tiou_reference's expression, elementwise
-                    iou = np.where(inter > 0.0, inter / ((e[m] - s[m]) + (e - s) - inter), 0.0)
-                    if gaussian:
-                        hit = (iou > 0.0) & (w > -np.inf)
-                        w[hit] = w[hit] * decay_exp_reference((iou[hit] * iou[hit]) / sigma)
-                    else:
-                        hit = (iou > nms_thr) & (w > -np.inf)
-                        w[hit] = w[hit] * (1.0 - iou[hit])
-        new_offs.append(int(keep[:hi].sum()))
-    src = np.flatnonzero(keep).astype(np.int32)                                       # S6: input order
-    total = int(src.size)
-    rows_out = max(total, 1) if cap is None else int(cap)
-    if rows_out < 1:
-        raise ValueError('cap >= 1 expected, got %d' % rows_out)
-    k = min(total, rows_out)
-    o_seg, o_frames, o_score = np.zeros((rows_out, 3), np.float64), np.zeros((rows_out, 3), np.int32), np.zeros((rows_out, 2), np.float32)
-    o_src = np.zeros(rows_out, np.int32)
-    o_seg[:k], o_frames[:k], o_score[:k], o_src[:k] = seg[src[:k]], frames[src[:k]], final[src[:k]], src[:k]
-    out = Detections(torch.from_numpy(o_seg).to(dev), torch.from_numpy(o_frames).to(dev), torch.from_numpy(o_score).to(dev),
-                     torch.tensor(new_offs, dtype=torch.int32, device=dev), torch.tensor([total], dtype=torch.int32, device=dev), det.n_classes, rows_out)
-    return out, torch.from_numpy(keep).to(dev), torch.from_numpy(o_src).to(dev)
+    for rows in _groups(det, seg):                                                    # S1
+        s, e = seg[rows, 1], seg[rows, 2]
+        w = sc[rows, col].astype(np.float64)                                          # S2: -inf marks a row that is out, or selected
+        w = np.where(np.isfinite(w), w, -np.inf)
+        selected = 0
+        with np.errstate(all='ignore'):
+            while True:                                                               # S3
+                m = int(np.argmax(w))                                                 # (the first of equal maxima: the lowest row)
+                wm = w[m]
+                if wm == -np.inf or not wm >= floor or (soft.max_keep > 0 and selected >= soft.max_keep):
+                    break
+                keep[rows[m]], final[rows[m], col] = 1, np.float32(wm)
+                selected += 1
+                w[m] = -np.inf
+                inter = np.where(e[m] < e, e[m], e) - np.where(s[m] > s, s[m], s)      # S4: tiou_reference's expression, elementwise
+                iou = np.where(inter > 0.0, inter / ((e[m] - s[m]) + (e - s) - inter), 0.0)
+                if gaussian:
+                    hit = (iou > 0.0) & (w > -np.inf)
+                    w[hit] = w[hit] * decay_exp_reference((iou[hit] * iou[hit]) / sigma)
+                else:
+                    hit = (iou > nms_thr) & (w > -np.inf)
+                    w[hit] = w[hit] * (1.0 - iou[hit])
+    return _compacted(det, keep, final, cap)                                          # S6
 
 
 def propose(probs, valid_t, fps=None, start=None, levels=(0.8, 0.65, 0.5, 0.35, 0.2), nms_thr=0.5, score='max', max_gap=0, min_len=1, out=None,

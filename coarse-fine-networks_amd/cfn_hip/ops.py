@@ -1675,6 +1675,42 @@ def seg_labels(seg, offsets, fps, window, n_classes, t_max, out=None):
     return out
 
 
+# ---- argument checks shared by the segment operators below (decode, levels, NMS, soft-NMS, segment AP) ---------------------------------------
+def _one_gpu(what, host, **tensors):
+    """every argument a contiguous device tensor, all on one GPU -> that device.  host: the host spelling that the refusal names"""
+    dev = None
+    for name, t in tensors.items():
+        if not torch.is_tensor(t) or t.device.type != 'cuda' or (dev is not None and t.device != dev):
+            raise RuntimeError('%s: %s is on %s: device tensors on one GPU expected (there is no CPU path; %s is the host spelling)'
+                               % (what, name, getattr(t, 'device', 'the host (a %s)' % type(t).__name__), host))
+        if not t.is_contiguous():
+            raise RuntimeError('%s: %s must be contiguous' % (what, name))
+        dev = t.device
+    return dev
+
+
+def _out_tuple(what, out, dev, slots, ws_bytes):
+    """slots: (name, dtype, trailing shape, rows, exact) per output, exact: rows == or >=.  out=None: new tensors for the slots and a uint8
+    workspace of ws_bytes behind them; otherwise the caller's tuple, checked against the same list (the workspace: 8-byte aligned, >= ws_bytes)"""
+    if out is None:
+        return tuple(torch.empty(rows, *trail, dtype=dt, device=dev) for _, dt, trail, rows, _ in slots) \
+            + (torch.empty(ws_bytes, dtype=torch.uint8, device=dev),)
+    out = tuple(out)
+    if len(out) != len(slots) + 1 or any(y.dtype != dt or tuple(y.shape[1:]) != tuple(trail) or y.dim() != 1 + len(trail) or not y.is_contiguous()
+                                         or (y.shape[0] != rows if exact else y.shape[0] < rows) for y, (_, dt, trail, rows, exact) in zip(out, slots)) \
+            or out[-1].dtype != torch.uint8 or out[-1].dim() != 1 or out[-1].numel() < ws_bytes or out[-1].data_ptr() % 8 or not out[-1].is_contiguous():
+        want = ', '.join('%s (%s%d%s) %s' % (name, '' if exact else '>= ', rows, ''.join(', %d' % w for w in trail) or ',', str(dt)[6:])
+                         for name, dt, trail, rows, exact in slots)
+        raise RuntimeError('%s: out: contiguous %s and an 8-byte aligned uint8 workspace of >= %d bytes expected, got %s'
+                           % (what, want, ws_bytes, [(y.dtype, tuple(y.shape)) for y in out]))
+    return out
+
+
+def _record_slots(cap):
+    """the three record buffers of a Detections"""
+    return [('seg', torch.float64, (3,), cap, False), ('frames', torch.int32, (3,), cap, False), ('score', torch.float32, (2,), cap, False)]
+
+
 # ---- activity segments from per-frame scores (csrc/detections.hip; the batch type, the host reference and the writer: cfn_hip/detections.py) --
 DECODE_MAX_TL = 65536
 
@@ -1692,6 +1728,49 @@ def decode_segments_workspace_bytes(B, C, TL):
     return n
 
 
+def _decode_arguments(what, probs, valid_t, fps, start, name, levels, max_gap, min_len, cap):
+    """the checks decode_segments and decode_segments_levels share.  name 'levels': levels (C, K); name 'thr': the K = 1 case, `levels` is
+    decode_segments' thr, a float or a (C,) tensor -> (B, C, K, TL, valid_t, fps, start and the thresholds as contiguous device tensors,
+    max_gap, min_len, cap, the device)"""
+    if not torch.is_tensor(probs) or probs.dtype != torch.float32 or probs.dim() != 3 or min(probs.shape) < 1 or not probs.is_contiguous():
+        raise RuntimeError('%s: probs: a contiguous (B, C, TL) float32 tensor expected, got %s %s'
+                           % (what, getattr(probs, 'dtype', type(probs).__name__), tuple(getattr(probs, 'shape', ()))))
+    B, C, TL = (int(s) for s in probs.shape)
+    got = '%s %s' % (getattr(levels, 'dtype', type(levels).__name__), tuple(getattr(levels, 'shape', ())))
+    if name == 'thr':
+        K = 1
+        if isinstance(levels, bool) or not isinstance(levels, (int, float, torch.Tensor)) \
+                or (torch.is_tensor(levels) and (levels.dtype != torch.float32 or tuple(levels.shape) != (C,))):
+            raise RuntimeError('%s: thr: a float or a (%d,) float32 tensor expected, got %s' % (what, C, got))
+    else:
+        if not torch.is_tensor(levels) or levels.dtype != torch.float32 or levels.dim() != 2 or int(levels.shape[0]) != C \
+                or not 1 <= int(levels.shape[1]) <= DECODE_MAX_LEVELS or not levels.is_contiguous():
+            raise RuntimeError('%s: levels: a contiguous (%d, K) float32 tensor with 1 <= K <= %d expected, got %s' % (what, C, DECODE_MAX_LEVELS, got))
+        K = int(levels.shape[1])
+    if TL > DECODE_MAX_TL or B > 65535 or C >= (1 << 19) or B * C * K * TL >= (1 << 31):
+        raise RuntimeError('%s: probs: B <= 65535, C < 2^19, TL <= %d and B * C * K * TL < 2^31 expected, got (%d, %d, %d) and K = %d'
+                           % (what, DECODE_MAX_TL, B, C, TL, K))
+    for arg, t, dt in (('valid_t', valid_t, torch.int32), ('fps', fps, torch.float64), ('start', start, torch.int32)):
+        if not torch.is_tensor(t) or t.dtype != dt or tuple(t.shape) != (B,):
+            raise RuntimeError('%s: %s (%d,) %s expected, got %s %s' % (what, arg, B, dt, getattr(t, 'dtype', type(t).__name__), tuple(getattr(t, 'shape', ()))))
+    max_gap, min_len = int(max_gap), int(min_len)
+    if max_gap < 0:
+        raise RuntimeError('%s: max_gap >= 0 expected, got %d' % (what, max_gap))
+    if min_len < 1:
+        raise RuntimeError('%s: min_len >= 1 expected, got %d' % (what, min_len))
+    cap = decode_segments_levels_cap(B, C, K, TL) if cap is None else int(cap)
+    if cap < 1 or cap >= (1 << 31):
+        raise RuntimeError('%s: cap in [1, 2^31) expected, got %d' % (what, cap))
+    valid_t, fps, start = valid_t.contiguous(), fps.contiguous(), start.contiguous()
+    tensors = dict(probs=probs, valid_t=valid_t, fps=fps, start=start)
+    if torch.is_tensor(levels):
+        levels = tensors[name] = levels.contiguous()
+    dev = _one_gpu(what, 'cfn_hip.detections.' + ('decode_reference' if name == 'thr' else 'decode_levels_reference'), **tensors)
+    if not torch.is_tensor(levels):
+        levels = torch.full((C,), float(levels), dtype=torch.float32, device=dev)
+    return B, C, K, TL, valid_t, fps, start, levels, max_gap, min_len, cap, dev
+
+
 def decode_segments(probs, valid_t, fps, start, thr, max_gap=0, min_len=1, cap=None, out=None):
     """probs (B, C, TL) fp32 on the GPU; valid_t (B,) int32; fps (B,) fp64; start (B,) int32 = first frame of each window
     (SegLabels.window[:, 0]); thr: a float or a (C,) fp32 device tensor -> (seg (cap, 3) fp64 rows [class, start_s, end_s], frames (cap, 3)
@@ -1701,54 +1780,11 @@ def decode_segments(probs, valid_t, fps, start, thr, max_gap=0, min_len=1, cap=N
     rows >= cap are not written (cap=None: B * C * ((TL + 1) // 2), which cannot overflow).  Three launches, no atomics, nothing is read
     back (no wait, capturable with out=); `max_gap`, `min_len` and `cap` are host ints.  out: the five preallocated tensors and a uint8
     workspace of decode_segments_workspace_bytes(B, C, TL) bytes (then thr must be a tensor for nothing to be allocated).  No gradient, no CPU path."""
-    if not torch.is_tensor(probs) or probs.dtype != torch.float32 or probs.dim() != 3 or min(probs.shape) < 1 or not probs.is_contiguous():
-        raise RuntimeError('decode_segments: probs: a contiguous (B, C, TL) float32 tensor expected, got %s %s'
-                           % (getattr(probs, 'dtype', type(probs).__name__), tuple(getattr(probs, 'shape', ()))))
-    B, C, TL = (int(s) for s in probs.shape)
-    if TL > DECODE_MAX_TL or B > 65535 or C >= (1 << 19) or B * C * TL >= (1 << 31):
-        raise RuntimeError('decode_segments: probs: B <= 65535, C < 2^19, TL <= %d and B * C * TL < 2^31 expected, got (%d, %d, %d)'
-                           % (DECODE_MAX_TL, B, C, TL))
-    for name, t, dt in (('valid_t', valid_t, torch.int32), ('fps', fps, torch.float64), ('start', start, torch.int32)):
-        if not torch.is_tensor(t) or t.dtype != dt or tuple(t.shape) != (B,):
-            raise RuntimeError('decode_segments: %s (%d,) %s expected, got %s %s'
-                               % (name, B, dt, getattr(t, 'dtype', type(t).__name__), tuple(getattr(t, 'shape', ()))))
-    if torch.is_tensor(thr):
-        if thr.dtype != torch.float32 or tuple(thr.shape) != (C,):
-            raise RuntimeError('decode_segments: thr: a float or a (%d,) float32 tensor expected, got %s %s' % (C, thr.dtype, tuple(thr.shape)))
-    elif isinstance(thr, bool) or not isinstance(thr, (int, float)):
-        raise RuntimeError('decode_segments: thr: a float or a (%d,) float32 tensor expected, got %s' % (C, type(thr).__name__))
-    max_gap, min_len = int(max_gap), int(min_len)
-    if max_gap < 0:
-        raise RuntimeError('decode_segments: max_gap >= 0 expected, got %d' % max_gap)
-    if min_len < 1:
-        raise RuntimeError('decode_segments: min_len >= 1 expected, got %d' % min_len)
-    cap = decode_segments_cap(B, C, TL) if cap is None else int(cap)
-    if cap < 1 or cap >= (1 << 31):
-        raise RuntimeError('decode_segments: cap in [1, 2^31) expected, got %d' % cap)
-    dev = probs.device
-    for name, t in (('probs', probs), ('valid_t', valid_t), ('fps', fps), ('start', start), ('thr', thr)):
-        if torch.is_tensor(t) and (t.device.type != 'cuda' or t.device != dev):
-            raise RuntimeError('decode_segments: %s is on %s: device tensors on one GPU expected (there is no CPU path; '
-                               'cfn_hip.detections.decode_reference is the host spelling)' % (name, t.device))
-    if not torch.is_tensor(thr):
-        thr = torch.full((C,), float(thr), dtype=torch.float32, device=dev)
-    ws_bytes = decode_segments_workspace_bytes(B, C, TL)
-    if out is None:
-        out = (torch.empty(cap, 3, dtype=torch.float64, device=dev), torch.empty(cap, 3, dtype=torch.int32, device=dev),
-               torch.empty(cap, 2, dtype=torch.float32, device=dev), torch.empty(B + 1, dtype=torch.int32, device=dev),
-               torch.empty(1, dtype=torch.int32, device=dev), torch.empty(ws_bytes, dtype=torch.uint8, device=dev))
-    else:
-        out = tuple(out)
-        want = ((torch.float64, 3), (torch.int32, 3), (torch.float32, 2))
-        if len(out) != 6 or any(y.dtype != dt or y.dim() != 2 or y.shape[1] != w or y.shape[0] < cap or not y.is_contiguous()
-                                for y, (dt, w) in zip(out, want)) \
-                or out[3].dtype != torch.int32 or tuple(out[3].shape) != (B + 1,) or out[4].dtype != torch.int32 or tuple(out[4].shape) != (1,) \
-                or out[5].dtype != torch.uint8 or out[5].dim() != 1 or out[5].numel() < ws_bytes or out[5].data_ptr() % 8 \
-                or not (out[3].is_contiguous() and out[5].is_contiguous()):
-            raise RuntimeError('decode_segments: out: contiguous seg (>= %d, 3) fp64, frames (>= %d, 3) int32, score (>= %d, 2) fp32, offsets (%d,) '
-                               'int32, total (1,) int32 and an 8-byte aligned uint8 workspace of >= %d bytes expected, got %s'
-                               % (cap, cap, cap, B + 1, ws_bytes, [(y.dtype, tuple(y.shape)) for y in out]))
-    call('cfn_decode_segments', probs, valid_t.contiguous(), fps.contiguous(), start.contiguous(), thr.contiguous(), out[0], out[1], out[2], out[3],
+    what = 'decode_segments'
+    B, C, _, TL, valid_t, fps, start, thr, max_gap, min_len, cap, dev = _decode_arguments(what, probs, valid_t, fps, start, 'thr', thr, max_gap, min_len, cap)
+    out = _out_tuple(what, out, dev, _record_slots(cap) + [('offsets', torch.int32, (), B + 1, True), ('total', torch.int32, (), 1, True)],
+                     decode_segments_workspace_bytes(B, C, TL))
+    call('cfn_decode_segments', probs, valid_t, fps, start, thr, out[0], out[1], out[2], out[3],
          out[4], out[5], B, C, TL, max_gap, min_len, cap)
     return out[:5]
 
@@ -1779,53 +1815,11 @@ def decode_segments_levels(probs, valid_t, fps, start, levels, max_gap=0, min_le
     Three launches, nothing is read back (capturable with out=).  out: the six tensors and a uint8 workspace of
     decode_segments_levels_workspace_bytes(B, C, K, TL) bytes.  No gradient, no CPU path."""
     what = 'decode_segments_levels'
-    if not torch.is_tensor(probs) or probs.dtype != torch.float32 or probs.dim() != 3 or min(probs.shape) < 1 or not probs.is_contiguous():
-        raise RuntimeError('%s: probs: a contiguous (B, C, TL) float32 tensor expected, got %s %s'
-                           % (what, getattr(probs, 'dtype', type(probs).__name__), tuple(getattr(probs, 'shape', ()))))
-    B, C, TL = (int(s) for s in probs.shape)
-    if not torch.is_tensor(levels) or levels.dtype != torch.float32 or levels.dim() != 2 or int(levels.shape[0]) != C \
-            or not 1 <= int(levels.shape[1]) <= DECODE_MAX_LEVELS or not levels.is_contiguous():
-        raise RuntimeError('%s: levels: a contiguous (%d, K) float32 tensor with 1 <= K <= %d expected, got %s %s'
-                           % (what, C, DECODE_MAX_LEVELS, getattr(levels, 'dtype', type(levels).__name__), tuple(getattr(levels, 'shape', ()))))
-    K = int(levels.shape[1])
-    if TL > DECODE_MAX_TL or B > 65535 or C >= (1 << 19) or B * C * K * TL >= (1 << 31):
-        raise RuntimeError('%s: probs: B <= 65535, C < 2^19, TL <= %d and B * C * K * TL < 2^31 expected, got (%d, %d, %d) and K = %d'
-                           % (what, DECODE_MAX_TL, B, C, TL, K))
-    for name, t, dt in (('valid_t', valid_t, torch.int32), ('fps', fps, torch.float64), ('start', start, torch.int32)):
-        if not torch.is_tensor(t) or t.dtype != dt or tuple(t.shape) != (B,):
-            raise RuntimeError('%s: %s (%d,) %s expected, got %s %s' % (what, name, B, dt, getattr(t, 'dtype', type(t).__name__), tuple(getattr(t, 'shape', ()))))
-    max_gap, min_len = int(max_gap), int(min_len)
-    if max_gap < 0:
-        raise RuntimeError('%s: max_gap >= 0 expected, got %d' % (what, max_gap))
-    if min_len < 1:
-        raise RuntimeError('%s: min_len >= 1 expected, got %d' % (what, min_len))
-    cap = decode_segments_levels_cap(B, C, K, TL) if cap is None else int(cap)
-    if cap < 1 or cap >= (1 << 31):
-        raise RuntimeError('%s: cap in [1, 2^31) expected, got %d' % (what, cap))
-    dev = probs.device
-    for name, t in (('probs', probs), ('valid_t', valid_t), ('fps', fps), ('start', start), ('levels', levels)):
-        if t.device.type != 'cuda' or t.device != dev:
-            raise RuntimeError('%s: %s is on %s: device tensors on one GPU expected (there is no CPU path; '
-                               'cfn_hip.detections.decode_levels_reference is the host spelling)' % (what, name, t.device))
-    ws_bytes = decode_segments_levels_workspace_bytes(B, C, K, TL)
-    if out is None:
-        out = (torch.empty(cap, 3, dtype=torch.float64, device=dev), torch.empty(cap, 3, dtype=torch.int32, device=dev),
-               torch.empty(cap, 2, dtype=torch.float32, device=dev), torch.empty(cap, dtype=torch.uint8, device=dev),
-               torch.empty(B + 1, dtype=torch.int32, device=dev), torch.empty(1, dtype=torch.int32, device=dev),
-               torch.empty(ws_bytes, dtype=torch.uint8, device=dev))
-    else:
-        out = tuple(out)
-        want = ((torch.float64, 3), (torch.int32, 3), (torch.float32, 2))
-        if len(out) != 7 or any(y.dtype != dt or y.dim() != 2 or y.shape[1] != w or y.shape[0] < cap or not y.is_contiguous()
-                                for y, (dt, w) in zip(out, want)) \
-                or out[3].dtype != torch.uint8 or out[3].dim() != 1 or out[3].numel() < cap or not out[3].is_contiguous() \
-                or out[4].dtype != torch.int32 or tuple(out[4].shape) != (B + 1,) or out[5].dtype != torch.int32 or tuple(out[5].shape) != (1,) \
-                or out[6].dtype != torch.uint8 or out[6].dim() != 1 or out[6].numel() < ws_bytes or out[6].data_ptr() % 8 \
-                or not (out[4].is_contiguous() and out[6].is_contiguous()):
-            raise RuntimeError('%s: out: contiguous seg (>= %d, 3) fp64, frames (>= %d, 3) int32, score (>= %d, 2) fp32, level (>= %d,) uint8, offsets '
-                               '(%d,) int32, total (1,) int32 and an 8-byte aligned uint8 workspace of >= %d bytes expected, got %s'
-                               % (what, cap, cap, cap, cap, B + 1, ws_bytes, [(y.dtype, tuple(y.shape)) for y in out]))
-    call('cfn_decode_segments_levels', probs, valid_t.contiguous(), fps.contiguous(), start.contiguous(), levels, out[0], out[1], out[2], out[3],
+    B, C, K, TL, valid_t, fps, start, levels, max_gap, min_len, cap, dev = _decode_arguments(what, probs, valid_t, fps, start, 'levels', levels, max_gap,
+                                                                                             min_len, cap)
+    out = _out_tuple(what, out, dev, _record_slots(cap) + [('level', torch.uint8, (), cap, False), ('offsets', torch.int32, (), B + 1, True),
+                                                           ('total', torch.int32, (), 1, True)], decode_segments_levels_workspace_bytes(B, C, K, TL))
+    call('cfn_decode_segments_levels', probs, valid_t, fps, start, levels, out[0], out[1], out[2], out[3],
          out[4], out[5], out[6], B, C, K, TL, max_gap, min_len, cap)
     return out[:6]
 
@@ -1839,12 +1833,7 @@ def nms_segments_workspace_bytes(B, C, cap_in):
 
 def _nms_arguments(what, seg, frames, score, offsets, n_classes, score_col, cap_out, out, workspace_bytes):
     """the checks nms_segments and soft_nms_segments share -> (B, n_classes, score_col, cap_in, cap_out, out: the seven tensors and the workspace)"""
-    for name, t in (('seg', seg), ('frames', frames), ('score', score), ('offsets', offsets)):
-        if not torch.is_tensor(t) or t.device.type != 'cuda' or t.device != getattr(seg, 'device', None):
-            raise RuntimeError('%s: %s: device tensors on one GPU expected (there is no CPU path; cfn_hip.detections.%s is the host '
-                               'spelling), got %s' % (what, name, what.replace('_segments', '_reference'), getattr(t, 'device', type(t).__name__)))
-        if not t.is_contiguous():
-            raise RuntimeError('%s: %s must be contiguous' % (what, name))
+    dev = _one_gpu(what, 'cfn_hip.detections.' + what.replace('_segments', '_reference'), seg=seg, frames=frames, score=score, offsets=offsets)
     if seg.dtype != torch.float64 or seg.dim() != 2 or seg.shape[1] != 3 or seg.shape[0] < 1:
         raise RuntimeError('%s: seg: a (cap_in, 3) float64 tensor with cap_in >= 1 expected, got %s %s' % (what, seg.dtype, tuple(seg.shape)))
     cap_in = int(seg.shape[0])
@@ -1859,28 +1848,11 @@ def _nms_arguments(what, seg, frames, score, offsets, n_classes, score_col, cap_
     cap_out = cap_in if cap_out is None else int(cap_out)
     if cap_out < 1 or cap_out >= (1 << 31):
         raise RuntimeError('%s: cap_out in [1, 2^31) expected, got %d' % (what, cap_out))
-    dev = seg.device
-    ws_bytes = workspace_bytes(B, n_classes, cap_in)
-    if out is None:
-        out = (torch.empty(cap_out, 3, dtype=torch.float64, device=dev), torch.empty(cap_out, 3, dtype=torch.int32, device=dev),
-               torch.empty(cap_out, 2, dtype=torch.float32, device=dev), torch.empty(B + 1, dtype=torch.int32, device=dev),
-               torch.empty(1, dtype=torch.int32, device=dev), torch.empty(cap_in, dtype=torch.uint8, device=dev),
-               torch.empty(cap_out, dtype=torch.int32, device=dev), torch.empty(ws_bytes, dtype=torch.uint8, device=dev))
-    else:
-        out = tuple(out)
-        want = ((torch.float64, 3), (torch.int32, 3), (torch.float32, 2))
-        if len(out) != 8 or any(y.dtype != dt or y.dim() != 2 or y.shape[1] != w or y.shape[0] < cap_out or not y.is_contiguous()
-                                for y, (dt, w) in zip(out, want)) \
-                or out[3].dtype != torch.int32 or tuple(out[3].shape) != (B + 1,) or out[4].dtype != torch.int32 or tuple(out[4].shape) != (1,) \
-                or out[5].dtype != torch.uint8 or out[5].dim() != 1 or out[5].numel() < cap_in or not out[5].is_contiguous() \
-                or out[6].dtype != torch.int32 or out[6].dim() != 1 or out[6].numel() < cap_out or not out[6].is_contiguous() \
-                or out[7].dtype != torch.uint8 or out[7].dim() != 1 or out[7].numel() < ws_bytes or out[7].data_ptr() % 8 \
-                or not (out[3].is_contiguous() and out[7].is_contiguous()) \
-                or any(y.data_ptr() == x.data_ptr() for y, x in zip(out[:3], (seg, frames, score))):
-            raise RuntimeError('%s: out: contiguous seg (>= %d, 3) fp64, frames (>= %d, 3) int32, score (>= %d, 2) fp32 (none of them an input), offsets '
-                               '(%d,) int32, total (1,) int32, keep (>= %d,) uint8, src (>= %d,) int32 and an 8-byte aligned uint8 workspace of >= %d '
-                               'bytes expected, got %s' % (what, cap_out, cap_out, cap_out, B + 1, cap_in, cap_out, ws_bytes,
-                                                           [(y.dtype, tuple(y.shape)) for y in out]))
+    out = _out_tuple(what, out, dev, _record_slots(cap_out) + [('offsets', torch.int32, (), B + 1, True), ('total', torch.int32, (), 1, True),
+                                                               ('keep', torch.uint8, (), cap_in, False), ('src', torch.int32, (), cap_out, False)],
+                     workspace_bytes(B, n_classes, cap_in))
+    if any(y.data_ptr() == x.data_ptr() for y, x in zip(out[:3], (seg, frames, score))):
+        raise RuntimeError('%s: out: seg, frames and score must not be the inputs' % what)
     return B, n_classes, score_col, cap_in, cap_out, out
 
 
@@ -1956,15 +1928,7 @@ def segap_workspace_bytes(B, C, det_cap, n_seg):
 
 
 def _segap_dev(what, **tensors):
-    dev = None
-    for name, t in tensors.items():
-        if not torch.is_tensor(t) or t.device.type != 'cuda' or (dev is not None and t.device != dev):
-            raise RuntimeError('%s: %s: device tensors on one GPU expected (there is no CPU path; cfn_hip.segap.match_reference / ap_reference '
-                               'are the host spelling), got %s' % (what, name, getattr(t, 'device', type(t).__name__)))
-        if not t.is_contiguous():
-            raise RuntimeError('%s: %s must be contiguous' % (what, name))
-        dev = t.device
-    return dev
+    return _one_gpu(what, 'cfn_hip.segap.match_reference / ap_reference', **tensors)
 
 
 def segap_match(det_seg, det_score, det_offsets, seg, offsets, fps, window, tiou, n_classes, t_max, score_col=0, want_match=True, out=None):

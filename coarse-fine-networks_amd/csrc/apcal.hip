@@ -230,8 +230,7 @@ extern "C" int cfn_ap_calibrate(const float* sorted_scores, const unsigned char*
     CfnProfScope prof(CFN_K_ELEMWISE, st, 0.0);                            // (the row count is on the device: tools/calibrate_bench.py states the bytes)
     hipLaunchKernelGGL(ap_calibrate_kernel, dim3((unsigned)C), dim3(AP_CTHREADS), 0, st, sorted_scores, sorted_targets, count, kinds, values, thr, cut,
                        tp, ok, stat, K, cap);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? CFN_OK : cfn_fail(CFN_ERR_LAUNCH, "ap_calibrate: %s", hipGetErrorString(e));
+    return cfn_launch_ok("ap_calibrate");
 }
 
 extern "C" int cfn_ap_calibrate_tile(void) { return AP_CTILE; }

@@ -31,11 +31,6 @@
 
 typedef unsigned __attribute__((ext_vector_type(4))) apu4;
 
-static int ap_launch_ok(const char* what) {       // (no accumulation records to commit: these kernels need nothing from the deterministic mode)
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? CFN_OK : cfn_fail(CFN_ERR_LAUNCH, "%s: %s", what, hipGetErrorString(e));
-}
-
 // -----------------------------------------------------------------------------------------------------------------------------------------
 // append
 // -----------------------------------------------------------------------------------------------------------------------------------------
@@ -80,7 +75,7 @@ extern "C" int cfn_ap_append(const float* probs, const float* labels, const int*
     hipLaunchKernelGGL(ap_append_kernel, dim3((unsigned)cfn_cdiv(TL, 256), (unsigned)K, (unsigned)B), dim3(256), 0, st, probs, labels, valid, scores,
                        targets, (const int*)count, flags, B, K, TL, cap);
     hipLaunchKernelGGL(ap_advance_kernel, dim3(1), dim3(1), 0, st, valid, count, flags, B, TL, cap);
-    return ap_launch_ok("ap_append");
+    return cfn_launch_ok("ap_append");
 }
 
 // -----------------------------------------------------------------------------------------------------------------------------------------
@@ -241,7 +236,7 @@ extern "C" int cfn_ap_sort(const float* scores, const unsigned char* targets, co
     CfnProfScope prof(CFN_K_ELEMWISE, st, 0.0);                            // (the row count is on the device: tools/ap_meter_bench.py states the bytes)
     hipLaunchKernelGGL(ap_sort_kernel, dim3((unsigned)K), dim3(AP_THREADS), 0, st, scores, targets, count, sorted_scores, sorted_targets, tmp_keys,
                        tmp_targets, cap, 0);
-    return ap_launch_ok("ap_sort");
+    return cfn_launch_ok("ap_sort");
 }
 
 // cfn_ap_sort with one count per class: counts (K) int32 (the stores of cfn_segap_append)
@@ -254,7 +249,7 @@ extern "C" int cfn_ap_sort_counts(const float* scores, const unsigned char* targ
     CfnProfScope prof(CFN_K_ELEMWISE, st, 0.0);
     hipLaunchKernelGGL(ap_sort_kernel, dim3((unsigned)K), dim3(AP_THREADS), 0, st, scores, targets, counts, sorted_scores, sorted_targets, tmp_keys,
                        tmp_targets, cap, 1);
-    return ap_launch_ok("ap_sort_counts");
+    return cfn_launch_ok("ap_sort_counts");
 }
 
 extern "C" int cfn_ap_sort_tile(void) { return AP_TILE; }
@@ -329,5 +324,5 @@ extern "C" int cfn_ap_reduce(const unsigned char* sorted_targets, const int* cou
     hipStream_t st = (hipStream_t)stream;
     CfnProfScope prof(CFN_K_ELEMWISE, st, 0.0);
     hipLaunchKernelGGL(ap_reduce_kernel, dim3((unsigned)K), dim3(AP_THREADS), 0, st, sorted_targets, count, ap, cap);
-    return ap_launch_ok("ap_reduce");
+    return cfn_launch_ok("ap_reduce");
 }

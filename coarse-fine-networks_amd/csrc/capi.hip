@@ -22,9 +22,14 @@ int cfn_fail(int code, const char* fmt, ...) {
 static int cfn_det_flush(const char* what);
 static bool g_det_on = false;
 
+int cfn_launch_ok(const char* what) {
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? CFN_OK : cfn_fail(CFN_ERR_LAUNCH, "%s: %s", what, hipGetErrorString(e));
+}
+
 int cfn_check_launch(const char* what) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return cfn_fail(CFN_ERR_LAUNCH, "%s: %s", what, hipGetErrorString(e));
+    const int bad = cfn_launch_ok(what);
+    if (bad) return bad;
     if (g_det_on) return cfn_det_flush(what);
     return CFN_OK;
 }

@@ -15,7 +15,9 @@ enum { CFN_ACT_NONE = 0, CFN_ACT_RELU = 1, CFN_ACT_SWISH = 2, CFN_ACT_SIGMOID = 
 
 extern "C" const char* cfn_last_error(void);
 int cfn_fail(int code, const char* fmt, ...);  // records the message, returns code
-int cfn_check_launch(const char* what);        // hipGetLastError -> CFN_ERR_LAUNCH
+int cfn_check_launch(const char* what);        // hipGetLastError -> CFN_ERR_LAUNCH; in deterministic mode, commits the accumulation records
+int cfn_launch_ok(const char* what);           // hipGetLastError -> CFN_ERR_LAUNCH alone: for entry points whose kernels accumulate nothing across
+                                               // workgroups (the AP meters), so the deterministic mode has nothing to commit and they stay capturable
 
 #define CFN_REQUIRE(cond, ...) \
     do { if (!(cond)) return cfn_fail(CFN_ERR_ARG, __VA_ARGS__); } while (0)

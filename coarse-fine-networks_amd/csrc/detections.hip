@@ -18,7 +18,8 @@
 //           workspace.  A row without an active frame ends here.  Otherwise det_plan() marks run starts and ends per word (gap closing looks
 //           at most max_gap / 64 + 1 words back / ahead and stops at the first word with a bit), scans the end counts, finds each start's end
 //           (same word, or a binary search in the scanned counts) for min_len, and the row's count of kept runs goes to the workspace.
-//   scan    one workgroup turns the B * C counts into row bases (in place), offsets[b] and total.
+//   scan    one workgroup turns the B * C counts into row bases (in place), offsets[b] and total (seg_launch_scan of seg_common.h: NMS and
+//           Soft-NMS launch the same kernel, which is defined here).
 //   write   a row with a non-zero count loads its mask from the workspace, repeats det_plan(), scans the kept starts, and its waves take the
 //           kept runs in turn: 64 frames per step, only active frames are read again, wave reductions (fp64 butterfly: a fixed order),
 //           lane 0 stores the record at base + rank if that is < cap.
@@ -29,7 +30,7 @@
 // (b, c, k): it reads probs row / K against levels[row % (C * K)] (levels (C, K), row c = class c's thresholds in the caller's order), the
 // scan's offsets boundary sits at C * K, and the write stores c in seg and k in level (cap) uint8.  Output order (b, c, k, t0);
 // cfn_decode_segments is K = 1 without the level column: its results and its workspace are what they were.
-#include "cfn_common.h"
+#include "seg_common.h"
 
 #define DS_THREADS 256
 #define DS_PASS 1024                 // frames per pass of a workgroup (4 waves x 64 lanes x 4 frames)
@@ -51,28 +52,6 @@ __device__ __forceinline__ ds_u64 ds_spread16(ds_u64 x) {
 __device__ __forceinline__ ds_u64 ds_uni(ds_u64 v) {
     const unsigned lo = cfn_uni((unsigned)v), hi = cfn_uni((unsigned)(v >> 32));
     return ((ds_u64)hi << 32) | lo;
-}
-
-// exclusive scan of one int per thread over the workgroup (wave scans + the four wave totals in LDS); total = the sum
-__device__ __forceinline__ int ds_block_scan(int v, int* s_wave, int& total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    int inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int o = __shfl_up(inc, d, 64);
-        if (lane >= d) inc += o;
-    }
-    __syncthreads();                                                       // (s_wave may still be read from the scan before)
-    if (lane == 63) s_wave[wave] = inc;
-    __syncthreads();
-    int before = 0, sum = 0;
-    for (int i = 0; i < nw; ++i) {
-        const int x = s_wave[i];
-        if (i < wave) before += x;
-        sum += x;
-    }
-    total = sum;
-    return before + inc - v;
 }
 
 struct DsRow {                       // the row's words in LDS: masks [nwords], exclusive counts [nwords + 1]
@@ -153,7 +132,7 @@ __device__ __forceinline__ int ds_plan(const DsRow& r, int nwords, int max_gap, 
         n_end += __builtin_popcountll(e);
     }
     int total;
-    int run = ds_block_scan(n_end, s_wave, total);
+    int run = seg_block_scan(n_end, s_wave, total);
     if (threadIdx.x == 0) r.PE[0] = 0;
     for (int w = w_lo; w < w_hi; ++w) {
         run += __builtin_popcountll(r.E[w]);
@@ -233,21 +212,22 @@ __global__ __launch_bounds__(DS_THREADS) void det_count_kernel(const float* __re
     const int w_lo = min(tid * wpt, nwords), w_hi = min(w_lo + wpt, nwords);
     const int n_keep = ds_plan(r, nwords, max_gap, min_len, s_wave, w_lo, w_hi);
     int total;
-    ds_block_scan(n_keep, s_wave, total);
+    seg_block_scan(n_keep, s_wave, total);
     if (tid == 0) counts[row] = total;
 }
 
-// counts[0 .. n) -> exclusive sums in place, counts[n] = total; offsets[b] = sum of the rows of samples < b; one workgroup
-__global__ __launch_bounds__(1024) void det_scan_kernel(int* __restrict__ counts, int* __restrict__ offsets, int* __restrict__ total_out, long n, int B,
-                                                        int C) {
+// seg_launch_scan of seg_common.h: counts[0 .. n), clamped to [0, count_max], -> exclusive sums in place, counts[n] = total;
+// offsets[b] = the sum of the rows of samples < b; one workgroup
+__global__ __launch_bounds__(1024) void seg_scan_kernel(int* __restrict__ counts, int* __restrict__ offsets, int* __restrict__ total_out, long n, int B,
+                                                        int C, long count_max) {
     __shared__ int s_wave[16];
     const int tid = threadIdx.x;
     int carry = 0;
     for (long i0 = 0; i0 < n; i0 += 1024) {
         const long i = i0 + tid;
-        const int v = i < n ? counts[i] : 0;
+        const int v = i < n ? (int)seg_clampl(counts[i], 0, count_max) : 0;
         int total;
-        const int ex = carry + ds_block_scan(v, s_wave, total);
+        const int ex = carry + seg_block_scan(v, s_wave, total);
         if (i < n) {
             counts[i] = ex;
             if (i % C == 0) offsets[i / C] = ex;
@@ -259,6 +239,10 @@ __global__ __launch_bounds__(1024) void det_scan_kernel(int* __restrict__ counts
         offsets[B] = carry;
         total_out[0] = carry;
     }
+}
+
+void seg_launch_scan(int* counts, int* offsets, int* total, long n, int B, int C, long count_max, hipStream_t st) {
+    hipLaunchKernelGGL(seg_scan_kernel, dim3(1), dim3(1024), 0, st, counts, offsets, total, n, B, C, count_max);
 }
 
 __global__ __launch_bounds__(DS_THREADS) void det_write_kernel(const float* __restrict__ probs, const double* __restrict__ fps, const int* __restrict__ start,
@@ -281,7 +265,7 @@ __global__ __launch_bounds__(DS_THREADS) void det_write_kernel(const float* __re
     const int w_lo = min(tid * wpt, nwords), w_hi = min(w_lo + wpt, nwords);
     const int n_keep = ds_plan(r, nwords, max_gap, min_len, s_wave, w_lo, w_hi);
     int total;
-    int run = ds_block_scan(n_keep, s_wave, total);
+    int run = seg_block_scan(n_keep, s_wave, total);
     for (int w = w_lo; w < w_hi; ++w) {
         r.PK[w] = run;
         run += __builtin_popcountll(r.K[w]);
@@ -372,7 +356,7 @@ static int ds_decode(const char* what, const float* probs, const int* valid_t, c
     CfnProfScope prof(CFN_K_ELEMWISE, st, (double)rows * TL * 4.0);
     if (vec) hipLaunchKernelGGL(det_count_kernel<true>, dim3((unsigned)rows), dim3(DS_THREADS), lds, st, probs, valid_t, thr, masks, counts, C, K, TL, nwords, max_gap, min_len);
     else hipLaunchKernelGGL(det_count_kernel<false>, dim3((unsigned)rows), dim3(DS_THREADS), lds, st, probs, valid_t, thr, masks, counts, C, K, TL, nwords, max_gap, min_len);
-    hipLaunchKernelGGL(det_scan_kernel, dim3(1), dim3(1024), 0, st, counts, offsets, total, rows, B, C * K);
+    seg_launch_scan(counts, offsets, total, rows, B, C * K, 0x7fffffffL, st);                    // (det_count_kernel's counts are in [0, 32768] already)
     hipLaunchKernelGGL(det_write_kernel, dim3((unsigned)rows), dim3(DS_THREADS), lds, st, probs, fps, start, (const ds_u64*)masks, (const int*)counts, seg, frames, score, level,
                        C, K, TL, nwords, max_gap, min_len, cap);
     return cfn_check_launch(what);

@@ -6,8 +6,9 @@
 //      w1 = ((double)(window[b,0] + n) - 0.5) / fps[b];  s' = s > w0 ? s : w0,  e' = e < w1 ? e : w1 (max / min; a NaN bound gives way to the
 //      window's).  A row PARTICIPATES iff n > 0, its class is an integer of [0, C) and e' > s'.  n_gt[c] counts participating rows.
 //   2. tIoU of a detection (sd, ed) and a clipped row (s', e'): inter = min(ed, e') - max(sd, s'); 0 unless inter > 0, otherwise
-//      inter / ((ed - sd) + (e' - s') - inter).  Plain IEEE fp64, no product (nothing can contract), ONE division.
-//   3. within a (video, class) group the detections are taken by score[:, score_col] descending (fp32), ties by row index ascending.
+//      inter / ((ed - sd) + (e' - s') - inter).  Plain IEEE fp64, no product (nothing can contract), ONE division (seg_tiou of seg_common.h).
+//   3. within a (video, class) group the detections are taken by score[:, score_col] descending (fp32), ties by row index ascending
+//      (seg_rank of seg_common.h on the raw scores: see there for NaN).
 //   4. greedy matching, independently per threshold k: a detection takes the participating row of its group that is not used up at k and has
 //      the largest tIoU among those with tIoU >= tiou[k] (and > 0); ties go to the lowest row index.  It is then a true positive at k and
 //      the row is used up at k; otherwise it is a false positive at k.
@@ -21,7 +22,7 @@
 // Launches, ordered by the stream alone (no atomics except one flag bit, no allocation, no synchronisation, no floating-point accumulation
 // across workgroups):
 //   match    one wave per (video, class) group.  The group's detections are a contiguous range of the video's rows (decode orders by
-//            (b, c, t0)): two binary searches on the class column.  Lanes hold the video's ground-truth rows, SA_GT_TILE = 64 at a time;
+//            (b, c, t0)): two binary searches on the class column (seg_group of seg_common.h).  Lanes hold the video's ground-truth rows, SA_GT_TILE = 64 at a time;
 //            a lane computes the tIoU of its row ONCE per detection for all thresholds, a ballot finds the candidates at k (none: a false
 //            positive; one: the match), a wave argmax on (tIoU, lane) otherwise.  A video of at most one tile keeps its rows and the byte of
 //            used-up thresholds in registers; a larger one (the general path) walks its tiles per detection, carries the best (tIoU, row)
@@ -34,7 +35,7 @@
 //   reduce   grid (C, n_thr): the walk of cfn_ap_reduce over bit k of the sorted bytes, divided by n_gt[c]; then one wave for map.
 // Everything but B, C, t_max, n_thr, score_col and the capacities is DATA read on the device: offsets, counts and orders are clamped, so a
 // bad batch gives wrong values, never a store outside the outputs.
-#include "cfn_common.h"
+#include "seg_common.h"
 
 #define SA_FLAG_OVERFLOW 2
 #define SA_GT_TILE 64
@@ -43,11 +44,6 @@
 #define SA_RTHREADS 256
 #define SA_RPT 16
 #define SA_RTILE (SA_RTHREADS * SA_RPT)
-
-static int sa_launch_ok(const char* what) {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? CFN_OK : cfn_fail(CFN_ERR_LAUNCH, "%s: %s", what, hipGetErrorString(e));
-}
 
 // workspace: int32 dstart, dcount, gcount, base [B * C] each, fit [2], order [det_cap]; then n_seg bytes
 struct SaWs { int *dstart, *dcount, *gcount, *base, *fit, *order; unsigned char* used; };
@@ -60,17 +56,6 @@ static inline SaWs sa_carve(void* ws, long groups, long det_cap) {
     return w;
 }
 
-__device__ __forceinline__ long sa_clampl(long v, long lo, long hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
-// first row i of [lo, hi) whose class is not below key (all lanes walk the same way; at most 32 steps whatever the data)
-__device__ __forceinline__ long sa_lower(const double* __restrict__ seg, long lo, long hi, double key) {
-    while (lo < hi) {
-        const long mid = (lo + hi) >> 1;
-        if (seg[3 * mid] < key) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
 // rule 1 for row g: the clipped bounds; true iff the row participates in class cd
 __device__ __forceinline__ bool sa_gt_row(const double* __restrict__ gseg, long g, long g1, double cd, int n, double w0, double w1, double& sp,
                                           double& ep) {
@@ -80,13 +65,6 @@ __device__ __forceinline__ bool sa_gt_row(const double* __restrict__ gseg, long 
     sp = s > w0 ? s : w0;
     ep = e < w1 ? e : w1;
     return n > 0 && cls == cd && ep > sp;
-}
-
-// rule 2
-__device__ __forceinline__ double sa_tiou(double sd, double ed, double sp, double ep) {
-    const double inter = (ed < ep ? ed : ep) - (sd > sp ? sd : sp);
-    if (!(inter > 0.0)) return 0.0;
-    return inter / ((ed - sd) + (ep - sp) - inter);
 }
 
 // the candidate lane with the largest v, the lowest such lane on a tie; at least one lane is a candidate.  Every lane gets (lane, value).
@@ -118,15 +96,12 @@ __global__ __launch_bounds__(64) void segap_match_kernel(const double* __restric
     const double cd = (double)c;
 
     // the group's detections: rows [d0, d1) of the video's range
-    const long o0 = sa_clampl(doff[b], 0, dcap);
-    const long o1 = sa_clampl(doff[b + 1], o0, dcap);
-    const long d0 = sa_lower(dseg, o0, o1, cd);
-    const long d1 = sa_lower(dseg, d0, o1, cd + 1.0);
-    const int nd = (int)(d1 - d0);
+    int nd;
+    const long d0 = seg_group(dseg, doff, b, c, dcap, nd);
 
     // the video's ground truth and window (rule 1)
-    const long g0 = sa_clampl(goff[b], 0, S);
-    const long g1 = sa_clampl(goff[b + 1], g0, S);
+    const long g0 = seg_clampl(goff[b], 0, S);
+    const long g1 = seg_clampl(goff[b + 1], g0, S);
     const bool one = g1 - g0 <= SA_GT_TILE;
     const long wfirst = window[2 * b];
     const int n = min(max(window[2 * b + 1], 0), t_max);
@@ -161,26 +136,10 @@ __global__ __launch_bounds__(64) void segap_match_kernel(const double* __restric
     if (small) {
         for (int i = lane; i < nd; i += 64) s_score[i] = dscore[2 * (d0 + i) + score_col];
         __syncthreads();
-        for (int i = lane; i < nd; i += 64) {
-            const float si = s_score[i];
-            int r = 0;
-            for (int j = 0; j < nd; ++j) {
-                const float sj = s_score[j];
-                r += (sj > si || (sj == si && j < i)) ? 1 : 0;
-            }
-            s_order[r] = i;                                                // (r < nd: at most nd - 1 rows are in front of one)
-        }
+        for (int i = lane; i < nd; i += 64) s_order[seg_rank([&](int j) { return s_score[j]; }, i, nd)] = i;
         __syncthreads();
     } else {
-        for (int i = lane; i < nd; i += 64) {
-            const float si = dscore[2 * (d0 + i) + score_col];
-            int r = 0;
-            for (int j = 0; j < nd; ++j) {
-                const float sj = dscore[2 * (d0 + j) + score_col];
-                r += (sj > si || (sj == si && j < i)) ? 1 : 0;
-            }
-            order[r] = i;
-        }
+        for (int i = lane; i < nd; i += 64) order[seg_rank([&](int j) { return dscore[2 * (d0 + j) + score_col]; }, i, nd)] = i;
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");                 // the other lanes' ranks are read back through memory
         __syncthreads();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
@@ -198,7 +157,7 @@ __global__ __launch_bounds__(64) void segap_match_kernel(const double* __restric
             const int i = cfn_uni(min(max(order[r], 0), nd - 1));          // (NaN scores may leave a rank empty: any row of the group then)
             const long di = d0 + i;
             const double sd = dseg[3 * di + 1], ed = dseg[3 * di + 2];
-            const double v = part ? sa_tiou(sd, ed, sp, ep) : 0.0;
+            const double v = part ? seg_tiou(sd, ed, sp, ep) : 0.0;
             unsigned tpb = 0u;
             int mine = -1;                                                 // lane k: the match at threshold k
 #pragma unroll
@@ -232,7 +191,7 @@ __global__ __launch_bounds__(64) void segap_match_kernel(const double* __restric
         for (long t0 = g0; t0 < g1; t0 += SA_GT_TILE) {
             double sp, ep;
             const bool part = sa_gt_row(gseg, t0 + lane, g1, cd, n, w0, w1, sp, ep);
-            const double v = part ? sa_tiou(sd, ed, sp, ep) : 0.0;
+            const double v = part ? seg_tiou(sd, ed, sp, ep) : 0.0;
             const unsigned used = part ? ws_used[t0 + lane] : 0u;
 #pragma unroll
             for (int k = 0; k < SA_MAX_THR; ++k) {
@@ -268,8 +227,8 @@ __global__ __launch_bounds__(1024) void segap_plan_kernel(const int* __restrict_
     const int tid = threadIdx.x;
     int over = 0;
     for (int c = tid; c < C; c += 1024) {
-        long total = sa_clampl(counts[c], 0, cap);
-        for (int b = 0; b < B; ++b) total += sa_clampl(ws_dcount[(long)b * C + c], 0, dcap);
+        long total = seg_clampl(counts[c], 0, cap);
+        for (int b = 0; b < B; ++b) total += seg_clampl(ws_dcount[(long)b * C + c], 0, dcap);
         if (total > cap) over = 1;
     }
     over = __syncthreads_or(over);                                         // (also: every count has been read before one is advanced)
@@ -279,10 +238,10 @@ __global__ __launch_bounds__(1024) void segap_plan_kernel(const int* __restrict_
     }
     if (over) return;
     for (int c = tid; c < C; c += 1024) {
-        long run = sa_clampl(counts[c], 0, cap), gt = 0;
+        long run = seg_clampl(counts[c], 0, cap), gt = 0;
         for (int b = 0; b < B; ++b) {
             ws_base[(long)b * C + c] = (int)run;
-            run += sa_clampl(ws_dcount[(long)b * C + c], 0, dcap);
+            run += seg_clampl(ws_dcount[(long)b * C + c], 0, dcap);
             gt += max(ws_gcount[(long)b * C + c], 0);
         }
         counts[c] = (int)run;
@@ -298,9 +257,9 @@ __global__ __launch_bounds__(64) void segap_copy_kernel(const float* __restrict_
     if (ws_fit[0] != 1) return;
     const long grp = blockIdx.x;
     const int c = (int)(grp % C);
-    const long d0 = sa_clampl(ws_dstart[grp], 0, dcap);
-    const long nd = sa_clampl(ws_dcount[grp], 0, dcap - d0);
-    const long base = sa_clampl(ws_base[grp], 0, cap);
+    const long d0 = seg_clampl(ws_dstart[grp], 0, dcap);
+    const long nd = seg_clampl(ws_dcount[grp], 0, dcap - d0);
+    const long base = seg_clampl(ws_base[grp], 0, cap);
     for (long i = threadIdx.x; i < nd && base + i < cap; i += 64) {
         const long dst = (long)c * cap + base + i;
         scores[dst] = dscore[2 * (d0 + i) + score_col];
@@ -317,7 +276,7 @@ __global__ __launch_bounds__(SA_RTHREADS) void segap_reduce_kernel(const unsigne
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int c = blockIdx.x, k = blockIdx.y;
     const unsigned char* tg = sorted_tps + (long)c * cap;
-    const long n = sa_clampl(counts[c], 0, cap);
+    const long n = seg_clampl(counts[c], 0, cap);
     unsigned seen = 0u;
     double acc = 0.0;
     for (long base = 0; base < n; base += SA_RTILE) {
@@ -404,7 +363,7 @@ extern "C" int cfn_segap_match(const double* det_seg, const float* det_score, co
     CfnProfScope prof(CFN_K_ELEMWISE, st, 0.0);
     hipLaunchKernelGGL(segap_match_kernel, dim3((unsigned)groups), dim3(64), 0, st, det_seg, det_score, det_offsets, seg, offsets, fps, window, tiou, tp,
                        match, w.dstart, w.dcount, w.gcount, w.order, w.used, C, t_max, n_thr, score_col, det_cap, n_seg);
-    return sa_launch_ok(what);
+    return cfn_launch_ok(what);
 }
 
 extern "C" int cfn_segap_append(const float* det_score, const unsigned char* tp, void* workspace, float* scores, unsigned char* tps, int* counts,
@@ -423,7 +382,7 @@ extern "C" int cfn_segap_append(const float* det_score, const unsigned char* tp,
                        det_cap, cap);
     hipLaunchKernelGGL(segap_copy_kernel, dim3((unsigned)groups), dim3(64), 0, st, det_score, tp, (const int*)w.dstart, (const int*)w.dcount,
                        (const int*)w.base, (const int*)w.fit, scores, tps, C, score_col, det_cap, cap);
-    return sa_launch_ok(what);
+    return cfn_launch_ok(what);
 }
 
 extern "C" int cfn_segap_reduce(const unsigned char* sorted_tps, const int* counts, const int* n_gt, float* ap, float* map, int C, int n_thr, long cap,
@@ -436,5 +395,5 @@ extern "C" int cfn_segap_reduce(const unsigned char* sorted_tps, const int* coun
     CfnProfScope prof(CFN_K_ELEMWISE, st, 0.0);
     hipLaunchKernelGGL(segap_reduce_kernel, dim3((unsigned)C, (unsigned)n_thr), dim3(SA_RTHREADS), 0, st, sorted_tps, counts, n_gt, ap, C, cap);
     hipLaunchKernelGGL(segap_map_kernel, dim3(1), dim3(64), 0, st, (const float*)ap, n_gt, map, C, n_thr);
-    return sa_launch_ok(what);
+    return cfn_launch_ok(what);
 }

@@ -2,11 +2,11 @@
 // (csrc/detections.hip, cfn_decode_segments_levels) and the writer / the segment-AP meter.  The rules (cfn_hip/detections.py spells the same):
 //
 //   N1. groups are (video, class) row ranges: the rows offsets[b] .. offsets[b + 1] (clamped to [0, cap_in]) whose class column is c, found by
-//       two binary searches on the class column as segap_match_kernel finds them (the class column does not decrease inside a video).
+//       two binary searches on the class column (seg_group of seg_common.h; the class column does not decrease inside a video).
 //   N2. order inside a group: score[:, score_col] descending (fp32), ties by row index ascending (segap.py rule 3).  A NaN score ranks as
-//       -inf, so the ranks are a permutation of the group whatever the data.
+//       -inf, so the ranks are a permutation of the group whatever the data (seg_nan_low and seg_rank of seg_common.h).
 //   N3. tIoU of (s0, e0) and (s1, e1): inter = min(e0, e1) - max(s0, s1); 0 unless inter > 0, otherwise inter / ((e0 - s0) + (e1 - s1) - inter):
-//       plain IEEE fp64, no product, ONE division (segap.py rule 2).
+//       plain IEEE fp64, no product, ONE division (segap.py rule 2; seg_tiou of seg_common.h).
 //   N4. greedy: walk the group in the order of N2; a candidate is KEPT iff no candidate kept before it has tIoU with it > nms_thr (strict).  A
 //       suppressed candidate suppresses nothing.
 //   N5. the output is a stable compaction: kept rows in their input order, seg / frames / score copied bit for bit; offsets and total are the
@@ -14,73 +14,20 @@
 //   N6. keep (cap_in) uint8 (written for the rows of the batch's groups only) and src (cap_out) int32 = the input row of each output row.
 //
 // Three launches, ordered by the stream alone; no atomics, no allocation, nothing is read back:
-//   select   one wave per group.  Rank by counting (O(nd^2 / 64), as segap_match_kernel).  The walk: the candidate at rank r is skipped if its
+//   select   one wave per group.  Rank by counting (O(nd^2 / 64), seg_rank).  The walk: the candidate at rank r is skipped if its
 //            suppressed flag is set; otherwise it is kept and the lanes take the ranks above r, 64 at a time in tiles aligned to 64, and set
 //            the flag where the tIoU is above nms_thr: O(kept * nd / 64).  The flag of rank j belongs to lane j & 63 and to no other: a lane
 //            reads back only what it wrote itself, the flag of rank r reaches the wave through a ballot.  Up to NMS_DET_TILE = 1024 candidates
 //            the start / end (in rank order), the scores and the order live in LDS and the flags in one register per lane (16 bits); a larger
 //            group (the general path) keeps its order and its flag bytes in the workspace: the ORDER is written by one lane and read by
-//            others, so it passes the release / acquire fence of segap_match_kernel; the flags stay lane-owned.
-//   scan     one workgroup: the groups' kept counts -> bases in place, offsets[b], total (the scheme of det_scan_kernel).
+//            others, so it passes a release / acquire fence pair around the barrier (see seg_rank); the flags stay lane-owned.
+//   scan     one workgroup: the groups' kept counts -> bases in place, offsets[b], total (seg_launch_scan of seg_common.h).
 //   write    one wave per group: 64 rows at a time, a kept row goes to base + the number of kept rows in front of it (ballot / popcount).
 // offsets, classes, ranks and counts are DATA: every index is clamped, so a bad batch gives wrong values, never a store outside the outputs.
-#include "cfn_common.h"
+#include "seg_common.h"
 
 #define NMS_DET_TILE 1024
 #define NMS_FLAG_WORDS (NMS_DET_TILE / 64)
-
-__device__ __forceinline__ long nms_clampl(long v, long lo, long hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
-// first row i of [lo, hi) whose class is not below key (all lanes walk the same way; at most 32 steps whatever the data)
-__device__ __forceinline__ long nms_lower(const double* __restrict__ seg, long lo, long hi, double key) {
-    while (lo < hi) {
-        const long mid = (lo + hi) >> 1;
-        if (seg[3 * mid] < key) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
-// rule N1: the rows [d0, d0 + nd) of group (b, c)
-__device__ __forceinline__ long nms_group(const double* __restrict__ seg, const int* __restrict__ offsets, int b, int c, long cap_in, int& nd) {
-    const long o0 = nms_clampl(offsets[b], 0, cap_in);
-    const long o1 = nms_clampl(offsets[b + 1], o0, cap_in);
-    const long d0 = nms_lower(seg, o0, o1, (double)c);
-    const long d1 = nms_lower(seg, d0, o1, (double)c + 1.0);
-    nd = (int)(d1 - d0);
-    return d0;
-}
-
-// rule N3
-__device__ __forceinline__ double nms_tiou(double s0, double e0, double s1, double e1) {
-    const double inter = (e0 < e1 ? e0 : e1) - (s0 > s1 ? s0 : s1);
-    if (!(inter > 0.0)) return 0.0;
-    return inter / ((e0 - s0) + (e1 - s1) - inter);
-}
-
-// rule N2's key: a NaN ranks as -inf
-__device__ __forceinline__ float nms_key(float s) { return s != s ? -INFINITY : s; }
-
-// exclusive scan of one int per thread over a workgroup of 1024 (wave scans + the wave totals in LDS); total = the sum
-__device__ __forceinline__ int nms_block_scan(int v, int* s_wave, int& total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    int inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int o = __shfl_up(inc, d, 64);
-        if (lane >= d) inc += o;
-    }
-    __syncthreads();                                                       // (s_wave may still be read from the scan before)
-    if (lane == 63) s_wave[wave] = inc;
-    __syncthreads();
-    int before = 0, sum = 0;
-    for (int i = 0; i < nw; ++i) {
-        const int x = s_wave[i];
-        if (i < wave) before += x;
-        sum += x;
-    }
-    total = sum;
-    return before + inc - v;
-}
 
 // grid (B * C), one wave each
 __global__ __launch_bounds__(64) void nms_select_kernel(const double* __restrict__ seg, const float* __restrict__ score, const int* __restrict__ offsets,
@@ -94,23 +41,17 @@ __global__ __launch_bounds__(64) void nms_select_kernel(const double* __restrict
     const long grp = blockIdx.x;
     const int b = (int)(grp / C), c = (int)(grp - (long)b * C);
     int nd;
-    const long d0 = nms_group(seg, offsets, b, c, cap_in, nd);
+    const long d0 = seg_group(seg, offsets, b, c, cap_in, nd);
     if (nd <= 0) {
         if (lane == 0) counts[grp] = 0;
         return;
     }
 
     if (nd <= NMS_DET_TILE) {
-        for (int i = lane; i < nd; i += 64) s_key[i] = nms_key(score[2 * (d0 + i) + score_col]);
+        for (int i = lane; i < nd; i += 64) s_key[i] = seg_nan_low(score[2 * (d0 + i) + score_col]);
         __syncthreads();
         for (int i = lane; i < nd; i += 64) {                              // rule N2: rank by counting, a permutation
-            const float si = s_key[i];
-            int r = 0;
-            for (int j = 0; j < nd; ++j) {
-                const float sj = s_key[j];
-                r += (sj > si || (sj == si && j < i)) ? 1 : 0;
-            }
-            r = min(r, nd - 1);                                            // (r < nd already: at most nd - 1 rows are in front of one)
+            const int r = seg_rank([&](int j) { return s_key[j]; }, i, nd);
             s_order[r] = i;
             s_start[r] = seg[3 * (d0 + i) + 1];
             s_end[r] = seg[3 * (d0 + i) + 2];
@@ -123,7 +64,7 @@ __global__ __launch_bounds__(64) void nms_select_kernel(const double* __restrict
             const double s0 = s_start[r], e0 = s_end[r];
             for (int t = (r + 1) >> 6; 64 * t < nd; ++t) {
                 const int j = 64 * t + lane;
-                if (j > r && j < nd && nms_tiou(s0, e0, s_start[j], s_end[j]) > nms_thr) sup |= 1u << t;
+                if (j > r && j < nd && seg_tiou(s0, e0, s_start[j], s_end[j]) > nms_thr) sup |= 1u << t;
             }
         }
         int kept = 0;
@@ -141,13 +82,7 @@ __global__ __launch_bounds__(64) void nms_select_kernel(const double* __restrict
     int* order = ws_order + d0;
     unsigned char* flag = ws_flag + d0;
     for (int i = lane; i < nd; i += 64) {
-        const float si = nms_key(score[2 * (d0 + i) + score_col]);
-        int r = 0;
-        for (int j = 0; j < nd; ++j) {
-            const float sj = nms_key(score[2 * (d0 + j) + score_col]);
-            r += (sj > si || (sj == si && j < i)) ? 1 : 0;
-        }
-        order[min(r, nd - 1)] = i;
+        order[seg_rank([&](int j) { return seg_nan_low(score[2 * (d0 + j) + score_col]); }, i, nd)] = i;
         flag[i] = 0;                                                       // (rank i's flag: lane i & 63 = this lane owns it)
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");                     // the other lanes' ranks are read back through memory
@@ -161,7 +96,7 @@ __global__ __launch_bounds__(64) void nms_select_kernel(const double* __restrict
         for (int j = ((r + 1) >> 6) * 64 + lane; j < nd; j += 64) {
             if (j <= r || flag[j]) continue;
             const long rj = d0 + min(max(order[j], 0), nd - 1);
-            if (nms_tiou(s0, e0, seg[3 * rj + 1], seg[3 * rj + 2]) > nms_thr) flag[j] = 1;
+            if (seg_tiou(s0, e0, seg[3 * rj + 1], seg[3 * rj + 2]) > nms_thr) flag[j] = 1;
         }
     }
     int kept = 0;
@@ -174,42 +109,21 @@ __global__ __launch_bounds__(64) void nms_select_kernel(const double* __restrict
     if (lane == 0) counts[grp] = kept;
 }
 
-// counts[0 .. n) -> exclusive sums in place, counts[n] = total; offsets[b] = sum of the groups of videos < b; one workgroup
-__global__ __launch_bounds__(1024) void nms_scan_kernel(int* __restrict__ counts, int* __restrict__ offsets, int* __restrict__ total_out, long n, int B,
-                                                        int C, long cap_in) {
-    __shared__ int s_wave[16];
-    const int tid = threadIdx.x;
-    int carry = 0;
-    for (long i0 = 0; i0 < n; i0 += 1024) {
-        const long i = i0 + tid;
-        const int v = i < n ? (int)nms_clampl(counts[i], 0, cap_in) : 0;
-        int total;
-        const int ex = carry + nms_block_scan(v, s_wave, total);
-        if (i < n) {
-            counts[i] = ex;
-            if (i % C == 0) offsets[i / C] = ex;
-        }
-        carry += total;
-    }
-    if (tid == 0) {
-        counts[n] = carry;
-        offsets[B] = carry;
-        total_out[0] = carry;
-    }
-}
-
-// grid (B * C), one wave each
+// grid (B * C), one wave each: the stable compaction of rules N5 / N6 and S6.  FINALS (Soft-NMS): column score_col of the output comes from
+// ws_final, the other column and everything else are copied; otherwise both score columns are copied (ws_final and score_col are not read)
+template <bool FINALS>
 __global__ __launch_bounds__(64) void nms_write_kernel(const double* __restrict__ seg, const int* __restrict__ frames, const float* __restrict__ score,
                                                        const int* __restrict__ offsets, const unsigned char* __restrict__ keep,
-                                                       const int* __restrict__ bases, double* __restrict__ out_seg, int* __restrict__ out_frames,
-                                                       float* __restrict__ out_score, int* __restrict__ src, int C, long cap_in, long cap_out) {
+                                                       const int* __restrict__ bases, const float* __restrict__ ws_final, double* __restrict__ out_seg,
+                                                       int* __restrict__ out_frames, float* __restrict__ out_score, int* __restrict__ src, int C,
+                                                       int score_col, long cap_in, long cap_out) {
     const int lane = threadIdx.x;
     const long grp = blockIdx.x;
     long base = bases[grp];
     if (bases[grp + 1] - base <= 0 || base < 0 || base >= cap_out) return; // (wave uniform) nothing kept, or all of it behind cap_out
     const int b = (int)(grp / C), c = (int)(grp - (long)b * C);
     int nd;
-    const long d0 = nms_group(seg, offsets, b, c, cap_in, nd);
+    const long d0 = seg_group(seg, offsets, b, c, cap_in, nd);
     for (int i0 = 0; i0 < nd && base < cap_out; i0 += 64) {
         const long i = d0 + i0 + lane;
         const bool k = i0 + lane < nd && keep[i] != 0;
@@ -218,7 +132,12 @@ __global__ __launch_bounds__(64) void nms_write_kernel(const double* __restrict_
         if (k && dst < cap_out) {
             out_seg[3 * dst + 0] = seg[3 * i + 0]; out_seg[3 * dst + 1] = seg[3 * i + 1]; out_seg[3 * dst + 2] = seg[3 * i + 2];
             out_frames[3 * dst + 0] = frames[3 * i + 0]; out_frames[3 * dst + 1] = frames[3 * i + 1]; out_frames[3 * dst + 2] = frames[3 * i + 2];
-            out_score[2 * dst + 0] = score[2 * i + 0]; out_score[2 * dst + 1] = score[2 * i + 1];
+            if (FINALS) {
+                out_score[2 * dst + score_col] = ws_final[i];
+                out_score[2 * dst + 1 - score_col] = score[2 * i + 1 - score_col];
+            } else {
+                out_score[2 * dst + 0] = score[2 * i + 0]; out_score[2 * dst + 1] = score[2 * i + 1];
+            }
             src[dst] = (int)i;
         }
         base += __popcll(m);
@@ -239,10 +158,10 @@ extern "C" long cfn_nms_segments_workspace_bytes(int B, int C, long cap_in) {
 
 extern "C" int cfn_nms_det_tile(void) { return NMS_DET_TILE; }
 
-extern "C" int cfn_nms_segments(const double* seg, const int* frames, const float* score, const int* offsets, double* out_seg, int* out_frames,
-                                float* out_score, int* out_offsets, int* out_total, unsigned char* keep, int* src, void* workspace, int B, int C,
-                                int score_col, double nms_thr, long cap_in, long cap_out, void* stream) {
-    const char* what = "cfn_nms_segments";
+// the argument checks that cfn_nms_segments and cfn_soft_nms_segments share
+static int nms_check(const char* what, const void* seg, const void* frames, const void* score, const void* offsets, const void* out_seg,
+                     const void* out_frames, const void* out_score, const void* out_offsets, const void* out_total, const void* keep, const void* src,
+                     const void* workspace, int B, int C, int score_col, double nms_thr, long cap_in, long cap_out) {
     CFN_REQUIRE(seg && frames && score && offsets && out_seg && out_frames && out_score && out_offsets && out_total && keep && src && workspace,
                 "%s: null tensor", what);
     CFN_REQUIRE(nms_shape_ok(B, C, cap_in), "%s: bad shape (B %d, C %d in [1, 65535]; cap_in %ld in [1, 2^31))", what, B, C, cap_in);
@@ -251,6 +170,16 @@ extern "C" int cfn_nms_segments(const double* seg, const int* frames, const floa
     CFN_REQUIRE(nms_thr >= 0.0 && nms_thr <= 1.0, "%s: nms_thr in [0, 1] expected, got %g", what, nms_thr);
     CFN_REQUIRE(((uintptr_t)workspace & 7) == 0, "%s: workspace on an 8-byte boundary expected", what);
     CFN_REQUIRE(seg != out_seg && frames != out_frames && score != out_score, "%s: the outputs must not be the inputs", what);
+    return CFN_OK;
+}
+
+extern "C" int cfn_nms_segments(const double* seg, const int* frames, const float* score, const int* offsets, double* out_seg, int* out_frames,
+                                float* out_score, int* out_offsets, int* out_total, unsigned char* keep, int* src, void* workspace, int B, int C,
+                                int score_col, double nms_thr, long cap_in, long cap_out, void* stream) {
+    const char* what = "cfn_nms_segments";
+    if (const int bad = nms_check(what, seg, frames, score, offsets, out_seg, out_frames, out_score, out_offsets, out_total, keep, src, workspace, B, C,
+                                  score_col, nms_thr, cap_in, cap_out))
+        return bad;
     hipStream_t st = (hipStream_t)stream;
     const long groups = (long)B * C;
     int* counts = (int*)workspace;
@@ -258,9 +187,9 @@ extern "C" int cfn_nms_segments(const double* seg, const int* frames, const floa
     unsigned char* flag = (unsigned char*)(order + cap_in);
     CfnProfScope prof(CFN_K_ELEMWISE, st, 0.0);
     hipLaunchKernelGGL(nms_select_kernel, dim3((unsigned)groups), dim3(64), 0, st, seg, score, offsets, keep, counts, order, flag, C, score_col, nms_thr, cap_in);
-    hipLaunchKernelGGL(nms_scan_kernel, dim3(1), dim3(1024), 0, st, counts, out_offsets, out_total, groups, B, C, cap_in);
-    hipLaunchKernelGGL(nms_write_kernel, dim3((unsigned)groups), dim3(64), 0, st, seg, frames, score, offsets, (const unsigned char*)keep, (const int*)counts,
-                       out_seg, out_frames, out_score, src, C, cap_in, cap_out);
+    seg_launch_scan(counts, out_offsets, out_total, groups, B, C, cap_in, st);
+    hipLaunchKernelGGL(nms_write_kernel<false>, dim3((unsigned)groups), dim3(64), 0, st, seg, frames, score, offsets, (const unsigned char*)keep,
+                       (const int*)counts, (const float*)nullptr, out_seg, out_frames, out_score, src, C, score_col, cap_in, cap_out);
     return cfn_check_launch(what);
 }
 
@@ -289,8 +218,8 @@ extern "C" int cfn_nms_segments(const double* seg, const int* frames, const floa
 //                 the rounds.  Up to NMS_DET_TILE candidates start, end and w live in LDS (24 KB; start and end are written once, before
 //                 the one barrier in front of the rounds); a larger group keeps w in the workspace (8 bytes per candidate, still lane
 //                 owned) and reads seg, which nobody writes, from memory.  O(selected * nd / 64) per group; max_keep bounds it.
-//   scan          nms_scan_kernel as it is.
-//   soft_write    nms_write_kernel, with column score_col from the finals.
+//   scan          seg_launch_scan, as hard NMS.
+//   write         nms_write_kernel<true>: column score_col from the finals.
 #define SOFT_NONE 0x7fffffff
 
 // rule S5 (the constants fold at compile time: one correctly rounded division each)
@@ -380,7 +309,7 @@ __device__ __forceinline__ int soft_group(const double* __restrict__ seg, const 
             if (!(w > -INFINITY)) continue;                                // selected, or out from the start
             const double s1 = TILE ? s_start[j] : seg[3 * (d0 + j) + 1];
             const double e1 = TILE ? s_end[j] : seg[3 * (d0 + j) + 2];
-            w = soft_decay(w, nms_tiou(s0, e0, s1, e1), method, nms_thr, sigma);
+            w = soft_decay(w, seg_tiou(s0, e0, s1, e1), method, nms_thr, sigma);
             w_own[j] = w;
             if (w > bw) { bw = w; bj = j; }
         }
@@ -399,7 +328,7 @@ __global__ __launch_bounds__(64) void soft_select_kernel(const double* __restric
     const long grp = blockIdx.x;
     const int b = (int)(grp / C), c = (int)(grp - (long)b * C);
     int nd;
-    const long d0 = nms_group(seg, offsets, b, c, cap_in, nd);
+    const long d0 = seg_group(seg, offsets, b, c, cap_in, nd);
     int selected = 0;
     if (nd > NMS_DET_TILE)                                                 // (wave uniform)
         selected = soft_group<false>(seg, score, keep, ws_final + d0, nullptr, nullptr, ws_w + d0, d0, nd, score_col, method, nms_thr, sigma, min_score,
@@ -407,35 +336,6 @@ __global__ __launch_bounds__(64) void soft_select_kernel(const double* __restric
     else if (nd > 0)
         selected = soft_group<true>(seg, score, keep, ws_final + d0, s_start, s_end, s_w, d0, nd, score_col, method, nms_thr, sigma, min_score, max_keep);
     if (threadIdx.x == 0) counts[grp] = selected;
-}
-
-// grid (B * C), one wave each: nms_write_kernel with column score_col from the finals (rule S6)
-__global__ __launch_bounds__(64) void soft_write_kernel(const double* __restrict__ seg, const int* __restrict__ frames, const float* __restrict__ score,
-                                                        const int* __restrict__ offsets, const unsigned char* __restrict__ keep,
-                                                        const int* __restrict__ bases, const float* __restrict__ ws_final, double* __restrict__ out_seg,
-                                                        int* __restrict__ out_frames, float* __restrict__ out_score, int* __restrict__ src, int C,
-                                                        int score_col, long cap_in, long cap_out) {
-    const int lane = threadIdx.x;
-    const long grp = blockIdx.x;
-    long base = bases[grp];
-    if (bases[grp + 1] - base <= 0 || base < 0 || base >= cap_out) return; // (wave uniform) nothing selected, or all of it behind cap_out
-    const int b = (int)(grp / C), c = (int)(grp - (long)b * C);
-    int nd;
-    const long d0 = nms_group(seg, offsets, b, c, cap_in, nd);
-    for (int i0 = 0; i0 < nd && base < cap_out; i0 += 64) {
-        const long i = d0 + i0 + lane;
-        const bool k = i0 + lane < nd && keep[i] != 0;
-        const unsigned long long m = __ballot(k);
-        const long dst = base + __popcll(m & ((1ull << lane) - 1));
-        if (k && dst < cap_out) {
-            out_seg[3 * dst + 0] = seg[3 * i + 0]; out_seg[3 * dst + 1] = seg[3 * i + 1]; out_seg[3 * dst + 2] = seg[3 * i + 2];
-            out_frames[3 * dst + 0] = frames[3 * i + 0]; out_frames[3 * dst + 1] = frames[3 * i + 1]; out_frames[3 * dst + 2] = frames[3 * i + 2];
-            out_score[2 * dst + score_col] = ws_final[i];
-            out_score[2 * dst + 1 - score_col] = score[2 * i + 1 - score_col];
-            src[dst] = (int)i;
-        }
-        base += __popcll(m);
-    }
 }
 
 // workspace: fp64 working scores [cap_in]; then fp32 finals [cap_in] and int32 counts / bases [B * C + 1]; rounded up to 8 bytes
@@ -449,18 +349,13 @@ extern "C" int cfn_soft_nms_segments(const double* seg, const int* frames, const
                                      int score_col, double nms_thr, int method, double sigma, double min_score, int max_keep, long cap_in, long cap_out,
                                      void* stream) {
     const char* what = "cfn_soft_nms_segments";
-    CFN_REQUIRE(seg && frames && score && offsets && out_seg && out_frames && out_score && out_offsets && out_total && keep && src && workspace,
-                "%s: null tensor", what);
-    CFN_REQUIRE(nms_shape_ok(B, C, cap_in), "%s: bad shape (B %d, C %d in [1, 65535]; cap_in %ld in [1, 2^31))", what, B, C, cap_in);
-    CFN_REQUIRE(cap_out >= 1 && cap_out < (1L << 31), "%s: cap_out in [1, 2^31) expected, got %ld", what, cap_out);
-    CFN_REQUIRE(score_col == 0 || score_col == 1, "%s: score_col 0 (max) or 1 (mean) expected, got %d", what, score_col);
-    CFN_REQUIRE(nms_thr >= 0.0 && nms_thr <= 1.0, "%s: nms_thr in [0, 1] expected, got %g", what, nms_thr);
     CFN_REQUIRE(method == 0 || method == 1, "%s: method 0 (linear) or 1 (gaussian) expected, got %d", what, method);
     CFN_REQUIRE(sigma >= 0x1p-6 && sigma <= 0x1p20, "%s: sigma in [1/64, 2^20] expected, got %g", what, sigma);
     CFN_REQUIRE(min_score >= 0.0 && min_score <= 1.0, "%s: min_score in [0, 1] expected, got %g", what, min_score);
     CFN_REQUIRE(max_keep >= 0, "%s: max_keep >= 0 expected (0: no limit), got %d", what, max_keep);
-    CFN_REQUIRE(((uintptr_t)workspace & 7) == 0, "%s: workspace on an 8-byte boundary expected", what);
-    CFN_REQUIRE(seg != out_seg && frames != out_frames && score != out_score, "%s: the outputs must not be the inputs", what);
+    if (const int bad = nms_check(what, seg, frames, score, offsets, out_seg, out_frames, out_score, out_offsets, out_total, keep, src, workspace, B, C,
+                                  score_col, nms_thr, cap_in, cap_out))
+        return bad;
     hipStream_t st = (hipStream_t)stream;
     const long groups = (long)B * C;
     double* ws_w = (double*)workspace;
@@ -469,8 +364,8 @@ extern "C" int cfn_soft_nms_segments(const double* seg, const int* frames, const
     CfnProfScope prof(CFN_K_ELEMWISE, st, 0.0);
     hipLaunchKernelGGL(soft_select_kernel, dim3((unsigned)groups), dim3(64), 0, st, seg, score, offsets, keep, counts, ws_w, ws_final, C, score_col, method,
                        nms_thr, sigma, min_score, max_keep, cap_in);
-    hipLaunchKernelGGL(nms_scan_kernel, dim3(1), dim3(1024), 0, st, counts, out_offsets, out_total, groups, B, C, cap_in);
-    hipLaunchKernelGGL(soft_write_kernel, dim3((unsigned)groups), dim3(64), 0, st, seg, frames, score, offsets, (const unsigned char*)keep, (const int*)counts,
+    seg_launch_scan(counts, out_offsets, out_total, groups, B, C, cap_in, st);
+    hipLaunchKernelGGL(nms_write_kernel<true>, dim3((unsigned)groups), dim3(64), 0, st, seg, frames, score, offsets, (const unsigned char*)keep, (const int*)counts,
                        (const float*)ws_final, out_seg, out_frames, out_score, src, C, score_col, cap_in, cap_out);
     return cfn_check_launch(what);
 }

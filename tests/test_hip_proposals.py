@@ -204,6 +204,27 @@ def test_nms_chain_and_level_order_ties():
     assert propose(p.to(DEV), valid.to(DEV), levels=(0.3, 0.8), nms_thr=0.3, score='mean').frames[0].cpu().tolist() == [4, 6, 3]
 
 
+def test_nms_ranks_nan_scores_as_minus_infinity_on_both_paths():
+    """rule N2 with NaN scores, which no decode gives: a NaN ranks as -inf, behind every finite score and in row order among its like, so
+    the ranks stay a permutation.  A group of 65 (the lane-tile edge, LDS path) and one of 1025 (the workspace path) with NaN at rows 0, 63,
+    64 and the last row.  Row 0 lies apart from everything: kept.  The last row repeats the segment of row 1, finite and apart from the
+    rest: suppressed.  nms_reference spells the NaN rule and is the oracle"""
+    det = candidates(11, [{0: 65, 1: 1025}], 2, span=130.0)
+    seg, score = det.seg.clone(), det.score.clone()
+    nan_rows = []
+    for d0, nd in ((0, 65), (65, 1025)):
+        seg[d0, 1:] = torch.tensor([1000.0, 1010.0], dtype=torch.float64)
+        seg[d0 + 1, 1:] = seg[d0 + nd - 1, 1:] = torch.tensor([2000.0, 2010.0], dtype=torch.float64)
+        nan_rows += sorted({d0, d0 + 63, d0 + 64, d0 + nd - 1})
+    score[nan_rows] = float('nan')
+    det = det._replace(seg=seg, score=score)
+    kept, ref, keep = _nms_checked(det, 0.5)
+    assert 0 < kept < int(det.total)
+    of_nan = keep[nan_rows]
+    assert int(of_nan.sum()) >= 2 and int((of_nan == 0).sum()) >= 2                      # per group: at least one NaN row kept, one suppressed
+    assert keep[[0, 65]].tolist() == [1, 1] and keep[[1, 66]].tolist() == [1, 1] and keep[[64, 1089]].tolist() == [0, 0]
+
+
 @pytest.mark.parametrize('name', ['a', 'b', 'c'])
 def test_golden_labels_round_trip_through_both_kernels(name):
     """ops.seg_labels(batch) decoded at levels (0.75, 0.5, 0.25): three identical copies; NMS at 0.5 leaves decode(thr=0.5) row for row, and

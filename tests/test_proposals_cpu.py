@@ -45,6 +45,25 @@ def _nms(rows, thr, score='max', C=1, **kw):
     return [(float(s), float(e)) for _, s, e in out.seg[:n].tolist()], keep.tolist()
 
 
+def test_a_nan_score_ranks_as_minus_infinity_and_ties_go_to_the_lower_row():
+    """One group, nms_thr 0.5, neighbours shifted by one second overlap with tIoU 9/11.  N2 orders the rows 1, 2 (0.5 twice: the lower row
+    first), then the keys of -inf in row order: 0, 3, 4, 5, 6 (NaN and a true -inf are one key).  N4: 1 is kept and suppresses 2 and 0;
+    3 is kept -- a NaN row can be kept -- and suppresses 4; 5 (-inf) is kept and suppresses 6, the NaN row behind it"""
+    nan, ninf = float('nan'), float('-inf')
+    rows = [(0, 0, 10, nan, nan), (0, 1, 11, 0.5, 0.5), (0, 2, 12, 0.5, 0.5), (0, 20, 30, nan, nan), (0, 21, 31, nan, nan),
+            (0, 39, 49, ninf, ninf), (0, 40, 50, nan, nan)]
+    from cfn_hip.detections import nms_reference
+    det = fx.make_det([rows], 1)
+    for col in ('max', 'mean'):
+        out, keep, src = nms_reference(det, 0.5, col)
+        assert keep.tolist() == [0, 1, 0, 1, 0, 1, 0] and out.check() == 3 and src.tolist() == [1, 3, 5]
+        assert out.seg[:, 1:].tolist() == [[1.0, 11.0], [20.0, 30.0], [39.0, 49.0]]
+        assert torch.equal(out.score.view(torch.int32), det.score[[1, 3, 5]].view(torch.int32))      # (a NaN is copied bit for bit too)
+    assert nms_reference(det, 0.9)[1].tolist() == [1] * 7                               # 9/11 = 0.82 is not above 0.9: nothing falls
+    # as +inf, or compared raw (never above, never equal), row 0 would be walked before row 1 and kept
+    assert nms_reference(fx.make_det([rows[:2]], 1), 0.5)[1].tolist() == [0, 1]
+
+
 def test_the_chain_separates_greedy_from_suppressed_by_any_higher_ranked():
     """A (0, 10) 0.9, B (4, 14) 0.8, C (8, 18) 0.7: tIoU AB = BC = 6/14, AC = 2/18.  At 0.4 B falls to A, and C, which only B could have
     suppressed, is kept (N4: a suppressed candidate suppresses nothing)"""

@@ -2034,6 +2034,97 @@ def segap_value(scores, tps, counts, n_gt, n_thr, out=None):
     return ap, mp
 
 
+# ---- proposal recall at N per video, AR@N (csrc/segrecall.hip; the rule, the host reference and the meter: cfn_hip/recall.py) ----------------
+SEG_RECALL_MAX_THR = 16
+SEG_RECALL_MAX_N = 1024
+SEG_RECALL_RANK_TILE = 256       # scores of a video per LDS tile of the rank kernel (cfn_seg_recall_rank_tile())
+
+
+def seg_recall_workspace_bytes(B, C, det_cap, n_seg, n_thr):
+    n = int(query('cfn_seg_recall_workspace_bytes', int(B), int(C), int(det_cap), int(n_seg), int(n_thr)))
+    if n < 0:
+        raise RuntimeError('seg_recall: B and C in [1, 65535], det_cap and n_seg in [1, 2^31) and n_thr in [1, %d] expected, got (%d, %d, %d, %d, %d)'
+                           % (SEG_RECALL_MAX_THR, B, C, det_cap, n_seg, n_thr))
+    return n
+
+
+def seg_recall_state_size(n_thr, n_max):
+    """int64 values of a recall state: hist (n_thr, n_max), n_gt, n_videos, n_props"""
+    return int(n_thr) * int(n_max) + 3
+
+
+def _seg_recall_state(what, state, n_thr, n_max):
+    if not 1 <= n_thr <= SEG_RECALL_MAX_THR or not 1 <= n_max <= SEG_RECALL_MAX_N:
+        raise RuntimeError('%s: n_thr in [1, %d] and n_max in [1, %d] expected, got %d and %d' % (what, SEG_RECALL_MAX_THR, SEG_RECALL_MAX_N, n_thr, n_max))
+    if state.dtype != torch.int64 or tuple(state.shape) != (seg_recall_state_size(n_thr, n_max),):
+        raise RuntimeError('%s: state: (%d,) int64 expected (hist (%d, %d), n_gt, n_videos, n_props), got %s %s'
+                           % (what, seg_recall_state_size(n_thr, n_max), n_thr, n_max, state.dtype, tuple(state.shape)))
+
+
+def seg_recall_add(det_seg, det_score, det_offsets, seg, offsets, fps, window, tiou, state, n_classes, t_max, n_max, score_col=0, out=None):
+    """One batch into a proposal-recall state (rules R1-R5 of cfn_hip/recall.py): detections (det_seg (cap, 3) fp64, det_score (cap, 2) fp32,
+    det_offsets (B + 1,) int32) against the ground truth (seg (S, 3) fp64, offsets (B + 1,) int32, fps (B,) fp64, window (B, 2) int32) at
+    tiou (n_thr,) fp64 on the device, 1 <= n_thr <= 16 -> hit (n_thr, S) int32: the video rank of the first candidate of the row's video and
+    class that reaches tiou[k], n_max when none of the n_max best does, -1 for a row that does not participate.  state (n_thr * n_max + 3,)
+    int64 advances in place.  Three launches, nothing is read back (capturable with out=).  `n_classes`, `t_max`, `n_max` (1 .. 1024) and
+    `score_col` (0 = max, 1 = mean) are host ints.  out: (hit, a uint8 workspace of seg_recall_workspace_bytes(B, C, cap, S, n_thr) bytes).
+    No CPU path."""
+    what = 'seg_recall_add'
+    dev = _one_gpu(what, 'cfn_hip.recall.recall_reference', det_seg=det_seg, det_score=det_score, det_offsets=det_offsets, seg=seg, offsets=offsets,
+                   fps=fps, window=window, tiou=tiou, state=state)
+    if det_seg.dtype != torch.float64 or det_seg.dim() != 2 or det_seg.shape[1] != 3 or det_seg.shape[0] < 1:
+        raise RuntimeError('%s: det_seg: a (cap, 3) float64 tensor with cap >= 1 expected, got %s %s' % (what, det_seg.dtype, tuple(det_seg.shape)))
+    cap = int(det_seg.shape[0])
+    if det_score.dtype != torch.float32 or tuple(det_score.shape) != (cap, 2):
+        raise RuntimeError('%s: det_score (%d, 2) float32 expected, got %s %s' % (what, cap, det_score.dtype, tuple(det_score.shape)))
+    if seg.dtype != torch.float64 or seg.dim() != 2 or seg.shape[1] != 3 or seg.shape[0] < 1:
+        raise RuntimeError('%s: seg: a (S, 3) float64 tensor with S >= 1 expected, got %s %s' % (what, seg.dtype, tuple(seg.shape)))
+    S = int(seg.shape[0])
+    if offsets.dtype != torch.int32 or offsets.dim() != 1 or offsets.numel() < 2:
+        raise RuntimeError('%s: offsets (B + 1,) int32 expected, got %s %s' % (what, offsets.dtype, tuple(offsets.shape)))
+    B = int(offsets.numel()) - 1
+    if det_offsets.dtype != torch.int32 or tuple(det_offsets.shape) != (B + 1,):
+        raise RuntimeError('%s: det_offsets (%d,) int32 expected (one batch size for detections and ground truth), got %s %s'
+                           % (what, B + 1, det_offsets.dtype, tuple(det_offsets.shape)))
+    if fps.dtype != torch.float64 or tuple(fps.shape) != (B,) or window.dtype != torch.int32 or tuple(window.shape) != (B, 2):
+        raise RuntimeError('%s: fps (%d,) float64 and window (%d, 2) int32 expected, got %s %s and %s %s'
+                           % (what, B, B, fps.dtype, tuple(fps.shape), window.dtype, tuple(window.shape)))
+    if tiou.dtype != torch.float64 or tiou.dim() != 1 or not 1 <= tiou.numel() <= SEG_RECALL_MAX_THR:
+        raise RuntimeError('%s: tiou: 1 to %d float64 thresholds expected, got %s %s' % (what, SEG_RECALL_MAX_THR, tiou.dtype, tuple(tiou.shape)))
+    n_thr, n_classes, t_max, n_max, score_col = int(tiou.numel()), int(n_classes), int(t_max), int(n_max), int(score_col)
+    if n_classes < 1 or t_max < 1 or score_col not in (0, 1):
+        raise RuntimeError('%s: n_classes >= 1, t_max >= 1 and score_col 0 (max) or 1 (mean) expected, got %d, %d, %d' % (what, n_classes, t_max, score_col))
+    _seg_recall_state(what, state, n_thr, n_max)
+    ws_bytes = seg_recall_workspace_bytes(B, n_classes, cap, S, n_thr)
+    if out is None:
+        out = (torch.empty(n_thr, S, dtype=torch.int32, device=dev), torch.empty(ws_bytes, dtype=torch.uint8, device=dev))
+    else:
+        out = tuple(out)
+        if len(out) != 2 or out[0].dtype != torch.int32 or tuple(out[0].shape) != (n_thr, S) or not out[0].is_contiguous() or out[0].device != dev \
+                or out[1].dtype != torch.uint8 or out[1].dim() != 1 or out[1].numel() < ws_bytes or out[1].data_ptr() % 8 or not out[1].is_contiguous() \
+                or out[1].device != dev:
+            raise RuntimeError('%s: out: hit (%d, %d) int32 and an 8-byte aligned uint8 workspace of >= %d bytes on %s expected' % (what, n_thr, S, ws_bytes, dev))
+    call('cfn_seg_recall_add', det_seg, det_score, det_offsets, seg, offsets, fps, window, tiou, out[0], state, out[1], B, n_classes, t_max, n_thr,
+         n_max, score_col, cap, S)
+    return out[0]
+
+
+def seg_recall_value(state, n_thr, n_max, out=None):
+    """Rule R6 of cfn_hip/recall.py: a recall state -> (n_thr * n_max + n_max + 2,) fp64 on the device: recall (n_thr, n_max), ar (n_max,), auc,
+    avg_props.  One launch, nothing is read back.  out: the tensor to fill."""
+    what = 'seg_recall_value'
+    n_thr, n_max = int(n_thr), int(n_max)
+    dev = _one_gpu(what, 'cfn_hip.recall.recall_from_state', state=state)
+    _seg_recall_state(what, state, n_thr, n_max)
+    n = n_thr * n_max + n_max + 2
+    if out is None:
+        out = torch.empty(n, dtype=torch.float64, device=dev)
+    elif not torch.is_tensor(out) or out.dtype != torch.float64 or tuple(out.shape) != (n,) or out.device != dev or not out.is_contiguous():
+        raise RuntimeError('%s: out: (%d,) float64 on %s expected' % (what, n, dev))
+    call('cfn_seg_recall_value', state, out, n_thr, n_max)
+    return out
+
+
 # ---- baseline JPEG frames decoded on the GPU (csrc/jpegdec.hip; the host side and the batch type: cfn_hip/jpegdec.py) ------------------------
 def jpeg_workspace_bytes(rows, slots, lanes, blocks_max, entropy=None, sub_bytes=None, max_subs=None):
     """bytes of workspace cfn_jpeg_decode_u8 needs for `rows` frames into `slots` = clips x Tmax frame slots.  entropy, sub_bytes,

@@ -51,10 +51,10 @@ def _np(t, dtype):
     return np.ascontiguousarray((t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)).astype(dtype, copy=False))
 
 
-def _tiou_list(tiou):
+def _tiou_list(tiou, most=8):
     th = [float(x) for x in (tiou.tolist() if torch.is_tensor(tiou) or isinstance(tiou, np.ndarray) else tiou)]
-    if not 1 <= len(th) <= 8 or not all(0.0 < x <= 1.0 for x in th):
-        raise ValueError('tiou: 1 to 8 thresholds in (0, 1] expected, got %r' % (th,))
+    if not 1 <= len(th) <= most or not all(0.0 < x <= 1.0 for x in th):
+        raise ValueError('tiou: 1 to %d thresholds in (0, 1] expected, got %r' % (most, th))
     return th
 
 
@@ -176,6 +176,20 @@ def ap_reference(batches, n_classes, tiou=DEFAULT_TIOU, score_col=0):
             'scores': [np.asarray(s, np.float32) for s in scores], 'tps': [np.asarray(t, np.uint8) for t in tps], 'batches': per_batch}
 
 
+def ground_truth(labels, device):
+    """labels (a SegLabels, or the dense pair (labels (B, C, TL) fp32, valid_t (B,))) -> (seg, offsets, fps, window, t_max) on `device`: what
+    SegmentAPMeter and cfn_hip.recall.ProposalRecallMeter match against"""
+    if isinstance(labels, SegLabels):
+        labels = labels.to(device)
+        return labels.seg, labels.offsets, labels.fps, labels.window, int(labels.t_max)
+    dense, valid_t = labels
+    dense, valid_t = dense.to(device), valid_t.to(device, torch.int32)
+    gt = decode(dense.detach().float().contiguous(), valid_t, thr=0.5)             # frame units: fps = 1, start = 0
+    B, TL = int(dense.shape[0]), int(dense.shape[2])
+    window = torch.stack([torch.zeros_like(valid_t), valid_t], 1).contiguous()
+    return gt.seg, gt.offsets, torch.ones(B, dtype=torch.float64, device=device), window, TL
+
+
 class SegmentAPMeter(object):
     """Segment-level AP over a validation phase, resident on the GPU: class-major stores scores (C, cap) fp32 and tps (C, cap) uint8,
     counts (C,), n_gt (C,) and a flag word on the device.
@@ -271,15 +285,7 @@ class SegmentAPMeter(object):
 
     def ground_truth(self, labels):
         """labels (a SegLabels, or the dense pair (labels (B, C, TL) fp32, valid_t (B,))) -> (seg, offsets, fps, window, t_max) on the device"""
-        if isinstance(labels, SegLabels):
-            labels = labels.to(self.device)
-            return labels.seg, labels.offsets, labels.fps, labels.window, int(labels.t_max)
-        dense, valid_t = labels
-        dense, valid_t = dense.to(self.device), valid_t.to(self.device, torch.int32)
-        gt = decode(dense.detach().float().contiguous(), valid_t, thr=0.5)             # frame units: fps = 1, start = 0
-        B, TL = int(dense.shape[0]), int(dense.shape[2])
-        window = torch.stack([torch.zeros_like(valid_t), valid_t], 1).contiguous()
-        return gt.seg, gt.offsets, torch.ones(B, dtype=torch.float64, device=self.device), window, TL
+        return ground_truth(labels, self.device)
 
     @property
     def n_levels(self):

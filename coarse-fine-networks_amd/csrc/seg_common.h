@@ -1,5 +1,5 @@
-// The rules that the segment kernels share, stated once: detections.hip (decode), segnms.hip (NMS, Soft-NMS) and segap.hip (segment AP) all
-// work on Detections (seg (cap, 3) fp64 rows [class, start_s, end_s], score (cap, 2) fp32, offsets (B + 1,) int32) and on their
+// The rules that the segment kernels share, stated once: detections.hip (decode), segnms.hip (NMS, Soft-NMS), segap.hip (segment AP) and
+// segrecall.hip (proposal recall) all work on Detections (seg (cap, 3) fp64 rows [class, start_s, end_s], score (cap, 2) fp32, offsets (B + 1,) int32) and on their
 // (video, class) groups.  These rules are bit-exact statements that the numpy references spell too (cfn_hip/detections.py, cfn_hip/segap.py):
 // change one here and every kernel follows.  Everything is __forceinline__, so a kernel pays nothing for sharing them (tools/kernel_resources.sh).
 #pragma once
@@ -34,6 +34,18 @@ __device__ __forceinline__ double seg_tiou(double s0, double e0, double s1, doub
     const double inter = (e0 < e1 ? e0 : e1) - (s0 > s1 ? s0 : s1);
     if (!(inter > 0.0)) return 0.0;
     return inter / ((e0 - s0) + (e1 - s1) - inter);
+}
+
+// Rule 1 of segap.hip for ground-truth row g (R1 of segrecall.hip): the bounds clipped to the window (w0, w1) -- max / min, a NaN bound gives way
+// to the window's; true iff the row participates in class cd: g < g1, n > 0, the class column equals cd and e' > s'.
+__device__ __forceinline__ bool seg_gt_row(const double* __restrict__ gseg, long g, long g1, double cd, int n, double w0, double w1, double& sp,
+                                           double& ep) {
+    sp = 0.0; ep = 0.0;
+    if (g >= g1) return false;
+    const double cls = gseg[3 * g], s = gseg[3 * g + 1], e = gseg[3 * g + 2];
+    sp = s > w0 ? s : w0;
+    ep = e < w1 ? e : w1;
+    return n > 0 && cls == cd && ep > sp;
 }
 
 // Rank by counting (rule N2 of segnms.hip, rule 3 of segap.hip): the rank of row i among the nd rows of a group, key descending (fp32),

@@ -56,17 +56,6 @@ static inline SaWs sa_carve(void* ws, long groups, long det_cap) {
     return w;
 }
 
-// rule 1 for row g: the clipped bounds; true iff the row participates in class cd
-__device__ __forceinline__ bool sa_gt_row(const double* __restrict__ gseg, long g, long g1, double cd, int n, double w0, double w1, double& sp,
-                                          double& ep) {
-    sp = 0.0; ep = 0.0;
-    if (g >= g1) return false;
-    const double cls = gseg[3 * g], s = gseg[3 * g + 1], e = gseg[3 * g + 2];
-    sp = s > w0 ? s : w0;
-    ep = e < w1 ? e : w1;
-    return n > 0 && cls == cd && ep > sp;
-}
-
 // the candidate lane with the largest v, the lowest such lane on a tie; at least one lane is a candidate.  Every lane gets (lane, value).
 __device__ __forceinline__ int sa_argmax(double v, bool cand, int lane, double& best) {
     double bv = cand ? v : -1.0;
@@ -111,7 +100,7 @@ __global__ __launch_bounds__(64) void segap_match_kernel(const double* __restric
     int ng = 0;
     for (long t0 = g0; t0 < g1; t0 += SA_GT_TILE) {
         double sp, ep;
-        const bool part = sa_gt_row(gseg, t0 + lane, g1, cd, n, w0, w1, sp, ep);
+        const bool part = seg_gt_row(gseg, t0 + lane, g1, cd, n, w0, w1, sp, ep);
         if (!one && part) ws_used[t0 + lane] = 0;                          // (a row belongs to one group; the same lane reads it back below)
         ng += __popcll(__ballot(part));
     }
@@ -151,7 +140,7 @@ __global__ __launch_bounds__(64) void segap_match_kernel(const double* __restric
 
     if (one) {                                                             // rule 4, the video's rows in one tile of lanes
         double sp, ep;
-        const bool part = sa_gt_row(gseg, g0 + lane, g1, cd, n, w0, w1, sp, ep);
+        const bool part = seg_gt_row(gseg, g0 + lane, g1, cd, n, w0, w1, sp, ep);
         unsigned used = 0u;                                                // bit k: the lane's row is used up at threshold k
         for (int r = 0; r < nd; ++r) {
             const int i = cfn_uni(min(max(order[r], 0), nd - 1));          // (NaN scores may leave a rank empty: any row of the group then)
@@ -190,7 +179,7 @@ __global__ __launch_bounds__(64) void segap_match_kernel(const double* __restric
         for (int k = 0; k < SA_MAX_THR; ++k) { bv[k] = 0.0; bi[k] = -1; }
         for (long t0 = g0; t0 < g1; t0 += SA_GT_TILE) {
             double sp, ep;
-            const bool part = sa_gt_row(gseg, t0 + lane, g1, cd, n, w0, w1, sp, ep);
+            const bool part = seg_gt_row(gseg, t0 + lane, g1, cd, n, w0, w1, sp, ep);
             const double v = part ? seg_tiou(sd, ed, sp, ep) : 0.0;
             const unsigned used = part ? ws_used[t0 + lane] : 0u;
 #pragma unroll

@@ -34,6 +34,7 @@ from train_fine import lr_warmup, flatten_clips   # noqa: E402
 from train_fine import add_detect_args, detect_argv, detect_writer, calibration_from_args, calibration_line, check_calibration   # noqa: E402
 from train_fine import (check_segment_ap, seg_ap_arguments, seg_ap_argv, seg_ap_from_args, segment_ap_add,   # noqa: E402
                         segment_ap_line)
+from train_fine import check_proposal_recall, prop_recall_argv, prop_recall_from_args, proposal_recall_add, proposal_recall_line   # noqa: E402
 from cfn_hip.u8clips import RawU8Clips, U8Clips, CHARADES_MEAN, CHARADES_STD   # noqa: E402,F401
 from cfn_hip.featpack import PackedFeats          # noqa: E402
 
@@ -182,9 +183,11 @@ def run(init_lr=INIT_LR, warmup_steps=0, max_epochs=200, mode='rgb', root=None, 
         batch_size=BS * BS_UPSCALE, frames=80 * 4, dataloaders=None, max_steps=None,
         save_model='models/coarse_fineFEAT_charades_', pretrained='models/x3d_multigrid_kinetics_fb_pretrained.pt',
         csv_path='localize_corr_v1.csv', log=print, phase_hook=None, input_norm=None, device_ap=False,
-        fused_loss=False, jpeg_entropy=None, detections=None, segment_ap=None, calibration=None):
+        fused_loss=False, jpeg_entropy=None, detections=None, segment_ap=None, calibration=None, proposal_recall=None):
     """detections: a cfn_hip.detections.DetectionWriter -- every validation phase decodes its probs into activity segments on the GPU and
     rank 0 writes all ranks' videos as JSON lines (see train_fine.run).  None: nothing changes.
+    proposal_recall: a cfn_hip.recall.ProposalRecallMeter -- fed the Detections of the writer or of the segment-AP meter in every validation
+    phase, one ' Epoch:E val AR@1: ...' line per phase, any world size (see train_fine.run).  None: nothing changes.
     calibration: a cfn_hip.calibrate.Calibration -- per-class thresholds from the training AP rows wherever a training mAP is taken and in
     front of a validation phase that no mAP line has calibrated for, read by the writer's / the meter's decode (see train_fine.run).  Needs device_ap=True.  None: nothing changes.
     input_norm: see build_model -- needed when the loaders collate uint8 frames (collate.coarse_collate_u8, or coarse_collate_raw_u8:
@@ -199,6 +202,7 @@ def run(init_lr=INIT_LR, warmup_steps=0, max_epochs=200, mode='rgb', root=None, 
     fused = True if fused_loss else None
     rank, world, dev = cdist.init_from_env()
     check_segment_ap(segment_ap, world)
+    check_proposal_recall(proposal_recall, detections, segment_ap)
     check_calibration(calibration, device_ap, dev)
     gamma_tau = 5
     clip_frames = frames * 2 // (gamma_tau * 2)
@@ -266,7 +270,9 @@ def run(init_lr=INIT_LR, warmup_steps=0, max_epochs=200, mode='rgb', root=None, 
                     if detections is not None:      # decoded on the device; the segments stay there until the end of the phase
                         det = detections.add(probs, valid_t, seg_batch, name)
                     if segment_ap is not None:      # train_fine.run: the same segments, matched against the segment labels on the device
-                        segment_ap_add(segment_ap, det, probs, valid_t, seg_batch, labels, writer=detections)
+                        det = segment_ap_add(segment_ap, det, probs, valid_t, seg_batch, labels, writer=detections)
+                    if proposal_recall is not None:      # train_fine.run: the same Detections once more
+                        proposal_recall_add(proposal_recall, det, valid_t, seg_batch, labels)
                     tot_cls += float(cls_loss)
                     tot_loc += float(loc_loss)
                 if train and steps % max(iters // 2, 1) == 0:
@@ -308,6 +314,10 @@ def run(init_lr=INIT_LR, warmup_steps=0, max_epochs=200, mode='rgb', root=None, 
                         detections.flush(epoch_path(detections.path, epochs), [r for part in det_rows for r in part])
                 if segment_ap is not None:
                     log(segment_ap_line(segment_ap, epochs))
+                if proposal_recall is not None:
+                    line = proposal_recall_line(proposal_recall, epochs)      # (a collective under a world size above 1: every rank)
+                    if rank == 0:
+                        log(line)
                 if write_file:          # the reference closes the CSV after the first val phase (:295)
                     write_file.close()
                     write_file = writer = None
@@ -341,8 +351,9 @@ if __name__ == '__main__':
                                   os.path.abspath(__file__), '--batch-size', str(args.batch_size)] +
                                  (['--max-steps', str(args.max_steps)] if args.max_steps else []) + (['--device-ap'] if args.device_ap else []) +
                                  (['--fused-loss'] if args.fused_loss else []) + (['--jpeg-entropy', args.jpeg_entropy] if args.jpeg_entropy else []) +
-                                 detect_argv(args) + seg_ap_argv(args), env=env))
+                                 detect_argv(args) + seg_ap_argv(args) + prop_recall_argv(args), env=env))
     if 'RANK' not in os.environ:
         os.environ['CUDA_VISIBLE_DEVICES'] = args.gpu
     run(batch_size=args.batch_size, max_steps=args.max_steps, device_ap=args.device_ap, fused_loss=args.fused_loss, jpeg_entropy=args.jpeg_entropy,
-        detections=detect_writer(args), segment_ap=seg_ap_from_args(args), calibration=calibration_from_args(args))
+        detections=detect_writer(args), segment_ap=seg_ap_from_args(args), calibration=calibration_from_args(args),
+        proposal_recall=prop_recall_from_args(args))

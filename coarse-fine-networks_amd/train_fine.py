@@ -277,7 +277,7 @@ _ap_rows = metrics.ap_rows      # per video: (scores (v,157), targets (v,157)) n
 def run(init_lr=INIT_LR, warmup_steps=0, max_epochs=200, mode='rgb', root=None, train_split=None,
         batch_size=BS * BS_UPSCALE, frames=80 * 4, dataloaders=None, max_steps=None, save_model='models/fine_charades_',
         pretrained='models/x3d_multigrid_kinetics_fb_pretrained.pt', log=print, phase_hook=None, input_norm=None,
-        device_ap=False, fused_loss=False, jpeg_entropy=None, detections=None, segment_ap=None, calibration=None):
+        device_ap=False, fused_loss=False, jpeg_entropy=None, detections=None, segment_ap=None, calibration=None, proposal_recall=None):
     """detections: a cfn_hip.detections.DetectionWriter -- every validation phase decodes its probs into activity segments on the GPU
     (cfn_hip.ops.decode_segments) and rank 0 writes them, all ranks' videos, as JSON lines to the writer's path with the epoch inserted
     (cfn_hip.detections.epoch_path); seconds when the loaders collate SegLabel samples, frames otherwise.  None: nothing changes.
@@ -287,6 +287,10 @@ def run(init_lr=INIT_LR, warmup_steps=0, max_epochs=200, mode='rgb', root=None, 
     raises.  None: nothing changes.  A writer or a meter made with levels= decodes with cfn_hip.detections.propose instead (candidates at K
     levels, then temporal NMS -- soft-NMS when it was also made with soft=); the meter is still fed the writer's batch when both are given.
     calibration: a cfn_hip.calibrate.Calibration whose thr_vector / levels the writer and the meter were made with -- wherever a
+    proposal_recall: a cfn_hip.recall.ProposalRecallMeter -- every validation phase feeds it the very Detections the writer or the segment-AP
+    meter made (no second decode, so one of the two must be given) and logs ' Epoch:E val AR@1: ... AR@10: ... AR@N: ... AUC: ... props/video:
+    ...' behind the other lines.  Its state is additive, so unlike segment_ap a world size above 1 is allowed: the line's value is all-reduced
+    and rank 0 logs it.  None: nothing changes.
     training mAP is taken the same sorted rows give the per-class thresholds (StepMetrics.mean_ap(calibration): no read-back of its own), and
     a validation phase that starts with rows the meter still holds calibrates from those first (StepMetrics.calibrate); each is followed by one
     ' Epoch:E calibrated ...' line (Calibration.summary_line, one read-back of a few integers).  The validation decode then reads the updated
@@ -304,6 +308,7 @@ def run(init_lr=INIT_LR, warmup_steps=0, max_epochs=200, mode='rgb', root=None, 
     fused = True if fused_loss else None
     rank, world, dev = cdist.init_from_env()
     check_segment_ap(segment_ap, world)
+    check_proposal_recall(proposal_recall, detections, segment_ap)
     check_calibration(calibration, device_ap, dev)
     gamma_tau = {'S': 6, 'M': 5, 'XL': 5}[X3D_VERSION]
     crop = {'S': 160, 'M': 224, 'XL': 312}[X3D_VERSION]
@@ -369,7 +374,9 @@ def run(init_lr=INIT_LR, warmup_steps=0, max_epochs=200, mode='rgb', root=None, 
                     if detections is not None:      # decoded on the device; the segments stay there until the end of the phase
                         det = detections.add(probs, valid_t, seg_batch, _name)
                     if segment_ap is not None:      # matched and appended on the device; nothing is read back before the end of the phase
-                        segment_ap_add(segment_ap, det, probs, valid_t, seg_batch, labels, writer=detections)
+                        det = segment_ap_add(segment_ap, det, probs, valid_t, seg_batch, labels, writer=detections)
+                    if proposal_recall is not None:      # the same Detections once more; its counts stay on the device
+                        proposal_recall_add(proposal_recall, det, valid_t, seg_batch, labels)
                     tot_cls += float(cls_loss)
                     tot_loc += float(loc_loss)
                 if train and steps % max(iters // 2, 1) == 0:
@@ -407,6 +414,10 @@ def run(init_lr=INIT_LR, warmup_steps=0, max_epochs=200, mode='rgb', root=None, 
                         detections.flush(epoch_path(detections.path, epochs), [r for part in det_rows for r in part])
                 if segment_ap is not None:
                     log(segment_ap_line(segment_ap, epochs))
+                if proposal_recall is not None:
+                    line = proposal_recall_line(proposal_recall, epochs)      # (a collective under a world size above 1: every rank)
+                    if rank == 0:
+                        log(line)
                 val_apm.reset()
                 cal_seen = calibration.updates if calibration is not None else 0
                 lr_sched.step()            # once per val phase, as the reference (not per epoch, not per step)
@@ -452,6 +463,30 @@ def segment_ap_add(meter, det, probs, valid_t, seg_batch, labels, writer=None):
     elif det is None:
         det = decode(probs.detach(), valid_t, fps, start, meter.thr, meter.max_gap, meter.min_len)
     meter.add(det, seg_batch if fps is not None else (labels, valid_t), levels=levels)
+    return det
+
+
+def check_proposal_recall(meter, detections, segment_ap):
+    """a ProposalRecallMeter is fed the Detections of the writer or of the segment-AP meter: without either no decode exists"""
+    if meter is not None and detections is None and segment_ap is None:
+        raise RuntimeError('proposal_recall: the meter is fed the segments a DetectionWriter (detections=) or a SegmentAPMeter (segment_ap=) decodes '
+                           'in the validation phase, and neither was given: a decode does not exist')
+
+
+def proposal_recall_add(meter, det, valid_t, seg_batch, labels):
+    """one validation batch into the recall meter: `det` = what the writer or the segment-AP meter decoded; the ground truth as segment_ap_add
+    takes it"""
+    meter.add(det, seg_batch.to(det.seg.device) if isinstance(seg_batch, SegLabels) else (labels, valid_t.to(torch.int32)))
+
+
+def proposal_recall_line(meter, epochs):
+    """the phase's line (ONE read-back; summed over the ranks of a process group), and the meter is empty again"""
+    v = meter.value(group=None)
+    meter.reset()
+    ar = v['ar']
+    at = sorted({1, min(10, meter.n_max), meter.n_max})
+    return ' Epoch:{} val {} AUC: {:.4f} props/video: {:.1f}'.format(epochs, ' '.join('AR@{}: {:.4f}'.format(n, float(ar[n - 1])) for n in at),
+                                                                    float(v['auc']), float(v['avg_props']))
 
 
 def segment_ap_line(meter, epochs):
@@ -508,6 +543,12 @@ def add_detect_args(parser):
     g.add_argument('--detect-soft-sigma', type=float, default=None, help='with --detect-soft-nms gaussian: sigma, in [1/64, 2^20] (default 0.5)')
     g.add_argument('--detect-min-score', type=float, default=None, help='with --detect-soft-nms: stop at the first decayed score below this (default 0.001)')
     g.add_argument('--detect-max-keep', type=int, default=None, help='with --detect-soft-nms: at most N segments per video and class (default 0: no limit)')
+    g.add_argument('--prop-recall', action='store_true',
+                   help='log the proposal recall AR@N of every validation phase (needs --detect or --seg-ap, whose decode it is fed: with '
+                        '--detect-levels the proposals; any number of processes)')
+    g.add_argument('--prop-recall-n', type=int, default=100, help='with --prop-recall: the largest N, 1 to 1024')
+    g.add_argument('--prop-recall-tiou', default='0.5,0.55,0.6,0.65,0.7,0.75,0.8,0.85,0.9,0.95', help='with --prop-recall: 1 to 16 tIoU thresholds in (0, 1]')
+    g.add_argument('--prop-recall-score', choices=('max', 'mean'), default='max', help='with --prop-recall: the score column the candidates of a video are ranked by')
     g.add_argument('--detect-calibrate', metavar='SPEC', default=None,
                    help="per-class thresholds calibrated on the GPU from the training AP rows (needs --device-ap): f1 | precision:P | recall:Q replaces "
                         "--detect-thr once the first training mAP is taken; recall:Q1,Q2,... (ascending: thresholds high to low) replaces the same "
@@ -547,6 +588,27 @@ def detect_argv(args):
          if getattr(args, k, None) is not None for x in (flag, f(getattr(args, k)))] + \
         (['--detect-calibrate', args.detect_calibrate] if getattr(args, 'detect_calibrate', None) is not None else [])
     return ['--detect', args.detect, '--detect-thr', repr(args.detect_thr), '--detect-gap', str(args.detect_gap), '--detect-min-len', str(args.detect_min_len)] + more
+
+
+def prop_recall_argv(args):
+    """the --prop-recall options of `args` as a worker's command line"""
+    if not getattr(args, 'prop_recall', False):
+        return []
+    return ['--prop-recall', '--prop-recall-n', str(args.prop_recall_n), '--prop-recall-tiou', args.prop_recall_tiou, '--prop-recall-score',
+            args.prop_recall_score]
+
+
+def prop_recall_from_args(args, n_classes=157, device=None):
+    """the meter of --prop-recall on this rank's GPU, or None.  It is fed the decode of --detect or --seg-ap (the proposals with --detect-levels):
+    without either no decode exists and the option is refused"""
+    if not getattr(args, 'prop_recall', False):
+        return None
+    if not getattr(args, 'detect', None) and not getattr(args, 'seg_ap', False):
+        raise ValueError('--prop-recall measures the segments that --detect PATH or --seg-ap decode in the validation phase (with --detect-levels: the '
+                         'proposals), and neither is given: there is no decode to measure')
+    from cfn_hip.recall import ProposalRecallMeter
+    return ProposalRecallMeter(cdist.local_device() if device is None else device, n_classes, [float(x) for x in args.prop_recall_tiou.split(',')],
+                               args.prop_recall_n, args.prop_recall_score)
 
 
 def calibration_from_args(args, n_classes=157, device=None):
@@ -628,8 +690,9 @@ if __name__ == '__main__':
         sys.exit(_spawn(args.gpu, ['--batch-size', str(args.batch_size)] +
                         (['--max-steps', str(args.max_steps)] if args.max_steps else []) + (['--device-ap'] if args.device_ap else []) +
                         (['--fused-loss'] if args.fused_loss else []) + (['--jpeg-entropy', args.jpeg_entropy] if args.jpeg_entropy else []) +
-                        detect_argv(args) + seg_ap_argv(args)))
+                        detect_argv(args) + seg_ap_argv(args) + prop_recall_argv(args)))
     if 'RANK' not in os.environ:
         os.environ['CUDA_VISIBLE_DEVICES'] = args.gpu
     run(batch_size=args.batch_size, max_steps=args.max_steps, device_ap=args.device_ap, fused_loss=args.fused_loss, jpeg_entropy=args.jpeg_entropy,
-        detections=detect_writer(args), segment_ap=seg_ap_from_args(args), calibration=calibration_from_args(args))
+        detections=detect_writer(args), segment_ap=seg_ap_from_args(args), calibration=calibration_from_args(args),
+        proposal_recall=prop_recall_from_args(args))

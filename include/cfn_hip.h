@@ -789,6 +789,45 @@ int cfn_ap_calibrate(const float* sorted_scores, const unsigned char* sorted_tar
                      void* stream);
 int cfn_ap_calibrate_tile(void);
 
+/* =====================================================================================================================
+ * Proposal recall at N per video, AR@N (csrc/segrecall.hip; the rule, the numpy reference and the meter: cfn_hip/recall.py).
+ * How many ground-truth segments at least one of the N best candidates of their video covers at a tIoU threshold: what a
+ * proposal stage (cfn_decode_segments_levels, cfn_nms_segments, cfn_soft_nms_segments) is judged by.  Inputs as cfn_segap_match
+ * takes them: det_seg (det_cap, 3) fp64, det_score (det_cap, 2) fp32, det_offsets (B + 1) int32; seg (n_seg, 3) fp64, offsets
+ * (B + 1) int32, fps (B) fp64, window (B, 2) int32, t_max; tiou (n_thr) fp64 on the device, 1 <= n_thr <= 16, each in (0, 1], any
+ * order; n_max in [1, 1024]; score_col 0 = max, 1 = mean.
+ *     R1. participation and window clip: rule 1 of segment AP above, to the bit.  Row g belongs to video b iff offsets[b] <= g <
+ *         offsets[b + 1] (clamped to [0, n_seg], expected not to decrease; found by binary search).
+ *     R2. tIoU: rule 2 of segment AP.
+ *     R3. video rank: the candidates of video b are the rows det_offsets[b] .. det_offsets[b + 1], clamped to [0, det_cap], ALL
+ *         classes together, ranked by det_score[:, score_col] descending (fp32), a NaN taken as -inf, ties to the lower row: a
+ *         permutation of 0 .. n_b - 1.
+ *     R4. first hit: for a participating row g (video b, class c) and threshold k, hit[k, g] = the smallest video rank among the
+ *         candidates of the SAME video and class whose tIoU with g is > 0 and >= tiou[k]; n_max when there is none or the smallest
+ *         is >= n_max; -1 for a row that does not participate.  No one-to-one matching.
+ *     R5. state: int64 hist (n_thr, n_max), then n_gt, n_videos, n_props (n_thr * n_max + 3 values).  hist[k, hit[k, g]] += 1 for
+ *         every participating g with hit < n_max; n_gt += the participating rows; n_videos += B; n_props += the sum of the clamped
+ *         n_b.  Integer adds only: the same in every run, and additive over batches and over data-parallel ranks.
+ *     R6. value, fp64: recall[k, n] = (double)(hist[k, 0] + .. + hist[k, n]) / (double)n_gt (N = n + 1; 0 when n_gt == 0);
+ *         ar[n] = (recall[0, n] + .. + recall[n_thr - 1, n]) / n_thr in k order; auc = (ar[0] + .. + ar[n_max - 1]) / n_max in n
+ *         order; avg_props = n_props / n_videos (0 without videos).  No product: bit-equal to the numpy reference.
+ *   cfn_seg_recall_add (3 launches): R1-R5.  hit (n_thr, n_seg) int32 is written whole; state advances in place; `workspace`:
+ *     cfn_seg_recall_workspace_bytes(B, C, det_cap, n_seg, n_thr) bytes on an 8-byte boundary (the video ranks).  The rank is by
+ *     counting through LDS tiles of cfn_seg_recall_rank_tile() = 256 scores, a grid over (tile of rows, video): O(n_b^2) per video.
+ *     The first hit takes one wave per ground-truth row; the histogram one workgroup per threshold (LDS integer atomics).
+ *   cfn_seg_recall_value (1 launch): R6 into out (n_thr * n_max + n_max + 2) fp64: recall, ar, auc, avg_props.
+ * Everything but the host ints is read on the device only and clamped: a bad batch gives wrong values, never an access outside
+ * the buffers.  Ordered by the stream alone; no allocation, no synchronisation (capturable).  Return 1 for null pointers, B or C
+ * outside [1, 65535], t_max < 1, n_thr outside [1, 16], n_max outside [1, 1024], score_col outside {0, 1}, det_cap or n_seg outside
+ * [1, 2^31) or a misaligned workspace; cfn_seg_recall_workspace_bytes -1 for the same shapes and n_thr.
+ * ===================================================================================================================== */
+long cfn_seg_recall_workspace_bytes(int B, int C, long det_cap, long n_seg, int n_thr);
+int cfn_seg_recall_rank_tile(void);
+int cfn_seg_recall_add(const double* det_seg, const float* det_score, const int* det_offsets, const double* seg, const int* offsets,
+                       const double* fps, const int* window, const double* tiou, int* hit, long* state, void* workspace, int B, int C,
+                       int t_max, int n_thr, int n_max, int score_col, long det_cap, long n_seg, void* stream);
+int cfn_seg_recall_value(const long* state, double* out, int n_thr, int n_max, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -878,6 +878,79 @@ def average_precision(scores, targets, count, out=None):
     return ap_reduce(st, count)
 
 
+# ---- merge class-major AP stores (csrc/apmerge.hip; the rule M1-M4, the numpy reference and the gather over ranks: cfn_hip/apmerge.py) ------
+AP_FLAG_BAD_SOURCE = 4
+AP_MERGE_TILE = 2048             # rows per workgroup of cfn_ap_merge's copy (cfn_ap_merge_tile(); tests place sizes on its edges)
+
+
+def ap_merge_workspace_bytes(R, C):
+    n = int(query('cfn_ap_merge_workspace_bytes', int(R), int(C)))
+    if n < 0:
+        raise RuntimeError('ap_merge: R and C in [1, 65535] expected, got (%d, %d)' % (R, C))
+    return n
+
+
+def ap_merge(dst_scores, dst_payload, dst_counts, dst_extra, dst_flags, src_scores, src_payload, src_counts, src_extra, src_flags, out=None):
+    """Append R source stores behind the rows a destination store holds, in part order, in place (rules M1-M4 of cfn_hip/apmerge.py):
+    dst_scores (C, cap_d) fp32, dst_payload (C, cap_d) uint8, dst_counts (n_cnt,) int32 with n_cnt 1 (one count for all classes: the frame
+    meter) or C (segment AP), dst_extra (n_extra,) int32 or None (additive integers carried along: n_gt), dst_flags one int32; src_scores
+    (R, C, cap_s), src_payload (R, C, cap_s), src_counts (R, n_cnt), src_extra (R, n_extra) or None, src_flags (R,); all contiguous on one
+    GPU, sources and destination apart.  All or nothing: a total past cap_d sets AP_FLAG_OVERFLOW, a source count outside [0, cap_s]
+    AP_FLAG_BAD_SOURCE, and nothing else changes; the sources' flags are OR-ed in either way.  Two launches, nothing is read back (no
+    wait).  out: a uint8 workspace of ap_merge_workspace_bytes(R, C) bytes on an 8-byte boundary (capturable with it).  Returns the
+    workspace.  No CPU path (apmerge.merge_reference is the host spelling)."""
+    what = 'ap_merge'
+    tensors = dict(dst_scores=dst_scores, dst_payload=dst_payload, dst_counts=dst_counts, dst_flags=dst_flags, src_scores=src_scores,
+                   src_payload=src_payload, src_counts=src_counts, src_flags=src_flags)
+    if (dst_extra is None) != (src_extra is None):
+        raise RuntimeError('%s: dst_extra and src_extra: both or neither expected' % what)
+    if dst_extra is not None:
+        tensors.update(dst_extra=dst_extra, src_extra=src_extra)
+    dev = _one_gpu(what, 'cfn_hip.apmerge.merge_reference', **tensors)
+    if dst_scores.dtype != torch.float32 or dst_scores.dim() != 2 or min(dst_scores.shape) < 1 or dst_payload.dtype != torch.uint8 \
+            or tuple(dst_payload.shape) != tuple(dst_scores.shape):
+        raise RuntimeError('%s: destination: class-major stores expected, scores (C, cap_d) fp32 and payload (C, cap_d) uint8; got %s %s, %s %s'
+                           % (what, dst_scores.dtype, tuple(dst_scores.shape), dst_payload.dtype, tuple(dst_payload.shape)))
+    C, cap_d = int(dst_scores.shape[0]), int(dst_scores.shape[1])
+    if src_scores.dtype != torch.float32 or src_scores.dim() != 3 or int(src_scores.shape[1]) != C or min(src_scores.shape) < 1 \
+            or src_payload.dtype != torch.uint8 or tuple(src_payload.shape) != tuple(src_scores.shape):
+        raise RuntimeError('%s: sources: scores (R, %d, cap_s) fp32 and payload (R, %d, cap_s) uint8 expected; got %s %s, %s %s'
+                           % (what, C, C, src_scores.dtype, tuple(src_scores.shape), src_payload.dtype, tuple(src_payload.shape)))
+    R, cap_s = int(src_scores.shape[0]), int(src_scores.shape[2])
+    n_cnt = int(dst_counts.numel())
+    if dst_counts.dtype != torch.int32 or dst_counts.dim() != 1 or n_cnt not in (1, C) or src_counts.dtype != torch.int32 \
+            or tuple(src_counts.shape) != (R, n_cnt):
+        raise RuntimeError('%s: dst_counts (1,) or (%d,) int32 and src_counts (%d, n_cnt) int32 expected, got %s %s and %s %s'
+                           % (what, C, R, dst_counts.dtype, tuple(dst_counts.shape), src_counts.dtype, tuple(src_counts.shape)))
+    n_extra = 0
+    if dst_extra is not None:
+        n_extra = int(dst_extra.numel())
+        if dst_extra.dtype != torch.int32 or dst_extra.dim() != 1 or src_extra.dtype != torch.int32 or tuple(src_extra.shape) != (R, n_extra):
+            raise RuntimeError('%s: dst_extra (n_extra,) int32 and src_extra (%d, n_extra) int32 expected, got %s %s and %s %s'
+                               % (what, R, dst_extra.dtype, tuple(dst_extra.shape), src_extra.dtype, tuple(src_extra.shape)))
+        if n_extra == 0:
+            dst_extra = src_extra = None
+    if dst_flags.dtype != torch.int32 or dst_flags.numel() != 1 or src_flags.dtype != torch.int32 or tuple(src_flags.shape) != (R,):
+        raise RuntimeError('%s: dst_flags one int32 and src_flags (%d,) int32 expected, got %s %s and %s %s'
+                           % (what, R, dst_flags.dtype, tuple(dst_flags.shape), src_flags.dtype, tuple(src_flags.shape)))
+    if not (1 <= R <= 65535 and C <= 65535 and cap_s < (1 << 31) and cap_d < (1 << 31)):
+        raise RuntimeError('%s: R and C <= 65535 and capacities < 2^31 expected, got R %d, C %d, cap_s %d, cap_d %d' % (what, R, C, cap_s, cap_d))
+    lo, hi = dst_scores.data_ptr(), dst_scores.data_ptr() + 4 * C * cap_d
+    plo, phi = dst_payload.data_ptr(), dst_payload.data_ptr() + C * cap_d
+    if (src_scores.data_ptr() < hi and lo < src_scores.data_ptr() + 4 * R * C * cap_s) \
+            or (src_payload.data_ptr() < phi and plo < src_payload.data_ptr() + R * C * cap_s):
+        raise RuntimeError('%s: sources and destination overlap' % what)
+    ws_bytes = ap_merge_workspace_bytes(R, C)
+    if out is None:
+        out = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    elif not torch.is_tensor(out) or out.dtype != torch.uint8 or out.dim() != 1 or out.numel() < ws_bytes or out.data_ptr() % 8 \
+            or not out.is_contiguous() or out.device != dev:
+        raise RuntimeError('%s: out: an 8-byte aligned uint8 workspace of >= %d bytes on %s expected' % (what, ws_bytes, dev))
+    call('cfn_ap_merge', dst_scores, dst_payload, dst_counts, dst_extra, dst_flags, src_scores, src_payload, src_counts, src_extra, src_flags, out,
+         R, C, n_cnt, n_extra, cap_s, cap_d)
+    return out
+
+
 # ---- per-class decode thresholds from the sorted AP rows (csrc/apcal.hip; the rule and the Calibration: cfn_hip/calibrate.py) -------------
 AP_CALIBRATE_TILE = 8192         # rows per tile of cfn_ap_calibrate's second walk (cfn_ap_calibrate_tile(); tests place sizes on its edges)
 AP_CALIBRATE_MAX_K = 16

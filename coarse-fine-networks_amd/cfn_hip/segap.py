@@ -33,8 +33,9 @@ int32, ``fps (B)`` fp64, ``window (B, 2)`` int32 (the tensors of ``SegLabels``) 
 
 ``match_reference`` and ``ap_reference`` spell the rules in numpy on any device and are the tests' reference; ``SegmentAPMeter`` is the
 device-resident meter.  Limits: B and C <= 65535; at most 8 thresholds; the order inside a (video, class) group is rank by counting,
-O(nd^2) in its detections; ONE process: AP is not additive, and merging the stores of several data-parallel ranks is out of scope (the
-training entry points refuse a world size above 1 with a meter).
+O(nd^2) in its detections.  AP is not additive, so a plain meter is ONE process's (the training entry points refuse it under a world size
+above 1); a meter made with ``across_ranks=True`` evaluates the stores of all data-parallel ranks appended in rank order
+(cfn_hip/apmerge.py: rules M1-M4), and ``merge`` / ``merged`` do the same for meters of one process.
 
 This module is host only (numpy + torch) apart from the calls into cfn_hip.ops.
 """
@@ -211,13 +212,19 @@ class SegmentAPMeter(object):
     temporal NMS) in place of decode; the meter only keeps the three for them.  A batch of proposals can hold K times the rows of a decode:
     ``add(levels=K)`` multiplies growing mode's bound (post-NMS groups can still exceed (TL + 1) // 2 rows).  soft (a
     cfn_hip.detections.SoftNMS, with `levels`): propose's second stage is soft_nms; kept for the entry points like the three.
-    One process only: merging the stores of data-parallel ranks is out of scope."""
+    A meter made without the next two arguments is one process's, exactly as before.  across_ranks=True (group: the process group, None =
+    the default one): under a world size above 1 ``value_device()`` and ``value()`` evaluate the stores of ALL ranks, appended in rank order
+    into a fresh store (cfn_hip.apmerge.gather_stores): every rank gets the same bits, those of one process fed the ranks' batches one rank
+    after another.  The call is then a collective that every rank must make; the rank's own stores are untouched, so ``reset()`` and further
+    ``add``s behave as before.  Without a process group, or with a world size of 1, nothing is gathered or copied.  ``merge(*others)`` and
+    ``SegmentAPMeter.merged(parts)`` append other meters' rows within one process (ONE ops.ap_merge)."""
 
     MIN_CAPACITY = 1024
 
     def __init__(self, device, n_classes, tiou=DEFAULT_TIOU, score='max', capacity=None, thr=0.5, max_gap=0, min_len=1, levels=None, nms=None,
-                 nms_score='max', soft=None):
+                 nms_score='max', soft=None, across_ranks=False, group=None):
         self.device = torch.device(device)
+        self.across_ranks, self.group = bool(across_ranks), group
         if self.device.type != 'cuda':
             raise RuntimeError('SegmentAPMeter keeps its rows on a GPU (got device %s); cfn_hip.segap.ap_reference is the host spelling' % self.device)
         if score not in SCORE_COLUMNS:
@@ -320,22 +327,89 @@ class SegmentAPMeter(object):
         ops.segap_append(dscore, tp, ws, self._scores, self._tps, self.counts, self.n_gt, self.flags, B, self.score_col)
         return tp, match
 
-    def value_device(self):
-        """(ap (n_thr, C) fp32, map (n_thr,) fp32) on the device; reads nothing back (the flags are not looked at: value() does)"""
-        from . import ops
+    @property
+    def settings(self):
+        """what two meters must share for their rows to be one metric's"""
+        return self.n_classes, self.tiou, self.score
+
+    def _part(self):
+        """this meter's store as apmerge.stack_parts takes it, and the host's upper bound of its fullest class"""
+        cap = int(self._scores.shape[1])
+        return (self._scores, self._tps, self.counts, self.n_gt, self.flags), (min(self._bound, cap) if self.capacity is None else cap)
+
+    def merge(self, *others):
+        """append the rows of `others` (SegmentAPMeters of the same classes, tiou and score, on any GPU) behind this meter's, in the order
+        given, in place: ONE ops.ap_merge with R = len(others) (rules M1-M4 of cfn_hip/apmerge.py).  The meter is then, bit for bit, what
+        it would be had it been fed its own batches and then the others', one after another.  The others stay untouched.  Growing mode
+        reserves from the host's bounds, which stay upper bounds (the one read-back of add()'s reserve where they pass the capacity); a
+        fixed capacity never reads back: a merge that does not fit changes nothing, is flagged on the device and reported by value()."""
+        from . import apmerge, ops
+        for o in others:
+            if not isinstance(o, SegmentAPMeter) or o.settings != self.settings:
+                raise ValueError('SegmentAPMeter.merge: a SegmentAPMeter of the same classes, tiou and score expected, got %r against %r'
+                                 % (getattr(o, 'settings', type(o).__name__), self.settings))
+            if o is self:
+                raise ValueError('SegmentAPMeter.merge: a meter cannot be merged into itself (sources and destination must not overlap)')
+        if not others:
+            return self
+        parts, bounds = zip(*(o._part() for o in others))
+        parts = [tuple(t.to(self.device) for t in p) for p in parts]
+        if self.capacity is None:
+            self._reserve(sum(bounds))
+        # (one part goes as its own stores, whole: no copy, and the tiles behind its counts exit; several are stacked at the largest host bound)
+        src = apmerge.stack_parts(parts, m=int(parts[0][0].shape[1]) if len(parts) == 1 else max(bounds))
+        ops.ap_merge(self._scores, self._tps, self.counts, self.n_gt, self.flags, *src)
+        return self
+
+    @classmethod
+    def merged(cls, parts, capacity=None):
+        """a NEW meter (parts[0]'s settings and device; growing, or of the fixed `capacity`) that holds the parts' rows in list order, through
+        ONE ops.ap_merge with R = len(parts): the code path the gather over ranks takes behind its collectives"""
+        parts = list(parts)
+        if not parts:
+            raise ValueError('SegmentAPMeter.merged: at least one meter expected')
+        p = parts[0]
+        new = cls(p.device, p.n_classes, p.tiou, p.score, capacity, p.thr, p.max_gap, p.min_len, p.levels, p.nms if p.levels is not None else None,
+                  p.nms_score, p.soft)
+        return new.merge(*parts)
+
+    def _across(self):
+        from . import apmerge
+        return self.across_ranks and apmerge.world_size(self.group) > 1
+
+    def _evaluate(self):
+        """(ap, map, flags) on the device: of this meter's rows, or -- across_ranks under a world size above 1 -- of all ranks' rows in rank
+        order (apmerge.gather_stores: a collective; this rank's stores stay untouched)"""
+        from . import apmerge, ops
+        C, n_thr = self.n_classes, len(self.tiou)
+        if self._across():
+            scores, tps, state = apmerge.gather_stores(self._scores, self._tps, self._state, C, self.group)
+            ap, mp = ops.segap_value(scores, tps, state[:C], state[C:2 * C], n_thr)
+            return ap, mp, state[2 * C:]
         if self._sort_bufs is None:
             C, cap = self._scores.shape
             self._sort_bufs = (torch.empty_like(self._scores), torch.empty_like(self._tps), torch.empty(C, cap, dtype=torch.int32, device=self.device),
                                torch.empty_like(self._tps))
         out = self._sort_bufs + (torch.empty(len(self.tiou), self.n_classes, dtype=torch.float32, device=self.device),
                                  torch.empty(len(self.tiou), dtype=torch.float32, device=self.device))
-        return ops.segap_value(self._scores, self._tps, self.counts, self.n_gt, len(self.tiou), out=out)
+        ap, mp = ops.segap_value(self._scores, self._tps, self.counts, self.n_gt, len(self.tiou), out=out)
+        return ap, mp, self.flags
+
+    def value_device(self):
+        """(ap (n_thr, C) fp32, map (n_thr,) fp32) on the device; reads nothing back (the flags are not looked at: value() does).  With
+        across_ranks under a world size above 1: of all ranks' rows in rank order, the same bits on every rank -- a COLLECTIVE that every
+        rank must make (and the one read-back of two ints that sizes the gather)."""
+        return self._evaluate()[:2]
 
     def value(self):
-        """(ap (n_thr, C), map (n_thr,)) as float32 CPU tensors, with ONE read-back; raises if a batch did not fit a fixed capacity"""
+        """(ap (n_thr, C), map (n_thr,)) as float32 CPU tensors, with ONE read-back; raises if a batch did not fit a fixed capacity (on any
+        rank, with across_ranks) or a merge met a malformed source"""
         from . import ops
-        ap, mp = self.value_device()
-        host = torch.cat([ap.reshape(-1).view(torch.int32), mp.view(torch.int32), self.flags]).cpu()
+        ap, mp, flags = self._evaluate()
+        host = torch.cat([ap.reshape(-1).view(torch.int32), mp.view(torch.int32), flags]).cpu()
+        if int(host[-1]) & ops.AP_FLAG_BAD_SOURCE:
+            raise RuntimeError('SegmentAPMeter: a merge met a source store whose count was outside [0, capacity] (a malformed source) and was '
+                               'refused: the value would miss those rows')
         if int(host[-1]) & ops.SEGAP_FLAG_OVERFLOW:
             if self.capacity is None:
                 raise RuntimeError('SegmentAPMeter: a batch held more detections of one class than the growing stores had reserved (%d rows per '

@@ -313,7 +313,9 @@ def run(init_lr=INIT_LR, warmup_steps=0, max_epochs=200, mode='rgb', root=None, 
                     if rank == 0:
                         detections.flush(epoch_path(detections.path, epochs), [r for part in det_rows for r in part])
                 if segment_ap is not None:
-                    log(segment_ap_line(segment_ap, epochs))
+                    line = segment_ap_line(segment_ap, epochs)      # (a collective with an across_ranks meter: every rank)
+                    if rank == 0:
+                        log(line)
                 if proposal_recall is not None:
                     line = proposal_recall_line(proposal_recall, epochs)      # (a collective under a world size above 1: every rank)
                     if rank == 0:

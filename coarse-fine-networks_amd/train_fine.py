@@ -283,8 +283,9 @@ def run(init_lr=INIT_LR, warmup_steps=0, max_epochs=200, mode='rgb', root=None, 
     (cfn_hip.detections.epoch_path); seconds when the loaders collate SegLabel samples, frames otherwise.  None: nothing changes.
     segment_ap: a cfn_hip.segap.SegmentAPMeter -- every validation phase matches the same decoded segments (the writer's decode; the meter's
     own thr / max_gap / min_len without a writer) against the batch's segment labels on the GPU and logs ' Epoch:E val seg-mAP@t: ...' behind the
-    existing line.  One process only: AP is not additive and merging the stores of several ranks is out of scope, so a world size above 1
-    raises.  None: nothing changes.  A writer or a meter made with levels= decodes with cfn_hip.detections.propose instead (candidates at K
+    existing line.  AP is not additive, so a plain meter is one process's and a world size above 1 raises; a meter made with across_ranks=True
+    (--seg-ap-all-ranks) evaluates the stores of all ranks appended in rank order on the GPU (cfn_hip/apmerge.py): every rank builds the line
+    (a collective), rank 0 logs it.  None: nothing changes.  A writer or a meter made with levels= decodes with cfn_hip.detections.propose instead (candidates at K
     levels, then temporal NMS -- soft-NMS when it was also made with soft=); the meter is still fed the writer's batch when both are given.
     calibration: a cfn_hip.calibrate.Calibration whose thr_vector / levels the writer and the meter were made with -- wherever a
     proposal_recall: a cfn_hip.recall.ProposalRecallMeter -- every validation phase feeds it the very Detections the writer or the segment-AP
@@ -413,7 +414,9 @@ def run(init_lr=INIT_LR, warmup_steps=0, max_epochs=200, mode='rgb', root=None, 
                     if rank == 0:
                         detections.flush(epoch_path(detections.path, epochs), [r for part in det_rows for r in part])
                 if segment_ap is not None:
-                    log(segment_ap_line(segment_ap, epochs))
+                    line = segment_ap_line(segment_ap, epochs)      # (a collective with an across_ranks meter under a world size above 1: every rank)
+                    if rank == 0:
+                        log(line)
                 if proposal_recall is not None:
                     line = proposal_recall_line(proposal_recall, epochs)      # (a collective under a world size above 1: every rank)
                     if rank == 0:
@@ -427,10 +430,12 @@ def run(init_lr=INIT_LR, warmup_steps=0, max_epochs=200, mode='rgb', root=None, 
 
 
 def check_segment_ap(meter, world):
-    """a SegmentAPMeter works in ONE process: AP is not additive, and merging the stores of several ranks is out of scope"""
-    if meter is not None and world > 1:
-        raise RuntimeError('segment_ap: a SegmentAPMeter holds the detections of ONE process; AP is not additive over ranks and merging their '
-                           'stores is not implemented (world size %d): validate on one GPU, or leave segment_ap=None' % world)
+    """a plain SegmentAPMeter works in ONE process: AP is not additive.  One made with across_ranks=True (--seg-ap-all-ranks) evaluates the
+    stores of all ranks appended in rank order (cfn_hip/apmerge.py) and passes"""
+    if meter is not None and world > 1 and not getattr(meter, 'across_ranks', False):
+        raise RuntimeError('segment_ap: a SegmentAPMeter holds the detections of ONE process; AP is not additive over ranks and this meter does '
+                           'not merge their stores (world size %d): validate on one GPU, leave segment_ap=None, or make the meter with '
+                           'across_ranks=True (--seg-ap-all-ranks)' % world)
 
 
 def check_calibration(calibration, device_ap, dev=None):
@@ -499,10 +504,13 @@ def segment_ap_line(meter, epochs):
 def seg_ap_arguments(parser):
     """the --seg-ap group: segment-level AP at tIoU thresholds of every validation phase (cfn_hip.segap.SegmentAPMeter)"""
     g = parser.add_argument_group('segment AP')
-    g.add_argument('--seg-ap', action='store_true', help='log seg-mAP@tIoU of every validation phase (one process only)')
+    g.add_argument('--seg-ap', action='store_true', help='log seg-mAP@tIoU of every validation phase (one process; several ranks with --seg-ap-all-ranks)')
     g.add_argument('--seg-ap-tiou', default='0.1,0.3,0.5,0.7,0.9', help='1 to 8 tIoU thresholds in (0, 1], comma separated')
     g.add_argument('--seg-ap-score', choices=('max', 'mean'), default='max', help='the score column detections are ranked by')
     g.add_argument('--seg-ap-capacity', type=int, default=None, help='rows per class, fixed (default: the stores grow)')
+    g.add_argument('--seg-ap-all-ranks', action='store_true',
+                   help='with --seg-ap under several ranks: evaluate the detections of ALL ranks, their stores appended in rank order on the GPU '
+                        '(every rank gets the same value; rank 0 logs it)')
     return parser
 
 
@@ -511,7 +519,8 @@ def seg_ap_argv(args):
     if not args.seg_ap:
         return []
     return ['--seg-ap', '--seg-ap-tiou', args.seg_ap_tiou, '--seg-ap-score', args.seg_ap_score] + \
-        (['--seg-ap-capacity', str(args.seg_ap_capacity)] if args.seg_ap_capacity is not None else [])
+        (['--seg-ap-capacity', str(args.seg_ap_capacity)] if args.seg_ap_capacity is not None else []) + \
+        (['--seg-ap-all-ranks'] if getattr(args, 'seg_ap_all_ranks', False) else [])
 
 
 def seg_ap_from_args(args, n_classes=157, calibration=None):
@@ -521,7 +530,8 @@ def seg_ap_from_args(args, n_classes=157, calibration=None):
     from cfn_hip.segap import SegmentAPMeter
     thr, more = _calibrated(args.detect_thr, detect_levels(args), calibration_from_args(args, n_classes) if calibration is None else calibration)
     return SegmentAPMeter(torch.device('cuda', torch.cuda.current_device()), n_classes, [float(x) for x in args.seg_ap_tiou.split(',')], args.seg_ap_score,
-                          args.seg_ap_capacity, thr, args.detect_gap, args.detect_min_len, **more)
+                          args.seg_ap_capacity, thr, args.detect_gap, args.detect_min_len, across_ranks=bool(getattr(args, 'seg_ap_all_ranks', False)),
+                          **more)
 
 
 def add_detect_args(parser):

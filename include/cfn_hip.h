@@ -828,6 +828,43 @@ int cfn_seg_recall_add(const double* det_seg, const float* det_score, const int*
                        int t_max, int n_thr, int n_max, int score_col, long det_cap, long n_seg, void* stream);
 int cfn_seg_recall_value(const long* state, double* out, int n_thr, int n_max, void* stream);
 
+/* =====================================================================================================================
+ * Merge class-major AP stores (csrc/apmerge.hip; the rule, the numpy reference, the gather over data-parallel ranks:
+ * cfn_hip/apmerge.py).  cfn_ap_append's stores (ONE count for all classes) and cfn_segap_append's (one count per class plus
+ * n_gt) share one layout; AP is not additive, but the sort behind it is stable and breaks ties in insertion order, so stores
+ * appended in a FIXED order give every rank the bits one process would have produced, fed the parts' batches one part after
+ * another.
+ *   destination: scores (C, cap_d) fp32, payload (C, cap_d) uint8, counts (n_cnt) int32 with n_cnt == 1 (one count for all
+ *     classes) or C, extra (n_extra) int32 (additive integers carried along: n_gt; NULL with n_extra == 0), ONE flags word.
+ *   sources: R >= 1 parts in one call: scores (R, C, cap_s), payload (R, C, cap_s), counts (R, n_cnt), extra (R, n_extra),
+ *     flags (R).  Sources and destination do not overlap.
+ *     M1. a source count outside [0, cap_s] makes the call a refusal: nothing is written, no count or extra changes, and flag
+ *         bit 2 (value 4, "malformed source") is set.
+ *     M2. totals in 64-bit integers: tot[c] = counts_d[c] + sum_r counts_s[r][c].  Any tot[c] > cap_d (or a destination count
+ *         below 0) is a refusal: nothing is written, nothing changes, the overflow bit (value 2, cfn_ap_append's) is set.  Any
+ *         summed extra that leaves int32 is a refusal in the same way.  All or nothing, as cfn_ap_append.
+ *     M3. otherwise row i of part r, class c goes to destination row counts_d[c] + sum_{q<r} counts_s[q][c] + i.  Scores and
+ *         payload are copied as BITS (NaN payloads, -0.0 and denormals stay as they are); counts and extras advance by the
+ *         sums; rows behind the new counts are untouched.
+ *     M4. in every case, refusals included, flags |= OR_r flags_s[r]: a batch dropped on any rank taints the merged value.
+ * cfn_ap_merge: 2 launches.  plan (one workgroup) validates, takes the per-count prefix sums over the parts into `workspace`
+ *   (cfn_ap_merge_workspace_bytes(R, C) bytes on an 8-byte boundary, caller owned until the call has passed on the stream),
+ *   decides refusal and commits counts, extras and flags.  copy: a grid over (tile of cfn_ap_merge_tile() = 2048 rows of cap_s,
+ *   class, part) that reads only the workspace's verdict, bases and counts, never the destination counts; tiles behind a
+ *   part's count exit, so no grid size depends on a device value.  Scores go as dwords, as 16-byte vectors where both sides
+ *   share their phase; the payload is right at every (source, destination) byte alignment: head and tail bytes singly, the
+ *   body as destination-aligned dwords assembled from the source, and nothing outside a tile's source rows is read.
+ * Ordered by the stream alone; no atomics, no allocation, no synchronisation, no read-back (capturable).  Counts are DATA:
+ * what plan leaves in the workspace is clamped where copy reads it, so nothing is stored outside the destination.  Returns
+ * 1 for null pointers (the extras may be NULL with n_extra == 0), C or R outside [1, 65535], cap_s or cap_d outside
+ * [1, 2^31), n_cnt not in {1, C}, n_extra < 0, or a misaligned workspace; cfn_ap_merge_workspace_bytes -1 for such R or C.
+ * ===================================================================================================================== */
+long cfn_ap_merge_workspace_bytes(int R, int C);
+int cfn_ap_merge_tile(void);
+int cfn_ap_merge(float* dst_scores, unsigned char* dst_payload, int* dst_counts, int* dst_extra, int* dst_flags,
+                 const float* src_scores, const unsigned char* src_payload, const int* src_counts, const int* src_extra,
+                 const int* src_flags, void* workspace, int R, int C, int n_cnt, int n_extra, long cap_s, long cap_d, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

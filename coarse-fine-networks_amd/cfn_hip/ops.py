@@ -1533,6 +1533,17 @@ def conv3d_dense(x, w, kernel, stride, padding, A=None, B=None, act=ACT_NONE, st
     return _ConvDense.apply(x, A, B, w, act, kernel, stride, padding, stats)
 
 
+def conv3d_dense_route(op, N, Cin, Cout, T, H, W, geom=None, flags=0, cus=0):
+    """the kernel a dense conv of this shape runs on (cfn_conv3d_dense_route, include/cfn_hip.h): host only.  op 0 forward, 1 data gradient,
+    2 weight gradient, 3 stem forward, 4 stem weight gradient; geom = (kernel, stride, padding) flattened to 9 ints (ops 0-2);
+    cus = 0: the current device's CUs (256 without a device)"""
+    out = ctypes.create_string_buffer(256)
+    g = (ctypes.c_int * 9)(*geom) if geom is not None else None
+    if query('cfn_conv3d_dense_route', op, N, Cin, Cout, T, H, W, g, flags, cus, out, 256):
+        raise RuntimeError(last_error())
+    return out.value.decode()
+
+
 class _FusionGather(Function):
     """z[r,c,k,p] = sum_t x[b] at[b] GX[r] mask[b] / (sum_t at GX mask + 1e-6), at = sigmoid(at_raw + at_bias), r = b*crops + j
     (cfn_fusion_gather_*)"""

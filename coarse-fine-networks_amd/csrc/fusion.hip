@@ -5,7 +5,7 @@
 //     (7 -> 56/28/14: each output cell copies exactly one input cell) and materialises a
 //     (B,C,T',K,h,w) product; every quantity is constant over the (h/7 x w/7) blocks, so the 7x7
 //     result up-sampled is identical (measured 3e-8).
-#include "cfn_common.h"
+#include "dense_plan.h"
 #include <stdlib.h>
 
 // salconv.hip
@@ -203,7 +203,7 @@ extern "C" int cfn_conv3d_dense_bwd_data(const float* gy, const float* y, const 
     CFN_REQUIRE((A == nullptr) == (B == nullptr), "cfn_conv3d_dense_bwd_data: A/B mismatch");
     CFN_REQUIRE(A == nullptr || (x && gA && gB), "cfn_conv3d_dense_bwd_data: prologue needs x, gA, gB");
     CFN_REQUIRE(gsumsq == nullptr || y != nullptr, "cfn_conv3d_dense_bwd_data: gsumsq needs y");
-    CFN_REQUIRE((long)N * Cin <= 65535, "cfn_conv3d_dense_bwd_data: N*Cin exceeds grid.y");
+    CFN_REQUIRE(dense_dgrad_fits(N, Cin), "cfn_conv3d_dense_bwd_data: N*Cin exceeds grid.y");
     DenseBwdArgs a = {};
     a.gy = gy; a.y = gsumsq ? y : nullptr; a.gs = gsum; a.gq = gsumsq; a.w = w; a.x = x; a.A = A; a.B = B; a.gx = gx;
     a.gA = gA; a.gB = gB; a.Cin = Cin; a.Cout = Cout; a.Ti = T; a.Hi = Hi; a.Wi = Wi; a.act = act;
@@ -219,29 +219,46 @@ extern "C" int cfn_conv3d_dense_bwd_data(const float* gy, const float* y, const 
         const int rs = sal_dgrad_try_launch(gy, a.y, gsum, gsumsq, w, x, A, B, act, gx, gA, gB, N, Cin, Cout, T, Hi, Wi, geom, st);
         if (rs >= 0) return rs;
     }
-    const int ncls = a.sT * a.sH * a.sW;
-    const long pcls = (long)cfn_cdiv(T, a.sT) * cfn_cdiv(Hi, a.sH) * cfn_cdiv(Wi, a.sW);     // largest class
-    {   // all-input-channels variant when the whole layer's weights fit in LDS
-        const int CI = Cin <= 8 ? 8 : (Cin <= 24 ? 24 : 32);
-        const size_t lds_all = ((size_t)2 * Cout + (size_t)Cout * a.kT * a.kH * a.kW * CI + 8 * CI) * sizeof(float);
-        if (Cin <= 32 && lds_all <= 64 * 1024 && ncls <= 64 && N <= 65535) {
-            const dim3 grid(cfn_cdiv(pcls, 256), N, ncls);
+    DensePlan p;
+    CFN_REQUIRE(dense_dgrad_plan(dense_shape(N, Cin, Cout, T, Hi, Wi, geom, act), p), "cfn_conv3d_dense_bwd_data: stride / weight slice too large");
+    const dim3 grid(p.grid[0], p.grid[1], p.grid[2]);
+    const size_t lds = p.lds;
+    if (p.family == DN_ALLCI) {
 #define CFN_DENSE_GO(CIV)                                                                                                 \
-            do {                                                                                                           \
-                auto k = conv3d_dense_bwd_data_allci_kernel<CIV>;                                                          \
-                if (lds_all > 48 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_all); \
-                hipLaunchKernelGGL(k, grid, dim3(256), lds_all, st, a);                                                    \
-            } while (0)
-            if (CI == 8) CFN_DENSE_GO(8); else if (CI == 24) CFN_DENSE_GO(24); else CFN_DENSE_GO(32);
+        do {                                                                                                               \
+            auto k = conv3d_dense_bwd_data_allci_kernel<CIV>;                                                              \
+            if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
+            hipLaunchKernelGGL(k, grid, dim3(256), lds, st, a);                                                            \
+        } while (0)
+        if (p.v[0] == 8) CFN_DENSE_GO(8); else if (p.v[0] == 24) CFN_DENSE_GO(24); else CFN_DENSE_GO(32);
 #undef CFN_DENSE_GO
-            return cfn_check_launch("conv3d_dense_bwd_data(all channels)");
-        }
+        return cfn_check_launch("conv3d_dense_bwd_data(all channels)");
     }
-    const size_t lds = ((size_t)2 * Cout + (size_t)Cout * a.kT * a.kH * a.kW) * sizeof(float);
-    CFN_REQUIRE(ncls <= 64 && lds <= 60 * 1024, "cfn_conv3d_dense_bwd_data: stride / weight slice too large");
     if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)conv3d_dense_bwd_data_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(conv3d_dense_bwd_data_kernel, dim3(cfn_cdiv(pcls, 256), N * Cin, ncls), dim3(256), lds, st, a);
+    hipLaunchKernelGGL(conv3d_dense_bwd_data_kernel, grid, dim3(256), lds, st, a);
     return cfn_check_launch("conv3d_dense_bwd_data");
+}
+
+// What the saliency kernel left: the all-input-channels variant (v = {CI}) when the whole layer's weights fit in LDS, else one input channel per
+// workgroup row.  false = stride classes or weight slice too large for either (the entry point fails)
+bool dense_dgrad_plan(const DenseShape& s, DensePlan& p) {
+    const int* g = s.g;
+    const int KV = g[0] * g[1] * g[2], ncls = g[3] * g[4] * g[5];
+    const long pcls = (long)cfn_cdiv(s.T, g[3]) * cfn_cdiv(s.Hi, g[4]) * cfn_cdiv(s.Wi, g[5]);     // largest class
+    p = DensePlan{};
+    p.wg = 256;
+    const int CI = s.Cin <= 8 ? 8 : (s.Cin <= 24 ? 24 : 32);
+    const size_t lds_all = ((size_t)2 * s.Cout + (size_t)s.Cout * KV * CI + 8 * CI) * sizeof(float);
+    if (s.Cin <= 32 && lds_all <= 64 * 1024 && ncls <= 64 && s.N <= 65535) {
+        p.family = DN_ALLCI; p.v[0] = CI; p.lds = lds_all;
+        p.grid[0] = (unsigned)cfn_cdiv(pcls, 256); p.grid[1] = (unsigned)s.N; p.grid[2] = (unsigned)ncls;
+        return true;
+    }
+    p.family = DN_PERCH;
+    p.lds = ((size_t)2 * s.Cout + (size_t)s.Cout * KV) * sizeof(float);
+    if (ncls > 64 || p.lds > 60 * 1024) return false;
+    p.grid[0] = (unsigned)cfn_cdiv(pcls, 256); p.grid[1] = (unsigned)(s.N * s.Cin); p.grid[2] = (unsigned)ncls;
+    return true;
 }
 
 // ---------------------------------------------------------------------------------------------------------

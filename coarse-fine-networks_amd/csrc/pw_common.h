@@ -136,6 +136,9 @@ bool pw_route_short(const PwBwdShape& s, const PwSwitches& sw, PwBwdPlan& p);   
 int pwss_wgrad_try_bf16(const uint16_t* gy, const uint16_t* y, const double* gs, const double* gq, const double* gsc, const uint16_t* x,
                         const double* pa, const double* pb, int act, double* gw, int N, int M, int K, int Q, hipStream_t st);
 
+// ---- dense convs (stem, saliency): the plans live in dense_plan.h, the launchers below call them ---------------------------------------------
+#include "dense_plan.h"
+
 // pwwgrad.hip: the direct-operand weight gradient of a dense conv (stem, saliency); -1 = shape not handled
 int pwd_wgrad_try_dense(const float* gy, const float* y, const double* gs, const double* gq, const float* x, const double* pa,
                         const double* pb, int act, double* gw, int N, int M, int Cimg, int T, int Hi, int Wi, const int* g,

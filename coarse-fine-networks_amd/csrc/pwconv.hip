@@ -794,6 +794,23 @@ static int dense_geom(ARGS& a, int Cimg, int T, int Hi, int Wi, const int* g) {
     return CFN_OK;
 }
 
+// The implicit-GEMM forward of a dense conv: tile plan (pw_plan patches `a`) and template choice.  v = {MT, mode, STATS, ACT}; false: beyond the
+// descriptor range
+static bool dense_gemm_pick(PwArgs& a, bool stats, DensePlan& p) {
+    p = DensePlan{};
+    if (!pw_plan(a, p.v[0], p.grid[0], p.lds)) return false;
+    p.family = DN_GEMM; p.v[1] = PW_FWD; p.v[2] = stats; p.v[3] = a.act == CFN_ACT_RELU ? CFN_ACT_RELU : CFN_ACT_NONE;
+    p.grid[1] = p.grid[2] = 1; p.wg = 256;
+    return true;
+}
+
+// The LDS-staged weight gradient of a dense conv: every shape.  v = {MTW, NTW}
+static void dense_wg_pick(WgArgs& a, DensePlan& p) {
+    p = DensePlan{};
+    wg_plan(a, p.v[0], p.v[1]);
+    p.family = DN_WG; p.grid[0] = wg_blocks(a); p.grid[1] = p.grid[2] = 1; p.wg = 256; p.lds = wg_lds(p.v[0], p.v[1]);
+}
+
 extern "C" int cfn_conv3d_dense_fwd(const float* x, const double* A, const double* B, int act, const float* w, float* y,
                                     double* sum, double* sumsq, int N, int Cin, int Cout, int T, int Hi, int Wi,
                                     const int* geom, void* stream) {
@@ -816,13 +833,16 @@ extern "C" int cfn_conv3d_dense_fwd(const float* x, const double* A, const doubl
         const int rs = sal_fwd_try_launch(x, A, B, act, w, y, sum, sumsq, N, Cin, Cout, T, Hi, Wi, geom, st);
         if (rs >= 0) return rs;
     }
-    int MT; unsigned blocks; size_t lds;
-    if (!pw_plan(a, MT, blocks, lds)) return pw_too_large(a);
-    if (sum) {
-        if (act == CFN_ACT_RELU) return pw_launch_mt<PW_FWD, true, CFN_ACT_RELU, true>(a, MT, blocks, lds, st);
+    DensePlan p;
+    if (!dense_gemm_pick(a, sum != nullptr, p)) return pw_too_large(a);
+    const int MT = p.v[0];
+    const unsigned blocks = p.grid[0];
+    const size_t lds = p.lds;
+    if (p.v[2]) {
+        if (p.v[3] == CFN_ACT_RELU) return pw_launch_mt<PW_FWD, true, CFN_ACT_RELU, true>(a, MT, blocks, lds, st);
         return pw_launch_mt<PW_FWD, true, CFN_ACT_NONE, true>(a, MT, blocks, lds, st);
     }
-    if (act == CFN_ACT_RELU) return pw_launch_mt<PW_FWD, false, CFN_ACT_RELU, true>(a, MT, blocks, lds, st);
+    if (p.v[3] == CFN_ACT_RELU) return pw_launch_mt<PW_FWD, false, CFN_ACT_RELU, true>(a, MT, blocks, lds, st);
     return pw_launch_mt<PW_FWD, false, CFN_ACT_NONE, true>(a, MT, blocks, lds, st);
 }
 
@@ -837,8 +857,9 @@ extern "C" int cfn_conv3d_dense_bwd_weight(const float* gy, const float* y, cons
     int rc = dense_geom(a, Cin, T, Hi, Wi, geom);
     if (rc) return rc;
     a.N = N; a.M = Cout; a.K = Cin * a.kT * a.kH * a.kW;
-    int MTW, NTW;
-    wg_plan(a, MTW, NTW);
+    DensePlan pg;
+    dense_wg_pick(a, pg);
+    const int MTW = pg.v[0], NTW = pg.v[1];
     hipStream_t st = (hipStream_t)stream;
     CfnProfScope prof(CFN_K_STEM, st, 4.0 * N * ((double)Cin * a.Pin + (double)Cout * a.Q));
     {   // LDS-tiled persistent kernel (salconv.hip) for the Grid Pool saliency shapes
@@ -878,4 +899,23 @@ extern "C" int cfn_stem_conv_bwd_weight(const float* gy, const float* x, double*
     }
     return cfn_conv3d_dense_bwd_weight(gy, nullptr, nullptr, nullptr, x, nullptr, nullptr, CFN_ACT_NONE, gw, N, Cimg, Cout, T, Hi, Wi,
                                        kStemGeom, stream);
+}
+
+// ---- the same arithmetic for the host-only query (cfn_conv3d_dense_route, denseroute.hip) ----
+// the implicit-GEMM forward of a dense conv.  v = {MT, mode, STATS, ACT}; false: beyond the descriptor range (the entry point fails)
+bool dense_gemm_plan(const DenseShape& s, DensePlan& p) {
+    PwArgs a = {};
+    a.act = s.act;
+    if (dense_geom(a, s.Cin, s.T, s.Hi, s.Wi, s.g)) return false;
+    a.N = s.N; a.M = s.Cout; a.K = s.Cin * a.kT * a.kH * a.kW; a.Cin = a.K;
+    return dense_gemm_pick(a, s.stats, p);
+}
+
+// the LDS-staged weight gradient of a dense conv: every shape.  v = {MTW, NTW}
+bool dense_wg_plan(const DenseShape& s, DensePlan& p) {
+    WgArgs a = {};
+    if (dense_geom(a, s.Cin, s.T, s.Hi, s.Wi, s.g)) return false;
+    a.N = s.N; a.M = s.Cout; a.K = s.Cin * a.kT * a.kH * a.kW;
+    dense_wg_pick(a, p);
+    return true;
 }

@@ -312,17 +312,34 @@ int pwd_wgrad_launch(const PwBwdPlan& p, const float* gy, const float* y, const 
 int pwd_wgrad_try_dense(const float* gy, const float* y, const double* gs, const double* gq, const float* x, const double* pa,
                         const double* pb, int act, double* gw, int N, int M, int Cimg, int T, int Hi, int Wi, const int* g,
                         hipStream_t st) {
+    DenseShape s = dense_shape(N, Cimg, M, T, Hi, Wi, g, act);
+    s.align_g = (unsigned)(((uintptr_t)gy | (uintptr_t)(y ? y : gy)) & 15);
+    DensePlan p;
+    if (!dense_wd_plan(s, p)) return -1;
     const int To = (T + 2 * g[6] - g[0]) / g[3] + 1, Ho = (Hi + 2 * g[7] - g[1]) / g[4] + 1, Wo = (Wi + 2 * g[8] - g[2]) / g[5] + 1;
-    const int K = Cimg * g[0] * g[1] * g[2];
-    const long Ql = (long)To * Ho * Wo;
-    if (To < 1 || Ho < 1 || Wo < 1 || Wo % 4 != 0 || Ql >= (1L << 30)) return -1;
-    const int Q = (int)Ql;
-    if (!wd_common_ok((unsigned)(((uintptr_t)gy | (uintptr_t)(y ? y : gy)) & 15), act, M, K, Q)) return -1;
-    if ((long)Cimg * T * Hi * Wi * 4 >= (1L << 31) - 64) return -1;
+    const int K = Cimg * g[0] * g[1] * g[2], Q = To * Ho * Wo;
     WdArgs a = {gy, y, gs, gq, x, pa, pb, gw, N, M, K, Q, act};
     a.Pin = T * Hi * Wi; a.Hi = Hi; a.Wi = Wi; a.Ho = Ho; a.Wo = Wo; a.stride = 1; a.Ti = T; a.Cimg = Cimg;
     a.kT = g[0]; a.kH = g[1]; a.kW = g[2]; a.sT = g[3]; a.sH = g[4]; a.sW = g[5]; a.pT = g[6]; a.pH = g[7]; a.pW = g[8];
-    // one 32x32 tile per wave when the whole problem is one or two tiles (stem: 24 x 27): no idle tile slots
-    if (cfn_cdiv(M, 32) * cfn_cdiv(K, 32) <= 2) return wd_launch<2, 1, 1>(a, st);
+    if (p.v[2] == 1) return wd_launch<2, 1, 1>(a, st);
     return wd_launch<2, 3, 3>(a, st);
+}
+
+// false = not handled (the LDS-staged kernel runs): whole 16-byte groups of output columns and of positions, aligned gy / y.  v = {ACT, 2, TM, TN}
+bool dense_wd_plan(const DenseShape& s, DensePlan& p) {
+    const int* g = s.g;
+    const int To = (s.T + 2 * g[6] - g[0]) / g[3] + 1, Ho = (s.Hi + 2 * g[7] - g[1]) / g[4] + 1, Wo = (s.Wi + 2 * g[8] - g[2]) / g[5] + 1;
+    const int M = s.Cout, K = s.Cin * g[0] * g[1] * g[2];
+    const long Ql = (long)To * Ho * Wo;
+    if (To < 1 || Ho < 1 || Wo < 1 || Wo % 4 != 0 || Ql >= (1L << 30)) return false;
+    const int Q = (int)Ql;
+    if (!wd_common_ok(s.align_g, s.act, M, K, Q)) return false;
+    if ((long)s.Cin * s.T * s.Hi * s.Wi * 4 >= (1L << 31) - 64) return false;
+    // one 32x32 tile per wave when the whole problem is one or two tiles (stem: 24 x 27): no idle tile slots
+    const int tm = cfn_cdiv(M, 32) * cfn_cdiv(K, 32) <= 2 ? 1 : 3;
+    p = DensePlan{};
+    p.family = DN_WD; p.v[0] = s.act == CFN_ACT_RELU || s.act == CFN_ACT_SWISH ? s.act : CFN_ACT_NONE; p.v[1] = 2; p.v[2] = p.v[3] = tm;
+    wd_strips(s.N, M, K, Q, tm, tm, p.grid[0]);
+    p.grid[1] = p.grid[2] = 1; p.wg = 64 * WD_WAVES; p.lds = 0;
+    return true;
 }

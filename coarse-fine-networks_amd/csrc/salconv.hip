@@ -209,35 +209,38 @@ __global__ __launch_bounds__(256, NT == 4 ? 1 : 2) void sal_fwd_kernel(const Sal
     }
 }
 
+#define SAL_FWD_NT 1          // 32-position tiles per wave
+
+// false = shape not handled (the implicit GEMM runs).  v = {WI, NT, PRO}
+bool sal_fwd_plan(const DenseShape& s, int cus, DensePlan& p) {
+    if (!sal_common_ok(s) || s.Cout > 32 || (s.align_x & 15)) return false;
+    if ((long)SAL_CW * s.T * s.Hi * s.Wi * 4 >= 0x7fff0000L) return false;
+    const int To = (s.T - 1) / 2 + 1, Ho = s.Hi / 2;
+    const int WO = s.Wi / 2, TR = 32 / WO, RB = SAL_FWD_NT * TR, RIN = 2 * RB + 1, PITCH = s.Wi + 4;
+    p = DensePlan{};
+    p.bands = cfn_cdiv(Ho, RB);
+    p.chunk = sal_fwd_chunk(s.N, p.bands, To, cus > 0 ? cus : dense_cu_count());      // two resident workgroups per CU (LDS / registers)
+    p.nchunks = cfn_cdiv(To, p.chunk);
+    p.last = To - (p.nchunks - 1) * p.chunk;
+    const long blocks = (long)s.N * p.bands * p.nchunks;
+    if (blocks >= (1L << 31)) return false;
+    p.family = DN_SAL_FWD; p.v[0] = s.Wi; p.v[1] = SAL_FWD_NT; p.v[2] = s.pro;
+    p.items = (int)blocks; p.grid[0] = (unsigned)blocks; p.grid[1] = p.grid[2] = 1; p.wg = 256;
+    p.lds = ((size_t)4 * SAL_CW * RIN * PITCH + (size_t)SAL_FWD_NT * 4 * 16 * 64) * sizeof(float);
+    return true;
+}
+
 // -1 = shape not handled (the caller runs the implicit GEMM)
 int sal_fwd_try_launch(const float* x, const double* A, const double* B, int act, const float* w, float* y, double* sum,
                        double* sumsq, int N, int Cin, int Cout, int T, int Hi, int Wi, const int* g, hipStream_t st) {
-    static const int want[9] = {3, 3, 3, 2, 2, 2, 1, 1, 1};
-    for (int i = 0; i < 9; ++i) if (g[i] != want[i]) return -1;
-    if (Cin != SAL_CIN || Cout > 32 || (Wi != 56 && Wi != 28) || (Hi & 1) || Hi < 2 || ((uintptr_t)x & 15)) return -1;
-    if (A && act != CFN_ACT_RELU) return -1;
-    if (!A && act != CFN_ACT_NONE) return -1;
-    if ((long)SAL_CW * T * Hi * Wi * 4 >= 0x7fff0000L) return -1;
-    SalArgs a = {x, A, B, w, y, sum, sumsq, N, Cout, T, (T - 1) / 2 + 1, Hi, Hi / 2};
-    constexpr int NT = 1;                            // 32-position tiles per wave
-    const int WO = Wi / 2, TR = 32 / WO, RB = NT * TR, RIN = 2 * RB + 1, PITCH = Wi + 4;
-    a.bands = cfn_cdiv(a.Ho, RB);
-    // chunk length: whole rounds of one workgroup per CU where possible (a 1.25-round grid costs a full second round)
-    int cus = 256;
-    const int per_cu = 2;                            // resident workgroups per CU (LDS / registers)
-    { int dev = 0; hipDeviceProp_t pr; if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess) cus = pr.multiProcessorCount; }
-    int best = 4; double bestc = 1e30;
-    for (int to = 2; to <= 16; ++to) {
-        const long blocks = (long)N * a.bands * cfn_cdiv(a.To, to);
-        const double rounds = (double)cfn_cdiv(blocks, (long)cus * per_cu);
-        const double cost = rounds * (3.0 * to + 1.0);          // MFMA sets per block: 3 per output frame + the halo frame's one
-        if (cost < bestc - 1e-9) { bestc = cost; best = to; }
-    }
-    a.TO = best;
-    a.nchunks = cfn_cdiv(a.To, a.TO);
-    const long blocks = (long)N * a.bands * a.nchunks;
-    if (blocks >= (1L << 31)) return -1;
-    const size_t lds = ((size_t)4 * SAL_CW * RIN * PITCH + (size_t)NT * 4 * 16 * 64) * sizeof(float);
+    DenseShape s = dense_shape(N, Cin, Cout, T, Hi, Wi, g, act);
+    s.pro = A != nullptr; s.stats = sum != nullptr; s.align_x = (unsigned)((uintptr_t)x & 15);
+    DensePlan p;
+    if (!sal_fwd_plan(s, 0, p)) return -1;
+    SalArgs a = {x, A, B, w, y, sum, sumsq, N, Cout, T, (T - 1) / 2 + 1, Hi, Hi / 2, p.bands, p.nchunks, p.chunk};
+    constexpr int NT = SAL_FWD_NT;
+    const long blocks = p.grid[0];
+    const size_t lds = p.lds;
 #define SAL_GO(WIV, NTV, PROV)                                                                                         \
     do {                                                                                                               \
         auto k = sal_fwd_kernel<WIV, NTV, PROV>;                                                                       \
@@ -462,39 +465,56 @@ __global__ __launch_bounds__(512, 2) void sal_dgrad_kernel(const SalBwdArgs a) {
     }
 }
 
-// -1 = shape not handled
-int sal_dgrad_try_launch(const float* gy, const float* y, const double* gs, const double* gq, const float* w, const float* x,
-                         const double* A, const double* B, int act, float* gx, double* gA, double* gB, int N, int Cin, int Cout,
-                         int T, int Hi, int Wi, const int* g, hipStream_t st) {
-    static const int want[9] = {3, 3, 3, 2, 2, 2, 1, 1, 1};
-    for (int i = 0; i < 9; ++i) if (g[i] != want[i]) return -1;
-    if (Cin != SAL_CIN || Cout != 24 || (Wi != 56 && Wi != 28) || (Hi & 1) || Hi < 2) return -1;
-    if (A && act != CFN_ACT_RELU) return -1;
-    if (!A && act != CFN_ACT_NONE) return -1;
-    if ((long)24 * T * Hi * Wi * 4 >= 0x7fff0000L) return -1;
-    SalBwdArgs a = {};
-    a.gy = gy; a.y = gq ? y : nullptr; a.gs = gs; a.gq = gq; a.w = w; a.x = x; a.pa = A; a.pb = B; a.gx = gx; a.gA = gA; a.gB = gB;
-    a.N = N; a.T = T; a.To = (T - 1) / 2 + 1; a.Hi = Hi; a.Ho = Hi / 2;
-    const int WO = Wi / 2, TRA = 32 / WO, BA = 4 * TRA, GROWS = BA + 1, GP = (WO + 4) & ~3;
-    a.bands = cfn_cdiv(a.Ho, BA);
-    const int NU = (T + 1) / 2;
-    int cus = 256;
-    { int dev = 0; hipDeviceProp_t pr; if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess) cus = pr.multiProcessorCount; }
+// false = shape not handled.  v = {WI, PRO, HASY}.  The kernel moves g', y, x and gx eight bytes at a time (raw_buffer_load_b64 / _store_b64 at
+// offsets that are multiples of 8 from the tensor's start), so every tensor it touches has to start on an 8-byte boundary.  The gate is a
+// precaution: the kernel was never run on a tensor 4 bytes off, so that it would misbehave there is supposed, not shown (tensors from the
+// framework's allocator are 256-byte aligned: the gate costs the model nothing).
+bool sal_dgrad_plan(const DenseShape& s, int cus, DensePlan& p) {
+    if (!sal_common_ok(s) || s.Cout != 24) return false;
+    if (((s.align_g | s.align_out) & 7) || (s.pro && (s.align_x & 7))) return false;
+    if ((long)24 * s.T * s.Hi * s.Wi * 4 >= 0x7fff0000L) return false;
+    const int Ho = s.Hi / 2;
+    const int WO = s.Wi / 2, TRA = 32 / WO, BA = 4 * TRA, GROWS = BA + 1, GP = (WO + 4) & ~3;
+    p = DensePlan{};
+    p.bands = cfn_cdiv(Ho, BA);
+    const int NU = (s.T + 1) / 2;
+    if (cus <= 0) cus = dense_cu_count();
     // chunk length (even): whole rounds of 2 groups per CU, the weight image (62 KB per workgroup) amortised over >= 8 steps where the clip allows
     int best = 2; double bestc = 1e30;
     for (int ch = 2; ch <= 64; ch += 2) {
-        const long groups = (long)N * a.bands * cfn_cdiv(NU, ch);
+        const long groups = (long)s.N * p.bands * cfn_cdiv(NU, ch);
         const double rounds = (double)cfn_cdiv(groups, 2L * cus);
         const double cost = rounds * (ch + 1.5);                // + the workgroup's start-up (weights, two frames) in steps
         if (cost < bestc - 1e-9) { bestc = cost; best = ch; }
     }
-    a.CH = best;
-    a.nchunks = cfn_cdiv(NU, a.CH);
-    const long groups = (long)N * a.bands * a.nchunks;
-    if (groups >= (1L << 30)) return -1;
-    a.ngroups = (int)groups;
-    const long blocks = (groups + 1) / 2;
-    const size_t lds = ((size_t)648 * 24 + (size_t)2 * SAL_CIN * 2 * GROWS * GP + 96) * sizeof(float);
+    p.chunk = best;
+    p.nchunks = cfn_cdiv(NU, p.chunk);
+    p.last = NU - (p.nchunks - 1) * p.chunk;
+    const long groups = (long)s.N * p.bands * p.nchunks;
+    if (groups >= (1L << 30)) return false;
+    p.items = (int)groups;
+    p.family = DN_SAL_DGRAD; p.v[0] = s.Wi; p.v[1] = s.pro; p.v[2] = s.y;
+    p.grid[0] = (unsigned)((groups + 1) / 2); p.grid[1] = p.grid[2] = 1; p.wg = 512;
+    p.lds = ((size_t)648 * 24 + (size_t)2 * SAL_CIN * 2 * GROWS * GP + 96) * sizeof(float);
+    return true;
+}
+
+// -1 = shape not handled
+int sal_dgrad_try_launch(const float* gy, const float* y, const double* gs, const double* gq, const float* w, const float* x,
+                         const double* A, const double* B, int act, float* gx, double* gA, double* gB, int N, int Cin, int Cout,
+                         int T, int Hi, int Wi, const int* g, hipStream_t st) {
+    DenseShape s = dense_shape(N, Cin, Cout, T, Hi, Wi, g, act);
+    s.pro = A != nullptr; s.gs = gs != nullptr; s.y = gq != nullptr;
+    s.align_g = (unsigned)(((uintptr_t)gy | (uintptr_t)(gq ? y : gy)) & 15); s.align_x = (unsigned)((uintptr_t)(A ? x : nullptr) & 15);
+    s.align_out = (unsigned)((uintptr_t)gx & 15);
+    DensePlan p;
+    if (!sal_dgrad_plan(s, 0, p)) return -1;
+    SalBwdArgs a = {};
+    a.gy = gy; a.y = gq ? y : nullptr; a.gs = gs; a.gq = gq; a.w = w; a.x = x; a.pa = A; a.pb = B; a.gx = gx; a.gA = gA; a.gB = gB;
+    a.N = N; a.T = T; a.To = (T - 1) / 2 + 1; a.Hi = Hi; a.Ho = Hi / 2;
+    a.bands = p.bands; a.CH = p.chunk; a.nchunks = p.nchunks; a.ngroups = p.items;
+    const long blocks = p.grid[0];
+    const size_t lds = p.lds;
 #define SAL_DG(WIV, PROV, YV)                                                                                          \
     do {                                                                                                               \
         auto k = sal_dgrad_kernel<WIV, PROV, YV>;                                                                      \
@@ -686,38 +706,51 @@ __global__ __launch_bounds__(512, 2) void sal_wgrad_kernel(const SalBwdArgs a) {
     }
 }
 
-// -1 = shape not handled
-int sal_wgrad_try_launch(const float* gy, const float* y, const double* gs, const double* gq, const float* x, const double* A,
-                         const double* B, int act, double* gw, int N, int Cin, int Cout, int T, int Hi, int Wi, const int* g,
-                         hipStream_t st) {
-    static const int want[9] = {3, 3, 3, 2, 2, 2, 1, 1, 1};
-    for (int i = 0; i < 9; ++i) if (g[i] != want[i]) return -1;
-    if (Cin != SAL_CIN || Cout != 24 || (Wi != 56 && Wi != 28) || (Hi & 1) || Hi < 2 || ((uintptr_t)x & 15)) return -1;
-    if (A && act != CFN_ACT_RELU) return -1;
-    if (!A && act != CFN_ACT_NONE) return -1;
-    if ((long)24 * T * Hi * Wi * 4 >= 0x7fff0000L) return -1;
-    SalBwdArgs a = {};
-    a.gy = gy; a.y = gq ? y : nullptr; a.gs = gs; a.gq = gq; a.x = x; a.pa = A; a.pb = B; a.gw = gw;
-    a.N = N; a.T = T; a.To = (T - 1) / 2 + 1; a.Hi = Hi; a.Ho = Hi / 2;
-    const int WO = Wi / 2, RB = 56 / WO, RIN = 2 * RB + 1, PITCH = Wi + 4;
-    a.bands = cfn_cdiv(a.Ho, RB);
-    int cus = 256;
-    { int dev = 0; hipDeviceProp_t pr; if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess) cus = pr.multiProcessorCount; }
+// false = shape not handled.  v = {WI, PRO, HASY}.  x is read 16 bytes at a time, g' and y 8 bytes at a time (the g' / y gate: a precaution,
+// as in sal_dgrad_plan)
+bool sal_wgrad_plan(const DenseShape& s, int cus, DensePlan& p) {
+    if (!sal_common_ok(s) || s.Cout != 24 || (s.align_x & 15) || (s.align_g & 7)) return false;
+    if ((long)24 * s.T * s.Hi * s.Wi * 4 >= 0x7fff0000L) return false;
+    const int To = (s.T - 1) / 2 + 1, Ho = s.Hi / 2;
+    const int WO = s.Wi / 2, RB = 56 / WO, RIN = 2 * RB + 1, PITCH = s.Wi + 4;
+    p = DensePlan{};
+    p.bands = cfn_cdiv(Ho, RB);
+    if (cus <= 0) cus = dense_cu_count();
     // chunk length (even): items spread evenly over one persistent workgroup per CU; a chunk pays one extra (halo) frame
     int best = 2; double bestc = 1e30;
     for (int ch = 2; ch <= 64; ch += 2) {
-        const long items = (long)N * a.bands * cfn_cdiv(a.To, ch);
+        const long items = (long)s.N * p.bands * cfn_cdiv(To, ch);
         const double per = (double)cfn_cdiv(items, cus);
         const double cost = per * (ch + 0.75);
         if (cost < bestc - 1e-9) { bestc = cost; best = ch; }
     }
-    a.CH = best;
-    a.nchunks = cfn_cdiv(a.To, a.CH);
-    const long items = (long)N * a.bands * a.nchunks;
-    if (items >= (1L << 30)) return -1;
-    a.ngroups = (int)items;
-    const long blocks = items < cus ? items : cus;
-    const size_t lds = ((size_t)3 * SAL_CIN * RIN * PITCH + (size_t)SAL_CIN * 57 + 96) * sizeof(float);
+    p.chunk = best;
+    p.nchunks = cfn_cdiv(To, p.chunk);
+    p.last = To - (p.nchunks - 1) * p.chunk;
+    const long items = (long)s.N * p.bands * p.nchunks;
+    if (items >= (1L << 30)) return false;
+    p.items = (int)items;
+    p.family = DN_SAL_WGRAD; p.v[0] = s.Wi; p.v[1] = s.pro; p.v[2] = s.y;
+    p.grid[0] = (unsigned)(items < cus ? items : cus); p.grid[1] = p.grid[2] = 1; p.wg = 512;
+    p.lds = ((size_t)3 * SAL_CIN * RIN * PITCH + (size_t)SAL_CIN * 57 + 96) * sizeof(float);
+    return true;
+}
+
+// -1 = shape not handled
+int sal_wgrad_try_launch(const float* gy, const float* y, const double* gs, const double* gq, const float* x, const double* A,
+                         const double* B, int act, double* gw, int N, int Cin, int Cout, int T, int Hi, int Wi, const int* g,
+                         hipStream_t st) {
+    DenseShape s = dense_shape(N, Cin, Cout, T, Hi, Wi, g, act);
+    s.pro = A != nullptr; s.gs = gs != nullptr; s.y = gq != nullptr;
+    s.align_g = (unsigned)(((uintptr_t)gy | (uintptr_t)(gq ? y : gy)) & 15); s.align_x = (unsigned)((uintptr_t)x & 15);
+    DensePlan p;
+    if (!sal_wgrad_plan(s, 0, p)) return -1;
+    SalBwdArgs a = {};
+    a.gy = gy; a.y = gq ? y : nullptr; a.gs = gs; a.gq = gq; a.x = x; a.pa = A; a.pb = B; a.gw = gw;
+    a.N = N; a.T = T; a.To = (T - 1) / 2 + 1; a.Hi = Hi; a.Ho = Hi / 2;
+    a.bands = p.bands; a.CH = p.chunk; a.nchunks = p.nchunks; a.ngroups = p.items;
+    const long blocks = p.grid[0];
+    const size_t lds = p.lds;
 #define SAL_WG(WIV, PROV, YV)                                                                                          \
     do {                                                                                                               \
         auto k = sal_wgrad_kernel<WIV, PROV, YV>;                                                                      \

@@ -248,34 +248,36 @@ __global__ __launch_bounds__(256, 2) void sal_fwdb_kernel(const SalBArgs a) {
     }
 }
 
-// -1 = shape not handled, or cfn_pw_split_terms != 6 (the caller runs the exact-fp32 kernel of salconv.hip); same contract as sal_fwd_try_launch
+// false = shape not handled, or cfn_pw_split_terms != 6 (the exact-fp32 kernel of salconv.hip runs).  v = {WI, PRO}
+bool salb_fwd_plan(const DenseShape& s, int cus, DensePlan& p) {
+    if (!sal_common_ok(s) || s.Cout > 32 || (s.align_x & 15)) return false;
+    if (pws_terms_now() != 6) return false;                           // the arithmetic setting of the pointwise contractions governs this one as well
+    if ((long)SALB_CIN * s.T * s.Hi * s.Wi * 4 >= 0x7fff0000L) return false;
+    const int To = (s.T - 1) / 2 + 1, Ho = s.Hi / 2;
+    const int WO = s.Wi / 2, TR = 32 / WO, RIN = 2 * TR + 1, PITCHC = s.Wi + 1;
+    p = DensePlan{};
+    p.bands = cfn_cdiv(Ho, TR);
+    p.chunk = sal_fwd_chunk(s.N, p.bands, To, cus > 0 ? cus : dense_cu_count());
+    p.nchunks = cfn_cdiv(To, p.chunk);
+    p.last = To - (p.nchunks - 1) * p.chunk;
+    const long blocks = (long)s.N * p.bands * p.nchunks;
+    if (blocks >= (1L << 31)) return false;
+    p.family = DN_SALB; p.v[0] = s.Wi; p.v[1] = s.pro;
+    p.items = (int)blocks; p.grid[0] = (unsigned)blocks; p.grid[1] = p.grid[2] = 1; p.wg = 256;
+    p.lds = (size_t)2 * 3 * RIN * PITCHC * SALB_PIX + (size_t)4 * 4 * 64 * 16;
+    return true;
+}
+
+// -1 = not handled (the caller runs the exact-fp32 kernel of salconv.hip); same contract as sal_fwd_try_launch
 int salb_fwd_try_launch(const float* x, const double* A, const double* B, int act, const float* w, float* y, double* sum, double* sumsq, int N, int Cin, int Cout,
                         int T, int Hi, int Wi, const int* g, hipStream_t st) {
-    static const int want[9] = {3, 3, 3, 2, 2, 2, 1, 1, 1};
-    for (int i = 0; i < 9; ++i) if (g[i] != want[i]) return -1;
-    if (Cin != SALB_CIN || Cout > 32 || (Wi != 56 && Wi != 28) || (Hi & 1) || Hi < 2 || ((uintptr_t)x & 15)) return -1;
-    if (A && act != CFN_ACT_RELU) return -1;
-    if (!A && act != CFN_ACT_NONE) return -1;
-    if (pws_terms_now() != 6) return -1;                              // the arithmetic setting of the pointwise contractions governs this one as well
-    if ((long)SALB_CIN * T * Hi * Wi * 4 >= 0x7fff0000L) return -1;
-    SalBArgs a = {x, A, B, w, y, sum, sumsq, N, Cout, T, (T - 1) / 2 + 1, Hi, Hi / 2};
-    const int WO = Wi / 2, TR = 32 / WO, RIN = 2 * TR + 1, PITCHC = Wi + 1;
-    a.bands = cfn_cdiv(a.Ho, TR);
-    // chunk length: whole rounds of two workgroups per CU where possible (a 1.25-round grid costs a full second round)
-    int cus = 256;
-    { int dev = 0; hipDeviceProp_t pr; if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess) cus = pr.multiProcessorCount; }
-    int best = 4; double bestc = 1e30;
-    for (int to = 2; to <= 16; ++to) {
-        const long blocks = (long)N * a.bands * cfn_cdiv(a.To, to);
-        const double rounds = (double)cfn_cdiv(blocks, (long)cus * 2);
-        const double cost = rounds * (3.0 * to + 1.0);               // MFMA sets per block: 3 per output frame + the halo frame's one
-        if (cost < bestc - 1e-9) { bestc = cost; best = to; }
-    }
-    a.TO = best;
-    a.nchunks = cfn_cdiv(a.To, a.TO);
-    const long blocks = (long)N * a.bands * a.nchunks;
-    if (blocks >= (1L << 31)) return -1;
-    const size_t lds = (size_t)2 * 3 * RIN * PITCHC * SALB_PIX + (size_t)4 * 4 * 64 * 16;
+    DenseShape s = dense_shape(N, Cin, Cout, T, Hi, Wi, g, act);
+    s.pro = A != nullptr; s.stats = sum != nullptr; s.align_x = (unsigned)((uintptr_t)x & 15);
+    DensePlan p;
+    if (!salb_fwd_plan(s, 0, p)) return -1;
+    SalBArgs a = {x, A, B, w, y, sum, sumsq, N, Cout, T, (T - 1) / 2 + 1, Hi, Hi / 2, p.bands, p.nchunks, p.chunk};
+    const size_t lds = p.lds;
+    const long blocks = p.grid[0];
 #define SALB_GO(WIV, PROV)                                                                                              \
     do {                                                                                                                \
         auto k = sal_fwdb_kernel<WIV, PROV>;                                                                            \

@@ -5,7 +5,7 @@
 // of input rows of one frame in LDS once (coalesced float4 rows, zero halo) and the im2col operand of the MFMA comes out of
 // LDS:  Y[co][pos] = sum_k W[co][k] * X[k][pos],  k = (ci,kh,kw) -> v_mfma_f32_32x32x2 with the 32 x 28 weight operand
 // resident in registers (14 k-pairs), lane <-> output position, so every store instruction writes full 128-byte lines.
-#include "cfn_common.h"
+#include "dense_plan.h"
 #include <stdlib.h>
 
 typedef float __attribute__((ext_vector_type(16))) st16;
@@ -89,18 +89,37 @@ __global__ __launch_bounds__(256) void stem_fwd_kernel(const StemArgs a) {
     }
 }
 
+static const int kStemG[9] = {1, 3, 3, 1, 2, 2, 0, 1, 1};
+
+// false = shape not handled (the implicit GEMM runs).  v = {3}; chunk = RB, the band's output rows
+bool stem_fwd_plan(const DenseShape& s, DensePlan& p) {
+    if (s.Cin != 3 || s.Cout > 32 || (s.Wi & 3) || (s.Hi & 1) || (s.align_x & 15)) return false;
+    const int Ho = s.Hi / 2;
+    p = DensePlan{};
+    p.chunk = (Ho % 8 == 0) ? 8 : 4;
+    p.bands = cfn_cdiv(Ho, p.chunk);
+    p.lds = (size_t)3 * (2 * p.chunk + 1) * (s.Wi + 8) * sizeof(float);
+    if (p.lds > 64 * 1024) return false;
+    const long blocks = (long)s.N * s.T * p.bands;
+    if (blocks >= (1L << 31)) return false;
+    p.family = DN_STEM_FWD; p.v[0] = 3;
+    p.items = (int)blocks; p.grid[0] = (unsigned)blocks; p.grid[1] = p.grid[2] = 1; p.wg = 256;
+    return true;
+}
+
 // -1 = shape not handled (the caller uses the implicit-GEMM path)
 int stem_fwd_try_launch(const float* x, const float* w, float* y, int N, int Cimg, int Cout, int T, int Hi, int Wi, hipStream_t st) {
-    if (Cimg != 3 || Cout > 32 || (Wi & 3) || (Hi & 1) || ((uintptr_t)x & 15)) return -1;
+    DenseShape s = dense_shape(N, Cimg, Cout, T, Hi, Wi, kStemG, CFN_ACT_NONE);
+    s.align_x = (unsigned)((uintptr_t)x & 15);
+    DensePlan p;
+    if (!stem_fwd_plan(s, p)) return -1;
     StemArgs a = {x, w, y, N, Cout, T, Hi, Wi, Hi / 2, Wi / 2};
-    a.RB = (a.Ho % 8 == 0) ? 8 : 4;
+    a.RB = p.chunk;
     a.RIN = 2 * a.RB + 1;
     a.WPAD = Wi + 8;
-    a.bands = cfn_cdiv(a.Ho, a.RB);
-    const size_t lds = (size_t)3 * a.RIN * a.WPAD * sizeof(float);
-    if (lds > 64 * 1024) return -1;
-    const long blocks = (long)N * T * a.bands;
-    if (blocks >= (1L << 31)) return -1;
+    a.bands = p.bands;
+    const size_t lds = p.lds;
+    const long blocks = p.grid[0];
     auto k = stem_fwd_kernel<3>;
     if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(256), lds, st, a);
@@ -226,19 +245,35 @@ __global__ __launch_bounds__(512, 2) void stem_wgrad_kernel(const StemWgArgs a) 
 }
 
 // -1 = shape not handled (the caller uses the implicit-GEMM path); probe: 0 = handled, nothing launched
-int stem_wgrad_try_launch(const float* gy, const float* x, double* gw, int N, int Cimg, int Cout, int T, int Hi, int Wi, hipStream_t st, bool probe) {
-    if (Cimg != 3 || Cout != 24 || Hi != 224 || Wi != 224 || (((uintptr_t)x | (uintptr_t)gy) & 15)) return -1;
-    if ((long)24 * T * 112 * 112 * 4 >= 0x7fff0000L) return -1;
-    const long items = (long)N * T * 28;
-    if (items >= (1L << 30)) return -1;
-    if (probe) return 0;
-    static int cus = 0;
-    if (!cus) { int dev = 0; hipDeviceProp_t pr; cus = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess) ? pr.multiProcessorCount : 256; }
+// false = shape not handled.  cus < 0: the shape gates only; 0: the current device's CUs (asked once per process).  chunk = items per workgroup
+bool stem_wgrad_plan(const DenseShape& s, int cus, DensePlan& p) {
+    if (s.Cin != 3 || s.Cout != 24 || s.Hi != 224 || s.Wi != 224 || ((s.align_x | s.align_g) & 15)) return false;
+    if ((long)24 * s.T * 112 * 112 * 4 >= 0x7fff0000L) return false;
+    const long items = (long)s.N * s.T * 28;
+    if (items >= (1L << 30)) return false;
+    p = DensePlan{};
+    p.family = DN_STEM_WGRAD; p.items = (int)items; p.bands = 28;
+    if (cus < 0) return true;
+    static int dev_cus = 0;
+    if (cus == 0) { if (!dev_cus) dev_cus = dense_cu_count(); cus = dev_cus; }
     long blocks = (long)cus * 2;      // persistent workgroups per CU (8 x 256 x 224 x 224: 1: 726 us, 2: 655 us; gather-form kernel 1346)
     if (blocks > items) blocks = items;
     const long per = (items + blocks - 1) / blocks;
     blocks = (items + per - 1) / per;
-    StemWgArgs a = {gy, x, gw, N, T, (int)items, (int)per};
+    p.chunk = (int)per; p.nchunks = (int)blocks; p.last = (int)(items - (blocks - 1) * per);
+    p.grid[0] = (unsigned)blocks; p.grid[1] = p.grid[2] = 1; p.wg = 512;
+    p.lds = 0;      // no dynamic LDS: the kernel's two images are static __shared__ arrays
+    return true;
+}
+
+int stem_wgrad_try_launch(const float* gy, const float* x, double* gw, int N, int Cimg, int Cout, int T, int Hi, int Wi, hipStream_t st, bool probe) {
+    DenseShape s = dense_shape(N, Cimg, Cout, T, Hi, Wi, kStemG, CFN_ACT_NONE);
+    s.align_x = (unsigned)((uintptr_t)x & 15); s.align_g = (unsigned)((uintptr_t)gy & 15);
+    DensePlan p;
+    if (!stem_wgrad_plan(s, probe ? -1 : 0, p)) return -1;
+    if (probe) return 0;
+    const long blocks = p.grid[0];
+    StemWgArgs a = {gy, x, gw, N, T, p.items, p.chunk};
     hipLaunchKernelGGL(stem_wgrad_kernel, dim3((unsigned)blocks), dim3(512), 0, st, a);
     return cfn_check_launch("stem_conv_wgrad");
 }

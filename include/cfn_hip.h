@@ -213,6 +213,14 @@ int cfn_conv3d_dense_bwd_data(const float* gy, const float* y, const double* gsu
 int cfn_conv3d_dense_bwd_weight(const float* gy, const float* y, const double* gsum, const double* gsumsq, const float* x,
                                 const double* A, const double* B, int act, double* gw, int N, int Cin, int Cout, int T, int Hi,
                                 int Wi, const int* geom, void* stream);
+/* Which kernel a dense conv call would launch: op 0 cfn_conv3d_dense_fwd, 1 _bwd_data, 2 _bwd_weight, 3 cfn_stem_conv_fwd, 4 cfn_stem_conv_bwd_weight
+ * (geom ignored for 3, 4) -- the plan functions the launchers call, asked without a device or a stream.  flags: 1 = prologue A, B present (ReLU;
+ * with 32: Swish), 2 = statistics (forward: sum, sumsq; backward: gsum), 4 = gsumsq and y present, 16 = every tensor misaligned by 4 bytes; one alone:
+ * 64 = x, 128 = gy and y, 256 = the output (y / gx).  cus: the
+ * number of CUs to plan for, 0 = those of the current device (256 where there is none).  Writes one line into out: family, kernel with its
+ * template arguments, grid= (workgroups), wg=, lds= (dynamic LDS bytes); the saliency kernels add bands= chunk= nchunks= last= (length of the last chunk) items=, the
+ * stem kernels bands= chunk= (rows per band / items per workgroup) items=; "declined" where the entry point would refuse the call. */
+int cfn_conv3d_dense_route(int op, int N, int Cin, int Cout, int T, int Hi, int Wi, const int* geom, int flags, int cus, char* out, int cap);
 
 /* ---- Gaussian temporal alignment: Gaussian.forward x3d_coarse.py:256-286 (called at :651 / :657).
  * meta (B,4) int64 [start, frames, nf, step] (only columns 0 and 3 are read), mask (B,Tf), gx (B*crops,K) CDF knots or NULL

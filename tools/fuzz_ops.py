@@ -11,6 +11,8 @@ sys.path.insert(0, os.path.join(ROOT, 'coarse-fine-networks_amd'))
 import torch                      # noqa: E402
 import torch.nn.functional as F   # noqa: E402
 from cfn_hip import ops           # noqa: E402
+sys.path.insert(0, os.path.join(ROOT, 'tests'))
+import dense_ref64                # noqa: E402  (the fp64 reference of the dense convs)
 
 DEV = 'cuda'
 
@@ -148,7 +150,8 @@ def pool_case(g, rng):
 
 
 def dense_case(g, rng):
-    """dense implicit-GEMM conv of the Grid Pool saliency branch (csrc/salconv.hip, salconvb.hip, the im2col route): fp64 reference on the CPU"""
+    """dense implicit-GEMM conv of the Grid Pool saliency branch (csrc/salconv.hip, salconvb.hip, the im2col route): the fp64 reference of
+    tests/dense_ref64.py on the device"""
     N, Ci, Co = rng.choice([1, 2]), rng.choice([3, 4, 5, 8, 24, 24, 24]), rng.choice([1, 4, 7, 20, 24, 24, 40])
     T, H = rng.choice([1, 2, 5, 6, 9, 12, 17]), rng.choice([7, 8, 9, 14, 16, 20, 28, 56])
     W = rng.choice([H, H, 28, 56, 16, 7])
@@ -160,19 +163,19 @@ def dense_case(g, rng):
     A = (1 + 0.2 * torch.randn(N, Ci, generator=g)).to(DEV).requires_grad_(True) if pro else None
     B = (0.3 * torch.randn(N, Ci, generator=g)).to(DEV).requires_grad_(True) if pro else None
     y, s, q = ops.conv3d_dense(x, w, k, st, pd, A, B, act if pro else 0, True)
-    xd, wd = x.detach().double().cpu().requires_grad_(True), w.detach().double().cpu().requires_grad_(True)
-    Ad = A.detach().double().cpu().requires_grad_(True) if pro else None
-    Bd = B.detach().double().cpu().requires_grad_(True) if pro else None
-    z = act_ref(xd * Ad.view(N, Ci, 1, 1, 1) + Bd.view(N, Ci, 1, 1, 1), act) if pro else xd
-    ref = F.conv3d(z, wd, stride=st, padding=pd)
-    e = [relerr(y.cpu(), ref), relerr(s.cpu(), ref.sum((2, 3, 4))), relerr(q.cpu(), (ref * ref).sum((2, 3, 4)))]
-    go = torch.randn(y.shape, generator=g)
-    gs, gq = torch.randn(s.shape, generator=g) * 0.01, torch.randn(q.shape, generator=g) * 0.001
+    geom = tuple(k) + tuple(st) + tuple(pd)
+    Ad, Bd = (A.detach().double(), B.detach().double()) if pro else (None, None)
+    w2 = w.detach().reshape(Co, -1)
+    fw = dense_ref64.forward(x.detach(), Ad, Bd, act if pro else 0, w2, geom)
+    e = [relerr(y, fw['y']), relerr(s, fw['s']), relerr(q, fw['q'])]
+    go = torch.randn(y.shape, generator=g).to(DEV)
+    gs, gq = (torch.randn(s.shape, generator=g) * 0.01).to(DEV).to(s.dtype), (torch.randn(q.shape, generator=g) * 0.001).to(DEV).to(q.dtype)
     ins = (x, w) + ((A, B) if pro else ())
-    gr = torch.autograd.grad((y, s, q), ins, (go.to(DEV), gs.to(DEV).to(s.dtype), gq.to(DEV).to(q.dtype)))
-    loss = (ref * go.double()).sum() + (ref.sum((2, 3, 4)) * gs.double()).sum() + ((ref * ref).sum((2, 3, 4)) * gq.double()).sum()
-    grr = torch.autograd.grad(loss, (xd, wd) + ((Ad, Bd) if pro else ()))
-    e += [relerr(a.cpu(), b) for a, b in zip(gr, grr)]
+    gr = torch.autograd.grad((y, s, q), ins, (go, gs, gq))
+    bw = dense_ref64.backward(go, y.detach(), gs, gq, w2, x.detach(), Ad, Bd, act if pro else 0, geom)
+    e += [relerr(gr[0], bw['gx']), relerr(gr[1].reshape(Co, -1), bw['gw'])]
+    if pro:
+        e += [relerr(gr[2], bw['gA']), relerr(gr[3], bw['gB'])]
     return max(e), e
 
 

@@ -450,6 +450,15 @@ def pwconv_route(op, N, Cin, Cout, T, H, W, stride=1, act=ACT_NONE, flags=0):
     return out.value.decode()
 
 
+def dwconv3d_route(op, dtype, N, C, T, H, W, stride=1, act=ACT_NONE, flags=0):
+    """the kernel a depthwise 3x3x3 conv of this shape runs on (cfn_dwconv3d_route, include/cfn_hip.h): host only, no GPU needed.
+    op 0 forward, 1 data gradient, 2 weight gradient, 3 one-pass backward; dtype 0 fp32, 1 bf16, 2 fp16; H, W: the input plane"""
+    out = ctypes.create_string_buffer(256)
+    if query('cfn_dwconv3d_route', op, dtype, N, C, T, H, W, stride, act, flags, out, 256):
+        raise RuntimeError(last_error())
+    return out.value.decode()
+
+
 def _sfx(t):
     """entry-point suffix for the element type of an activation tensor"""
     return '_bf16' if t.dtype == torch.bfloat16 else ('_f16' if t.dtype == torch.float16 else '')

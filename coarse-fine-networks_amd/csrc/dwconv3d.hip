@@ -18,6 +18,7 @@
 // find their halo frames in that XCD's L2.
 #include "cfn_common.h"
 #include "h16.h"
+#include "dw_plan.h"
 
 // Element type of the activation tensors.  This file is compiled twice: as is (fp32 storage) and through
 // dwconv3d_bf16.hip (#define DW_BF16: bf16 storage, identical fp32 arithmetic, entry points suffixed _bf16, argument
@@ -26,11 +27,9 @@
 #ifdef DW_BF16
 typedef unsigned short dwe_t;
 #define DW_ES 2
-#define DWN(name) H16N(name)
 #else
 typedef float dwe_t;
 #define DW_ES 4
-#define DWN(name) name
 #endif
 typedef float __attribute__((ext_vector_type(4))) dw_f4;
 typedef float __attribute__((ext_vector_type(2))) dw_f2;
@@ -69,23 +68,6 @@ __device__ __forceinline__ void dw_bst2(dw_f2 v, __amdgpu_buffer_rsrc_t r, int v
     __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(i2v, v), r, vo, so, 0);
 }
 __device__ __forceinline__ float dw_rt(float v) { return v; }
-#endif
-
-enum { DW_FWD = 0, DW_DGRAD = 1, DW_WGRAD = 2 };
-int DWN(dw_small_fwd_try)(const dwe_t* x, const double* A, const double* B, int act, const float* w, dwe_t* y, double* sum, double* sumsq,
-                          int N, int C, int T, int Hi, int Wi, int stride, hipStream_t st, bool probe);   // dwsmall.hip (every element type)
-int DWN(dw_flatb_try)(const dwe_t* gy, const dwe_t* y, const double* gs, const double* gq, const float* w, const dwe_t* x,
-                      const double* A, const double* B, int act, dwe_t* gx, double* gA, double* gB, double* gw,
-                      int N, int C, int T, int H, int W, hipStream_t st, bool probe);                  // dwflatb.hip (every element type)
-int DWN(dw_cpbx_try)(const dwe_t* gy, const dwe_t* y, const double* gs, const double* gq, const float* w, const dwe_t* x,
-                     const double* A, const double* B, int act, dwe_t* gx, double* gA, double* gB, double* gw,
-                     int N, int C, int T, int H, int W, hipStream_t st, bool probe);                   // dwcpbx.hip (every element type)
-#ifndef DW_BF16
-int dw_flat_fwd_try(const float* x, const double* A, const double* B, int act, const float* w, float* y, double* sum, double* sumsq,
-                    int N, int C, int T, int Hi, int Wi, int stride, hipStream_t st, bool probe);    // dwflat.hip (fp32)
-#else
-int DWN(dw_cp_fwd_try)(const dwe_t* x, const double* A, const double* B, int act, const float* w, dwe_t* y, double* sum, double* sumsq,
-                       int N, int C, int T, int Hi, int Wi, int stride, hipStream_t st, bool probe);  // dwcp.hip (bf16 / fp16)
 #endif
 
 struct DwArgs {
@@ -1081,11 +1063,12 @@ __global__ __launch_bounds__(256) void dw3d_dgrad_s2_fast_kernel(const DwS2Args 
     }
 }
 
-// ---------------------------------------------------------------------------------------------
-// host side: geometry heuristics + dispatch
-// ---------------------------------------------------------------------------------------------
-struct DwPlan { int HS, VEC, MAXLD, threads; bool UNIW; size_t lds; unsigned blocks; };
 
+// ---------------------------------------------------------------------------------------------
+// host side: the plans of the band kernels and of the stride-2 data gradient (dw_plan.h; once, in the fp32 compilation), the launchers
+// and the entry points of this element type
+// ---------------------------------------------------------------------------------------------
+#ifndef DW_BF16
 // force_hs > 0: strip height asked for by the caller (fused backward), taken when it divides the plane
 static int pick_hs(int Ho, int mode, int S, int force_hs) {
     if (force_hs > 0 && Ho % force_hs == 0) return force_hs;
@@ -1101,29 +1084,31 @@ static int pick_hs(int Ho, int mode, int S, int force_hs) {
     return 1;
 }
 
-static int dw_plan_impl(DwArgs& a, int S, int mode, DwPlan& pl, bool allow_flat, int force_hs) {
-    a.Ho = (a.Hi + 2 - 3) / S + 1;
-    a.Wo = (a.Wi + 2 - 3) / S + 1;
-    const int HS = pick_hs(a.Ho, mode, S, force_hs);
-    const int G = a.Ho / HS;
-    if (a.Wo > 512) return cfn_fail(CFN_ERR_UNSUPPORTED, "dwconv3d: output width %d > 512 not supported", a.Wo);
+// the band scheme's geometry into r (the fields of DwArgs); r.v = {MODE, S, HS, VEC, MAXLD, UNIW} of dw3d_kernel
+static int band_plan_impl(const DwShape& s, int mode, DwRoute& r, bool allow_flat, int force_hs) {
+    const int S = s.stride, Hi = s.Hi, Wi = s.Wi, T = s.T;
+    r.Ho = (Hi + 2 - 3) / S + 1;
+    r.Wo = (Wi + 2 - 3) / S + 1;
+    const int HS = pick_hs(r.Ho, mode, S, force_hs);
+    const int G = r.Ho / HS;
+    if (r.Wo > 512) return cfn_fail(CFN_ERR_UNSUPPORTED, "dwconv3d: output width %d > 512 not supported", r.Wo);
     // loader: whole-float4 rows (4); else, when the width is even and the plane a whole number of float4s, float4s over
     // the contiguous plane (2, needs the band to cover the plane); else scalar (1)
-    const bool aligned16 = ((uintptr_t)a.src % 16 == 0) && (mode != DW_DGRAD || a.src2 == nullptr || (uintptr_t)a.src2 % 16 == 0);
-    int VEC = (a.Wi % 4 == 0) ? 4 : ((allow_flat && a.Wi % 2 == 0 && (a.Hi * a.Wi) % 4 == 0 && aligned16) ? 2 : 1);
+    const bool aligned16 = (mode == DW_DGRAD ? s.align_g : s.align_x) == 0;      // the staged tensors: x, or gy and y
+    int VEC = (Wi % 4 == 0) ? 4 : ((allow_flat && Wi % 2 == 0 && (Hi * Wi) % 4 == 0 && aligned16) ? 2 : 1);
     int GB;
     for (;; ) {
         const int LVh = VEC == 1 ? 1 : 4;
-        a.XO = VEC == 4 ? 4 : (VEC == 2 ? 2 : 1);
-        a.WP = VEC == 4 ? a.Wi + 8 : (VEC == 2 ? a.Wi + 4 : a.Wi + 2);
+        r.XO = VEC == 4 ? 4 : (VEC == 2 ? 2 : 1);
+        r.WP = VEC == 4 ? Wi + 8 : (VEC == 2 ? Wi + 4 : Wi + 2);
         // rows per band: largest divisor GB of G with GB*Wo <= 512 threads, LDS <= 64 KiB, loader capacity
         GB = G;
         for (;; ) {
             while (G % GB) --GB;
             const int rin = (GB * HS - 1) * S + 3;
-            const long ipcb = (long)GB * a.Wo;
+            const long ipcb = (long)GB * r.Wo;
             const long thr = (ipcb + 63) / 64 * 64;
-            const bool fits = ipcb <= 256 && (long)rin * a.WP * 8 <= 60 * 1024 && (long)rin * a.Wi <= (long)LVh * 8 * thr;
+            const bool fits = ipcb <= 256 && (long)rin * r.WP * 8 <= 60 * 1024 && (long)rin * Wi <= (long)LVh * 8 * thr;
             if (fits || GB == 1) break;
             --GB;
         }
@@ -1131,111 +1116,182 @@ static int dw_plan_impl(DwArgs& a, int S, int mode, DwPlan& pl, bool allow_flat,
         break;
     }
     const int LVh = VEC == 1 ? 1 : 4;
-    a.GB = GB;
-    a.nbands = G / GB;
-    a.RIN = (GB * HS - 1) * S + 3;
-    a.IPCb = GB * a.Wo;
-    if (a.IPCb > 512 || (long)a.RIN * a.WP * 8 > 150 * 1024)
-        return cfn_fail(CFN_ERR_UNSUPPORTED, "dwconv3d: plane %dx%d does not fit the LDS band scheme", a.Hi, a.Wi);
+    r.GB = GB;
+    r.nbands = G / GB;
+    r.RIN = (GB * HS - 1) * S + 3;
+    r.IPCb = GB * r.Wo;
+    if (r.IPCb > 512 || (long)r.RIN * r.WP * 8 > 150 * 1024)
+        return cfn_fail(CFN_ERR_UNSUPPORTED, "dwconv3d: plane %dx%d does not fit the LDS band scheme", Hi, Wi);
     // thread slots per channel: pad to whole waves when that costs <= 15 % idle lanes (=> wave-uniform channel,
     // weights in SGPRs)
-    const int ipc64 = (a.IPCb + 63) / 64 * 64;
-    pl.UNIW = a.IPCb >= 64 && ipc64 <= 256 && (ipc64 - a.IPCb) * 100 <= 15 * ipc64;
-    a.IPCp = pl.UNIW ? ipc64 : a.IPCb;
+    const int ipc64 = (r.IPCb + 63) / 64 * 64;
+    const bool UNIW = r.IPCb >= 64 && ipc64 <= 256 && (ipc64 - r.IPCb) * 100 <= 15 * ipc64;
+    r.IPCp = UNIW ? ipc64 : r.IPCb;
     // UNIW: 4-wave workgroups (several fit on a CU, barriers stay cheap)
     // small planes: up to 8 waves; the data gradient (most registers, two staged tensors) runs better as 4-wave
     // workgroups, several of which fit on a CU (measured at 4 clips: 14x14 0.31 -> 0.25 ms, 7x7 0.25 -> 0.16 ms)
     // 4-wave workgroups (two per CU at this variant's register budget) beat one 8-wave workgroup everywhere except the
     // 7x7 forward (measured, 8 clips: 56->28 s2 fwd 0.80 -> 0.70 ms, 28->14 s2 0.42 -> 0.35, 14x14 wgrad 0.47 -> 0.45)
-    const int wg = (pl.UNIW || mode != DW_FWD || a.Ho * a.Wo > 64 || S == 2) ? 256 : 512;
-    int CG = wg / a.IPCp;
+    const int wg = (UNIW || mode != DW_FWD || r.Ho * r.Wo > 64 || S == 2) ? 256 : 512;
+    int CG = wg / r.IPCp;
     if (CG < 1) CG = 1;
-    if (CG > a.C) CG = a.C;
+    if (CG > s.C) CG = s.C;
     if (CG > 128) CG = 128;
-    while (CG > 1 && ((long)CG * a.RIN * a.WP * 8 > 48 * 1024)) --CG;
+    while (CG > 1 && ((long)CG * r.RIN * r.WP * 8 > 48 * 1024)) --CG;
     int threads;
     for (;; --CG) {   // loader capacity: LV*8 elements per thread per frame
-        threads = (CG * a.IPCp + 63) / 64 * 64;
-        if ((long)CG * a.RIN * a.Wi <= (long)LVh * 8 * threads || CG == 1) break;
+        threads = (CG * r.IPCp + 63) / 64 * 64;
+        if ((long)CG * r.RIN * Wi <= (long)LVh * 8 * threads || CG == 1) break;
     }
-    if ((long)CG * a.RIN * a.Wi > (long)LVh * 8 * threads)
-        return cfn_fail(CFN_ERR_UNSUPPORTED, "dwconv3d: loader capacity exceeded for plane %dx%d", a.Hi, a.Wi);
-    if ((long)CG * a.T * a.Hi * a.Wi * DW_ES >= 0x7ffffff0L)
-        return cfn_fail(CFN_ERR_UNSUPPORTED, "dwconv3d: %d channels x %d frames of a %dx%d plane exceed the 2 GiB buffer range", CG, a.T, a.Hi, a.Wi);
-    a.CG = CG;
-    a.ngroups = cfn_cdiv(a.C, CG);
-    const long per_thread = ((long)CG * a.RIN * a.Wi + (long)LVh * threads - 1) / ((long)LVh * threads);
+    if ((long)CG * r.RIN * Wi > (long)LVh * 8 * threads)
+        return cfn_fail(CFN_ERR_UNSUPPORTED, "dwconv3d: loader capacity exceeded for plane %dx%d", Hi, Wi);
+    if ((long)CG * T * Hi * Wi * s.es >= 0x7ffffff0L)
+        return cfn_fail(CFN_ERR_UNSUPPORTED, "dwconv3d: %d channels x %d frames of a %dx%d plane exceed the 2 GiB buffer range", CG, T, Hi, Wi);
+    r.CG = CG;
+    r.ngroups = cfn_cdiv(s.C, CG);
+    const long per_thread = ((long)CG * r.RIN * Wi + (long)LVh * threads - 1) / ((long)LVh * threads);
     const int MAXLD = (LVh == 4 && per_thread <= 2) ? 2 : (per_thread <= 4 ? 4 : 8);
     // frames per chunk: as long as possible while keeping >= ~6 workgroups per CU in the grid
-    const long planes = (long)a.N * a.ngroups * a.nbands;
+    const long planes = (long)s.N * r.ngroups * r.nbands;
     // Whole rounds: resident workgroups per CU follow from the register budget of the variant (launch bounds),
     // so size the t-chunks such that the grid fills R full rounds of the chip (a 1.1-round grid costs 2 rounds).
-    const int per_cu = !pl.UNIW ? (threads > 256 ? 1 : (mode == DW_DGRAD ? 4 : 2)) : (MAXLD == 8 ? 2 : (MAXLD == 4 ? 3 : (mode == DW_FWD ? 4 : 3)));
+    const int per_cu = !UNIW ? (threads > 256 ? 1 : (mode == DW_DGRAD ? 4 : 2)) : (MAXLD == 8 ? 2 : (MAXLD == 4 ? 3 : (mode == DW_FWD ? 4 : 3)));
     const long slots = 256L * per_cu;
-    int TT = a.T;
+    int TT = T;
     for (int R = 1; R <= 8; ++R) {
         long nch = slots * R / planes;
         if (nch < 1) continue;
-        if (nch > a.T) nch = a.T;
-        TT = cfn_cdiv(a.T, nch);
+        if (nch > T) nch = T;
+        TT = cfn_cdiv(T, nch);
         if (TT <= 40) break;
     }
     if (TT < 8) TT = 8;
-    if (TT > a.T) TT = a.T;
-    a.TT = TT;
-    a.nchunks = cfn_cdiv(a.T, TT);
-    pl.HS = HS; pl.VEC = VEC; pl.MAXLD = MAXLD; pl.threads = threads;
-    pl.lds = ((size_t)2 * CG * a.RIN * a.WP + 2 * CG + (mode == DW_WGRAD ? 27 : 2) * CG * (threads / 64)) * sizeof(float);
-    pl.blocks = (unsigned)(planes * a.nchunks);
+    if (TT > T) TT = T;
+    r.TT = TT;
+    r.nchunks = cfn_cdiv(T, TT);
+    r.v[0] = mode; r.v[1] = S; r.v[2] = HS; r.v[3] = VEC; r.v[4] = MAXLD; r.v[5] = UNIW;
+    r.wg = threads;
+    r.lds = ((size_t)2 * CG * r.RIN * r.WP + 2 * CG + (mode == DW_WGRAD ? 27 : 2) * CG * (threads / 64)) * sizeof(float);
+    r.grid[0] = (unsigned)(planes * r.nchunks); r.grid[1] = r.grid[2] = 1;
     return CFN_OK;
 }
 
-static int dw_plan(DwArgs& a, int S, int mode, DwPlan& pl, int force_hs = 0) {
-    int rc = dw_plan_impl(a, S, mode, pl, true, force_hs);
+static bool band_plan(const DwShape& s, int mode, int force_hs, DwRoute& r) {
+    r.family = DW_FAM_BAND;
+    r.rc = band_plan_impl(s, mode, r, true, force_hs);
     // the flat loader exists for per-lane channels and <= 4 loads per thread only
-    if (rc == CFN_OK && pl.VEC == 2 && (pl.UNIW || pl.MAXLD == 8)) rc = dw_plan_impl(a, S, mode, pl, false, force_hs);
-    return rc;
+    if (r.rc == CFN_OK && r.v[3] == 2 && (r.v[5] || r.v[4] == 8)) r.rc = band_plan_impl(s, mode, r, false, force_hs);
+    return r.rc == CFN_OK;
+}
+bool dw_band_fwd_plan(const DwShape& s, DwRoute& r) { return band_plan(s, DW_FWD, 0, r); }
+bool dw_band_dgrad_plan(const DwShape& s, DwRoute& r) { return s.stride == 1 && band_plan(s, DW_DGRAD, 0, r); }
+bool dw_band_wgrad_plan(const DwShape& s, DwRoute& r) { return band_plan(s, DW_WGRAD, 0, r); }
+
+// fused data + weight gradient (stride 1, big planes: wave-uniform channels, float4 rows); r.v = {HS, VEC, MAXLD, UNIW} of dw3d_bwd_fused_kernel
+// (MAXLD 2 / 4 only -- measured: no gain on 14x14 / 7x7 planes)
+bool dw_bandf_plan(const DwShape& s, DwRoute& r) {
+    if (s.stride != 1) return false;
+    // 4-row strips first (164 VGPRs -> 3 waves per SIMD; measured 56x56: 1.92 ms against 2.18 ms with 7 rows and 2.35 ms
+    // for the two separate kernels), 7-row strips when 4 rows do not give wave-uniform channels (28x28)
+    for (int hs : {4, 0}) {
+        r = DwRoute{};
+        if (!band_plan(s, DW_WGRAD, hs, r)) continue;
+        const int HS = r.v[2], VEC = r.v[3], MAXLD = r.v[4];
+        if (!(r.v[5] && VEC == 4 && MAXLD != 8 && (HS == 4 || HS == 7))) continue;
+        r.lds = ((size_t)4 * r.CG * r.RIN * r.WP + 4 * r.CG + 27 * r.CG * (r.wg / 64)) * sizeof(float);
+        if (r.lds > 150 * 1024) return false;
+        r.family = DW_FAM_BANDF;
+        r.v[0] = HS; r.v[1] = 4; r.v[2] = MAXLD; r.v[3] = 1; r.v[4] = r.v[5] = 0;
+        return true;
+    }
+    r.rc = CFN_OK;                                 // small planes keep the two separate kernels
+    return false;
+}
+
+// stride-2 data gradient: r.v = {fast, PACKED}: dw3d_dgrad_s2_fast_kernel<PACKED> / dw3d_dgrad_s2_kernel<PACKED>
+bool dw_dgrad_s2_plan(const DwShape& s, DwRoute& r) {
+    if (s.stride != 2) return false;
+    const int T = s.T;
+    r.family = DW_FAM_DGRAD_S2;
+    r.Ho = (s.Hi + 2 - 3) / 2 + 1; r.Wo = (s.Wi + 2 - 3) / 2 + 1;
+    r.PB = r.Ho * r.Wo;
+    r.CPB = r.PB <= 128 ? 256 / r.PB : 1;
+    r.pblocks = cfn_cdiv((long)r.Ho * r.Wo, 256);
+    // even split of the plane: 28x28 = 784 positions are 4 x 196, not 3 x 256 + a 16-thread straggler that streams all
+    // frames for 2 % of the work
+    r.PBLK = (r.PB % r.pblocks == 0 && (r.PB / r.pblocks) % 4 == 0) ? r.PB / r.pblocks : 256;   // (uneven splits measured slower)
+    const int ygrid = cfn_cdiv(s.N * s.C, r.CPB);
+    if (!cfn_split_nc(ygrid, r.grid[1], r.grid[2])) { r.rc = cfn_fail(CFN_ERR_ARG, "cfn_dwconv3d_bwd_data: N*C exceeds grid.y"); return false; }
+    int TT = 64;
+    while (TT > 8 && (long)ygrid * r.pblocks * cfn_cdiv(T, TT) < 2048) TT >>= 1;
+    r.TT = TT > T ? T : TT;
+    r.nchunks = cfn_cdiv(T, r.TT);
+    r.v[0] = (s.Wi % 2 == 0) && s.pro && s.y && (long)r.CPB * T * s.Hi * s.Wi * s.es < 0x7ffffff0L;
+    r.v[1] = r.CPB > 1;
+    r.grid[0] = r.pblocks * r.nchunks; r.wg = 256;
+    return true;
+}
+#endif
+
+// (each launcher sits in front of the entry point that first uses it, the forward's first: hipcc lays the kernels out in the order of their first
+// use, and a kernel that addresses a device global relative to the program counter changes its instruction bytes when it moves)
+// the geometry fields DwArgs and DwFusedArgs share, from the route
+template <class Args>
+static void dw_fill_geometry(Args& a, const DwRoute& r) {
+    a.TT = r.TT; a.nchunks = r.nchunks; a.CG = r.CG; a.ngroups = r.ngroups; a.GB = r.GB; a.nbands = r.nbands;
+    a.IPCb = r.IPCb; a.IPCp = r.IPCp; a.RIN = r.RIN; a.WP = r.WP; a.XO = r.XO;
 }
 
 template <int MODE, int S, int HS>
-static int dw_launch_hs(const DwArgs& a, const DwPlan& pl, hipStream_t st) {
+static int dw_launch_hs(const DwArgs& a, const DwRoute& r, hipStream_t st) {
 #define DW_GO(VEC, MAXLD, UW)                                                                                          \
     do {                                                                                                               \
         auto k = dw3d_kernel<MODE, S, HS, VEC, MAXLD, UW>;                                                             \
-        if (pl.lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds); \
-        hipLaunchKernelGGL(k, dim3(pl.blocks), dim3(pl.threads), pl.lds, st, a);                                       \
+        if (r.lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)r.lds); \
+        hipLaunchKernelGGL(k, dim3(r.grid[0]), dim3(r.wg), r.lds, st, a);                                              \
     } while (0)
-    if (pl.UNIW) {
-        if (pl.VEC == 4 && pl.MAXLD == 2) DW_GO(4, 2, true);
-        else if (pl.VEC == 4 && pl.MAXLD == 4) DW_GO(4, 4, true);
-        else if (pl.VEC == 4) DW_GO(4, 8, true);
-        else if (pl.MAXLD == 4) DW_GO(1, 4, true);
+    const int VEC = r.v[3], MAXLD = r.v[4];
+    if (r.v[5]) {
+        if (VEC == 4 && MAXLD == 2) DW_GO(4, 2, true);
+        else if (VEC == 4 && MAXLD == 4) DW_GO(4, 4, true);
+        else if (VEC == 4) DW_GO(4, 8, true);
+        else if (MAXLD == 4) DW_GO(1, 4, true);
         else DW_GO(1, 8, true);
     } else {
-        if (pl.VEC == 2 && pl.MAXLD == 2) DW_GO(2, 2, false);
-        else if (pl.VEC == 2) DW_GO(2, 4, false);
-        else if (pl.VEC == 4 && pl.MAXLD == 2) DW_GO(4, 2, false);
-        else if (pl.VEC == 4 && pl.MAXLD == 4) DW_GO(4, 4, false);
-        else if (pl.VEC == 4) DW_GO(4, 8, false);
-        else if (pl.MAXLD == 4) DW_GO(1, 4, false);
+        if (VEC == 2 && MAXLD == 2) DW_GO(2, 2, false);
+        else if (VEC == 2) DW_GO(2, 4, false);
+        else if (VEC == 4 && MAXLD == 2) DW_GO(4, 2, false);
+        else if (VEC == 4 && MAXLD == 4) DW_GO(4, 4, false);
+        else if (VEC == 4) DW_GO(4, 8, false);
+        else if (MAXLD == 4) DW_GO(1, 4, false);
         else DW_GO(1, 8, false);
     }
 #undef DW_GO
     return cfn_check_launch("dwconv3d");
 }
 
+// the band kernel: the caller has set the tensors of its mode; shape and geometry come from the route
 template <int MODE, int S>
-static int dw_launch(const DwArgs& a, const DwPlan& pl, hipStream_t st) {
-    switch (pl.HS) {
-        case 7: return dw_launch_hs<MODE, S, 7>(a, pl, st);
-        case 4: return dw_launch_hs<MODE, S, 4>(a, pl, st);
-        case 2: return dw_launch_hs<MODE, S, 2>(a, pl, st);
-        default: return dw_launch_hs<MODE, S, 1>(a, pl, st);
+static int dw_band_launch(DwArgs& a, const DwShape& s, const DwRoute& r, hipStream_t st) {
+    a.N = s.N; a.C = s.C; a.T = s.T; a.Hi = s.Hi; a.Wi = s.Wi; a.Ho = r.Ho; a.Wo = r.Wo; a.act = s.act;
+    dw_fill_geometry(a, r);
+    switch (r.v[2]) {
+        case 7: return dw_launch_hs<MODE, S, 7>(a, r, st);
+        case 4: return dw_launch_hs<MODE, S, 4>(a, r, st);
+        case 2: return dw_launch_hs<MODE, S, 2>(a, r, st);
+        default: return dw_launch_hs<MODE, S, 1>(a, r, st);
     }
 }
 
-static double dw_bytes(const DwArgs& a, int tensors_in, int tensors_out) {
-    return (double)DW_ES * a.N * a.C * a.T * ((double)tensors_in * a.Hi * a.Wi + (double)tensors_out * a.Ho * a.Wo);
+// the forward's wave kernels: the flat kernels exist for fp32, the column-pair kernel for the 2-byte types; the chains of dwroute.hip name
+// neither for the other element size
+static int dw_fwd_wave_launch(const DwFwdPtrs& p, const DwShape& s, const DwRoute& r, hipStream_t st) {
+    if (r.family == DW_FAM_SMALL) return DWN(dw_small_launch)(p, s, r, st);
+#ifdef DW_BF16
+    return DWN(dw_cp_launch)(p, s, r, st);
+#else
+    return dw_flat_launch(p, s, r, st);
+#endif
 }
 
 extern "C" int DWN(cfn_dwconv3d_fwd)(const dwe_t* x, const double* A, const double* B, int act, const float* w, dwe_t* y,
@@ -1246,35 +1302,31 @@ extern "C" int DWN(cfn_dwconv3d_fwd)(const dwe_t* x, const double* A, const doub
     CFN_REQUIRE(stride == 1 || stride == 2, "cfn_dwconv3d_fwd: stride must be 1 or 2 (got %d)", stride);
     CFN_REQUIRE((A == nullptr) == (B == nullptr), "cfn_dwconv3d_fwd: A and B must both be given or both null");
     CFN_REQUIRE((sum == nullptr) == (sumsq == nullptr), "cfn_dwconv3d_fwd: sum and sumsq go together");
-    DwArgs a = {};
-    a.src = x; a.A = A; a.B = B; a.act = act; a.w = w; a.dst = y; a.s1 = sum; a.s2 = sumsq;
-    a.N = N; a.C = C; a.T = T; a.Hi = Hi; a.Wi = Wi;
-    hipStream_t st = (hipStream_t)stream;
-#ifndef DW_BF16
-    if (dw_flat_fwd_try(x, A, B, act, w, y, sum, sumsq, N, C, T, Hi, Wi, stride, st, true) == 0) {
-        // output planes 56x56 / 28x28 / 14x14 (stride 1 and 2) and 14 -> 7: flat kernels, every load of a work item up front (dwflat.hip)
-        const double po_ = stride == 1 ? (double)Hi * Wi : ((Hi - 1) / 2 + 1.0) * ((Wi - 1) / 2 + 1.0);
-        CfnProfScope prof(CFN_K_DWCONV_FWD, st, (double)DW_ES * N * C * T * ((double)Hi * Wi + po_) + 4.0 * C * 27);
-        return dw_flat_fwd_try(x, A, B, act, w, y, sum, sumsq, N, C, T, Hi, Wi, stride, st, false);
-    }
-#else
-    if (DWN(dw_cp_fwd_try)(x, A, B, act, w, y, sum, sumsq, N, C, T, Hi, Wi, stride, st, true) == 0) {
-        // output planes 56x56 / 28x28 / 14x14, stride 1 and 2: column-pair wave kernel (dwcp.hip)
-        const double po_ = stride == 1 ? (double)Hi * Wi : ((Hi - 1) / 2 + 1.0) * ((Wi - 1) / 2 + 1.0);
-        CfnProfScope prof(CFN_K_DWCONV_FWD, st, (double)DW_ES * N * C * T * ((double)Hi * Wi + po_) + 4.0 * C * 27);
-        return DWN(dw_cp_fwd_try)(x, A, B, act, w, y, sum, sumsq, N, C, T, Hi, Wi, stride, st, false);
-    }
-#endif
-    if (DWN(dw_small_fwd_try)(x, A, B, act, w, y, sum, sumsq, N, C, T, Hi, Wi, stride, st, true) == 0) {
-        // 7x7 stride 1: wave-per-channel kernel (dwsmall.hip)
-        CfnProfScope prof(CFN_K_DWCONV_FWD, st, (double)DW_ES * N * C * T * 2.0 * Hi * Wi + 4.0 * C * 27);
-        return DWN(dw_small_fwd_try)(x, A, B, act, w, y, sum, sumsq, N, C, T, Hi, Wi, stride, st, false);
-    }
-    DwPlan pl;
-    int rc = dw_plan(a, stride, DW_FWD, pl);
+    const DwFwdPtrs p = {x, A, B, w, y, sum, sumsq};
+    const DwShape s = dw_fwd_shape(p, N, C, T, Hi, Wi, stride, act, DW_ES);
+    DwRoute r;
+    const int rc = dw_route(DW_OP_FWD, s, r);
     if (rc) return rc;
-    CfnProfScope prof(CFN_K_DWCONV_FWD, st, (double)DW_ES * N * C * T * ((double)Hi * Wi + (double)a.Ho * a.Wo) + 4.0 * C * 27);
-    return stride == 1 ? dw_launch<DW_FWD, 1>(a, pl, st) : dw_launch<DW_FWD, 2>(a, pl, st);
+    hipStream_t st = (hipStream_t)stream;
+    CfnProfScope prof(CFN_K_DWCONV_FWD, st, r.bytes);
+    if (r.family != DW_FAM_BAND) return dw_fwd_wave_launch(p, s, r, st);
+    DwArgs a = {};
+    a.src = x; a.A = A; a.B = B; a.w = w; a.dst = y; a.s1 = sum; a.s2 = sumsq;
+    return stride == 1 ? dw_band_launch<DW_FWD, 1>(a, s, r, st) : dw_band_launch<DW_FWD, 2>(a, s, r, st);
+}
+
+static int dw_dgrad_s2_launch(const DwBwdPtrs& p, const DwShape& s, const DwRoute& r, hipStream_t st) {
+    DwS2Args a = {};
+    a.gy = (const dwe_t*)p.gy; a.y = s.y ? (const dwe_t*)p.y : nullptr; a.gs = p.gs; a.gq = p.gq; a.w = p.w; a.x = (const dwe_t*)p.x;
+    a.A = p.A; a.B = p.B; a.gx = (dwe_t*)p.gx; a.gA = p.gA; a.gB = p.gB;
+    a.C = s.C; a.T = s.T; a.Hi = s.Hi; a.Wi = s.Wi; a.Ho = r.Ho; a.Wo = r.Wo; a.act = s.act;
+    a.NC = s.N * s.C; a.PB = r.PB; a.CPB = r.CPB; a.pblocks = r.pblocks; a.PBLK = r.PBLK; a.TT = r.TT; a.nchunks = r.nchunks;
+    const dim3 grid(r.grid[0], r.grid[1], r.grid[2]);
+    if (r.v[0] && r.v[1]) hipLaunchKernelGGL(dw3d_dgrad_s2_fast_kernel<true>, grid, dim3(256), 0, st, a);
+    else if (r.v[0]) hipLaunchKernelGGL(dw3d_dgrad_s2_fast_kernel<false>, grid, dim3(256), 0, st, a);
+    else if (r.v[1]) hipLaunchKernelGGL(dw3d_dgrad_s2_kernel<true>, grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(dw3d_dgrad_s2_kernel<false>, grid, dim3(256), 0, st, a);
+    return cfn_check_launch("dwconv3d_bwd_data_s2");
 }
 
 extern "C" int DWN(cfn_dwconv3d_bwd_data)(const dwe_t* gy, const dwe_t* y, const double* gsum, const double* gsumsq,
@@ -1286,43 +1338,18 @@ extern "C" int DWN(cfn_dwconv3d_bwd_data)(const dwe_t* gy, const dwe_t* y, const
     CFN_REQUIRE((A == nullptr) == (B == nullptr), "cfn_dwconv3d_bwd_data: A/B mismatch");
     CFN_REQUIRE(A == nullptr || (x != nullptr && gA != nullptr && gB != nullptr), "cfn_dwconv3d_bwd_data: prologue needs x, gA, gB");
     CFN_REQUIRE(gsumsq == nullptr || y != nullptr, "cfn_dwconv3d_bwd_data: gsumsq needs y");
-    hipStream_t st = (hipStream_t)stream;
-    const int Ho = (Hi + 2 - 3) / stride + 1, Wo = (Wi + 2 - 3) / stride + 1;
-    CfnProfScope prof(CFN_K_DWCONV_BWD, st, 4.0 * N * C * T * ((double)Hi * Wi * (A ? 2 : 1) + (double)Ho * Wo * (y ? 2 : 1)));
-    if (stride == 2) {
-        DwS2Args a = {};
-        a.gy = gy; a.y = gsumsq ? y : nullptr; a.gs = gsum; a.gq = gsumsq; a.w = w; a.x = x; a.A = A; a.B = B; a.gx = gx;
-        a.gA = gA; a.gB = gB; a.C = C; a.T = T; a.Hi = Hi; a.Wi = Wi; a.Ho = Ho; a.Wo = Wo; a.act = act;
-        a.NC = N * C;
-        a.PB = Ho * Wo;
-        a.CPB = a.PB <= 128 ? 256 / a.PB : 1;
-        a.pblocks = cfn_cdiv((long)Ho * Wo, 256);
-        // even split of the plane: 28x28 = 784 positions are 4 x 196, not 3 x 256 + a 16-thread straggler that streams all
-        // frames for 2 % of the work
-        a.PBLK = (a.PB % a.pblocks == 0 && (a.PB / a.pblocks) % 4 == 0) ? a.PB / a.pblocks : 256;   // (uneven splits measured slower)
-        const int ygrid = cfn_cdiv(a.NC, a.CPB);
-        unsigned gy_, gz_;
-        CFN_REQUIRE(cfn_split_nc(ygrid, gy_, gz_), "cfn_dwconv3d_bwd_data: N*C exceeds grid.y");
-        int TT = 64;
-        while (TT > 8 && (long)ygrid * a.pblocks * cfn_cdiv(T, TT) < 2048) TT >>= 1;
-        a.TT = TT > T ? T : TT;
-        a.nchunks = cfn_cdiv(T, a.TT);
-        const bool fast = (Wi % 2 == 0) && A && a.y && a.gq && gA && (long)a.CPB * T * Hi * Wi * DW_ES < 0x7ffffff0L;
-        const dim3 grid(a.pblocks * a.nchunks, gy_, gz_);
-        if (fast && a.CPB > 1) hipLaunchKernelGGL(dw3d_dgrad_s2_fast_kernel<true>, grid, dim3(256), 0, st, a);
-        else if (fast) hipLaunchKernelGGL(dw3d_dgrad_s2_fast_kernel<false>, grid, dim3(256), 0, st, a);
-        else if (a.CPB > 1) hipLaunchKernelGGL(dw3d_dgrad_s2_kernel<true>, grid, dim3(256), 0, st, a);
-        else hipLaunchKernelGGL(dw3d_dgrad_s2_kernel<false>, grid, dim3(256), 0, st, a);
-        return cfn_check_launch("dwconv3d_bwd_data_s2");
-    }
-    DwArgs a = {};
-    a.src = gy; a.src2 = y; a.gs = gsum; a.gq = gsumsq; a.w = w; a.xin = x; a.A = A; a.B = B; a.act = act;
-    a.dst = gx; a.s1 = A ? gA : nullptr; a.s2 = A ? gB : nullptr;
-    a.N = N; a.C = C; a.T = T; a.Hi = Hi; a.Wi = Wi;
-    DwPlan pl;
-    int rc = dw_plan(a, 1, DW_DGRAD, pl);
+    const DwBwdPtrs p = {gy, y, gsum, gsumsq, w, x, A, B, gx, gA, gB, nullptr};
+    const DwShape s = dw_bwd_shape(p, N, C, T, Hi, Wi, stride, act, DW_ES);
+    DwRoute r;
+    const int rc = dw_route(DW_OP_DGRAD, s, r);
     if (rc) return rc;
-    return dw_launch<DW_DGRAD, 1>(a, pl, st);
+    hipStream_t st = (hipStream_t)stream;
+    CfnProfScope prof(CFN_K_DWCONV_BWD, st, r.bytes);
+    if (r.family == DW_FAM_DGRAD_S2) return dw_dgrad_s2_launch(p, s, r, st);
+    DwArgs a = {};
+    a.src = gy; a.src2 = y; a.gs = gsum; a.gq = gsumsq; a.w = w; a.xin = x; a.A = A; a.B = B;
+    a.dst = gx; a.s1 = A ? gA : nullptr; a.s2 = A ? gB : nullptr;
+    return dw_band_launch<DW_DGRAD, 1>(a, s, r, st);
 }
 
 extern "C" int DWN(cfn_dwconv3d_bwd_weight)(const dwe_t* gy, const dwe_t* y, const double* gsum, const double* gsumsq,
@@ -1332,32 +1359,36 @@ extern "C" int DWN(cfn_dwconv3d_bwd_weight)(const dwe_t* gy, const dwe_t* y, con
     CFN_REQUIRE(stride == 1 || stride == 2, "cfn_dwconv3d_bwd_weight: stride must be 1 or 2");
     CFN_REQUIRE((A == nullptr) == (B == nullptr), "cfn_dwconv3d_bwd_weight: A/B mismatch");
     CFN_REQUIRE(gsumsq == nullptr || y != nullptr, "cfn_dwconv3d_bwd_weight: gsumsq needs y");
-    DwArgs a = {};
-    a.src = x; a.A = A; a.B = B; a.act = act; a.gy = gy; a.yout = gsumsq ? y : nullptr; a.gs = gsum; a.gq = gsumsq;
-    a.s1 = gw;
-    a.N = N; a.C = C; a.T = T; a.Hi = Hi; a.Wi = Wi;
-    DwPlan pl;
-    int rc = dw_plan(a, stride, DW_WGRAD, pl);
+    const DwBwdPtrs p = {gy, y, gsum, gsumsq, nullptr, x, A, B, nullptr, nullptr, nullptr, gw};
+    const DwShape s = dw_bwd_shape(p, N, C, T, Hi, Wi, stride, act, DW_ES);
+    DwRoute r;
+    const int rc = dw_route(DW_OP_WGRAD, s, r);
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
-    CfnProfScope prof(CFN_K_DWCONV_WGRAD, st, 4.0 * N * C * T * ((double)Hi * Wi + (double)a.Ho * a.Wo * (a.yout ? 2 : 1)));
-    return stride == 1 ? dw_launch<DW_WGRAD, 1>(a, pl, st) : dw_launch<DW_WGRAD, 2>(a, pl, st);
+    CfnProfScope prof(CFN_K_DWCONV_WGRAD, st, r.bytes);
+    DwArgs a = {};
+    a.src = x; a.A = A; a.B = B; a.gy = gy; a.yout = gsumsq ? y : nullptr; a.gs = gsum; a.gq = gsumsq;
+    a.s1 = gw;
+    return stride == 1 ? dw_band_launch<DW_WGRAD, 1>(a, s, r, st) : dw_band_launch<DW_WGRAD, 2>(a, s, r, st);
 }
 
-// fused data + weight gradient (stride 1, big planes: wave-uniform channels, float4 rows); -1 = use the two kernels
-template <int HS>
-static int dwf_launch_hs(const DwFusedArgs& f, const DwPlan& pl, size_t lds, hipStream_t st) {
-#define CFN_DWF_GO(VECV, ML, UW)                                                                                       \
+static int dw_bandf_launch(const DwBwdPtrs& p, const DwShape& s, const DwRoute& r, hipStream_t st) {
+    DwFusedArgs f = {(const dwe_t*)p.gy, s.y ? (const dwe_t*)p.y : nullptr, p.gs, p.gq, p.w, (const dwe_t*)p.x, p.A, p.B, (dwe_t*)p.gx,
+                     p.A ? p.gA : nullptr, p.A ? p.gB : nullptr, p.gw, s.N, s.C, s.T, s.Hi, s.Wi, s.act};
+    dw_fill_geometry(f, r);
+#define CFN_DWF_GO(HS, ML)                                                                                             \
     do {                                                                                                               \
-        auto k = dw3d_bwd_fused_kernel<HS, VECV, ML, UW>;                                                              \
-        if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        hipLaunchKernelGGL(k, dim3(pl.blocks), dim3(pl.threads), lds, st, f);                                          \
+        auto k = dw3d_bwd_fused_kernel<HS, 4, ML, true>;                                                               \
+        if (r.lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)r.lds); \
+        hipLaunchKernelGGL(k, dim3(r.grid[0]), dim3(r.wg), r.lds, st, f);                                              \
     } while (0)
-    if (pl.MAXLD == 2) CFN_DWF_GO(4, 2, true); else CFN_DWF_GO(4, 4, true);   // measured: no gain on 14x14 / 7x7 planes
+    if (r.v[0] == 7) { if (r.v[2] == 2) CFN_DWF_GO(7, 2); else CFN_DWF_GO(7, 4); }
+    else { if (r.v[2] == 2) CFN_DWF_GO(4, 2); else CFN_DWF_GO(4, 4); }
 #undef CFN_DWF_GO
     return cfn_check_launch("dwconv3d_bwd_fused");
 }
 
+// data AND weight gradient of the stride-1 conv in one pass; -1 = use the two entry points above
 extern "C" int DWN(cfn_dwconv3d_bwd_fused)(const dwe_t* gy, const dwe_t* y, const double* gsum, const double* gsumsq,
                                       const float* w, const dwe_t* x, const double* A, const double* B, int act, dwe_t* gx,
                                       double* gA, double* gB, double* gw, int N, int C, int T, int H, int W, void* stream) {
@@ -1365,39 +1396,16 @@ extern "C" int DWN(cfn_dwconv3d_bwd_fused)(const dwe_t* gy, const dwe_t* y, cons
     CFN_REQUIRE((A == nullptr) == (B == nullptr), "cfn_dwconv3d_bwd_fused: A/B mismatch");
     CFN_REQUIRE(A == nullptr || (gA != nullptr && gB != nullptr), "cfn_dwconv3d_bwd_fused: prologue needs gA, gB");
     CFN_REQUIRE(gsumsq == nullptr || y != nullptr, "cfn_dwconv3d_bwd_fused: gsumsq needs y");
-    if (DWN(dw_flatb_try)(gy, y, gsum, gsumsq, w, x, A, B, act, gx, gA, gB, gw, N, C, T, H, W, (hipStream_t)stream, true) == 0) {
-        // 7x7: flat wave kernel, a lane per position (dwflatb.hip)
-        CfnProfScope prof(CFN_K_DWCONV_BWD, (hipStream_t)stream, (double)DW_ES * N * C * T * (double)H * W * (y ? 4 : 3));
-        return DWN(dw_flatb_try)(gy, y, gsum, gsumsq, w, x, A, B, act, gx, gA, gB, gw, N, C, T, H, W, (hipStream_t)stream, false);
-    }
-    if (DWN(dw_cpbx_try)(gy, y, gsum, gsumsq, w, x, A, B, act, gx, gA, gB, gw, N, C, T, H, W, (hipStream_t)stream, true) == 0) {
-        // 56x56 / 28x28 / 14x14: column-pair wave kernel with one LDS image, x / a in registers (dwcpbx.hip)
-        CfnProfScope prof(CFN_K_DWCONV_BWD, (hipStream_t)stream, (double)DW_ES * N * C * T * (double)H * W * (y ? 4 : 3));
-        return DWN(dw_cpbx_try)(gy, y, gsum, gsumsq, w, x, A, B, act, gx, gA, gB, gw, N, C, T, H, W, (hipStream_t)stream, false);
-    }
-    DwArgs a = {};
-    a.N = N; a.C = C; a.T = T; a.Hi = H; a.Wi = W;
-    DwPlan pl;
-    // 4-row strips first (164 VGPRs -> 3 waves per SIMD; measured 56x56: 1.92 ms against 2.18 ms with 7 rows and 2.35 ms
-    // for the two separate kernels), 7-row strips when 4 rows do not give wave-uniform channels (28x28)
-    int rc = CFN_ERR_UNSUPPORTED;
-    bool ok = false;
-    for (int hs : {4, 0}) {
-        rc = dw_plan(a, 1, DW_WGRAD, pl, hs);
-        if (rc == CFN_OK && pl.UNIW && pl.VEC == 4 && pl.MAXLD != 8 && (pl.HS == 4 || pl.HS == 7)) { ok = true; break; }
-    }
-    if (!ok) return -1;                            // small planes keep the two separate kernels
-    DwFusedArgs f = {gy, gsumsq ? y : nullptr, gsum, gsumsq, w, x, A, B, gx, A ? gA : nullptr, A ? gB : nullptr, gw,
-                     N, C, T, H, W, act};
-    f.TT = a.TT; f.nchunks = a.nchunks; f.CG = a.CG; f.ngroups = a.ngroups; f.GB = a.GB; f.nbands = a.nbands;
-    f.IPCb = a.IPCb; f.IPCp = a.IPCp; f.RIN = a.RIN; f.WP = a.WP; f.XO = a.XO;
-    const size_t lds = ((size_t)4 * a.CG * a.RIN * a.WP + 4 * a.CG + 27 * a.CG * (pl.threads / 64)) * sizeof(float);
-    if (lds > 150 * 1024) return -1;
+    const DwBwdPtrs p = {gy, y, gsum, gsumsq, w, x, A, B, gx, gA, gB, gw};
+    const DwShape s = dw_bwd_shape(p, N, C, T, H, W, 1, act, DW_ES);
+    DwRoute r;
+    const int rc = dw_route(DW_OP_FUSED, s, r);
+    if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
-    CfnProfScope prof(CFN_K_DWCONV_BWD, st, (double)DW_ES * N * C * T * (double)H * W * (y ? 4 : 3));
-    switch (pl.HS) {
-        case 7: return dwf_launch_hs<7>(f, pl, lds, st);
-        case 4: return dwf_launch_hs<4>(f, pl, lds, st);
-        default: return -1;
+    CfnProfScope prof(CFN_K_DWCONV_BWD, st, r.bytes);
+    switch (r.family) {
+        case DW_FAM_FLATB: return DWN(dw_flatb_launch)(p, s, r, st);
+        case DW_FAM_CPBX: return DWN(dw_cpbx_launch)(p, s, r, st);
+        default: return dw_bandf_launch(p, s, r, st);
     }
 }

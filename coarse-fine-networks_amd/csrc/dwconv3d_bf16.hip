@@ -5,5 +5,4 @@
 #define DwArgs DwArgsBf16
 #define DwFusedArgs DwFusedArgsBf16
 #define DwS2Args DwS2ArgsBf16
-#define DwPlan DwPlanBf16
 #include "dwconv3d.hip"

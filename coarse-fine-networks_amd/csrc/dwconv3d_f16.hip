@@ -6,5 +6,4 @@
 #define DwArgs DwArgsF16
 #define DwFusedArgs DwFusedArgsF16
 #define DwS2Args DwS2ArgsF16
-#define DwPlan DwPlanF16
 #include "dwconv3d.hip"

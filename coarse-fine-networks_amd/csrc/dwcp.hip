@@ -19,12 +19,17 @@
 // A band's input rows are one contiguous run of the (n, c, t) plane: every frame is NLD coalesced float4 loads per lane
 // (unconditional buffer loads: exact vmcnt waits), staged through a wave-private LDS image with a zero halo.  The four waves
 // of a workgroup are the bands of one (n, c, t-chunk) (56x56) or neighbouring t-chunks of one channel: halo rows / frames
-// come out of L2.  Shapes / activations outside this list use the band kernel (dw_cp_fwd_try returns -1).
-// Built through dwcp_bf16.hip / dwcp_f16.hip only: fp32 tensors take the flat kernels of dwflat.hip on every plane served here.
-#ifdef DW_BF16
+// come out of L2.  Shapes / activations outside this list use the band kernel (dw_cp_plan declines them).
+// Kernel and launcher are built through dwcp_bf16.hip / dwcp_f16.hip only: fp32 tensors take the flat kernels of dwflat.hip on every plane served
+// here.  The compilation of this file as it is holds dw_cp_plan alone (dw_plan.h: every plan is defined once, in the fp32 pass of its source).
 #include "cp_io.h"
+#include "dw_plan.h"
 #include <stdint.h>
 #include <stdlib.h>
+
+// the instances: W (OUTPUT width), S, HS, RG, D, OCC -- the plan names one by (W, S), the launcher launches it
+#define DW_CP_VARIANTS(X) X(56, 1, 2, 2, 2, 4) X(28, 1, 1, 4, 2, 4) X(14, 1, 2, 7, 4, 4) X(56, 2, 2, 2, 2, 4) X(28, 2, 1, 4, 2, 4) X(14, 2, 1, 7, 2, 4)
+#ifdef DW_BF16
 
 #define DwCpArgs H16N(DwCpArgs)
 struct DwCpArgs {
@@ -214,18 +219,24 @@ __global__ __launch_bounds__(256, OCC) void dw3d_cp_fwd_kernel(const DwCpArgs a)
     }
 }
 
-// returns -1 when the shape is not handled (caller goes on to the other kernels); probe: 0 = handled, nothing launched;
-// otherwise the launch status
-int CPN(dw_cp_fwd_try)(const cpe_t* x, const double* A, const double* B, int act, const float* w, cpe_t* y, double* sum, double* sumsq,
-                  int N, int C, int T, int Hi, int Wi, int stride, hipStream_t st, bool probe) {
-    if (Hi != Wi || (stride != 1 && stride != 2)) return -1;
+int CPN(dw_cp_launch)(const DwFwdPtrs& p, const DwShape& s, const DwRoute& r, hipStream_t st) {
+    DwCpArgs a = {(const cpe_t*)p.x, p.A, p.B, p.w, (cpe_t*)p.y, p.sum, p.sumsq, s.N, s.C, s.T, s.act, r.TT, r.nchunks, r.items};
+#define CFN_CP_GO(W, S, HS, RG, D, OCC) if (r.v[0] == W && r.v[1] == S) hipLaunchKernelGGL((dw3d_cp_fwd_kernel<W, S, HS, RG, D, OCC>), dim3(r.grid[0]), dim3(256), 0, st, a);
+    DW_CP_VARIANTS(CFN_CP_GO)
+#undef CFN_CP_GO
+    return cfn_check_launch("dwconv3d column-pair forward");
+}
+#else
+
+// v = {Wo, S, HS, RG, D, OCC} of dw3d_cp_fwd_kernel
+bool dw_cp_plan(const DwShape& s, DwRoute& r) {
+    const int Hi = s.Hi, stride = s.stride, T = s.T;
+    if (Hi != s.Wi || (stride != 1 && stride != 2)) return false;
     const int Ho = stride == 1 ? Hi : Hi / 2;
-    if ((stride == 2 && (Hi & 1)) || (Ho != 56 && Ho != 28 && Ho != 14)) return -1;
-    if (act != CFN_ACT_NONE && act != CFN_ACT_RELU && A != nullptr) return -1;      // branch-free prologue: none / ReLU (every X3D conv2)
-    if ((long)T * Hi * Wi * CP_ES >= 0x7fff0000L) return -1;
-    if ((((uintptr_t)x | (uintptr_t)y) & (4 * CP_ES - 1)) != 0) return -1;
-    if (probe) return 0;
-    DwCpArgs a = {x, A, B, w, y, sum, sumsq, N, C, T, act, 0, 0, 0};
+    if ((stride == 2 && (Hi & 1)) || (Ho != 56 && Ho != 28 && Ho != 14)) return false;
+    if (s.act != CFN_ACT_NONE && s.act != CFN_ACT_RELU && s.pro) return false;      // branch-free prologue: none / ReLU (every X3D conv2)
+    if ((long)T * Hi * s.Wi * s.es >= 0x7fff0000L) return false;
+    if (((s.align_x | s.align_out) & (4 * s.es - 1)) != 0) return false;
     // lanes = column pairs x row groups (few rows per lane = few accumulators = many resident waves, which is what these
     // kernels need: measured on 56x56, 8 clips x T=256: 7 rows per lane, 168 VGPRs, 3 waves per SIMD: 3.5 TB/s; 2 rows, 93
     // VGPRs, 5 waves: 5.1 TB/s; capped at 80 / 64 VGPRs the spills cost 1.6x / 3x)
@@ -234,7 +245,7 @@ int CPN(dw_cp_fwd_try)(const cpe_t* x, const double* A, const double* B, int act
     const int NB = Ho == 56 ? 14 : Ho == 28 ? 7 : (stride == 2 ? 2 : 1);
     // t-chunks: >= ~6 rounds of the chip's resident waves (16 per CU) so that the tail of the last round stays small; the
     // chunk length + 2 halo frames is a multiple of the unrolled trip (6 or 12 steps) where T allows it
-    const long units = (long)N * C * NB;
+    const long units = (long)s.N * s.C * NB;
     const int U = (Ho == 14 && stride == 1) ? 12 : 6;
     long nch = (6L * 256 * 16 + units - 1) / units;
     if (nch < 1) nch = 1;
@@ -246,17 +257,14 @@ int CPN(dw_cp_fwd_try)(const cpe_t* x, const double* A, const double* B, int act
     // 0.730 / 0.731 / 0.723, 28->14 0.357 / 0.365 / 0.380 / 0.374 / 0.377; the stride-1 planes are within +-2 % from 16 up
     if (stride == 2 && TT > 16) TT = 16;
     if (TT > T) TT = T;
-    a.TT = TT;
-    a.nchunks = (T + TT - 1) / TT;
-    a.total_waves = units * a.nchunks;
-    const unsigned blocks = (unsigned)((a.total_waves + 3) / 4);
-#define CFN_CP_GO(...) hipLaunchKernelGGL((dw3d_cp_fwd_kernel<__VA_ARGS__>), dim3(blocks), dim3(256), 0, st, a)
-    if (stride == 1) {
-        if (Ho == 56) CFN_CP_GO(56, 1, 2, 2, 2, 4); else if (Ho == 28) CFN_CP_GO(28, 1, 1, 4, 2, 4); else CFN_CP_GO(14, 1, 2, 7, 4, 4);
-    } else {
-        if (Ho == 56) CFN_CP_GO(56, 2, 2, 2, 2, 4); else if (Ho == 28) CFN_CP_GO(28, 2, 1, 4, 2, 4); else CFN_CP_GO(14, 2, 1, 7, 2, 4);
-    }
-#undef CFN_CP_GO
-    return cfn_check_launch("dwconv3d column-pair forward");
+    r.family = DW_FAM_CP;
+    r.TT = TT;
+    r.nchunks = (T + TT - 1) / TT;
+    r.items = units * r.nchunks;
+    r.grid[0] = (unsigned)((r.items + 3) / 4); r.grid[1] = r.grid[2] = 1; r.wg = 256;
+#define CFN_CP_IS(W, S, HS, RG, D, OCC) if (Ho == W && stride == S) { const int v[6] = {W, S, HS, RG, D, OCC}; for (int i = 0; i < 6; ++i) r.v[i] = v[i]; }
+    DW_CP_VARIANTS(CFN_CP_IS)
+#undef CFN_CP_IS
+    return true;
 }
 #endif

@@ -21,6 +21,7 @@
 // fp32, bf16 or fp16 tensors (cp_io.h: compiled again through dwcpb2x_bf16.hip / dwcpb2x_f16.hip; the LDS image, accumulators and every
 // reduction stay fp32 / fp64).
 #include "cp_io.h"
+#include "dw_plan.h"
 #include <stdint.h>
 #include <stdlib.h>
 
@@ -271,21 +272,31 @@ __global__ __launch_bounds__(256, OCC) void dw3d_cpx_bwd_s2_kernel(const DwCpb2x
     }
 }
 
-// returns -1 when the shape is not handled; probe: 0 = handled, nothing launched.  H, W: input size.
-int CPN(dw_cpb2x_try)(const cpe_t* gy, const cpe_t* y, const double* gs, const double* gq, const float* w, const cpe_t* x,
-                 const double* A, const double* B, int act, cpe_t* gx, double* gA, double* gB, double* gw,
-                 int N, int C, int T, int H, int W, hipStream_t st, bool probe) {
-    if (H != W || (H != 112 && H != 56 && H != 28)) return -1;
-    if (A != nullptr && act != CFN_ACT_NONE && act != CFN_ACT_RELU) return -1;      // act' from the sign of a: none / ReLU (every X3D conv2)
-    if ((long)T * H * W * CP_ES >= 0x7fff0000L) return -1;
-    if ((((uintptr_t)gy | (uintptr_t)x | (uintptr_t)gx | (uintptr_t)(y ? y : gy)) & (4 * CP_ES - 1)) != 0) return -1;
-    if (probe) return 0;
-    const bool hasy = y != nullptr && gq != nullptr;
-    DwCpb2xArgs a = {gy, hasy ? y : nullptr, gs, hasy ? gq : nullptr, w, x, A, B, gx, A ? gA : nullptr, A ? gB : nullptr, gw, N, C, T, act, 0, 0, 0};
+// the instances: WO, RG, OCC (each with HASY false / true) -- the plan names one by WO, the launcher launches it
+#define DW_CPB2X_VARIANTS(X) X(56, 2, 3) X(28, 4, 3) X(14, 7, 3)
+
+static int CPN(dw_cpb2x_launch)(const DwBwdPtrs& p, const DwShape& s, const DwRoute& r, hipStream_t st) {
+    DwCpb2xArgs a = {(const cpe_t*)p.gy, s.y ? (const cpe_t*)p.y : nullptr, p.gs, s.y ? p.gq : nullptr, p.w, (const cpe_t*)p.x, p.A, p.B, (cpe_t*)p.gx,
+                     p.A ? p.gA : nullptr, p.A ? p.gB : nullptr, p.gw, s.N, s.C, s.T, s.act, r.TT, r.nchunks, r.items};
+#define CFN_CPB2X_GO(WO, RG, OCC) if (r.v[0] == WO) { if (s.y) hipLaunchKernelGGL((dw3d_cpx_bwd_s2_kernel<WO, RG, OCC, true>), dim3(r.grid[0]), dim3(256), 0, st, a); \
+                                                      else hipLaunchKernelGGL((dw3d_cpx_bwd_s2_kernel<WO, RG, OCC, false>), dim3(r.grid[0]), dim3(256), 0, st, a); }
+    DW_CPB2X_VARIANTS(CFN_CPB2X_GO)
+#undef CFN_CPB2X_GO
+    return cfn_check_launch("dwconv3d stride-2 column-pair fused backward (one image)");
+}
+
+#ifndef DW_BF16
+// stride 2, 112 -> 56, 56 -> 28, 28 -> 14 (Hi, Wi: the INPUT plane): v = {WO, RG, OCC, HASY} of dw3d_cpx_bwd_s2_kernel
+bool dw_cpb2x_plan(const DwShape& s, DwRoute& r) {
+    const int H = s.Hi, T = s.T;
+    if (s.stride != 2 || H != s.Wi || (H != 112 && H != 56 && H != 28)) return false;
+    if (s.pro && s.act != CFN_ACT_NONE && s.act != CFN_ACT_RELU) return false;      // act' from the sign of a: none / ReLU (every X3D conv2)
+    if ((long)T * H * s.Wi * s.es >= 0x7fff0000L) return false;
+    if (((s.align_g | s.align_x | s.align_out) & (4 * s.es - 1)) != 0) return false;
     const int NB = H == 112 ? 28 : H == 56 ? 7 : 2;
     // t-chunks of ~52 frames (a wave's fixed cost -- LDS clear, pipeline fill, the 27-value reduction -- is worth a few frame steps); more
     // chunks only while the grid has fewer than ~2 rounds of the resident waves (12 per CU)
-    const long units = (long)N * C * NB;
+    const long units = (long)s.N * s.C * NB;
     long nch = (T + 26) / 52;
     if (nch < 1) nch = 1;
     while (units * nch < 2L * 256 * 12 && (T + nch) / (nch + 1) >= 16) ++nch;
@@ -294,22 +305,18 @@ int CPN(dw_cpb2x_try)(const cpe_t* gy, const cpe_t* y, const double* gs, const d
     // 2.76 / 2.68 / 2.76 / 2.82 / 2.88 / 2.76 ms, 56->28 1.36 / 1.38 / 1.40 / 1.44 / 1.40 / 1.41, 28->14 0.71 / 0.71 / 0.72 / 0.74 / 0.73 / 0.74
     if (TT > 24) TT = 24;
     if (TT > T) TT = T;
-    a.TT = TT;
-    a.nchunks = (T + TT - 1) / TT;
-    a.total_waves = units * a.nchunks;
-    const unsigned blocks = (unsigned)((a.total_waves + 3) / 4);
-#define CFN_CPB2X_GO(...) do { if (hasy) hipLaunchKernelGGL((dw3d_cpx_bwd_s2_kernel<__VA_ARGS__, true>), dim3(blocks), dim3(256), 0, st, a); \
-                               else hipLaunchKernelGGL((dw3d_cpx_bwd_s2_kernel<__VA_ARGS__, false>), dim3(blocks), dim3(256), 0, st, a); } while (0)
-    if (H == 112) CFN_CPB2X_GO(56, 2, 3);
-    else if (H == 56) CFN_CPB2X_GO(28, 4, 3);
-    else CFN_CPB2X_GO(14, 7, 3);
-#undef CFN_CPB2X_GO
-    return cfn_check_launch("dwconv3d stride-2 column-pair fused backward (one image)");
+    r.family = DW_FAM_CPB2X;
+    r.TT = TT;
+    r.nchunks = (T + TT - 1) / TT;
+    r.items = units * r.nchunks;
+    r.grid[0] = (unsigned)((r.items + 3) / 4); r.grid[1] = r.grid[2] = 1; r.wg = 256;
+#define CFN_CPB2X_IS(WO, RG, OCC) if (H == 2 * WO) { r.v[0] = WO; r.v[1] = RG; r.v[2] = OCC; r.v[3] = s.y; }
+    DW_CPB2X_VARIANTS(CFN_CPB2X_IS)
+#undef CFN_CPB2X_IS
+    return true;
 }
+#endif
 
-int CPN(dw_flatb_s2_try)(const cpe_t* gy, const cpe_t* y, const double* gs, const double* gq, const float* w, const cpe_t* x,
-                         const double* A, const double* B, int act, cpe_t* gx, double* gA, double* gB, double* gw,
-                         int N, int C, int T, int H, int W, hipStream_t st, bool probe);              // dwflatb.hip (every element type)
 // C ABI (include/cfn_hip.h): data AND weight gradient of the stride-2 conv in one pass; -1 = not handled, call the two kernels
 extern "C" int CPN(cfn_dwconv3d_bwd_fused_s2)(const cpe_t* gy, const cpe_t* y, const double* gsum, const double* gsumsq, const float* w,
                                          const cpe_t* x, const double* A, const double* B, int act, cpe_t* gx, double* gA, double* gB,
@@ -319,16 +326,12 @@ extern "C" int CPN(cfn_dwconv3d_bwd_fused_s2)(const cpe_t* gy, const cpe_t* y, c
     CFN_REQUIRE((A == nullptr) == (B == nullptr), "cfn_dwconv3d_bwd_fused_s2: A/B mismatch");
     CFN_REQUIRE(A == nullptr || (gA != nullptr && gB != nullptr), "cfn_dwconv3d_bwd_fused_s2: prologue needs gA, gB");
     CFN_REQUIRE(gsumsq == nullptr || y != nullptr, "cfn_dwconv3d_bwd_fused_s2: gsumsq needs y");
+    const DwBwdPtrs p = {gy, y, gsum, gsumsq, w, x, A, B, gx, gA, gB, gw};
+    const DwShape s = dw_bwd_shape(p, N, C, T, H, W, 2, act, CP_ES);
+    DwRoute r;
+    const int rc = dw_route(DW_OP_FUSED, s, r);
+    if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
-    if (CPN(dw_flatb_s2_try)(gy, y, gsum, gsumsq, w, x, A, B, act, gx, gA, gB, gw, N, C, T, H, W, st, true) == 0) {
-        // 14 -> 7: flat wave kernel (dwflatb.hip)
-        CfnProfScope prof(CFN_K_DWCONV_BWD, st, (double)CP_ES * N * C * T * (2.0 * H * W + 49.0 * (y ? 2 : 1)));
-        return CPN(dw_flatb_s2_try)(gy, y, gsum, gsumsq, w, x, A, B, act, gx, gA, gB, gw, N, C, T, H, W, st, false);
-    }
-    if (CPN(dw_cpb2x_try)(gy, y, gsum, gsumsq, w, x, A, B, act, gx, gA, gB, gw, N, C, T, H, W, st, true) == 0) {
-        // 112 -> 56, 56 -> 28, 28 -> 14: the column-pair wave kernel above
-        CfnProfScope prof(CFN_K_DWCONV_BWD, st, (double)CP_ES * N * C * T * (2.0 * H * W + (double)(H / 2) * (W / 2) * (y ? 2 : 1)));
-        return CPN(dw_cpb2x_try)(gy, y, gsum, gsumsq, w, x, A, B, act, gx, gA, gB, gw, N, C, T, H, W, st, false);
-    }
-    return -1;
+    CfnProfScope prof(CFN_K_DWCONV_BWD, st, r.bytes);
+    return r.family == DW_FAM_FLATB_S2 ? CPN(dw_flatb_launch)(p, s, r, st) : CPN(dw_cpb2x_launch)(p, s, r, st);
 }

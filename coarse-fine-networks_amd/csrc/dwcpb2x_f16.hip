@@ -1,4 +1,4 @@
-// dwcpb2x.hip compiled for fp16 tensors (cp_io.h): entry point dw_cpb2x_try_f16
+// dwcpb2x.hip compiled for fp16 tensors (cp_io.h): launcher dw_cpb2x_launch_f16 and the C entry point
 // hipcc-flags: -fno-slp-vectorize
 #define DW_BF16 1
 #define CFN_F16 1

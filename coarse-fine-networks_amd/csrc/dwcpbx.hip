@@ -22,6 +22,7 @@
 // fp32, bf16 or fp16 tensors (cp_io.h: compiled again through dwcpbx_bf16.hip / dwcpbx_f16.hip; the LDS image, accumulators and every
 // reduction stay fp32 / fp64).
 #include "cp_io.h"
+#include "dw_plan.h"
 #include <stdint.h>
 #include <stdlib.h>
 
@@ -269,38 +270,47 @@ __global__ __launch_bounds__(256, OCC) void dw3d_cpx_bwd_kernel(const DwCpbxArgs
     }
 }
 
-// returns -1 when the shape is not handled (caller goes on to the band kernels); probe: 0 = handled, nothing launched
-int CPN(dw_cpbx_try)(const cpe_t* gy, const cpe_t* y, const double* gs, const double* gq, const float* w, const cpe_t* x,
-                const double* A, const double* B, int act, cpe_t* gx, double* gA, double* gB, double* gw,
-                int N, int C, int T, int H, int W, hipStream_t st, bool probe) {
-    if (H != W || (H != 56 && H != 28 && H != 14)) return -1;
-    if (A != nullptr && act != CFN_ACT_NONE && act != CFN_ACT_RELU) return -1;      // act' from the sign of a: none / ReLU (every X3D conv2)
-    if ((long)T * H * W * CP_ES >= 0x7fff0000L) return -1;
-    if ((((uintptr_t)gy | (uintptr_t)x | (uintptr_t)gx | (uintptr_t)(y ? y : gy)) & (4 * CP_ES - 1)) != 0) return -1;
-    if (probe) return 0;
-    const bool hasy = y != nullptr && gq != nullptr;
-    DwCpbxArgs a = {gy, hasy ? y : nullptr, gs, hasy ? gq : nullptr, w, x, A, B, gx, A ? gA : nullptr, A ? gB : nullptr, gw, N, C, T, act, 0, 0, 0};
+// the instances: W, HS, RG, D, OCC (each with HASY false / true) -- the plan names one by W, the launcher launches it
+// (deeper rings, 5 waves per SIMD on 28x28, one-row lanes on 56x56 / 14x14: all within the +-4 % run-to-run spread of these power-bound kernels)
+#define DW_CPBX_VARIANTS(X) X(56, 2, 2, 1, 3) X(28, 1, 4, 1, 4) X(14, 2, 7, 2, 3)
+
+int CPN(dw_cpbx_launch)(const DwBwdPtrs& p, const DwShape& s, const DwRoute& r, hipStream_t st) {
+    DwCpbxArgs a = {(const cpe_t*)p.gy, s.y ? (const cpe_t*)p.y : nullptr, p.gs, s.y ? p.gq : nullptr, p.w, (const cpe_t*)p.x, p.A, p.B, (cpe_t*)p.gx,
+                    p.A ? p.gA : nullptr, p.A ? p.gB : nullptr, p.gw, s.N, s.C, s.T, s.act, r.TT, r.nchunks, r.items};
+#define CFN_CPBX_GO(W, HS, RG, D, OCC) if (r.v[0] == W) { if (s.y) hipLaunchKernelGGL((dw3d_cpx_bwd_kernel<W, HS, RG, D, OCC, true>), dim3(r.grid[0]), dim3(256), 0, st, a); \
+                                                          else hipLaunchKernelGGL((dw3d_cpx_bwd_kernel<W, HS, RG, D, OCC, false>), dim3(r.grid[0]), dim3(256), 0, st, a); }
+    DW_CPBX_VARIANTS(CFN_CPBX_GO)
+#undef CFN_CPBX_GO
+    return cfn_check_launch("dwconv3d column-pair fused backward (one image)");
+}
+
+#ifndef DW_BF16
+// stride 1, 56x56 / 28x28 / 14x14: v = {W, HS, RG, D, OCC, HASY} of dw3d_cpx_bwd_kernel
+bool dw_cpbx_plan(const DwShape& s, DwRoute& r) {
+    const int H = s.Hi, T = s.T;
+    if (s.stride != 1 || H != s.Wi || (H != 56 && H != 28 && H != 14)) return false;
+    if (s.pro && s.act != CFN_ACT_NONE && s.act != CFN_ACT_RELU) return false;      // act' from the sign of a: none / ReLU (every X3D conv2)
+    if ((long)T * H * s.Wi * s.es >= 0x7fff0000L) return false;
+    if (((s.align_g | s.align_x | s.align_out) & (4 * s.es - 1)) != 0) return false;
     const int NB = H == 56 ? 14 : H == 28 ? 7 : 1;                                    // 14x14: the plane is one band
     // t-chunks of ~64 frames: a wave's fixed cost (LDS clear, pipeline fill, the 27-value reduction) is worth ~4 frame steps (measured on the
     // three-image predecessor of this kernel, 8 clips x T = 256, 56x56: chunks of 9 / 21 / 33 / 63 frames: 4.5 / 2.3 / 1.7 / 1.3 ms; same-box
     // sweep 16 / 24 / 32 / 48 / 52 / 64: 56x56 1.39 / 1.29 / 1.23 / 1.26 / 1.22 / 1.20 ms, 28x28 0.76 / 0.70 / 0.64 / 0.65 / 0.64 / 0.61,
     // 14x14 0.34 / 0.32 / 0.32 / 0.33 / 0.32 / 0.31); more chunks only while the grid has fewer than ~2 rounds of the resident waves (12 per CU)
-    const long units = (long)N * C * NB;
+    const long units = (long)s.N * s.C * NB;
     long nch = (T + 32) / 64;
     if (nch < 1) nch = 1;
     while (units * nch < 2L * 256 * 12 && (T + nch) / (nch + 1) >= 16) ++nch;
     int TT = (int)((T + nch - 1) / nch);
     if (TT > T) TT = T;
-    a.TT = TT;
-    a.nchunks = (T + TT - 1) / TT;
-    a.total_waves = units * a.nchunks;
-    const unsigned blocks = (unsigned)((a.total_waves + 3) / 4);
-#define CFN_CPBX_GO(...) do { if (hasy) hipLaunchKernelGGL((dw3d_cpx_bwd_kernel<__VA_ARGS__, true>), dim3(blocks), dim3(256), 0, st, a); \
-                              else hipLaunchKernelGGL((dw3d_cpx_bwd_kernel<__VA_ARGS__, false>), dim3(blocks), dim3(256), 0, st, a); } while (0)
-    // (deeper rings, 5 waves per SIMD on 28x28, one-row lanes on 56x56 / 14x14: all within the +-4 % run-to-run spread of these power-bound kernels)
-    if (H == 56) CFN_CPBX_GO(56, 2, 2, 1, 3);
-    else if (H == 28) CFN_CPBX_GO(28, 1, 4, 1, 4);
-    else CFN_CPBX_GO(14, 2, 7, 2, 3);
-#undef CFN_CPBX_GO
-    return cfn_check_launch("dwconv3d column-pair fused backward (one image)");
+    r.family = DW_FAM_CPBX;
+    r.TT = TT;
+    r.nchunks = (T + TT - 1) / TT;
+    r.items = units * r.nchunks;
+    r.grid[0] = (unsigned)((r.items + 3) / 4); r.grid[1] = r.grid[2] = 1; r.wg = 256;
+#define CFN_CPBX_IS(W, HS, RG, D, OCC) if (H == W) { const int v[6] = {W, HS, RG, D, OCC, s.y}; for (int i = 0; i < 6; ++i) r.v[i] = v[i]; }
+    DW_CPBX_VARIANTS(CFN_CPBX_IS)
+#undef CFN_CPBX_IS
+    return true;
 }
+#endif

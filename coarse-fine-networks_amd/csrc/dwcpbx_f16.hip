@@ -1,4 +1,4 @@
-// dwcpbx.hip compiled for fp16 tensors (cp_io.h): entry point dw_cpbx_try_f16
+// dwcpbx.hip compiled for fp16 tensors (cp_io.h): launcher dw_cpbx_launch_f16
 // hipcc-flags: -fno-slp-vectorize
 #define DW_BF16 1
 #define CFN_F16 1

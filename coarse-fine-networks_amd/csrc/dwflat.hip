@@ -23,6 +23,7 @@
 // 530 / 274; TO = 6 / 4: 527 / 548 and 263 / 273; a persistent producer / consumer version (4 loader waves that never store + 4 worker waves
 // that never load, LDS double buffer, one barrier per item) 610 / 295; with 8 of the 9 taps per frame switched off 466 (6.0 TB/s).
 #include "cfn_common.h"
+#include "dw_plan.h"
 #include <stdint.h>
 #include <stdlib.h>
 
@@ -463,57 +464,77 @@ __global__ __launch_bounds__(256, 4) void dw3d_flat14to7_fwd_kernel(const DwFlat
     }
 }
 
-// returns -1 when the shape is not handled; probe: 0 = handled, nothing launched; otherwise the launch status
-int dw_flat_fwd_try(const float* x, const double* A, const double* B, int act, const float* w, float* y, double* sum, double* sumsq,
-                    int N, int C, int T, int Hi, int Wi, int stride, hipStream_t st, bool probe) {
-    if (Hi != Wi) return -1;
-    if (stride == 2 && Hi == 14) {
-        if (act != CFN_ACT_NONE && act != CFN_ACT_RELU && A != nullptr) return -1;
-        if ((long)T * Hi * Wi * 4 >= 0x7fff0000L || (((uintptr_t)x | (uintptr_t)y) & 15) != 0) return -1;
-        const int TO = T >= 12 ? 8 : 4;
-        const long nch = (T + TO - 1) / TO, items = (long)N * C * nch, blocks = (items + 3) / 4;
-        if (blocks >= 0x7fffffffL) return -1;
-        if (probe) return 0;
-        DwFlatArgs a = {x, A, B, w, y, sum, sumsq, N, C, T, act, (int)nch, items};
-        if (TO == 8) hipLaunchKernelGGL((dw3d_flat14to7_fwd_kernel<8>), dim3((unsigned)blocks), dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((dw3d_flat14to7_fwd_kernel<4>), dim3((unsigned)blocks), dim3(256), 0, st, a);
-        return cfn_check_launch("dwconv3d flat 14->7 forward");
-    }
-    if (stride == 2) {
-        if (Hi != 112 && Hi != 56 && Hi != 28) return -1;
-        if (act != CFN_ACT_NONE && act != CFN_ACT_RELU && A != nullptr) return -1;
-        if ((long)T * Hi * Wi * 4 >= 0x7fff0000L || (((uintptr_t)x | (uintptr_t)y) & 15) != 0) return -1;
-        // same-box steady state, 8 clips x T = 256, dwcp.hip / this kernel at TO = 8 / 6 / 4: 112 -> 56 1373 / 1211 / 1260 / 1214 us, 56 -> 28
-        // 686 / 622 / 618 / 623, 28 -> 14 358 / 309 / 302 / 311; 2-row bands on 112 -> 56 (7 workgroups per CU, 1.25 x row re-reads): 1250
-        const int TO = T >= 12 ? 8 : 4;
-        const int NB = Hi == 112 ? 14 : Hi == 56 ? 4 : 1;
-        const long nch = (T + TO - 1) / TO, blocks = (long)N * C * nch * NB;
-        if (blocks >= 0x7fffffffL) return -1;
-        if (probe) return 0;
-        DwFlatArgs a = {x, A, B, w, y, sum, sumsq, N, C, T, act, (int)nch, blocks};
-#define CFN_FLAT_GO(...) hipLaunchKernelGGL((dw3d_flat_s2_fwd_kernel<__VA_ARGS__>), dim3((unsigned)blocks), dim3(256), 0, st, a)
-        if (Hi == 112) { if (TO == 8) CFN_FLAT_GO(56, 4, 8); else CFN_FLAT_GO(56, 4, 4); }
-        else if (Hi == 56) { if (TO == 8) CFN_FLAT_GO(28, 7, 8); else CFN_FLAT_GO(28, 7, 4); }
-        else { if (TO == 8) CFN_FLAT_GO(14, 14, 8); else CFN_FLAT_GO(14, 14, 4); }
-#undef CFN_FLAT_GO
-        return cfn_check_launch("dwconv3d flat stride-2 forward");
-    }
-    if (stride != 1 || (Hi != 56 && Hi != 28 && Hi != 14)) return -1;
-    if (act != CFN_ACT_NONE && act != CFN_ACT_RELU && A != nullptr) return -1;      // branch-free prologue: none / ReLU (every X3D conv2)
-    if ((long)T * Hi * Wi * 4 >= 0x7fff0000L) return -1;
-    if ((((uintptr_t)x | (uintptr_t)y) & 15) != 0) return -1;
+
+// ---- host: what each of the three sub-families takes (dw_plan.h), and the launcher ---------------------------------------------------------
+
+// what all three ask of a call: a square plane, a branch-free prologue (none / ReLU: every X3D conv2), frames within a buffer descriptor's range,
+// 16-byte aligned x and y
+static bool flat_common_ok(const DwShape& s) {
+    if (s.es != 4 || s.Hi != s.Wi) return false;
+    if (s.act != CFN_ACT_NONE && s.act != CFN_ACT_RELU && s.pro) return false;
+    if ((long)s.T * s.Hi * s.Wi * 4 >= 0x7fff0000L) return false;
+    return ((s.align_x | s.align_out) & 15) == 0;
+}
+
+static bool flat_accept(DwRoute& r, int family, long blocks, int TO, long nch, long items) {
+    if (blocks >= 0x7fffffffL) return false;
+    r.family = family;
+    r.grid[0] = (unsigned)blocks; r.grid[1] = r.grid[2] = 1; r.wg = 256;
+    r.TT = TO; r.nchunks = (int)nch; r.items = items;
+    return true;
+}
+
+// stride 2, 14 -> 7: dw3d_flat14to7_fwd_kernel<TO>, a wave per item
+bool dw_flat14to7_plan(const DwShape& s, DwRoute& r) {
+    if (s.stride != 2 || s.Hi != 14 || !flat_common_ok(s)) return false;
+    const int TO = s.T >= 12 ? 8 : 4;
+    const long nch = (s.T + TO - 1) / TO, items = (long)s.N * s.C * nch;
+    r.v[0] = TO;
+    return flat_accept(r, DW_FAM_FLAT14TO7, (items + 3) / 4, TO, nch, items);
+}
+
+// stride 2, 112 -> 56, 56 -> 28, 28 -> 14: dw3d_flat_s2_fwd_kernel<Wo, RB, TO>
+bool dw_flat_s2_plan(const DwShape& s, DwRoute& r) {
+    if (s.stride != 2 || (s.Hi != 112 && s.Hi != 56 && s.Hi != 28) || !flat_common_ok(s)) return false;
+    // same-box steady state, 8 clips x T = 256, dwcp.hip / this kernel at TO = 8 / 6 / 4: 112 -> 56 1373 / 1211 / 1260 / 1214 us, 56 -> 28
+    // 686 / 622 / 618 / 623, 28 -> 14 358 / 309 / 302 / 311; 2-row bands on 112 -> 56 (7 workgroups per CU, 1.25 x row re-reads): 1250
+    const int TO = s.T >= 12 ? 8 : 4;
+    const int NB = s.Hi == 112 ? 14 : s.Hi == 56 ? 4 : 1;
+    const long nch = (s.T + TO - 1) / TO, blocks = (long)s.N * s.C * nch * NB;
+    r.v[0] = s.Hi / 2; r.v[1] = s.Hi == 112 ? 4 : s.Hi == 56 ? 7 : 14; r.v[2] = TO;
+    return flat_accept(r, DW_FAM_FLAT_S2, blocks, TO, nch, blocks);
+}
+
+// stride 1: 56 / 28: dw3d_flat_fwd_kernel<W, RB, TO>, a workgroup per item; 14: dw3d_flat14_fwd_kernel<TO>, a wave per item
+bool dw_flat_plan(const DwShape& s, DwRoute& r) {
+    if (s.stride != 1 || (s.Hi != 56 && s.Hi != 28 && s.Hi != 14) || !flat_common_ok(s)) return false;
     // 8 output frames per item (10 input frames: 1.25 x temporal re-reads out of L2; 4 frames: 1.5 x, measured 5 % slower); short clips: 4
-    const int TO = T >= 12 ? 8 : 4;
-    const int NB = Hi == 56 ? 4 : 1;
-    const long nch = (T + TO - 1) / TO, items = (long)N * C * nch * NB;
-    const long blocks = Hi == 14 ? (items + 3) / 4 : items;
-    if (blocks >= 0x7fffffffL || (long)N * C * nch >= 0x7fffffffL) return -1;
-    if (probe) return 0;
-    DwFlatArgs a = {x, A, B, w, y, sum, sumsq, N, C, T, act, (int)nch, items};
-#define CFN_FLAT_GO(K, ...) hipLaunchKernelGGL((K<__VA_ARGS__>), dim3((unsigned)blocks), dim3(256), 0, st, a)
-    if (Hi == 56) { if (TO == 8) CFN_FLAT_GO(dw3d_flat_fwd_kernel, 56, 14, 8); else CFN_FLAT_GO(dw3d_flat_fwd_kernel, 56, 14, 4); }
-    else if (Hi == 28) { if (TO == 8) CFN_FLAT_GO(dw3d_flat_fwd_kernel, 28, 28, 8); else CFN_FLAT_GO(dw3d_flat_fwd_kernel, 28, 28, 4); }
-    else { if (TO == 8) CFN_FLAT_GO(dw3d_flat14_fwd_kernel, 8); else CFN_FLAT_GO(dw3d_flat14_fwd_kernel, 4); }
+    const int TO = s.T >= 12 ? 8 : 4;
+    const int NB = s.Hi == 56 ? 4 : 1;
+    const long nch = (s.T + TO - 1) / TO, items = (long)s.N * s.C * nch * NB;
+    if ((long)s.N * s.C * nch >= 0x7fffffffL) return false;
+    if (s.Hi == 14) r.v[0] = TO;
+    else { r.v[0] = s.Hi; r.v[1] = s.Hi == 56 ? 14 : 28; r.v[2] = TO; }
+    return flat_accept(r, DW_FAM_FLAT, s.Hi == 14 ? (items + 3) / 4 : items, TO, nch, items);
+}
+
+int dw_flat_launch(const DwFwdPtrs& p, const DwShape& s, const DwRoute& r, hipStream_t st) {
+    DwFlatArgs a = {(const float*)p.x, p.A, p.B, p.w, (float*)p.y, p.sum, p.sumsq, s.N, s.C, s.T, s.act, r.nchunks, r.items};
+    const int W = r.v[0], TO = r.TT;
+#define CFN_FLAT_GO(K, ...) do { if (TO == 8) hipLaunchKernelGGL((K<__VA_ARGS__, 8>), dim3(r.grid[0]), dim3(256), 0, st, a); \
+                                 else hipLaunchKernelGGL((K<__VA_ARGS__, 4>), dim3(r.grid[0]), dim3(256), 0, st, a); } while (0)
+    if (r.family == DW_FAM_FLAT14TO7) {
+        if (TO == 8) hipLaunchKernelGGL((dw3d_flat14to7_fwd_kernel<8>), dim3(r.grid[0]), dim3(256), 0, st, a);
+        else hipLaunchKernelGGL((dw3d_flat14to7_fwd_kernel<4>), dim3(r.grid[0]), dim3(256), 0, st, a);
+    } else if (r.family == DW_FAM_FLAT_S2) {
+        if (W == 56) CFN_FLAT_GO(dw3d_flat_s2_fwd_kernel, 56, 4); else if (W == 28) CFN_FLAT_GO(dw3d_flat_s2_fwd_kernel, 28, 7);
+        else CFN_FLAT_GO(dw3d_flat_s2_fwd_kernel, 14, 14);
+    } else if (s.Hi != 14) {
+        if (W == 56) CFN_FLAT_GO(dw3d_flat_fwd_kernel, 56, 14); else CFN_FLAT_GO(dw3d_flat_fwd_kernel, 28, 28);
+    } else {
+        if (TO == 8) hipLaunchKernelGGL((dw3d_flat14_fwd_kernel<8>), dim3(r.grid[0]), dim3(256), 0, st, a);
+        else hipLaunchKernelGGL((dw3d_flat14_fwd_kernel<4>), dim3(r.grid[0]), dim3(256), 0, st, a);
+    }
 #undef CFN_FLAT_GO
-    return cfn_check_launch("dwconv3d flat forward");
+    return cfn_check_launch(r.family == DW_FAM_FLAT14TO7 ? "dwconv3d flat 14->7 forward" : r.family == DW_FAM_FLAT_S2 ? "dwconv3d flat stride-2 forward" : "dwconv3d flat forward");
 }

@@ -17,6 +17,7 @@
 // fp32, bf16 or fp16 tensors (cp_io.h: compiled again through dwflatb_bf16.hip / dwflatb_f16.hip; LDS images, accumulators and every
 // reduction stay fp32 / fp64).
 #include "cp_io.h"
+#include "dw_plan.h"
 #include <stdint.h>
 #include <stdlib.h>
 
@@ -347,47 +348,48 @@ __global__ __launch_bounds__(256, 3) void dw3d_flat14to7_bwd_kernel(const DwFlat
     }
 }
 
-// stride 2: returns -1 when the shape is not handled (caller goes on to the column-pair kernel); H, W: INPUT plane
-int CPN(dw_flatb_s2_try)(const cpe_t* gy, const cpe_t* y, const double* gs, const double* gq, const float* w, const cpe_t* x,
-                    const double* A, const double* B, int act, cpe_t* gx, double* gA, double* gB, double* gw,
-                    int N, int C, int T, int H, int W, hipStream_t st, bool probe) {
-    if (H != 14 || W != 14) return -1;
-    if (A != nullptr && act != CFN_ACT_NONE && act != CFN_ACT_RELU) return -1;
-    if ((long)T * H * W * CP_ES >= 0x7fff0000L) return -1;
-    if ((((uintptr_t)x | (uintptr_t)gx) & (2 * CP_ES - 1)) != 0) return -1;
-    const int TO = T >= 12 ? 8 : 4;
-    const long nchunks = (T + TO - 1) / TO;
-    const int subs = 8;                                                             // chunks per wave, as in dw_flatb_try
-    const long nch = (nchunks + subs - 1) / subs, items = (long)N * C * nch, blocks = (items + 3) / 4;
-    if (blocks >= 0x7fffffffL) return -1;
-    if (probe) return 0;
-    DwFlatBArgs a = {gy, gq ? y : nullptr, gs, gq, w, x, A, B, gx, A ? gA : nullptr, A ? gB : nullptr, gw, N, C, T, act, (int)nch, subs, items};
-#define CFN_FLATB_GO(...) hipLaunchKernelGGL((dw3d_flat14to7_bwd_kernel<__VA_ARGS__>), dim3((unsigned)blocks), dim3(256), 0, st, a)
-    if (a.y) { if (TO == 8) CFN_FLATB_GO(8, true); else CFN_FLATB_GO(4, true); }
-    else { if (TO == 8) CFN_FLATB_GO(8, false); else CFN_FLATB_GO(4, false); }
+// stride 1 (dw3d_flat7_bwd_kernel) and stride 2 (dw3d_flat14to7_bwd_kernel; the route's family tells them apart), instance r.v = {TO, HASY}
+int CPN(dw_flatb_launch)(const DwBwdPtrs& p, const DwShape& s, const DwRoute& r, hipStream_t st) {
+    DwFlatBArgs a = {(const cpe_t*)p.gy, s.y ? (const cpe_t*)p.y : nullptr, p.gs, p.gq, p.w, (const cpe_t*)p.x, p.A, p.B, (cpe_t*)p.gx,
+                     p.A ? p.gA : nullptr, p.A ? p.gB : nullptr, p.gw, s.N, s.C, s.T, s.act, r.nchunks, r.subs, r.items};
+#define CFN_FLATB_GO(K) do { if (r.v[1]) { if (r.v[0] == 8) hipLaunchKernelGGL((K<8, true>), dim3(r.grid[0]), dim3(256), 0, st, a); \
+                                            else hipLaunchKernelGGL((K<4, true>), dim3(r.grid[0]), dim3(256), 0, st, a); } \
+                              else { if (r.v[0] == 8) hipLaunchKernelGGL((K<8, false>), dim3(r.grid[0]), dim3(256), 0, st, a); \
+                                     else hipLaunchKernelGGL((K<4, false>), dim3(r.grid[0]), dim3(256), 0, st, a); } } while (0)
+    if (r.family == DW_FAM_FLATB_S2) CFN_FLATB_GO(dw3d_flat14to7_bwd_kernel); else CFN_FLATB_GO(dw3d_flat7_bwd_kernel);
 #undef CFN_FLATB_GO
-    return cfn_check_launch("dwconv3d flat stride-2 backward");
+    return cfn_check_launch(r.family == DW_FAM_FLATB_S2 ? "dwconv3d flat stride-2 backward" : "dwconv3d flat backward");
 }
 
-// returns -1 when the shape is not handled (caller goes on to the column-pair / band kernels); probe: 0 = handled, nothing launched
-int CPN(dw_flatb_try)(const cpe_t* gy, const cpe_t* y, const double* gs, const double* gq, const float* w, const cpe_t* x,
-                 const double* A, const double* B, int act, cpe_t* gx, double* gA, double* gB, double* gw,
-                 int N, int C, int T, int H, int W, hipStream_t st, bool probe) {
-    if (H != W || H != 7) return -1;
-    if (A != nullptr && act != CFN_ACT_NONE && act != CFN_ACT_RELU) return -1;
-    if ((long)T * H * W * CP_ES >= 0x7fff0000L) return -1;
-    const int TO = T >= 12 ? 8 : 4;                                                // (16-frame items: 128 VGPRs + 670 spilled)
+#ifndef DW_BF16
+// what both ask of a call; a wave item = `subs` chunks of TO frames
+static bool flatb_plan(const DwShape& s, int family, DwRoute& r) {
+    if (s.pro && s.act != CFN_ACT_NONE && s.act != CFN_ACT_RELU) return false;
+    if ((long)s.T * s.Hi * s.Wi * s.es >= 0x7fff0000L) return false;
+    const int TO = s.T >= 12 ? 8 : 4;                                              // (16-frame items: 128 VGPRs + 670 spilled)
     // a wave takes `subs` consecutive chunks and reduces its 27 weight-gradient partials once (one chunk per wave: 55 k waves x 27 fp64 atomics per
     // launch made the kernel 2.6 x slower than the one it replaces)
-    const long nchunks = (T + TO - 1) / TO;
+    const long nchunks = (s.T + TO - 1) / TO;
     const int subs = 8;
-    const long nch = (nchunks + subs - 1) / subs, items = (long)N * C * nch, blocks = (items + 3) / 4;
-    if (blocks >= 0x7fffffffL) return -1;
-    if (probe) return 0;
-    DwFlatBArgs a = {gy, gq ? y : nullptr, gs, gq, w, x, A, B, gx, A ? gA : nullptr, A ? gB : nullptr, gw, N, C, T, act, (int)nch, subs, items};
-#define CFN_FLATB_GO(...) hipLaunchKernelGGL((dw3d_flat7_bwd_kernel<__VA_ARGS__>), dim3((unsigned)blocks), dim3(256), 0, st, a)
-    if (a.y) { if (TO == 8) CFN_FLATB_GO(8, true); else CFN_FLATB_GO(4, true); }
-    else { if (TO == 8) CFN_FLATB_GO(8, false); else CFN_FLATB_GO(4, false); }
-#undef CFN_FLATB_GO
-    return cfn_check_launch("dwconv3d flat backward");
+    const long nch = (nchunks + subs - 1) / subs, items = (long)s.N * s.C * nch, blocks = (items + 3) / 4;
+    if (blocks >= 0x7fffffffL) return false;
+    r.family = family;
+    r.v[0] = TO; r.v[1] = s.y;
+    r.TT = TO; r.nchunks = (int)nch; r.subs = subs; r.items = items;
+    r.grid[0] = (unsigned)blocks; r.grid[1] = r.grid[2] = 1; r.wg = 256;
+    return true;
 }
+
+// stride 2, 14 -> 7 (Hi, Wi: the INPUT plane): x and gx on whole element pairs
+bool dw_flatb_s2_plan(const DwShape& s, DwRoute& r) {
+    if (s.stride != 2 || s.Hi != 14 || s.Wi != 14) return false;
+    if (((s.align_x | s.align_out) & (2 * s.es - 1)) != 0) return false;
+    return flatb_plan(s, DW_FAM_FLATB_S2, r);
+}
+
+// stride 1, 7x7
+bool dw_flatb_plan(const DwShape& s, DwRoute& r) {
+    if (s.stride != 1 || s.Hi != s.Wi || s.Hi != 7) return false;
+    return flatb_plan(s, DW_FAM_FLATB, r);
+}
+#endif

@@ -21,6 +21,7 @@
 // fp32, bf16 or fp16 tensors (cp_io.h: compiled again through dwsmall_bf16.hip / dwsmall_f16.hip; LDS image, accumulators and statistics
 // stay fp32).
 #include "cp_io.h"
+#include "dw_plan.h"
 #include <stdlib.h>
 
 #ifdef DW_BF16
@@ -215,26 +216,31 @@ __global__ __launch_bounds__(256, 4) void dw3d_small_fwd_kernel(const DwSmallArg
     }
 }
 
-// returns -1 when the shape is not handled (caller uses the band kernel); probe: 0 = handled, nothing launched; otherwise the
-// launch status
-int CPN(dw_small_fwd_try)(const cpe_t* x, const double* A, const double* B, int act, const float* w, cpe_t* y, double* sum, double* sumsq,
-                     int N, int C, int T, int Hi, int Wi, int stride, hipStream_t st, bool probe) {
-    if (stride != 1 || Hi != 7 || Wi != 7) return -1;
-    if (act != CFN_ACT_NONE && act != CFN_ACT_RELU && A != nullptr) return -1;      // branch-free prologue: none / ReLU (every X3D conv2)
-    if ((long)T * Hi * Wi * CP_ES >= 0x7ffffff0L) return -1;
-    if (probe) return 0;
-    DwSmallArgs a = {x, A, B, w, y, sum, sumsq, N, C, T, act, 0, 0, 0};
-    // t-chunks: ~2 rounds of the chip at 24 resident waves per CU (6 per SIMD), at least 8 frames per chunk (halo re-reads)
-    const long planes = (long)N * C;
-    long nch = (2L * 256 * 24 + planes - 1) / planes;
-    if (nch < 1) nch = 1;
-    int TT = (int)((T + nch - 1) / nch);
-    if (TT < 8) TT = 8;
-    if (TT > T) TT = T;
-    a.TT = TT;
-    a.nchunks = (T + TT - 1) / TT;
-    a.total_waves = planes * a.nchunks;
-    const unsigned blocks = (unsigned)((a.total_waves + 3) / 4);
-    hipLaunchKernelGGL((dw3d_small_fwd_kernel<7, 1>), dim3(blocks), dim3(256), 0, st, a);
+int CPN(dw_small_launch)(const DwFwdPtrs& p, const DwShape& s, const DwRoute& r, hipStream_t st) {
+    DwSmallArgs a = {(const cpe_t*)p.x, p.A, p.B, p.w, (cpe_t*)p.y, p.sum, p.sumsq, s.N, s.C, s.T, s.act, r.TT, r.nchunks, r.items};
+    hipLaunchKernelGGL((dw3d_small_fwd_kernel<7, 1>), dim3(r.grid[0]), dim3(256), 0, st, a);
     return cfn_check_launch("dwconv3d small-plane forward");
 }
+
+#ifndef DW_BF16
+// 7x7, stride 1: dw3d_small_fwd_kernel<7, 1>
+bool dw_small_plan(const DwShape& s, DwRoute& r) {
+    if (s.stride != 1 || s.Hi != 7 || s.Wi != 7) return false;
+    if (s.act != CFN_ACT_NONE && s.act != CFN_ACT_RELU && s.pro) return false;      // branch-free prologue: none / ReLU (every X3D conv2)
+    if ((long)s.T * s.Hi * s.Wi * s.es >= 0x7ffffff0L) return false;
+    // t-chunks: ~2 rounds of the chip at 24 resident waves per CU (6 per SIMD), at least 8 frames per chunk (halo re-reads)
+    const long planes = (long)s.N * s.C;
+    long nch = (2L * 256 * 24 + planes - 1) / planes;
+    if (nch < 1) nch = 1;
+    int TT = (int)((s.T + nch - 1) / nch);
+    if (TT < 8) TT = 8;
+    if (TT > s.T) TT = s.T;
+    r.family = DW_FAM_SMALL;
+    r.v[0] = 7; r.v[1] = 1;
+    r.TT = TT;
+    r.nchunks = (s.T + TT - 1) / TT;
+    r.items = planes * r.nchunks;
+    r.grid[0] = (unsigned)((r.items + 3) / 4); r.grid[1] = r.grid[2] = 1; r.wg = 256;
+    return true;
+}
+#endif

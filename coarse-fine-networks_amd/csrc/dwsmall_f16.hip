@@ -1,4 +1,4 @@
-// dwsmall.hip compiled for fp16 tensors (cp_io.h): entry point dw_small_fwd_try_f16
+// dwsmall.hip compiled for fp16 tensors (cp_io.h): launcher dw_small_launch_f16
 #define DW_BF16 1
 #define CFN_F16 1
 #include "dwsmall.hip"

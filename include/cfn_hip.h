@@ -62,6 +62,15 @@ int cfn_dwconv3d_bwd_fused_s2(const float* gy, const float* y, const double* gsu
                               const float* x, const double* A, const double* B, int act, float* gx, double* gA, double* gB,
                               double* gw, int N, int C, int T, int H, int W, void* stream);
 
+/* Which kernel serves a depthwise 3x3x3 conv call, asked on the host (no GPU, no launch): the routing function the entry points above and their
+ * _bf16 / _f16 versions call (csrc/dwroute.hip).  op: 0 forward, 1 data gradient, 2 weight gradient, 3 one-pass backward (stride 1:
+ * cfn_dwconv3d_bwd_fused, stride 2: cfn_dwconv3d_bwd_fused_s2).  dtype: 0 fp32, 1 bf16, 2 fp16.  Hi, Wi: the conv's input plane.  flags: 1 prologue
+ * A, B given, 2 forward: statistics asked for, backward: gsum given, 4 gsumsq and y given, 16 every tensor aligned to its element only (the plans
+ * then see no wider alignment).  Writes "family kernel<template arguments> grid=.. wg=.. lds=..": the kernel as a kernel trace prints it, the grid in
+ * workgroups ("AxBxC" when it has more than one dimension), workgroup size, dynamic LDS bytes; "declined" where op 3 would return -1.  A shape the
+ * entry point refuses (output wider than 512, ...) returns the entry point's error. */
+int cfn_dwconv3d_route(int op, int dtype, int N, int C, int T, int Hi, int Wi, int stride, int act, int flags, char* out, int cap);
+
 /* ---- depthwise 5x1x1, pad (2,0,0): conv1_t x3d_fine.py:216-222 / x3d_coarse.py:502-508 ; plane = H*W ---- */
 int cfn_dwconv_t5_fwd(const float* x, const float* w, float* y, double* sum, double* sumsq, int N, int C, int T,
                       long plane, void* stream);

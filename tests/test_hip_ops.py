@@ -82,10 +82,14 @@ DW_CASES = [
     (1, 3, 20, 28, 28, 2, 1, True),
     (1, 3, 4, 40, 40, 1, 1, True),       # X3D-S sizes (HS=4 path)
     (1, 2, 3, 80, 80, 2, 1, True),
-    (1, 3, 3, 10, 10, 1, 2, True),       # HS=1 path
-    (2, 3, 2, 5, 5, 2, 1, True),
+    (1, 3, 3, 10, 10, 1, 2, True),       # HS=2 path (10 rows: neither 7 nor 4 divides them); the one-pass backward declines
+    (2, 3, 2, 5, 5, 2, 1, True),         # HS=1 path
     (1, 2, 1, 7, 7, 1, 1, True),         # T = 1
+    # the band kernel's one-pass backward (dw3d_bwd_fused_kernel), which the planes above leave to the wave kernels or decline
+    (1, 3, 4, 16, 16, 1, 1, True),       # 4-row strips: 4 x 16 = 64 thread slots per channel, wave uniform
+    (1, 3, 4, 28, 28, 1, 2, True),       # Swish prologue: not the column-pair kernel's; 4-row strips (196 slots) are not wave uniform, 7-row strips (112) are
 ]
+# (tests/test_dw_route_cpu.py pins the kernel of every case above and of WAVE_CASES below, for all four entry points and the three element types)
 
 
 @pytest.mark.parametrize('N,C,T,H,W,stride,act,pro', DW_CASES)

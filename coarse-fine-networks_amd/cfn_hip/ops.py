@@ -1544,7 +1544,8 @@ def conv3d_dense(x, w, kernel, stride, padding, A=None, B=None, act=ACT_NONE, st
 
 def conv3d_dense_route(op, N, Cin, Cout, T, H, W, geom=None, flags=0, cus=0):
     """the kernel a dense conv of this shape runs on (cfn_conv3d_dense_route, include/cfn_hip.h): host only.  op 0 forward, 1 data gradient,
-    2 weight gradient, 3 stem forward, 4 stem weight gradient; geom = (kernel, stride, padding) flattened to 9 ints (ops 0-2);
+    2 weight gradient, 3 stem forward, 4 stem weight gradient, 5 / 6 the stem on uint8 frames, forward / weight gradient ('convert ' + the line of
+    op 3 / 4 where stem_conv_u8 converts the frames first); geom = (kernel, stride, padding) flattened to 9 ints (ops 0-2);
     cus = 0: the current device's CUs (256 without a device)"""
     out = ctypes.create_string_buffer(256)
     g = (ctypes.c_int * 9)(*geom) if geom is not None else None

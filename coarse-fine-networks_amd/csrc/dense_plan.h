@@ -10,9 +10,11 @@ struct DenseShape {
     int act;                   // the prologue's activation (CFN_ACT_NONE without a prologue)
     bool pro, stats, gs, y;    // prologue A, B present; forward: sum / sumsq asked for; backward: gsum present; gsumsq and y present
     unsigned align_x, align_g, align_out;      // low 4 address bits of x, of gy | y (y where the entry point looks at it), of the output (y, gx)
+    bool u8;                   // the stem plans: x is uint8 frames (N, T, H, W, 3), decoded through a table while they are staged
 };
 
-enum { DN_SALB = 1, DN_SAL_FWD, DN_SAL_DGRAD, DN_SAL_WGRAD, DN_ALLCI, DN_PERCH, DN_GEMM, DN_WD, DN_WG, DN_STEM_FWD, DN_STEM_WGRAD };
+enum { DN_SALB = 1, DN_SAL_FWD, DN_SAL_DGRAD, DN_SAL_WGRAD, DN_ALLCI, DN_PERCH, DN_GEMM, DN_WD, DN_WG, DN_STEM_FWD, DN_STEM_WGRAD, DN_STEM_U8_FWD,
+       DN_STEM_U8_WGRAD };
 
 struct DensePlan {
     int family;
@@ -21,9 +23,11 @@ struct DensePlan {
     size_t lds;
     // the sal kernels: bands of output rows, chunk length (forward: output frames TO; data gradient: input frame pairs CH; weight gradient:
     // output frames CH), number of chunks, length of the last one, work items (forward: workgroups; data gradient: half-workgroup groups;
-    // weight gradient: items of the persistent loop).  stem_wgrad: items, chunk = items per workgroup.  stem_fwd: bands, chunk = RB
+    // weight gradient: items of the persistent loop).  stem_wgrad, stem_u8_wgrad: items, chunk = items per workgroup.  stem_fwd, stem_u8_fwd: bands, chunk = RB
     int bands, chunk, nchunks, last, items;
 };
+
+static const int kStemGeom[9] = {1, 3, 3, 1, 2, 2, 0, 1, 1};      // conv1_s
 
 inline DenseShape dense_shape(int N, int Cin, int Cout, int T, int Hi, int Wi, const int* g, int act) {
     DenseShape s = {N, Cin, Cout, T, Hi, Wi};
@@ -70,5 +74,5 @@ bool dense_dgrad_plan(const DenseShape& s, DensePlan& p);              // fusion
 bool dense_gemm_plan(const DenseShape& s, DensePlan& p);               // pwconv.hip    v = {MT, mode, STATS, ACT}; false: beyond the descriptor range
 bool dense_wg_plan(const DenseShape& s, DensePlan& p);                 // pwconv.hip    v = {MTW, NTW}
 bool dense_wd_plan(const DenseShape& s, DensePlan& p);                 // pwwgrad.hip   v = {ACT, 2, TM, TN}
-bool stem_fwd_plan(const DenseShape& s, DensePlan& p);                 // stem.hip      v = {3}
-bool stem_wgrad_plan(const DenseShape& s, int cus, DensePlan& p);      // stem.hip; cus < 0: the shape gates only
+bool stem_fwd_plan(const DenseShape& s, DensePlan& p);                 // stem.hip      v = {3}; s.u8: the uint8 family (launched by stem_u8.hip)
+bool stem_wgrad_plan(const DenseShape& s, int cus, DensePlan& p);      // stem.hip; cus < 0: the shape gates only; s.u8 as above

@@ -873,8 +873,6 @@ extern "C" int cfn_conv3d_dense_bwd_weight(const float* gy, const float* y, cons
     return wg_launch(a, MTW, NTW, st);
 }
 
-static const int kStemGeom[9] = {1, 3, 3, 1, 2, 2, 0, 1, 1};
-
 extern "C" int cfn_stem_conv_fwd(const float* x, const float* w, float* y, int N, int Cimg, int Cout, int T, int Hi, int Wi,
                                  void* stream) {
     CFN_REQUIRE(x && w && y, "cfn_stem_conv_fwd: null tensor");

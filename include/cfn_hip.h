@@ -184,8 +184,10 @@ int cfn_stem_pair_bwd(const float* gy, const float* y, const double* gsum, const
  * reference's); lengths (N) int32 or NULL (= all frames valid): frame t >= lengths[n] is zero padding and reads as 0.0.
  *   cfn_clip_u8_to_f32: x (N, 3, T, H, W) fp32, any H and W.
  *   cfn_stem_conv_u8_fwd / _bwd_weight: cfn_stem_conv_fwd / _bwd_weight of that clip without materialising it (Cimg must be 3;
- *   the forward is bit-identical).  They return -1, with nothing launched, for a shape the fused kernels do not take (forward:
- *   Cout > 32, W % 4, odd H; weight gradient: anything but 24 channels at 224 x 224): convert, then use the fp32 entry point. ---- */
+ *   the forward is bit-identical: one kernel body serves both kinds of clip).  They return -1, with nothing launched, for a shape the
+ *   fused kernels do not take (forward: Cout > 32, W % 4, odd H, frames off a 4-byte boundary, band image + table beyond 64 KiB of LDS;
+ *   weight gradient: anything but 24 channels at 224 x 224): convert, then use the fp32 entry point.  cfn_conv3d_dense_route, ops 5 and 6,
+ *   tells which on the host. ---- */
 int cfn_clip_u8_to_f32(const unsigned char* frames, const float* lut, const int* lengths, float* x, int N, int T, int H, int W,
                        void* stream);
 int cfn_stem_conv_u8_fwd(const unsigned char* frames, const float* lut, const int* lengths, const float* w, float* y, int N,
@@ -222,13 +224,15 @@ int cfn_conv3d_dense_bwd_data(const float* gy, const float* y, const double* gsu
 int cfn_conv3d_dense_bwd_weight(const float* gy, const float* y, const double* gsum, const double* gsumsq, const float* x,
                                 const double* A, const double* B, int act, double* gw, int N, int Cin, int Cout, int T, int Hi,
                                 int Wi, const int* geom, void* stream);
-/* Which kernel a dense conv call would launch: op 0 cfn_conv3d_dense_fwd, 1 _bwd_data, 2 _bwd_weight, 3 cfn_stem_conv_fwd, 4 cfn_stem_conv_bwd_weight
- * (geom ignored for 3, 4) -- the plan functions the launchers call, asked without a device or a stream.  flags: 1 = prologue A, B present (ReLU;
+/* Which kernel a dense conv call would launch: op 0 cfn_conv3d_dense_fwd, 1 _bwd_data, 2 _bwd_weight, 3 cfn_stem_conv_fwd, 4 cfn_stem_conv_bwd_weight,
+ * 5 cfn_stem_conv_u8_fwd, 6 cfn_stem_conv_u8_bwd_weight (geom ignored for 3 .. 6) -- the plan functions the launchers call, asked without a device or a stream.  flags: 1 = prologue A, B present (ReLU;
  * with 32: Swish), 2 = statistics (forward: sum, sumsq; backward: gsum), 4 = gsumsq and y present, 16 = every tensor misaligned by 4 bytes; one alone:
- * 64 = x, 128 = gy and y, 256 = the output (y / gx).  cus: the
+ * 64 = x, 128 = gy and y, 256 = the output (y / gx); ops 5, 6: 16 and 64 = the frames are off a 4-byte boundary.  cus: the
  * number of CUs to plan for, 0 = those of the current device (256 where there is none).  Writes one line into out: family, kernel with its
  * template arguments, grid= (workgroups), wg=, lds= (dynamic LDS bytes); the saliency kernels add bands= chunk= nchunks= last= (length of the last chunk) items=, the
- * stem kernels bands= chunk= (rows per band / items per workgroup) items=; "declined" where the entry point would refuse the call. */
+ * stem kernels bands= chunk= (rows per band / items per workgroup) items=; "declined" where the entry point would refuse the call.  Ops 5, 6 where
+ * the uint8 kernel does not take the call (the entry point returns -1): "convert " + the line of op 3 / 4 for the converted clip, a new, aligned
+ * allocation -- what ops.stem_conv_u8 and torch.ops.cfn.stem_conv_u8 then run. */
 int cfn_conv3d_dense_route(int op, int N, int Cin, int Cout, int T, int Hi, int Wi, const int* geom, int flags, int cus, char* out, int cap);
 
 /* ---- Gaussian temporal alignment: Gaussian.forward x3d_coarse.py:256-286 (called at :651 / :657).

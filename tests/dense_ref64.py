@@ -39,6 +39,7 @@ STEM = (1, 3, 3, 1, 2, 2, 0, 1, 1)
 PRO, STATS, Y, MISALIGNED, SWISH = 1, 2, 4, 16, 32
 MIS_X, MIS_G, MIS_OUT = 64, 128, 256      # one tensor alone off the boundary: x; gy and y; the output (y / gx)
 FWD, DGRAD, WGRAD, STEM_FWD, STEM_WGRAD = 0, 1, 2, 3, 4
+STEM_U8_FWD, STEM_U8_WGRAD = 5, 6      # uint8 frames (N, T, H, W, 3): MIS_X puts them off a 4-byte boundary; a declined call is 'convert ' + the line of op 3 / 4
 
 
 def gamma(n):

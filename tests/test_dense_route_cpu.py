@@ -1,5 +1,5 @@
-"""Which kernel serves a dense conv call (saliency convs, stem, generic shapes), asked on the host: cfn_conv3d_dense_route, the plan
-functions the launchers call.  The lines of the benchmark's saliency and stem shapes at 256 CUs are literals and are looked up in
+"""Which kernel serves a dense conv call (saliency convs, stem on fp32 clips and on uint8 frames, generic shapes), asked on the host:
+cfn_conv3d_dense_route, the plan functions the launchers call.  The lines of the benchmark's saliency and stem shapes at 256 CUs are literals and are looked up in
 profiles/dense_route_parent_coarse.csv / _coarse_t256.csv, the kernel traces of the commit BEFORE the plans were split from the launchers
 (bench.py --stream coarse [--frames 256] --steps 2 --warmup 1 under a kernel trace).  The traces record static LDS only (68096 bytes for
 stem_wgrad_kernel, 0 elsewhere); lds= is the DYNAMIC LDS a launcher asks for (0 for stem_wgrad_kernel), pinned from the plans' own
@@ -18,7 +18,8 @@ for p in (ROOT, PKG, os.path.join(ROOT, 'tests')):
         sys.path.insert(0, p)
 
 import dense_ref64 as R      # noqa: E402
-from dense_ref64 import DGRAD, FWD, MIS_G, MIS_OUT, MIS_X, MISALIGNED, PRO, SAL, STATS, STEM, STEM_FWD, STEM_WGRAD, SWISH, WGRAD, Y      # noqa: E402
+from dense_ref64 import (DGRAD, FWD, MIS_G, MIS_OUT, MIS_X, MISALIGNED, PRO, SAL, STATS, STEM, STEM_FWD, STEM_U8_FWD, STEM_U8_WGRAD,      # noqa: E402
+                         STEM_WGRAD, SWISH, WGRAD, Y)
 
 
 @pytest.fixture(scope='module')
@@ -72,7 +73,17 @@ BENCH_LINES = {
 
 ARGS = {'sal_fwdb_kernel': 'SalBArgs', 'sal_fwd_kernel': 'SalArgs', 'sal_dgrad_kernel': 'SalBwdArgs', 'sal_wgrad_kernel': 'SalBwdArgs',
         'conv3d_dense_bwd_data_allci_kernel': 'DenseBwdArgs', 'conv3d_dense_bwd_data_kernel': 'DenseBwdArgs', 'pw_gemm_kernel': 'PwArgs',
-        'pw_wgrad_kernel': 'WgArgs', 'pw_wgrad_direct_kernel': 'WdArgs', 'stem_fwd_kernel': 'StemArgs', 'stem_wgrad_kernel': 'StemWgArgs'}
+        'pw_wgrad_kernel': 'WgArgs', 'pw_wgrad_direct_kernel': 'WdArgs', 'stem_fwd_kernel': 'StemArgs', 'stem_wgrad_kernel': 'StemWgArgs',
+        'stem_u8_fwd_kernel': 'StemU8Args', 'stem_u8_wgrad_kernel': 'StemWgU8Args'}
+
+# the stem on uint8 frames (8 x T x 224 x 224 x 3), forward and weight gradient: grid, bands and chunk of the fp32 lines above (one plan serves both
+# sources); the forward's LDS holds the (3, 256) table behind the image: 47328 + 3072
+BENCH_U8_LINES = {
+    64: ['stem stem_u8_fwd_kernel grid=7168 wg=256 lds=50400 bands=14 chunk=8 items=7168',
+         'stem stem_u8_wgrad_kernel grid=512 wg=512 lds=0 bands=28 chunk=28 items=14336'],
+    256: ['stem stem_u8_fwd_kernel grid=28672 wg=256 lds=50400 bands=14 chunk=8 items=28672',
+          'stem stem_u8_wgrad_kernel grid=512 wg=512 lds=0 bands=28 chunk=112 items=57344'],
+}
 
 
 def as_trace_row(line):
@@ -97,6 +108,17 @@ def test_benchmark_routes_match_parent_trace(route, T, trace):
             ('sal_fwdb_kernel', 'sal_fwd_kernel', 'sal_dgrad_kernel', 'sal_wgrad_kernel', 'conv3d_dense_bwd_data_allci_kernel',
              'conv3d_dense_bwd_data_kernel', 'stem_fwd_kernel', 'stem_wgrad_kernel')}
     assert len(mine) == 9 and mine <= {as_trace_row(w) for w in BENCH_LINES[T]}
+
+
+@pytest.mark.parametrize('T', [64, 256])
+def test_benchmark_u8_routes_share_the_fp32_plan(route, T):
+    for op, want, f32 in zip((STEM_U8_FWD, STEM_U8_WGRAD), BENCH_U8_LINES[T], BENCH_LINES[T][-2:]):
+        line = route(op, 8, 3, 24, T, 224, 224)
+        assert line == want
+        f, g = R.fields(line), R.fields(f32)
+        assert all(f[k] == g[k] for k in ('family', 'grid', 'wg', 'bands', 'chunk', 'items'))
+        assert f['lds'] - g['lds'] == (3 * 256 * 4 if op == STEM_U8_FWD else 0)
+        assert as_trace_row(line)[0] == '%s(%s)' % (f['kernel'], ARGS[f['kernel']]) and as_trace_row(line)[1:] == as_trace_row(f32)[1:]
 
 
 def _claims():
@@ -187,6 +209,60 @@ def test_data_gradient_refuses_what_the_entry_point_refuses(route):
 @pytest.mark.parametrize('op,args,fam', DECLINES)
 def test_declines(route, op, args, fam):
     assert R.fields(route(op, *args))['family'] == fam, route(op, *args)
+
+
+# uint8 frames (ops 5, 6): (op, args, the uint8 kernel takes the call, family that runs -- behind 'convert ' where it does not)
+U8_ROUTES = [
+    (STEM_U8_FWD, (3, 3, 24, 3, 30, 35, None, 0), False, 'pw_gemm'),                  # W % 4 != 0
+    (STEM_U8_FWD, (2, 3, 24, 2, 33, 36, None, 0), False, 'pw_gemm'),                  # odd H
+    (STEM_U8_FWD, (1, 3, 33, 2, 8, 8, None, 0), False, 'pw_gemm'), (STEM_U8_FWD, (1, 3, 32, 2, 8, 8, None, 0), True, 'stem'),      # Cout
+    # frames off a 4-byte boundary: converted into a new, aligned clip, which the fp32 kernel takes
+    (STEM_U8_FWD, (1, 3, 24, 2, 8, 8, None, MIS_X), False, 'stem'), (STEM_U8_FWD, (1, 3, 24, 2, 8, 8, None, MISALIGNED), False, 'stem'),
+    (STEM_U8_FWD, (1, 3, 24, 2, 8, 8, None, MIS_OUT | MIS_G), True, 'stem'),
+    # 8-row bands at Wi = 312: the image alone fits 64 KiB (65280 B), image + table (68352 B) does not; 4-row bands: both fit
+    (STEM_FWD, (1, 3, 24, 1, 16, 312, None, 0), True, 'stem'), (STEM_U8_FWD, (1, 3, 24, 1, 16, 312, None, 0), False, 'stem'),
+    (STEM_FWD, (1, 3, 24, 1, 24, 312, None, 0), True, 'stem'), (STEM_U8_FWD, (1, 3, 24, 1, 24, 312, None, 0), True, 'stem'),
+    (STEM_U8_WGRAD, (1, 3, 24, 2, 224, 224, None, 0), True, 'stem'), (STEM_U8_WGRAD, (1, 3, 24, 2, 224, 224, None, MIS_OUT), True, 'stem'),
+    (STEM_U8_WGRAD, (2, 3, 24, 3, 160, 160, None, 0), False, 'wd'),                   # anything but 224 x 224
+    (STEM_U8_WGRAD, (1, 3, 25, 2, 224, 224, None, 0), False, 'wd'),                   # Cout
+    (STEM_U8_WGRAD, (1, 3, 24, 2, 224, 224, None, MIS_G), False, 'wg'),               # gy: misaligned for the fp32 kernels too
+    (STEM_U8_WGRAD, (1, 3, 24, 2, 224, 224, None, MIS_X), False, 'stem'),             # frames: the converted clip is aligned
+    (STEM_U8_WGRAD, (1, 3, 24, 2, 224, 224, None, MISALIGNED), False, 'wg'),
+]
+
+
+def _behind_conversion(flags):
+    """the flags of the fp32 call that follows a conversion: the clip is a new allocation and aligned, the other tensors are the caller's"""
+    return (flags & ~(MIS_X | MISALIGNED)) | ((MIS_G | MIS_OUT) if flags & MISALIGNED else 0)
+
+
+@pytest.mark.parametrize('op,args,takes,fam', U8_ROUTES)
+def test_u8_stem_routes(route, op, args, takes, fam):
+    line = route(op, *args)
+    if op in (STEM_FWD, STEM_WGRAD):
+        assert takes and R.fields(line)['family'] == fam, line
+        return
+    f32 = route(op - 2, *args[:-1], _behind_conversion(args[-1]))
+    assert line.startswith('convert ') == (not takes), line
+    if takes:
+        assert R.fields(line)['family'] == fam and R.fields(line)['kernel'] == ('stem_u8_fwd_kernel' if op == STEM_U8_FWD else 'stem_u8_wgrad_kernel'), line
+        assert all(R.fields(line)[k] == R.fields(f32)[k] for k in ('family', 'grid', 'wg', 'bands', 'chunk', 'items')), (line, f32)
+    else:
+        assert line == 'convert ' + f32 and R.fields(f32)['family'] == fam, (line, f32)
+
+
+def test_u8_stem_route_parts_from_fp32_at_the_lds_ceiling(route):
+    a, b = route(STEM_FWD, 1, 3, 24, 1, 16, 312), route(STEM_U8_FWD, 1, 3, 24, 1, 16, 312)
+    assert R.fields(a)['lds'] == 65280 and R.fields(a)['chunk'] == 8 and b == 'convert ' + a
+    a, b = R.fields(route(STEM_FWD, 1, 3, 24, 1, 24, 312)), R.fields(route(STEM_U8_FWD, 1, 3, 24, 1, 24, 312))
+    assert a['chunk'] == b['chunk'] == 4 and b['lds'] == a['lds'] + 3072 and b['kernel'] == 'stem_u8_fwd_kernel'
+
+
+def test_u8_stem_route_refuses_what_the_entry_point_refuses(route):
+    """uint8 frames have 3 interleaved channels: cfn_stem_conv_u8_fwd / _bwd_weight fail for any other Cimg"""
+    assert route(STEM_U8_FWD, 1, 4, 24, 2, 8, 8) == 'declined' and route(STEM_U8_WGRAD, 1, 1, 24, 1, 224, 224) == 'declined'
+    with pytest.raises(RuntimeError, match='0 .. 6'):
+        route(7, 1, 3, 24, 1, 8, 8)
 
 
 def test_exact_forward_runs_when_the_split_is_off(route):

@@ -20,10 +20,13 @@ DEV = 'cuda'
 MEAN, STD = [0.413, 0.368, 0.338], [0.131, 0.125, 0.132]
 LOGIT_TOL, GRAD_TOL = 1e-3, 5e-2                       # test_run_to_run_reproducibility
 
-# (N, T, H, W, lengths): the three X3D crops (S 160, M 224, XL 312: a 936-byte row pitch), W % 4 != 0 with an odd plane, a plane
-# that is a multiple of 4 but not of 16 pixels, odd H; lengths ragged, including 0 and T
-SHAPES = [(3, 3, 224, 224, [3, 0, 1]), (2, 3, 160, 160, [2, 3]), (2, 2, 312, 312, [2, 1]), (3, 3, 30, 35, [0, 3, 2]),
-          (2, 4, 6, 10, [4, 1]), (2, 2, 33, 36, [1, 2]), (1, 2, 224, 224, None)]
+# (N, T, H, W, lengths, the fused forward takes it): the three X3D crops (S 160, M 224, XL 312: a 936-byte row pitch), W % 4 != 0 with an
+# odd plane, a plane that is a multiple of 4 but not of 16 pixels, odd H; lengths ragged, including 0 and T; 16 x 312: bands of 8 output
+# rows, whose image fits the 64 KiB of LDS without the table (the fp32 kernel takes it) and not with it
+SHAPES = [(3, 3, 224, 224, [3, 0, 1], True), (2, 3, 160, 160, [2, 3], True), (2, 2, 312, 312, [2, 1], True), (3, 3, 30, 35, [0, 3, 2], False),
+          (2, 4, 6, 10, [4, 1], False), (2, 2, 33, 36, [1, 2], False), (1, 2, 224, 224, None, True), (1, 2, 16, 312, None, False)]
+# (the ids pytest gives (N, T, H, W, lengths) rows)
+SHAPE_IDS = ['%d-%d-%d-%d-%s' % (s[:4] + ('None' if s[4] is None else 'lengths%d' % i,)) for i, s in enumerate(SHAPES)]
 
 
 def _lut():
@@ -59,7 +62,7 @@ def test_clip_u8_to_f32_golden_fixture():
     assert torch.equal(x2, x)
 
 
-@pytest.mark.parametrize('N,T,H,W,lengths', SHAPES)
+@pytest.mark.parametrize('N,T,H,W,lengths', [s[:5] for s in SHAPES], ids=SHAPE_IDS)
 def test_clip_u8_to_f32_equals_cpu_gather(N, T, H, W, lengths):
     from cfn_hip import ops
     lut = _lut()
@@ -73,9 +76,9 @@ def test_clip_u8_to_f32_equals_cpu_gather(N, T, H, W, lengths):
             assert bool((got[n, :, ln:] == 0).all()) and bool((got[n, :, :ln] != 0).all())
 
 
-@pytest.mark.parametrize('N,T,H,W,lengths', SHAPES)
-def test_stem_conv_u8_forward_is_bit_identical(N, T, H, W, lengths):
-    """fused (W % 4 == 0, even H) and fallback routes: the same bits as the fp32 stem conv of the converted clip; padded frames give
+@pytest.mark.parametrize('N,T,H,W,lengths,fused', SHAPES, ids=SHAPE_IDS)
+def test_stem_conv_u8_forward_is_bit_identical(N, T, H, W, lengths, fused):
+    """fused (W % 4 == 0, even H, image and table within 64 KiB of LDS) and fallback routes: the same bits as the fp32 stem conv of the converted clip; padded frames give
     exact zeros"""
     from cfn_hip import ops
     lut = _lut().to(DEV)
@@ -90,24 +93,20 @@ def test_stem_conv_u8_forward_is_bit_identical(N, T, H, W, lengths):
     if lengths is not None:
         for n, k in enumerate(lengths):
             assert bool((got[n, :, k:] == 0).all())
-    fused = cfn_fused_forward(H, W)
     from cfn_hip import call_try
     y = torch.empty_like(want)
     took = call_try('cfn_stem_conv_u8_fwd', frames, lut, ln, w.reshape(24, 27).contiguous(), y, N, 3, 24, T, H, W)
     assert took == fused            # a shape the fused kernel does not take is REPORTED (and nothing is launched)
+    assert ops.conv3d_dense_route(5, N, 3, 24, T, H, W).startswith('convert') == (not fused)
     if took:
         assert torch.equal(y, want)
-
-
-def cfn_fused_forward(H, W):
-    return W % 4 == 0 and H % 2 == 0
 
 
 @pytest.mark.parametrize('N,T,H,W,lengths', [(2, 3, 224, 224, [3, 1]), (2, 2, 224, 224, None), (2, 3, 160, 160, [2, 3]), (3, 3, 30, 35, [0, 3, 2]),
                                              (2, 2, 312, 312, [2, 1])])
 def test_stem_conv_u8_weight_gradient(N, T, H, W, lengths):
     """against the fp64 conv3d weight gradient of the converted clip (CPU): the uint8 path's error is at most 2x the fp32 path's on the
-    same input (224 x 224: the fused twin of the LDS-staged kernel; other shapes: convert + the fp32 entry point)"""
+    same input (224 x 224: the LDS-staged kernel's body on the uint8 source; other shapes: convert + the fp32 entry point)"""
     from cfn_hip import ops
     lut = _lut()
     frames = _frames(11 + H, N, T, H, W)
@@ -133,9 +132,36 @@ def test_stem_conv_u8_weight_gradient(N, T, H, W, lengths):
     g64 = torch.zeros(24, 27, dtype=torch.float64, device=DEV)
     took = call_try('cfn_stem_conv_u8_bwd_weight', gy.to(DEV), frames.to(DEV), lut.to(DEV), ln, g64, N, 3, 24, T, H, W)
     assert took == (H == 224 and W == 224)
+    assert ops.conv3d_dense_route(6, N, 3, 24, T, H, W).startswith('convert') == (not took)
     import cfn_hip.torchlib  # noqa: F401
     gop = torch.ops.cfn.stem_conv_u8_backward(gy.to(DEV), frames.to(DEV), ln, lut.to(DEV), w.to(DEV)).cpu().double()
     assert float((gop - ref).abs().max()) / scale <= 2 * e32
+
+
+def test_stem_u8_weight_gradient_equals_fp32_bits_deterministic():
+    """deterministic mode, 224 x 224: cfn_stem_conv_u8_bwd_weight and cfn_stem_conv_bwd_weight on the converted clip fill the fp64 tile with
+    the same bits.  Both run one kernel body over the same partition of items over workgroups (one plan); a padded frame adds gy * 0.0 in the
+    fp32 source's run and is not multiplied in the uint8 source's, and the accumulators start at +0, so neither can produce a -0."""
+    import cfn_hip
+    from cfn_hip import call, call_try, ops
+    N, T, H, W, lengths = 2, 3, 224, 224, [3, 1]
+    lut = _lut().to(DEV)
+    frames = _frames(11 + H, N, T, H, W).to(DEV)
+    ln = _len(lengths)
+    gy = torch.randn(N, 24, T, H // 2, W // 2, generator=torch.Generator().manual_seed(2)).to(DEV)
+    x = ops.clip_u8_to_f32(frames, lut, ln)
+    prev = cfn_hip.deterministic(True)
+    try:
+        g8 = torch.zeros(24, 27, dtype=torch.float64, device=DEV)
+        g32 = torch.zeros(24, 27, dtype=torch.float64, device=DEV)
+        assert call_try('cfn_stem_conv_u8_bwd_weight', gy, frames, lut, ln, g8, N, 3, 24, T, H, W)
+        call('cfn_stem_conv_bwd_weight', gy, x, g32, N, 3, 24, T, H, W)
+        torch.cuda.synchronize()
+    finally:
+        cfn_hip.deterministic(prev)
+    assert bool((g32 != 0).all())
+    print('stem wgrad, deterministic: max |u8 - fp32| = %.3e' % float((g8 - g32).abs().max()))
+    assert torch.equal(g8.view(torch.int64), g32.view(torch.int64))
 
 
 def _compare_nets(run_f32, run_u8, net):

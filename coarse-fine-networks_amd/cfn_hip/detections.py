@@ -90,6 +90,11 @@ The rules, stated once (the kernels, the numpy references and include/cfn_hip.h 
         method unchanged when min_score is not above its scores; max_keep = 1 leaves each group's first row in the order of N2; the first
         selected row of every group is hard NMS's first kept row
 
+SMOOTHING (``filter=``; cfn_hip/scorefilter.py states the rule, F1-F6).  ``decode``, ``decode_levels``, ``propose`` and ``DetectionWriter``
+take ``filter=`` -- a ``cfn_hip.scorefilter.ScoreFilter`` (box, Gaussian or median over a per-class window) -- and so do ``decode_reference``
+and ``decode_levels_reference``: probs goes through the filter ONCE (one more launch; the references through ``filter_reference``), and
+everything behind it, the score columns included, reads the filtered tensor.  With None nothing changes, bit for bit.
+
 ``decode_levels_reference``, ``nms_reference`` and ``soft_nms_reference`` spell these in numpy on any device and are the tests' reference.
 Limits: K <= 16, B * C * K * TL < 2^31; NMS: B and C <= 65535, ranking is O(nd^2) and suppression O(kept * nd) per group of nd candidates;
 soft-NMS is O(selected * nd) per group, which max_keep bounds.  No accuracy gain is claimed: which levels, which nms_thr, and whether hard or
@@ -177,11 +182,21 @@ def _defaults(probs, fps, start):
     return fps, start
 
 
-def decode(probs, valid_t, fps=None, start=None, thr=0.5, max_gap=0, min_len=1, cap=None, out=None):
+def _filtered(probs, valid_t, filter, reference=False):
+    """probs through `filter` (a cfn_hip.scorefilter.ScoreFilter; None: probs itself): one launch, or filter_reference on the host"""
+    if filter is None:
+        return probs
+    from . import scorefilter
+    return scorefilter.filter_reference(probs, valid_t, filter) if reference else scorefilter.apply(probs, valid_t, filter)
+
+
+def decode(probs, valid_t, fps=None, start=None, thr=0.5, max_gap=0, min_len=1, cap=None, out=None, filter=None):
     """probs (B, C, TL) fp32 and valid_t (B,) int32 on the GPU -> Detections there (ops.decode_segments: three launches, nothing is read
     back).  fps=None: fps = 1 (and start=None: start = 0), so times are in frames, still with the half frame outward.  thr: a float or a
-    (C,) fp32 device tensor.  cap, out: see ops.decode_segments."""
+    (C,) fp32 device tensor.  cap, out: see ops.decode_segments.  filter: a ScoreFilter -- probs is smoothed first (one more launch, into a
+    new tensor; for a call that allocates nothing, hand decode the result of cfn_hip.scorefilter.apply(out=) instead)."""
     from . import ops
+    probs = _filtered(probs, valid_t, filter)
     fps, start = _defaults(probs, fps, start)
     C = int(probs.shape[1]) if probs.dim() == 3 else 0
     if cap is None and probs.dim() == 3:
@@ -190,11 +205,12 @@ def decode(probs, valid_t, fps=None, start=None, thr=0.5, max_gap=0, min_len=1, 
     return Detections(seg, frames, score, offsets, total, C, int(cap))
 
 
-def decode_reference(probs, valid_t, fps=None, start=None, thr=0.5, max_gap=0, min_len=1, cap=None):
+def decode_reference(probs, valid_t, fps=None, start=None, thr=0.5, max_gap=0, min_len=1, cap=None, filter=None):
     """decode() from the definition, rule by rule, in numpy; tensors on any device, the result on probs' device: the tests' reference and
     the CPU spelling.  cap=None: exactly the rows found (at least one, as SegLabels.seg is never empty); a cap keeps the first `cap` rows and
-    the true offsets / total, as the kernel does."""
+    the true offsets / total, as the kernel does.  filter: probs goes through cfn_hip.scorefilter.filter_reference first."""
     dev = probs.device
+    probs = _filtered(probs, valid_t, filter, reference=True)
     fps, start = _defaults(probs, fps, start)
     p = probs.detach().cpu().numpy()
     if p.dtype != np.float32 or p.ndim != 3:
@@ -262,11 +278,13 @@ def levels_tensor(levels, n_classes, device=None):
     return (t if device is None else t.to(device)).contiguous()
 
 
-def decode_levels(probs, valid_t, fps=None, start=None, levels=(0.5,), max_gap=0, min_len=1, cap=None, out=None):
+def decode_levels(probs, valid_t, fps=None, start=None, levels=(0.5,), max_gap=0, min_len=1, cap=None, out=None, filter=None):
     """probs (B, C, TL) fp32 and valid_t (B,) int32 on the GPU -> (Detections of the candidates at every level, level (cap,) uint8) there (rules
     L1-L4; ops.decode_segments_levels: three launches, nothing is read back).  levels: floats (every class) or a (C, K) fp32 tensor; fps, start
-    as decode().  cap, out: see ops.decode_segments_levels (with out=, hand a (C, K) device tensor for nothing to be allocated)."""
+    as decode().  cap, out: see ops.decode_segments_levels (with out=, hand a (C, K) device tensor for nothing to be allocated).  filter:
+    as decode()."""
     from . import ops
+    probs = _filtered(probs, valid_t, filter)
     fps, start = _defaults(probs, fps, start)
     C = int(probs.shape[1]) if probs.dim() == 3 else 0
     if not (torch.is_tensor(levels) and levels.dtype == torch.float32 and levels.dim() == 2 and levels.device == probs.device and levels.is_contiguous()):
@@ -277,10 +295,11 @@ def decode_levels(probs, valid_t, fps=None, start=None, levels=(0.5,), max_gap=0
     return Detections(seg, frames, score, offsets, total, C, int(cap)), level
 
 
-def decode_levels_reference(probs, valid_t, fps=None, start=None, levels=(0.5,), max_gap=0, min_len=1, cap=None):
+def decode_levels_reference(probs, valid_t, fps=None, start=None, levels=(0.5,), max_gap=0, min_len=1, cap=None, filter=None):
     """decode_levels() from rules L1-L4 in numpy: K decode_reference calls (one per level column), merged in (b, c, k, t0) order; tensors on
-    any device, the result on probs' device.  cap as in decode_reference."""
+    any device, the result on probs' device.  cap as in decode_reference.  filter: as decode_reference, applied once in front of the K calls."""
     dev = probs.device
+    probs = _filtered(probs, valid_t, filter, reference=True)
     B, C = int(probs.shape[0]), int(probs.shape[1])
     lv = levels_tensor(levels, C).cpu()
     K = int(lv.shape[1])
@@ -480,11 +499,13 @@ def soft_nms_reference(det, soft=SoftNMS(), nms_thr=0.5, score='max', cap=None):
 
 
 def propose(probs, valid_t, fps=None, start=None, levels=(0.8, 0.65, 0.5, 0.35, 0.2), nms_thr=0.5, score='max', max_gap=0, min_len=1, out=None,
-            reference=False, soft=None):
+            reference=False, soft=None, filter=None):
     """probs -> candidates at K levels -> NMS -> the post-NMS Detections, all on the device (six launches, nothing is read back).  Levels
     listed high to low prefer the tight segment among nested candidates under score='max' (rule N2).  out: (the out of decode_levels, the out
     of nms), both for the worst-case cap, for a call that allocates nothing (capturable).  reference=True: the numpy references instead.
-    soft: a SoftNMS -- the second stage is soft_nms in place of nms (nms_thr is then linear's threshold; out[1] is the out of soft_nms)."""
+    soft: a SoftNMS -- the second stage is soft_nms in place of nms (nms_thr is then linear's threshold; out[1] is the out of soft_nms).
+    filter: a ScoreFilter -- probs is smoothed once in front of the level decode (one more launch; filter_reference with reference=True)."""
+    probs = _filtered(probs, valid_t, filter, reference)
     if reference:
         cand, _ = decode_levels_reference(probs, valid_t, fps, start, levels, max_gap, min_len)
         return (nms_reference(cand, nms_thr, score) if soft is None else soft_nms_reference(cand, soft, nms_thr, score))[0]
@@ -513,10 +534,16 @@ class DetectionWriter(object):
     levels (floats or a (C, K) tensor), nms (a float of [0, 1], default 0.5), nms_score: with `levels` set add() runs propose() in place of
     decode() -- candidates at the K levels, then temporal NMS -- and keeps only the post-NMS batch (K times the rows); `thr` is then not
     used.  The JSON format is the same.  soft (a SoftNMS, with `levels`): the second stage of propose() is soft_nms -- `nms` is then linear's
-    threshold and the score column `nms_score` of the file holds the final, decayed scores."""
+    threshold and the score column `nms_score` of the file holds the final, decayed scores.  filter (a cfn_hip.scorefilter.ScoreFilter): every
+    add() smooths its probs first (one more launch) and decodes the filtered scores; None changes nothing."""
 
-    def __init__(self, path, thr=0.5, max_gap=0, min_len=1, max_pending_bytes=1 << 30, levels=None, nms=None, nms_score='max', soft=None):
+    def __init__(self, path, thr=0.5, max_gap=0, min_len=1, max_pending_bytes=1 << 30, levels=None, nms=None, nms_score='max', soft=None, filter=None):
         self.path, self.thr, self.max_gap, self.min_len = path, thr, int(max_gap), int(min_len)
+        if filter is not None:
+            from .scorefilter import ScoreFilter
+            if not isinstance(filter, ScoreFilter):
+                raise TypeError('DetectionWriter: filter: a cfn_hip.scorefilter.ScoreFilter expected, got %s' % type(filter).__name__)
+        self.filter = filter
         self.levels, self.nms, self.nms_score = levels, (0.5 if nms is None else float(nms)), nms_score
         if levels is None and nms is not None:
             raise ValueError('DetectionWriter: nms without levels: a single-level decode does not overlap itself (rule N7)')
@@ -565,11 +592,12 @@ class DetectionWriter(object):
         if isinstance(labels, SegLabels):
             labels = labels.to(probs.device)
             fps, start, unit = labels.fps, labels.window[:, 0].contiguous(), 's'
+        more = {} if self.filter is None else {'filter': self.filter}
         if self.levels is not None:             # decoder: propose's `reference` switch (decode_reference: the numpy references)
             det = propose(probs.detach(), valid_t.to(torch.int32), fps, start, self._levels(probs), self.nms, self.nms_score, self.max_gap, self.min_len,
-                          reference=decoder is decode_reference, soft=self.soft)
+                          reference=decoder is decode_reference, soft=self.soft, **more)
         else:
-            det = (decoder or decode)(probs.detach(), valid_t.to(torch.int32), fps, start, self._thr(probs), self.max_gap, self.min_len)
+            det = (decoder or decode)(probs.detach(), valid_t.to(torch.int32), fps, start, self._thr(probs), self.max_gap, self.min_len, **more)
         self._pending.append((det, names, unit))
         self._pending_bytes += sum(t.numel() * t.element_size() for t in det[:5])
         if self._pending_bytes > self.max_pending_bytes:

@@ -2007,6 +2007,51 @@ def soft_nms_segments(seg, frames, score, offsets, n_classes, method=1, sigma=0.
     return out[:7]
 
 
+# ---- temporal filtering of per-frame scores in front of the decode (csrc/scorefilter.hip; the rule, the host reference and the ScoreFilter type:
+# cfn_hip/scorefilter.py) ------------------------------------------------------------------------------------------------------------------------
+SCORE_FILTER_MAX_R = 32
+SCORE_FILTER_TILE = 256          # frames of a row per workgroup (cfn_score_filter_tile())
+SCORE_FILTER_MAX_TL = 65536
+
+
+def score_filter(probs, valid_t, radius, weights, method, out=None):
+    """probs (B, C, TL) fp32 on the GPU; valid_t (B,) int32; radius (C,) int32; weights (C, R + 1) fp64 with 0 <= R <= 32; method 0 (weighted
+    mean) or 1 (median), a host int -> out (B, C, TL) fp32: every frame in front of valid_t replaced by the weighted mean or the median of
+    its window of radius[c] frames on each side, truncated at the valid range; frames behind valid_t and classes of radius 0 copied bit for
+    bit; a window with a non-finite value gives the canonical NaN (rules F1-F6 of cfn_hip/scorefilter.py; filter_reference spells them on
+    the host).  One launch, no atomics, nothing is read back (no wait, capturable with out=).  out: a preallocated contiguous (B, C, TL)
+    fp32 tensor (a view inside a larger buffer will do) that does not overlap probs.  No gradient, no CPU path."""
+    what = 'score_filter'
+    if not torch.is_tensor(probs) or probs.dtype != torch.float32 or probs.dim() != 3 or min(probs.shape) < 1:
+        raise RuntimeError('%s: probs: a contiguous (B, C, TL) float32 tensor expected, got %s %s'
+                           % (what, getattr(probs, 'dtype', type(probs).__name__), tuple(getattr(probs, 'shape', ()))))
+    B, C, TL = (int(s) for s in probs.shape)
+    if B > 65535 or C > 65535 or TL > SCORE_FILTER_MAX_TL:
+        raise RuntimeError('%s: probs: B and C <= 65535 and TL <= %d expected, got (%d, %d, %d)' % (what, SCORE_FILTER_MAX_TL, B, C, TL))
+    for arg, t, dt, shape in (('valid_t', valid_t, torch.int32, (B,)), ('radius', radius, torch.int32, (C,))):
+        if not torch.is_tensor(t) or t.dtype != dt or tuple(t.shape) != shape:
+            raise RuntimeError('%s: %s %s %s expected, got %s %s' % (what, arg, shape, dt, getattr(t, 'dtype', type(t).__name__), tuple(getattr(t, 'shape', ()))))
+    if not torch.is_tensor(weights) or weights.dtype != torch.float64 or weights.dim() != 2 or int(weights.shape[0]) != C \
+            or not 1 <= int(weights.shape[1]) <= SCORE_FILTER_MAX_R + 1:
+        raise RuntimeError('%s: weights: a (%d, R + 1) float64 tensor with 0 <= R <= %d expected, got %s %s'
+                           % (what, C, SCORE_FILTER_MAX_R, getattr(weights, 'dtype', type(weights).__name__), tuple(getattr(weights, 'shape', ()))))
+    R = int(weights.shape[1]) - 1
+    if isinstance(method, bool) or not isinstance(method, int) or method not in (0, 1):
+        raise RuntimeError('%s: method 0 (weighted mean) or 1 (median) expected, got %r' % (what, method))
+    dev = _one_gpu(what, 'cfn_hip.scorefilter.filter_reference', probs=probs, valid_t=valid_t, radius=radius, weights=weights)
+    if out is None:
+        out = torch.empty(B, C, TL, dtype=torch.float32, device=dev)
+    else:
+        if not torch.is_tensor(out) or out.dtype != torch.float32 or tuple(out.shape) != (B, C, TL) or out.device != dev or not out.is_contiguous():
+            raise RuntimeError('%s: out: a contiguous (%d, %d, %d) float32 tensor on %s expected, got %s %s on %s'
+                               % (what, B, C, TL, dev, getattr(out, 'dtype', type(out).__name__), tuple(getattr(out, 'shape', ())), getattr(out, 'device', 'the host')))
+        nbytes = B * C * TL * 4
+        if out.data_ptr() < probs.data_ptr() + nbytes and probs.data_ptr() < out.data_ptr() + nbytes:
+            raise RuntimeError('%s: out must not be (or overlap) probs: a window reads frames that another thread has already written' % what)
+    call('cfn_score_filter', probs, valid_t, radius, weights, out, B, C, TL, R, method)
+    return out
+
+
 # ---- segment-level AP at temporal-IoU thresholds (csrc/segap.hip; the rule, the host reference and the meter: cfn_hip/segap.py) -------------
 SEGAP_GT_TILE = 64               # ground-truth rows of a video per tile of lanes (cfn_segap_gt_tile(); more take the general path)
 SEGAP_DET_TILE = 1024            # detections of a (video, class) group ordered in LDS (cfn_segap_det_tile(); more take the general path)

@@ -211,7 +211,8 @@ class SegmentAPMeter(object):
     levels, nms (default 0.5), nms_score: with `levels` set those entry points run cfn_hip.detections.propose (candidates at K levels, then
     temporal NMS) in place of decode; the meter only keeps the three for them.  A batch of proposals can hold K times the rows of a decode:
     ``add(levels=K)`` multiplies growing mode's bound (post-NMS groups can still exceed (TL + 1) // 2 rows).  soft (a
-    cfn_hip.detections.SoftNMS, with `levels`): propose's second stage is soft_nms; kept for the entry points like the three.
+    cfn_hip.detections.SoftNMS, with `levels`): propose's second stage is soft_nms; kept for the entry points like the three.  filter (a
+    cfn_hip.scorefilter.ScoreFilter): the entry points smooth the probs with it in front of their decode; kept for them like the rest.
     A meter made without the next two arguments is one process's, exactly as before.  across_ranks=True (group: the process group, None =
     the default one): under a world size above 1 ``value_device()`` and ``value()`` evaluate the stores of ALL ranks, appended in rank order
     into a fresh store (cfn_hip.apmerge.gather_stores): every rank gets the same bits, those of one process fed the ranks' batches one rank
@@ -222,8 +223,13 @@ class SegmentAPMeter(object):
     MIN_CAPACITY = 1024
 
     def __init__(self, device, n_classes, tiou=DEFAULT_TIOU, score='max', capacity=None, thr=0.5, max_gap=0, min_len=1, levels=None, nms=None,
-                 nms_score='max', soft=None, across_ranks=False, group=None):
+                 nms_score='max', soft=None, across_ranks=False, group=None, filter=None):
         self.device = torch.device(device)
+        if filter is not None:
+            from .scorefilter import ScoreFilter
+            if not isinstance(filter, ScoreFilter):
+                raise TypeError('SegmentAPMeter: filter: a cfn_hip.scorefilter.ScoreFilter expected, got %s' % type(filter).__name__)
+        self.filter = filter
         self.across_ranks, self.group = bool(across_ranks), group
         if self.device.type != 'cuda':
             raise RuntimeError('SegmentAPMeter keeps its rows on a GPU (got device %s); cfn_hip.segap.ap_reference is the host spelling' % self.device)
@@ -370,7 +376,7 @@ class SegmentAPMeter(object):
             raise ValueError('SegmentAPMeter.merged: at least one meter expected')
         p = parts[0]
         new = cls(p.device, p.n_classes, p.tiou, p.score, capacity, p.thr, p.max_gap, p.min_len, p.levels, p.nms if p.levels is not None else None,
-                  p.nms_score, p.soft)
+                  p.nms_score, p.soft, filter=p.filter)
         return new.merge(*parts)
 
     def _across(self):

@@ -185,7 +185,8 @@ def run(init_lr=INIT_LR, warmup_steps=0, max_epochs=200, mode='rgb', root=None, 
         csv_path='localize_corr_v1.csv', log=print, phase_hook=None, input_norm=None, device_ap=False,
         fused_loss=False, jpeg_entropy=None, detections=None, segment_ap=None, calibration=None, proposal_recall=None):
     """detections: a cfn_hip.detections.DetectionWriter -- every validation phase decodes its probs into activity segments on the GPU and
-    rank 0 writes all ranks' videos as JSON lines (see train_fine.run).  None: nothing changes.
+    rank 0 writes all ranks' videos as JSON lines (see train_fine.run).  None: nothing changes.  A writer or a segment-AP meter made with
+    filter= (--detect-smooth) smooths the probs in front of its decode; the frame-mAP line and the loss stay on the raw probs.
     proposal_recall: a cfn_hip.recall.ProposalRecallMeter -- fed the Detections of the writer or of the segment-AP meter in every validation
     phase, one ' Epoch:E val AR@1: ...' line per phase, any world size (see train_fine.run).  None: nothing changes.
     calibration: a cfn_hip.calibrate.Calibration -- per-class thresholds from the training AP rows wherever a training mAP is taken and in

@@ -287,6 +287,8 @@ def run(init_lr=INIT_LR, warmup_steps=0, max_epochs=200, mode='rgb', root=None, 
     (--seg-ap-all-ranks) evaluates the stores of all ranks appended in rank order on the GPU (cfn_hip/apmerge.py): every rank builds the line
     (a collective), rank 0 logs it.  None: nothing changes.  A writer or a meter made with levels= decodes with cfn_hip.detections.propose instead (candidates at K
     levels, then temporal NMS -- soft-NMS when it was also made with soft=); the meter is still fed the writer's batch when both are given.
+    A writer or a meter made with filter= (a cfn_hip.scorefilter.ScoreFilter, --detect-smooth) smooths the probs on the GPU in front of that decode
+    (DESIGN 4.23); the frame-mAP line and the loss stay on the raw probs.
     calibration: a cfn_hip.calibrate.Calibration whose thr_vector / levels the writer and the meter were made with -- wherever a
     proposal_recall: a cfn_hip.recall.ProposalRecallMeter -- every validation phase feeds it the very Detections the writer or the segment-AP
     meter made (no second decode, so one of the two must be given) and logs ' Epoch:E val AR@1: ... AR@10: ... AR@N: ... AUC: ... props/video:
@@ -455,7 +457,7 @@ def calibration_line(calibration, epochs):
 
 def segment_ap_add(meter, det, probs, valid_t, seg_batch, labels, writer=None):
     """one validation batch into the meter: `det` = what the DetectionWriter `writer` decoded (None: decode here with the meter's
-    parameters -- propose() when it has levels); ground truth = the batch's SegLabels (seconds), or the dense labels decoded into frame units"""
+    parameters and its filter -- propose() when it has levels); ground truth = the batch's SegLabels (seconds), or the dense labels decoded into frame units"""
     from cfn_hip.detections import decode, propose
     valid_t = valid_t.to(torch.int32)
     fps = start = None
@@ -464,9 +466,10 @@ def segment_ap_add(meter, det, probs, valid_t, seg_batch, labels, writer=None):
         fps, start = seg_batch.fps, seg_batch.window[:, 0].contiguous()
     levels = writer.n_levels if det is not None and writer is not None else meter.n_levels
     if det is None and meter.levels is not None:
-        det = propose(probs.detach(), valid_t, fps, start, meter.levels, meter.nms, meter.nms_score, meter.max_gap, meter.min_len, soft=meter.soft)
+        det = propose(probs.detach(), valid_t, fps, start, meter.levels, meter.nms, meter.nms_score, meter.max_gap, meter.min_len, soft=meter.soft,
+                      filter=getattr(meter, 'filter', None))
     elif det is None:
-        det = decode(probs.detach(), valid_t, fps, start, meter.thr, meter.max_gap, meter.min_len)
+        det = decode(probs.detach(), valid_t, fps, start, meter.thr, meter.max_gap, meter.min_len, filter=getattr(meter, 'filter', None))
     meter.add(det, seg_batch if fps is not None else (labels, valid_t), levels=levels)
     return det
 
@@ -528,10 +531,11 @@ def seg_ap_from_args(args, n_classes=157, calibration=None):
     if not args.seg_ap:
         return None
     from cfn_hip.segap import SegmentAPMeter
+    smooth = detect_smooth(args)                # (refuses --detect-calibrate before a calibration is made)
     thr, more = _calibrated(args.detect_thr, detect_levels(args), calibration_from_args(args, n_classes) if calibration is None else calibration)
     return SegmentAPMeter(torch.device('cuda', torch.cuda.current_device()), n_classes, [float(x) for x in args.seg_ap_tiou.split(',')], args.seg_ap_score,
                           args.seg_ap_capacity, thr, args.detect_gap, args.detect_min_len, across_ranks=bool(getattr(args, 'seg_ap_all_ranks', False)),
-                          **more)
+                          filter=smooth, **more)
 
 
 def add_detect_args(parser):
@@ -553,6 +557,10 @@ def add_detect_args(parser):
     g.add_argument('--detect-soft-sigma', type=float, default=None, help='with --detect-soft-nms gaussian: sigma, in [1/64, 2^20] (default 0.5)')
     g.add_argument('--detect-min-score', type=float, default=None, help='with --detect-soft-nms: stop at the first decayed score below this (default 0.001)')
     g.add_argument('--detect-max-keep', type=int, default=None, help='with --detect-soft-nms: at most N segments per video and class (default 0: no limit)')
+    g.add_argument('--detect-smooth', metavar='SPEC', default=None,
+                   help='smooth the per-frame scores on the GPU before they are thresholded: box:R | gaussian:SIGMA[:R] | median:R, R frames on each '
+                        'side (at most 32; gaussian default: ceil(3 SIGMA)), the window truncated at the ends of the video.  The frame-mAP line and '
+                        'the loss stay on the raw scores')
     g.add_argument('--prop-recall', action='store_true',
                    help='log the proposal recall AR@N of every validation phase (needs --detect or --seg-ap, whose decode it is fed: with '
                         '--detect-levels the proposals; any number of processes)')
@@ -587,6 +595,18 @@ def detect_levels(args):
     return more
 
 
+def detect_smooth(args):
+    """the ScoreFilter of --detect-smooth (cfn_hip.scorefilter.parse_spec), or None without the option"""
+    spec = getattr(args, 'detect_smooth', None)
+    if spec is None:
+        return None
+    if getattr(args, 'detect_calibrate', None) is not None:
+        raise ValueError('--detect-smooth with --detect-calibrate: the calibration rows are RAW frame scores (the training phases\' AP rows), so a '
+                         'threshold calibrated on them says nothing about the smoothed scores it would be applied to: drop one of the two')
+    from cfn_hip.scorefilter import parse_spec
+    return parse_spec(spec)
+
+
 def detect_argv(args):
     """the --detect group of `args` as a worker's command line"""
     if not args.detect:
@@ -596,7 +616,8 @@ def detect_argv(args):
         [x for flag, k, f in (('--detect-soft-nms', 'detect_soft_nms', str), ('--detect-soft-sigma', 'detect_soft_sigma', repr),
                               ('--detect-min-score', 'detect_min_score', repr), ('--detect-max-keep', 'detect_max_keep', str))
          if getattr(args, k, None) is not None for x in (flag, f(getattr(args, k)))] + \
-        (['--detect-calibrate', args.detect_calibrate] if getattr(args, 'detect_calibrate', None) is not None else [])
+        (['--detect-calibrate', args.detect_calibrate] if getattr(args, 'detect_calibrate', None) is not None else []) + \
+        (['--detect-smooth', args.detect_smooth] if getattr(args, 'detect_smooth', None) is not None else [])
     return ['--detect', args.detect, '--detect-thr', repr(args.detect_thr), '--detect-gap', str(args.detect_gap), '--detect-min-len', str(args.detect_min_len)] + more
 
 
@@ -669,8 +690,9 @@ def detect_writer(args, calibration=None):
     update in place reaches every later decode"""
     if not args.detect:
         return None
+    smooth = detect_smooth(args)                # (refuses --detect-calibrate before a calibration is made)
     thr, more = _calibrated(args.detect_thr, detect_levels(args), calibration_from_args(args) if calibration is None else calibration)
-    return DetectionWriter(args.detect, thr, args.detect_gap, args.detect_min_len, **more)
+    return DetectionWriter(args.detect, thr, args.detect_gap, args.detect_min_len, filter=smooth, **more)
 
 
 def _spawn(gpus, argv):

@@ -725,6 +725,39 @@ int cfn_soft_nms_segments(const double* seg, const int* frames, const float* sco
                           long cap_out, void* stream);
 
 /* =====================================================================================================================
+ * Temporal filtering of per-frame scores in front of the decode (csrc/scorefilter.hip; the rule, the numpy reference and the
+ * ScoreFilter type: cfn_hip/scorefilter.py).  Raw sigmoid scores flicker from frame to frame and rule 1 of cfn_decode_segments
+ * then breaks one activity into many runs; this is the box, Gaussian or median filter a caller would otherwise write in torch
+ * with an edge rule of their own.  probs (B, C, TL) fp32; valid_t (B) int32; radius (C) int32; weights (C, R + 1) fp64; host ints
+ * R in [0, 32] (windows of at most 65 frames) and method (0 = weighted mean, 1 = median) -> out (B, C, TL) fp32, not probs.
+ *     F1. n = min(max(valid_t[b], 0), TL), r = min(max(radius[c], 0), R).  Frames t >= n are copied from probs bit for bit; r = 0
+ *         copies every frame bit for bit, under either method
+ *     F2. the window of frame t < n is u in [max(0, t - r), min(n - 1, t + r)]: truncated at the valid range, no padding, no
+ *         reflection
+ *     F3. a window that holds a non-finite value gives the canonical quiet NaN 0x7fc00000 (cfn_decode_segments never activates
+ *         such a frame); so does a weighted mean whose quotient is a NaN (weights other than the documented table)
+ *     F4. weighted mean, u ascending throughout: num = the sum of weights[c, |u - t|] * (double)probs[b, c, u], den = the sum of
+ *         weights[c, |u - t|], both from 0.0; every product and every sum is rounded separately (no fused multiply-add); then ONE
+ *         IEEE fp64 division and ONE rounding to fp32.  The box filter is the table of ones; a Gaussian table is made on the HOST
+ *         (exp(-d * d / (2 sigma^2)), weights[c, 0] == 1.0), so no device exp is involved.  Weights are expected finite and
+ *         non-negative with weights[c, 0] > 0
+ *     F5. median: the window ordered by (value, u): rank(u) = #{v : p[v] < p[u] or (p[v] == p[u] and v < u)}, a stable sort, so
+ *         +0 / -0 ties are decided.  m window frames, m odd: the element of rank (m - 1) / 2; m even:
+ *         (float)(((double)a + (double)b) * 0.5) with a, b the elements of ranks m / 2 - 1 and m / 2
+ *     F6. no atomics, nothing is read back: the same bits in every run
+ *   1 launch, grid (tile of cfn_score_filter_tile() = 256 frames, class, video), one thread per frame; the tile, a halo of 32
+ *   frames on each side and the class's weight row are staged in LDS by bounds-checked loads that never leave row (b, c).  The
+ *   median ranks by counting over the LDS window: O(window^2) per frame.  valid_t, radius and weights are read on the device
+ *   only and the first two are clamped: a bad batch gives wrong values, never an access outside the buffers.  No allocation, no
+ *   synchronisation (capturable); nothing accumulates across threads, so the deterministic mode changes nothing.
+ * Returns 1 for null pointers, B or C outside [1, 65535], TL outside [1, 65536], R outside [0, 32], method outside {0, 1} or
+ * out == probs.
+ * ===================================================================================================================== */
+int cfn_score_filter_tile(void);
+int cfn_score_filter(const float* probs, const int* valid_t, const int* radius, const double* weights, float* out, int B, int C,
+                     int TL, int R, int method, void* stream);
+
+/* =====================================================================================================================
  * Segment-level average precision at temporal-IoU thresholds (csrc/segap.hip; the host reference and the meter:
  * cfn_hip/segap.py).  The first consumer of the pair cfn_seg_labels' seg / cfn_decode_segments' seg; the reference stops at probs
  * (train_fine.py:199-222), so the rule is stated here once:
